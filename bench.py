@@ -10,21 +10,28 @@ chromosome lengths, 3.09 Gb, N runs, repeat families, tandem repeats, segmental 
 resident; 1 M reads = 10 steps).  `--workload chr22` is configs[1] (the round-1 line), `--workload small` a plumbing check.
 
 One step = one pass of the whole hot path (read prep + features + seed lookup + filter / chain / extend + block chaining ->
-cords) over one batch.  Two timed regions run over the same batches: the batch already resident in HBM
-(`config.device_resident_reads_per_s`), and -- the line's `value`, SURVEY 8(d)'s metric -- host read blocks in -> host cords out
-through `lnr_filter_submit` / `lnr_filter_wait` with three batches in flight (reads up, cords down inside the clock).  The
-default line also measures the reference's DEFAULT mode on the same batches and context (`config.gap50`: `-g 1` = gaps of 50 and
-more re-mapped, with its own reference baseline and parity check; `--no-gap50` skips it) and the front-end binary end to end on
-FASTA files (`config.cli_end_to_end_reads_per_s`; `--no-cli`).  `--gap 50 [--dup 1]` makes the gap path the line itself;
-`--workload ccs_sv` is BASELINE configs[4] on one GPU (15 kb CCS-profile reads, SVs planted on the device, `-g 50 -dup 1`).
-Index build (and, for N > 1, its RCCL broadcast) happens once before the timed region and is reported in `config`.
+cords) over one batch.  The line's `value` (SURVEY 8(d)'s metric) and `ms_per_step` time host read blocks in -> host cords out
+through `lnr_filter_submit` / `lnr_filter_wait` with three batches in flight (reads up, cords down inside the clock): `--warmup`
+untimed steps, then exactly `--steps` timed ones.  A plain run does only that.  `--full` adds everything else, before and after it:
+a timed region with the batch already resident in HBM (`config.device_resident_reads_per_s`, per-read counters, stage times and
+the seed-lookup roofline), the reference's DEFAULT mode on the same batches and context (`config.gap50`: `-g 1` = gaps of 50 and
+more re-mapped, with its own reference baseline and parity check; `--no-gap50` skips it), the CPU baseline with its parity check
+(`--no-cpu-baseline` skips it) and the front-end binary end to end on FASTA files (`config.cli_end_to_end_reads_per_s`; `--no-cli`).
+`--gap 50 [--dup 1]` makes the gap path the line itself; `--workload ccs_sv` is BASELINE configs[4] on one GPU (15 kb CCS-profile
+reads, SVs planted on the device, `-g 50 -dup 1`).  Index build (and, for N > 1, its RCCL broadcast) happens once before the timed
+region and is reported in `config`.
+
+`--dump-outputs DIR` writes, after the timed steps, the cords the timed path handed out in its last step (rank 0's batch) as
+float64 .npy files, every value exact: `cords_per_read` (n_reads), `sample_reads` (a fixed seeded sample of read indices) and
+`cords_str` / `cords_end` (the cords of the sampled reads in order, one row per cord word split into its fields main, recd, strand,
+block_end, id, x, y).  Inputs are seeded, so two builds run with the same arguments can be compared file for file.
 
 N > 1: one process per GPU.  Launched either by the driver through torch.distributed.run, or by `python bench.py --gpus N`
 itself: with no WORLD_SIZE in the environment this script starts the N ranks as a child torch.distributed.run BEFORE any GPU
 call and relays rank 0's JSON line.  Rank 0 builds the packed index and broadcasts it over RCCL/xGMI; every rank then filters
 its own batches (weak scaling: per-GPU batch fixed, no data-path collective).
 
-CPU baseline (rank 0, N = 1): the REAL reference (oracle/_ref/libref_linear.so, the reference's own translation units compiled
+CPU baseline (`--full`, rank 0, N = 1): the REAL reference (oracle/_ref/libref_linear.so, the reference's own translation units compiled
 by oracle/Makefile; `kind: "reference"`) running its calculator loop on all host cores the process may use; where that library
 is absent the bit-exact restatement oracle/lnr_oracle.cpp (`kind: "port"`).  Test infrastructure, used here as the checker and
 as the timed CPU leg only.
@@ -116,6 +123,29 @@ def padded_layout(seq_len):
     return starts
 
 
+DUMP_SAMPLE_READS = 2048      # reads whose cords --dump-outputs writes in full
+DUMP_BYTES = 60_000_000       # the files of --dump-outputs stay below 64 MB together
+CORD_FIELDS = ((63, 1), (62, 1), (61, 1), (60, 1), (50, 10), (20, 30), (0, 20))   # main recd strand blockEnd id x y (include/linear_amd.h)
+
+
+def dump_outputs(d, coff, cs, ce):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = coff.size - 1
+    counts = np.diff(coff.astype(np.int64))
+    sample = np.sort(np.random.default_rng(20261016).choice(n, min(n, DUMP_SAMPLE_READS), replace=False))
+    idx = np.concatenate([np.arange(int(coff[i]), int(coff[i + 1])) for i in sample] + [np.zeros(0, np.int64)])
+    max_cords = max(0, DUMP_BYTES - 8 * (n + sample.size)) // (2 * 8 * len(CORD_FIELDS))
+    idx = idx[:max_cords]
+
+    def fields(w):
+        return np.stack([(w >> np.uint64(sh)) & np.uint64((1 << b) - 1) for sh, b in CORD_FIELDS], axis=1).astype(np.float64)
+    np.save(os.path.join(d, "cords_per_read.npy"), counts.astype(np.float64))
+    np.save(os.path.join(d, "sample_reads.npy"), sample.astype(np.float64))
+    np.save(os.path.join(d, "cords_str.npy"), fields(cs[idx]))
+    np.save(os.path.join(d, "cords_end.npy"), fields(ce[idx]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -137,7 +167,12 @@ def main():
     ap.add_argument("--gap", type=int, default=0, help="the reference's -g: 0 = apxMap only (the headline configuration); > 0 = cords go through the gap re-mapper (SURVEY 8 f1)")
     ap.add_argument("--dup", type=int, default=0, help="the reference's -dup (with --gap)")
     ap.add_argument("--small", action="store_true", help="alias of --workload small")
+    ap.add_argument("--full", action="store_true", help="also the device-resident timing with stage times and roofline, the -g 50 leg, the CPU baseline with parity "
+                    "and the front-end end to end (a plain run times only the headline path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the cords of the last timed step to DIR/*.npy (float64)")
     args = ap.parse_args()
+    if args.dump_outputs and args.seed_only:
+        ap.error("--dump-outputs: --seed-only hands no result to the host")
     if args.small:
         args.workload = "small"
     explicit = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
@@ -228,7 +263,7 @@ def main():
             t_ref = time.time() - t0
             t0 = time.time()
             info = flt.build_index_ptrs([gen.data_ptr() + o for o in offs[:-1]], [offs[i + 1] - offs[i] for i in range(len(offs) - 1)], T)
-            if world == 1 and not (args.no_cpu_baseline and args.no_cli) and not args.seed_only:
+            if args.full and world == 1 and not (args.no_cpu_baseline and args.no_cli) and not args.seed_only:
                 h = gen.cpu().numpy()
                 host_genome = [h[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
             del gen
@@ -313,15 +348,17 @@ def main():
             dt_ = float(t.item())
         return dt_, acc_
 
-    # (1) the batch resident in HBM (config.device_resident_reads_per_s; the roofline's seed launches are timed here)
-    dt_dev, acc = timed(step)
+    # (1) --full, or --seed-only whose line it is: the batch resident in HBM (config.device_resident_reads_per_s; the roofline's seed
+    # launches are timed here)
+    resident = args.full or args.seed_only
+    if resident:
+        dt_dev, acc = timed(step)
     # (2) THE METRIC (first read batch submitted -> last cords batch returned): host read blocks in, host cords out, through
     # lnr_filter_submit / lnr_filter_wait with three batches in flight (step k: submit(k + 2); wait(k) -- the wait downloads batch k's cords
     # while it computes batch k + 1, the upload of k + 2 runs under those kernels), in steady state: the pipeline is already full when the clock
     # starts, as it is for every later step.  Inside the clock: K uploads, K computes, K result downloads.  The two batches still in flight
     # after the last timed step are drained behind the clock.
     host_path = not args.seed_only
-    dt = dt_dev
     if host_path:
         nhb = max(3, min(4 if world > 1 else 8, nb))
         hb = []
@@ -332,28 +369,29 @@ def main():
         flt.filter_submit(*hb[0])
         flt.filter_submit(*hb[1 % nhb])
 
+        last = [None, None]
+
         def host_step(k):
             flt.filter_submit(*hb[(k + 2) % nhb])
+            last[0] = flt.filter_wait(copy=False)
+
+        def drain():
+            if args.dump_outputs and rank == 0:
+                last[1] = flt.cords_np(last[0])     # copied before the second next result reuses its host arrays
             flt.filter_wait(copy=False)
-        dt, acc_h = timed(host_step, post=lambda: (flt.filter_wait(copy=False), flt.filter_wait(copy=False)))
+            flt.filter_wait(copy=False)
+        dt, acc_h = timed(host_step, post=drain)
+        if last[1] is not None:
+            dump_outputs(args.dump_outputs, *last[1])
+            log(f"[bench] cords of the last timed step written to {args.dump_outputs}")
+    else:
+        dt = dt_dev
     if args.gap:
         flt.gap_stream(1)                 # (whatever the drained batch left: the timed batches above all ran in the extended state)
 
     K = max(args.steps, 1)
     total_reads = args.reads * K
-    # seed lookup: one launch per round (round 0 = whole reads, round 1 = the re-mapped gaps); timed by the library with HIP
-    # events recorded on the stream the kernels are launched on (lnr_api.hip seed_jobs, Timer t_seed)
-    launches = max(int(acc["seed_count_launches"]), 1)
-    seed_ms = acc["seed_count_ms"] / launches
-    seed_bytes = acc["seed_bytes"] / launches
-    achieved = seed_bytes / (seed_ms * 1e-3) / 1e9 if seed_ms > 0 else 0.0
-    wl_key = {"workload": args.workload, "scale": args.scale, "reads": args.reads, "read_len": args.read_len, "err": args.err,
-              "layout_threads": T, "seed_only": bool(args.seed_only)}
-    if args.gap:
-        wl_key["gap"] = args.gap
     dup_flag = " -dup 1" if args.dup else ""
-    traffic = recorded_traffic(wl_key, launches / K)
-    dev_rate = args.reads * world * args.steps / dt_dev
     rate = args.reads * world * args.steps / dt
 
     out = {
@@ -388,15 +426,33 @@ def main():
             "index_bytes": index_bytes,
             "index": {"nseq": int(info.nseq), "genome_bytes": int(info.genome_bytes), "hs_len": int(info.hs_len), "dir_len": int(info.dir_len),
                       "f2_len": int(info.f2_len), "samples": int(info.n_samples), "layout_threads": int(T)},
+        },
+    }
+    if resident:
+        # seed lookup: one launch per round (round 0 = whole reads, round 1 = the re-mapped gaps); timed by the library with HIP
+        # events recorded on the stream the kernels are launched on (lnr_api.hip seed_jobs, Timer t_seed)
+        launches = max(int(acc["seed_count_launches"]), 1)
+        seed_ms = acc["seed_count_ms"] / launches
+        seed_bytes = acc["seed_bytes"] / launches
+        achieved = seed_bytes / (seed_ms * 1e-3) / 1e9 if seed_ms > 0 else 0.0
+        wl_key = {"workload": args.workload, "scale": args.scale, "reads": args.reads, "read_len": args.read_len, "err": args.err,
+                  "layout_threads": T, "seed_only": bool(args.seed_only)}
+        if args.gap:
+            wl_key["gap"] = args.gap
+        traffic = recorded_traffic(wl_key, launches / K)
+        dev_rate = args.reads * world * args.steps / dt_dev
+        out["config"].update({
             "per_read": {"samples": acc["samples"] / total_reads, "lookups": acc["lookups"] / total_reads, "bucket_entries": acc["bucket_entries"] / total_reads,
                          "anchors": acc["anchors"] / total_reads, "cords": acc["cords"] / total_reads, "remap_reads_per_step": acc["remap_reads"] / K},
             "stage_ms_per_step": {"prep": acc["prep_ms"] / K, "seed": acc["seed_count_ms"] / K,
                                   "job": acc["job_ms"] / K, "tail": acc["tail_ms"] / K, "gap": acc.get("gap_ms", 0.0) / K, "total_device": acc["total_ms"] / K},
             "device_resident_reads_per_s": dev_rate,
             "gap_second_pass_per_step": acc.get("gap_second_pass", 0) / K,
-            "gap_path_note": "this line is -g " + str(args.gap) + "; the reference's default mode (-g 1 = gaps of 50 and more re-mapped) is measured in this same run: config.gap50_*",
-        },
-        "roofline": {
+        })
+        if args.full:
+            out["config"]["gap_path_note"] = ("this line is -g " + str(args.gap) + "; the reference's default mode (-g 1 = gaps of 50 and more re-mapped) is measured in "
+                                              "this same run: config.gap50_*")
+        out["roofline"] = {
             "bound": "hbm",
             "kernel": "seed lookup stage a3/a4/a7 (minimizers of the 2-bit packed read -> bucket lookup -> Y filter -> anchors), "
                       f"{launches / K:g} launches per step, averages per launch",
@@ -408,12 +464,11 @@ def main():
             "launch_ms": seed_ms,
             "traffic": traffic["bytes_per_launch"] if traffic else None,
             "traffic_source": traffic["source"] if traffic else None,
-        },
-    }
+        }
 
     # ---- the reference's DEFAULT mode in the same line: -g 1 (gaps of 50 and more re-mapped, mapper.cpp:207-231), same batches, same context
     gap50 = None
-    if args.gap == 0 and not args.no_gap50 and not args.seed_only and not double and world == 1 and rank == 0 and args.workload in ("grch38", "chr22"):
+    if args.full and args.gap == 0 and not args.no_gap50 and not args.seed_only and not double and world == 1 and rank == 0 and args.workload in ("grch38", "chr22"):
         flt.set_gap(1, 0)
         step(0)                                   # (also takes the stream through its first extension: the timed steps run in the steady state)
         sync()
@@ -435,10 +490,10 @@ def main():
 
     parity_ok = True
     out["config"]["host_path_reads_per_s"] = rate if host_path else None
-    if rank == 0:
+    if rank == 0 and resident and host_path:
         log(f"[bench] device-resident {dev_rate:.0f} reads/s; host entry point (pinned reads in, cords out, PCIe both ways, three batches in flight) {rate:.0f} reads/s = {rate / dev_rate:.0%}")
 
-    if rank == 0 and world == 1 and not double and not args.no_cpu_baseline and not args.seed_only and host_genome is not None:
+    if args.full and rank == 0 and world == 1 and not double and not args.no_cpu_baseline and not args.seed_only and host_genome is not None:
         # ---- CPU baseline + parity on a bounded sample of batch 0
         from oracle import pyorc
         pyorc.build(ref=False)
@@ -512,7 +567,7 @@ def main():
             log("[bench] PARITY FAILURE on the bench sample")
         chk.close()
 
-    if rank == 0 and world == 1 and not double and not args.seed_only and not args.no_cli and host_genome is not None and args.workload in ("grch38", "chr22", "small"):
+    if args.full and rank == 0 and world == 1 and not double and not args.seed_only and not args.no_cli and host_genome is not None and args.workload in ("grch38", "chr22", "small"):
         # ---- the front-end binary end to end: FASTA files in -> .sam out through reader -> GPU -> writer, batch 0 as a read file
         import re
         import shutil

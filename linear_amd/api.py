@@ -214,7 +214,7 @@ class Filter:
         n = off.size - 1
         out = LnrCords()
         self._ck(self.lib.lnr_filter_batch(self.h, _p(reads, _u8p), _p(off, _u64p), n, C.byref(out)))
-        return self._cords_np(out)
+        return self.cords_np(out)
 
     def host_alloc(self, nbytes: int) -> np.ndarray:
         """uint8 array over pinned host memory from lnr_host_alloc (freed with host_free or at close)."""
@@ -234,14 +234,16 @@ class Filter:
         self._inflight.append((reads, off))
 
     def filter_wait(self, copy: bool = True):
+        """Cords of the oldest submitted batch as numpy copies; copy=False returns the lnr_cords itself, whose host arrays stay valid
+        until the second next result of the context (cords_np copies them)."""
         out = LnrCords()
         self._ck(self.lib.lnr_filter_wait(self.h, C.byref(out)))
         if getattr(self, "_inflight", None):
             self._inflight.pop(0)
-        return self._cords_np(out) if copy else (out.n_reads, out.n_cords)
+        return self.cords_np(out) if copy else out
 
     @staticmethod
-    def _cords_np(out: "LnrCords"):
+    def cords_np(out: "LnrCords"):
         n = out.n_reads
         coff = np.ctypeslib.as_array(out.cord_off, shape=(n + 1,)).copy()
         if out.n_cords:
@@ -267,7 +269,7 @@ class Filter:
     def cords_to_host(self):
         out = LnrCords()
         self._ck(self.lib.lnr_cords_to_host(self.h, C.byref(out)))
-        return self._cords_np(out)
+        return self.cords_np(out)
 
     def seed_lookup_batch(self, reads: np.ndarray, off: np.ndarray):
         reads = np.ascontiguousarray(reads, dtype=np.uint8)

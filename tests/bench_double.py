@@ -78,7 +78,12 @@ class FilterDouble:
         assert self.inflight >= 1
         self.inflight -= 1
         time.sleep(0.002)
-        return self.n, 0
+        return self.n
+
+    @staticmethod
+    def cords_np(n):
+        # the double computes no cords: an empty result of n reads
+        return np.zeros(n + 1, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint64)
 
     def gap_stream(self, set_to=-1):
         return 0

@@ -1,7 +1,6 @@
 // tests/gpufilter_driver.cpp -- runs integration/gpu_filter.h (the reference-side binding a maintainer of xp3i4/linear adds: SeqAn StringSets in,
-// SeqAn StringSets out) on a real GPU.  Needs the reference's vendored SeqAn headers to COMPILE, so __graft_entry__.build() builds it where
-// /root/reference exists (tests/_build/gpufilter_driver, an untracked artefact that travels to the GPU box like the library itself);
-// tests/test_gpu_parity.py::test_gpu_seqan_side_binding_on_the_gpu runs it there.
+// SeqAn StringSets out) on a real GPU.  __graft_entry__.build() compiles it against the SeqAn stand-in tests/seqan_standin into
+// tests/_build/gpufilter_driver; tests/test_gpu_parity.py::test_gpu_seqan_side_binding_on_the_gpu runs it.
 //   usage: gpufilter_driver <case.bin> <out.bin> <T> <gap_len> <dup>
 //   case.bin: u32 nseq, {u64 len, bytes}*, u32 nreads, {u64 len, bytes}*   (Dna5 ordinals)
 //   out.bin : u32 nreads, {u64 ncords, cords_str words, cords_end words}*

@@ -479,17 +479,15 @@ def test_gpu_batch_rerun_on_per_read_overflow(case_inputs, monkeypatch):
 @pytest.mark.parametrize("gap_len,dup", [(0, 0), (50, 1)])
 def test_gpu_seqan_side_binding_on_the_gpu(case_inputs, tmp_path, gap_len, dup):
     """integration/gpu_filter.h -- the file INTEGRATION.md tells a maintainer of the reference to add: SeqAn StringSet<String<Dna5>> in, StringSet<String<
-    uint64_t>> out -- executed on the GPU: tests/_build/gpufilter_driver is compiled against the reference's vendored SeqAn headers by
-    __graft_entry__.build() where the reference tree is (here it is only run).  Two filterBlock calls on one binding; cords equal the goldens."""
+    uint64_t>> out -- executed on the GPU: tests/_build/gpufilter_driver is compiled by __graft_entry__.build() against the SeqAn stand-in
+    tests/seqan_standin (the binding against the real SeqAn headers: tests/test_boundary_compile_cpu.py).  Two filterBlock calls on one binding;
+    cords equal the goldens."""
     import struct
     import subprocess
     exe = os.path.join(os.path.dirname(__file__), "_build", "gpufilter_driver")
     if not os.path.exists(exe):
-        if os.path.exists("/root/reference/seqan/include/seqan/sequence.h"):
-            import __graft_entry__ as ge
-            ge.build()
-        else:
-            pytest.fail("tests/_build/gpufilter_driver is missing: __graft_entry__.build() makes it where /root/reference is present")
+        import __graft_entry__ as ge
+        ge.build()
     refs, reads, off = case_inputs("edge")
     n = off.size - 1
     with open(tmp_path / "case.bin", "wb") as f:

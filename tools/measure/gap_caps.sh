@@ -2,12 +2,12 @@
 # of the first launch, chr22 stand-in, 20 k reads, -g 50
 set -e
 cd "$(dirname "$0")/../.."
-out=gpurun_out/gap_caps.txt; : > $out
+out=measure_out/gap_caps.txt; : > $out
 run() {  # name, mode, cap, arena2
-  LNR_GAP_MODE=$2 LNR_GAP_WORK_CAP=$3 LNR_GAP_ARENA2_MB=$4 timeout -k 10 300 python bench.py --workload chr22 --reads 20000 --steps 2 --warmup 1 --gap 50 --no-cpu-baseline > gpurun_out/gm.json 2> gpurun_out/gm.log
+  LNR_GAP_MODE=$2 LNR_GAP_WORK_CAP=$3 LNR_GAP_ARENA2_MB=$4 timeout -k 10 300 python bench.py --full --workload chr22 --reads 20000 --steps 2 --warmup 1 --gap 50 --no-cpu-baseline > measure_out/gm.json 2> measure_out/gm.log
   python - "$1" >> $out <<'PY'
 import json, sys
-d = json.load(open("gpurun_out/gm.json"))
+d = json.load(open("measure_out/gm.json"))
 s = d["config"]["stage_ms_per_step"]
 print(f"{sys.argv[1]:34s} gap {s['gap']:9.1f} ms/step   second-pass reads/step {d['config'].get('gap_second_pass_per_step', -1):8.1f}   {d['value']:.0f} reads/s", flush=True)
 PY

@@ -1,7 +1,7 @@
 # kernel timeline of one step (last k_prep .. end) under rocprofv3 --kernel-trace: bash tools/measure/r3_timeline.sh <outdir> [bench args]
 OUT=gpurun_out/${1:-r3tl}; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p $OUT && rm -rf $OUT/prof
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cli "$@" > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.log || { tail -5 $OUT/bench_under_rocprof.log; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cli "$@" > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.log || { tail -5 $OUT/bench_under_rocprof.log; exit 1; }
 cp $(ls $OUT/prof/*/*kernel_stats.csv | tail -1) $OUT/kernel_stats.csv
 python3 - $OUT <<'PY'
 import csv, glob, sys

@@ -4,7 +4,7 @@ bench.py's roofline object.
 
     tools/pmc_seed_r02.py <fetch_dir> <write_dir> <rdreq_dir> profiles/r02 --steps 3 --warmup 1 --layout-threads 16
 
-The passes are separate rocprofv3 runs of the same command (`python3 bench.py --steps S --warmup W --no-cpu-baseline`), one
+The passes are separate rocprofv3 runs of the same command (`python3 bench.py --full --steps S --warmup W --no-cpu-baseline`), one
 counter set each (FETCH_SIZE takes 3 of the 4 TCC slots, WRITE_SIZE 2: /opt/skills/guides/MI355X_MICROARCH.md, PMC slots).
 Corrections as that guide's HBM section prescribes: both counters are in KiB; WRITE_SIZE is exact; FETCH_SIZE tallies every
 128-byte request at 64 B on gfx950, so it is doubled -- cross-checked here against TCC_EA0_RDREQ_sum x 128 B from the third pass."""
@@ -50,7 +50,7 @@ def main():
         "fetch_factor": 2.0,
         "rdreq_x_128B_per_launch": rdreq_b,
         "traffic_bytes_per_launch": 2.0 * fetch_b + write_b,
-        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc TCC_EA0_RDREQ_sum (three separate passes, KiB x 1024) of `python3 bench.py --steps %d --warmup %d "
+        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc TCC_EA0_RDREQ_sum (three separate passes, KiB x 1024) of `python3 bench.py --full --steps %d --warmup %d "
                   "--no-cpu-baseline --no-cli --no-gap50`, mean over the timed launches of lnr::k_seed_fused (two per step); FETCH_SIZE x 2 (gfx950: 128-byte requests tallied at 64 B, "
                   "MI355X_MICROARCH.md HBM section; the request counter x 128 B of the third pass gives %.3f of that), WRITE_SIZE exact" % (a.steps, a.warmup, rdreq_b / (2.0 * fetch_b)),
         "launches_seen": {"fetch": len(fe), "write": len(wr), "rdreq": len(rq)},

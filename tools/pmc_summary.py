@@ -1,15 +1,15 @@
 #!/usr/bin/env python3
 """Summarise the rocprofv3 PMC passes of bench.py into profiles/<round>/pmc_seed_fused.json.
 
-Usage (after the GPU runs below have been merged back into gpurun_out/):
-    tools/pmc_summary.py gpurun_out/final/pmc_fetch gpurun_out/final/pmc_write gpurun_out/final/calib profiles/r01 \
+Usage (after the GPU runs below, from the repository root):
+    tools/pmc_summary.py measure_out/final/pmc_fetch measure_out/final/pmc_write measure_out/final/calib profiles/r01 \
         --reads 100000 --read-len 10000 --err 0.1 --layout-threads 1 --steps 2 --warmup 1
 
 The passes are separate because FETCH_SIZE (3 TCC slots) and WRITE_SIZE (2) do not fit one pass
 (/opt/skills/guides/MI355X_MICROARCH.md, PMC slot table):
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/final/pmc_fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/final/pmc_write -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/final/calib     -- tools/calib_fetch
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d measure_out/final/pmc_fetch -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d measure_out/final/pmc_write -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d measure_out/final/calib     -- tools/calib_fetch
 
 Corrections, as that guide's HBM section prescribes: both counters are in KiB; WRITE_SIZE is exact; FETCH_SIZE reads
 half the bytes of a wide coalesced streaming load and is "uncalibrated" for other widths, so the factor for this
@@ -71,7 +71,7 @@ def main():
         "traffic_bytes_per_launch": fetch_factor * fetch_b + write_b,
         "calibration": calib,
         "stream16_factor_measured": stream_factor,
-        "source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, KiB x 1024) of `bench.py --steps %d --warmup %d --no-cpu-baseline`, "
+        "source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, KiB x 1024) of `bench.py --full --steps %d --warmup %d --no-cpu-baseline`, "
                   "mean over the timed launches of k_seed_fused; FETCH_SIZE x2 (gfx950 correction): tools/calib_fetch.hip counts %.1f B per independent 8-byte random read, "
                   "%.1f B per 4-byte one and %.2f of 16 B for the streaming read, all three saturating at the same counted rate (profiles/r01/calib_fetch_size.json), "
                   "i.e. every request is a 128-byte line tallied at 64 B"
