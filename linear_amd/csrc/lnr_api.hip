@@ -132,27 +132,21 @@ struct lnr_ctx {
     std::vector<u64> seq_len, seq_off, f2_off;
     u32 nbins = 0;
     size_t job_lds_bytes = 6 * 1024;    // LDS half of k_job's two-level arena (LNR_JOB_LDS_KB overrides, for tuning): 2.6 KB static + 6 KB x 16 workgroups fit a CU's 160 KB (measured: 5 KB +2 %, 7 KB +1 %)
-    size_t job_stage_bytes = 0;         // LDS stage of the blocked DP's predecessor window in the fused k_job (LNR_JOB_STAGE_KB; measured slower, off)
     u32 heavy_lds_kb = 48;              // LDS arena of k_job_heavy (LNR_HEAVY_LDS_KB)
     u32 mid_cap = 6144, mid_lds_kb = 24;   // reads with at least this many anchors run on 4 waves (k_job_mid: the DP is dealt over the waves); LNR_MID_CAP, LNR_MID_LDS_KB
     u32 heavy_cap = 0xffffffffu;        // reads with at least this many anchors (after the Y filter) take the 16-wave path (LNR_HEAVY_CAP overrides)
-    u32 dp_split_cap = 0xffffffffu, dp_split_cap_r1 = 0xffffffffu;   // reads with at least this many anchors take the split path pre -> 16-wave DP -> post (LNR_DP_SPLIT_CAP, LNR_DP_SPLIT_CAP_R1)
     u32 heavy_cap_r1 = 7000, mid_cap_r1 = 3000;   // the same cuts for the re-map round (LNR_HEAVY_CAP_R1, LNR_MID_CAP_R1)
-    bool lane_bulk_first = true;         // two lanes: which lane goes through the re-map round first (LNR_LANE_ORDER=heavy|bulk)
     u32 stop_after = 0;                  // diagnostic: LNR_STOP_AFTER (see JobArgs)
     u32 mid_waves = 0;                   // waves per read of the middle class (LNR_MID_WAVES=2|4; 0 = 2 in round 0 on a populated table, else 4)
     bool mid_cap_env = false;            // LNR_MID_CAP given: no density-dependent default
-    bool post_split = false;             // a11-a16 in k_post, one lane per read (LNR_POST_SPLIT=0: fused job kernels)
     int seed_bm = -1;                    // bucket bitmap in the seed kernel: -1 = by table density, 0 / 1 forced (LNR_SEED_BM)
     u32 prep_threads = 256;             // workgroup size of k_prep (LNR_PREP_THREADS: 64, 128 or 256)
     u32 prep_grid = 4096;               // workgroups of k_prep (LNR_PREP_GRID): they loop over the reads
     u32 bulk_delay_ticks = 10000;       // head start (100 MHz ticks) of the multi-wave kernels over the bulk kernel (LNR_BULK_DELAY_US)
-    u32 split_cap = 0xffffffffu;               // reads with at least this many anchors form the "heavy lane": their re-map round starts
-                                        // while the bulk of the batch is still in round 0 (LNR_SPLIT_CAP; 0xffffffff = one lane)
-    // Two lanes of streams: lane 0 = heavy reads, lane 1 = the bulk.  s_multi carries the multi-wave kernels (and the
-    // lane's seed / tail launches), s_bulk the single-wave kernel of the same launch.
-    hipStream_t s_multi[2] = {nullptr, nullptr}, s_bulk[2] = {nullptr, nullptr}, s_tail = nullptr;   // s_tail: early tail B of the reads that skip the re-map round
-    hipEvent_t ev_fork[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr}, ev_start = nullptr, ev_lane[2] = {nullptr, nullptr}, ev_prep = nullptr, ev_f1 = nullptr;
+    // Streams beside the main one (`stream`: seeds, tails, the 16-wave job kernel): s_spare carries the 4/2-wave job kernel when the 16-wave
+    // kernel is in the same launch, s_bulk the single-wave job kernel (and k_f1), s_tail the early tail B of the reads that skip the re-map round.
+    hipStream_t s_spare = nullptr, s_bulk = nullptr, s_tail = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join_spare = nullptr, ev_join_bulk = nullptr, ev_start = nullptr, ev_prep = nullptr, ev_f1 = nullptr;
     u32 cap_scale = 1;      // per-read capacities (cords, gaps) x this: raised for the re-run of a batch in which a read overflowed
     u32 cap_shrink = 1;     // diagnostic (LNR_CAP_SHRINK): capacities / this, to exercise that re-run
     u32 overflow_reruns = 0;
@@ -160,8 +154,6 @@ struct lnr_ctx {
     DevBuf hx_nkeys, hx_nvals; u32 hx_nnodes = 0; u64 hx_empty_dir = 0;   // HIndex (-i 2): dir = hdir[2^18] (head of the block of X, -1: none), hs = ysa, nodes of the large blocks
     DevBuf gap_arena, gap_flag, gap_next, d_seq_len, gap_prof, gap_first, gap_list, gap_rank, gap_weight;
     int gap_ext = 0;        // the read stream's state: 1 once a read of this context's stream went through mapExtend / mapExtends (lnr_gap_stream)   // the gap re-mapper (-g > 0): arenas of its workers, per-read retry flags, the two work counters
-    DevBuf bh;              // header words of the bucket lines as a dense table (k_ix_lines; LNR_SEED_BH=0 turns it off for A/B runs)
-    int use_bh = 0;        // (measured on the GRCh38 stand-in, same box, two runs each: 3.07 - 3.12 ms per launch with the table, 2.97 - 3.00 without: the early line fetch warms L2 / MALL for the DMA)
     DevBuf g, dir, hs, f2, d_seq_off, d_f2_off, bm, bl, ov;   // derived from dir / hs on every GPU: bm = bucket-non-empty bitmap, bl = bucket lines, ov = their aligned overflow lines (k_ix_lines)
     // ---- batch inputs / per-read arrays
     // host-buffer entry points: two input slots, so that the upload of the next batch (copy stream) runs under the kernels of
@@ -181,8 +173,9 @@ struct lnr_ctx {
     DevBuf cords, out_str, out_end, cords_off, cords_cap, ncords, nout, read_err;
     DevBuf gaps, gaps_off, gaps_cap, ngaps, remap, gdense, gcursor, gpos;
     PinBuf h_gaps, h_flags;             // pinned staging of the tail-A results
-    // ---- jobs: a JobSet is one seeded job list (device arrays + host mirrors); a Launch is the per-launch state of the
-    // job kernels (order, scratch); a TailBuf the per-launch state of a tail kernel.  Two of each: one per lane.
+    // ---- jobs: a JobSet is one seeded job list (device arrays + host mirrors), js[0] round 0 and js[1] the re-map round (each learns its
+    // own segment estimate and keeps its own capacities); a Launch is the per-launch state of the job kernels (order, scratch); a TailBuf
+    // the per-launch state of a tail kernel: tail A of the re-map round, the early and the late tail B.
     struct JobSet {
         DevBuf j_read, j_str, j_end, j_mode, j_cap, j_look, j_anc_off, j_nanc, grp_beg, anchors, seed_ctl;
         std::vector<u32> cap, look, nanc;
@@ -193,9 +186,9 @@ struct lnr_ctx {
         PinBuf h_rb;
     } js[2];
     // (host vectors that feed asynchronous uploads live here, not on the stack: the launch functions return before the copy ran)
-    struct Launch { DevBuf grp_order, j_scr_off, job_scr, jstate; std::vector<u32> h_order; std::vector<u64> h_scr_off; } ln[2];
-    struct TailBuf { DevBuf off, cap, scr, list; std::vector<u64> h_off; std::vector<u32> h_cap, h_list; } tb[3];
-    PinBuf h_rb[4];                     // pinned landing zones of the small readbacks (per stream that reads back)
+    struct Launch { DevBuf grp_order, j_scr_off, job_scr; std::vector<u32> h_order; std::vector<u64> h_scr_off; } ln;
+    struct TailBuf { DevBuf off, cap, scr, list; std::vector<u64> h_off; std::vector<u32> h_cap, h_list; } tb_remap, tb_early, tb_late;
+    PinBuf h_rb[3];                     // pinned landing zones of the small readbacks: [0] batch offsets, [1] tails on the main stream, [2] on s_tail
     DevBuf prof, tl; u32 tl_round = 0, tl_n[4] = {0, 0, 0, 0}; u32 tl_nh[4] = {0, 0, 0, 0};
     // ---- results
     DevBuf r_off, r_str, r_end;
@@ -204,16 +197,14 @@ struct lnr_ctx {
     PinBuf h_cords_str2[2], h_cords_end2[2], h_up[2];   // results land in pinned memory (DMA at link rate, no page faults), two result slots taken in turn: the
     std::vector<u64> h_cord_off2[2]; int res_slot = 0;    // arrays handed out stay valid until the SECOND next result (a writer thread formats batch k while k + 1 runs); h_up: upload staging ring
     hipEvent_t ev_up[2] = {nullptr, nullptr};
-    std::vector<u32> dbg_r0w;   // round-0 anchors per read (LNR_DEBUG_R1 diagnostic)
     u32 last_n = 0;
     u64 last_ncords = 0;
     lnr_stats stats{};
     Timer t_prep, t_job, t_tail, t_total, t_gap;
-    int gap_mode = 1, gap_team = 1; u32 gap_waves = 16384, gap_arena2_mb = 64;   // LNR_GAP_TEAM=0: one wave per flagged read, no helper waves   // LNR_GAP_MODE=1: the first launch of k_gap runs one wave per read as well (LNR_GAP_WAVES of them)
-    int gap_fused = 1; u32 gap_teams = 96, ncu = 0;   // the fused first stage (k_gap_all): LNR_GAP_FUSED=0 falls back to the three launches; LNR_GAP_TEAMS = team workgroups
+    u32 gap_arena2_mb = 64;    // arena of a team of the first stage of the gap re-mapper (LNR_GAP_ARENA2_MB)
+    u32 gap_teams = 96, ncu = 0;   // team workgroups of the first stage (k_gap_all; LNR_GAP_TEAMS)
     u32 gap_heavy_w = 60000;   // weight (k_gap_weight) from which a read is expected to need a team (LNR_GAP_HEAVY_W)
-    u32 gap_cap_ms = 0;    // first launch of the gap re-mapper: milliseconds after which a read is handed to the team launch (LNR_GAP_CAP_MS, 0 = never)
-    u64 gap_work_cap = 3000000;   // pair evaluations of the chain DPs one lane spends on a read before the read goes to the wave-per-read launch (LNR_GAP_WORK_CAP)
+    u64 gap_work_cap = 3000000;   // pair evaluations of the chain DPs a worker of the first stage spends on a read before it gives the read up to a team / the last launch (LNR_GAP_WORK_CAP)
 };
 
 namespace {
@@ -284,9 +275,8 @@ lnr_status build_seed_view(lnr_ctx *ctx) {
     if (nov < 0) { ctx->err = "overflow lines of the bucket view exceed 2^31"; return LNR_ERR_LIMIT; }
     ENSURE(ctx->ov, ((u64)nov + 1) * 128);
     ENSURE(ctx->bl, nb * 128);
-    if (ctx->use_bh) ENSURE(ctx->bh, nb * 8 + 16);
     hipLaunchKernelGGL(k_ix_lines, dim3((u32)((nb * 8 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dir.as<i32>(), ctx->hs.as<u64>(), ovoff.as<i32>(), nb, ctx->bl.as<ulonglong2>(),
-                       ctx->ov.as<u64>(), ctx->use_bh ? ctx->bh.as<u64>() : (u64 *)nullptr);
+                       ctx->ov.as<u64>());
     KCHECK();
     HIPCK(hipStreamSynchronize(ctx->stream));                 // ovoff / tmp go out of scope
     return LNR_OK;
@@ -534,11 +524,11 @@ lnr_status upload_on(lnr_ctx *ctx, DevBuf &b, const std::vector<T> &v, hipStream
 // the host reads the seed counts back and prepares the launch order (the GPU would idle there), not beside the seed kernel.
 lnr_status launch_f1(lnr_ctx *ctx, u32 n) {
     HIPCK(hipEventRecord(ctx->ev_prep, ctx->stream));
-    HIPCK(hipStreamWaitEvent(ctx->s_bulk[1], ctx->ev_prep, 0));
-    hipLaunchKernelGGL(k_f1, dim3(n), dim3(256), 0, ctx->s_bulk[1], ctx->pk.as<u64>(), ctx->nm.as<u32>(), ctx->pk_off.as<u64>(), ctx->rlen.as<u32>(), ctx->nf.as<u32>(), ctx->f1_off.as<u64>(), n,
+    HIPCK(hipStreamWaitEvent(ctx->s_bulk, ctx->ev_prep, 0));
+    hipLaunchKernelGGL(k_f1, dim3(n), dim3(256), 0, ctx->s_bulk, ctx->pk.as<u64>(), ctx->nm.as<u32>(), ctx->pk_off.as<u64>(), ctx->rlen.as<u32>(), ctx->nf.as<u32>(), ctx->f1_off.as<u64>(), n,
                        ctx->f1.as<F96>());
     KCHECK();
-    HIPCK(hipEventRecord(ctx->ev_f1, ctx->s_bulk[1]));
+    HIPCK(hipEventRecord(ctx->ev_f1, ctx->s_bulk));
     return LNR_OK;
 }
 
@@ -585,8 +575,7 @@ lnr_status seed_jobs(lnr_ctx *ctx, JobSet &S, const HostJobs &hj, hipStream_t st
             hipLaunchKernelGGL(k_seed_hindex, dim3(nj), dim3(64), 0, st, J, R, ctx->hs.as<u64>(), ctx->info.hs_len, ctx->hx_empty_dir, ctx->dir.as<i32>(), ctx->hx_nkeys.as<u64>(), ctx->hx_nvals.as<u32>(), ctx->hx_nnodes, nj, O,
                                S.est_x16);
         else
-        hipLaunchKernelGGL(k_seed_fused, dim3(nj), dim3(64), ctx->seed_lds_pad, st, J, R, ctx->bl.as<ulonglong2>(), use_bm ? ctx->bm.as<u32>() : (const u32 *)nullptr, ctx->ov.as<u64>(), nj, O, S.est_x16,
-                           ctx->use_bh ? ctx->bh.as<u64>() : (const u64 *)nullptr);
+        hipLaunchKernelGGL(k_seed_fused, dim3(nj), dim3(64), ctx->seed_lds_pad, st, J, R, ctx->bl.as<ulonglong2>(), use_bm ? ctx->bm.as<u32>() : (const u32 *)nullptr, ctx->ov.as<u64>(), nj, O, S.est_x16);
         KCHECK();
         S.t_seed.stop(st);
         if (f1_reads && attempt == 0) { lnr_status fs = launch_f1(ctx, f1_reads); if (fs != LNR_OK) return fs; }   // (beside the seed kernel instead: measured no faster)
@@ -635,24 +624,24 @@ lnr_status export_anchors(lnr_ctx *ctx, JobSet &S, u32 nj) {
     return LNR_OK;
 }
 
-// Per-read job kernels for the groups `groups` of the seeded job set S (hj = its host list).  Heaviest group first (anchors
-// that passed the Y filter are the work proxy), so the long tail of repeat-rich reads starts at once.  The multi-wave
-// kernels go to lane's s_multi and are launched first: a multi-wave workgroup only finds a CU with enough free wave slots
-// while the single-wave kernel has not flooded the chip (it refills every slot a finished wave frees -- a late heavy
-// launch was measured to start only when the bulk kernel drained, 47 ms late).  The bulk kernel follows on s_bulk.  On
-// return everything is enqueued and s_multi also waits for s_bulk; nothing is synchronised unless the scratch budget
-// forces several slices.
-lnr_status launch_jobs(lnr_ctx *ctx, JobSet &S, Launch &Lx, const HostJobs &hj, const std::vector<u32> &groups, int lane) {
-    u32 ngrp = (u32)groups.size();
+// Per-read job kernels for all groups of the seeded job set S (hj = its host list).  Heaviest group first (anchors that
+// passed the Y filter are the work proxy), so the long tail of repeat-rich reads starts at once.  The multi-wave kernels
+// are launched first: a multi-wave workgroup only finds a CU with enough free wave slots while the single-wave kernel has
+// not flooded the chip (it refills every slot a finished wave frees -- a late heavy launch was measured to start only
+// when the bulk kernel drained, 47 ms late).  The bulk kernel follows on s_bulk.  On return everything is enqueued and
+// the main stream waits for the side streams; nothing is synchronised unless the scratch budget forces several slices.
+lnr_status launch_jobs(lnr_ctx *ctx, JobSet &S, const HostJobs &hj) {
+    u32 ngrp = (u32)hj.grp_beg.size() - 1;
     if (ngrp == 0) return LNR_OK;
     Laps laps;
     u32 nj = hj.size();
-    hipStream_t sm = ctx->s_multi[lane], sb = ctx->s_bulk[lane];
+    Launch &Lx = ctx->ln;
+    hipStream_t sm = ctx->stream, sb = ctx->s_bulk;
     u64 budget = ctx->opts.scratch_budget ? ctx->opts.scratch_budget : (64ULL << 30);
     const std::vector<u32> &nanc = S.nanc;
     std::vector<u64> w(ngrp, 0);
-    for (u32 k = 0; k < ngrp; k++) for (u32 j = hj.grp_beg[groups[k]]; j < hj.grp_beg[groups[k] + 1]; j++) w[k] += nanc[j];
-    std::vector<u32> order(ngrp);   // indices into `groups`, heaviest first
+    for (u32 k = 0; k < ngrp; k++) for (u32 j = hj.grp_beg[k]; j < hj.grp_beg[k + 1]; j++) w[k] += nanc[j];
+    std::vector<u32> order(ngrp);   // groups, heaviest first
     {
         // counting sort by weight class (1/8-octave steps: "descending up to 9 %" is all the scheduler needs) in O(n),
         // then the small multi-wave prefix in exact order (the size-class cut below walks it)
@@ -667,21 +656,18 @@ lnr_status launch_jobs(lnr_ctx *ctx, JobSet &S, Launch &Lx, const HostJobs &hj, 
         for (u32 c = 0; c < NCLS; c++) cnt[c + 1] += cnt[c];
         for (u32 k = 0; k < ngrp; k++) order[cnt[gc[k]]++] = k;
         u32 nh = 0;
-        while (nh < ngrp && w[order[nh]] >= std::min<u64>(std::min(std::min(ctx->heavy_cap, ctx->mid_cap), std::min(ctx->heavy_cap_r1, ctx->mid_cap_r1)), std::min(ctx->dp_split_cap, ctx->dp_split_cap_r1)) / 2) nh++;
+        while (nh < ngrp && w[order[nh]] >= std::min(std::min(ctx->heavy_cap, ctx->mid_cap), std::min(ctx->heavy_cap_r1, ctx->mid_cap_r1)) / 2) nh++;
         // (exact order only for a short prefix: at human scale every read carries > 1500 mostly random anchors, the prefix was
         // 60 % of the batch and its sort 2.3 ms of host time per step with the GPU idle; without it the class cuts are exact
         // to the 1/8 octave, which only moves a few reads between kernels)
         if (nh <= 4096) std::stable_sort(order.begin(), order.begin() + nh, [&w](u32 a, u32 b) { return w[a] > w[b]; });
     }
-    std::vector<u32> &dev_order = Lx.h_order;
-    dev_order.resize(ngrp);
-    for (u32 k = 0; k < ngrp; k++) dev_order[k] = groups[order[k]];
+    Lx.h_order = order;
     laps.lap("order");
     lnr_status s;
-    if ((s = upload_on(ctx, Lx.grp_order, dev_order, sm)) != LNR_OK) return s;
+    if ((s = upload_on(ctx, Lx.grp_order, Lx.h_order, sm)) != LNR_OK) return s;
     laps.lap("upload-order");
     ENSURE(Lx.j_scr_off, (size_t)nj * 8);
-    ENSURE(Lx.jstate, (size_t)nj * 8 + 16);
     std::vector<u64> &scr_off = Lx.h_scr_off;
     scr_off.assign(nj, 0);
     auto grp_scr = [&](u32 g) { u64 b = 0; for (u32 j = hj.grp_beg[g]; j < hj.grp_beg[g + 1]; j++) b += align_up(job_scratch_bytes((u64)nanc[j] + 2), 256); return b; };
@@ -690,13 +676,13 @@ lnr_status launch_jobs(lnr_ctx *ctx, JobSet &S, Launch &Lx, const HostJobs &hj, 
         u64 scr = 0;
         u32 g1 = g0;
         while (g1 < ngrp) {
-            u64 s2 = scr + grp_scr(dev_order[g1]);
+            u64 s2 = scr + grp_scr(order[g1]);
             if (g1 > g0 && s2 > budget) break;
             scr = s2; g1++;
         }
         u64 so = 0;
         for (u32 k = g0; k < g1; k++)
-            for (u32 j = hj.grp_beg[dev_order[k]]; j < hj.grp_beg[dev_order[k] + 1]; j++) { scr_off[j] = so; so += align_up(job_scratch_bytes((u64)nanc[j] + 2), 256); }
+            for (u32 j = hj.grp_beg[order[k]]; j < hj.grp_beg[order[k] + 1]; j++) { scr_off[j] = so; so += align_up(job_scratch_bytes((u64)nanc[j] + 2), 256); }
         laps.lap("scr-layout");
         ENSURE(Lx.job_scr, std::max<u64>(so, 16));
         laps.lap("ensure-scr");
@@ -716,16 +702,12 @@ lnr_status launch_jobs(lnr_ctx *ctx, JobSet &S, Launch &Lx, const HostJobs &hj, 
         A.cords = ctx->cords.as<u64>(); A.cords_off = ctx->cords_off.as<u64>(); A.cords_cap = ctx->cords_cap.as<u32>(); A.ncords = ctx->ncords.as<u32>();
         A.read_err = ctx->read_err.as<i32>();
         A.nbins = ctx->nbins; A.grp_lo = g0; A.grp_hi = g1;
-        A.prof = nullptr; A.tl = nullptr; A.jstate = Lx.jstate.as<u32>(); A.stop_after = ctx->stop_after;
-        const bool split = ctx->post_split && ctx->stop_after == 0;
-        if (split) HIPCK(hipMemsetAsync(Lx.jstate.p, 0, (size_t)nj * 8, sm));   // a job the job kernel never reached reads as "not handed over"
+        A.prof = nullptr; A.tl = nullptr; A.stop_after = ctx->stop_after;
         // dynamic LDS = the job arena; the binning histogram borrows it first and sweeps the bin range in passes of that many
         // bins, so the LDS per workgroup (hence the residency of the bulk kernel) does not depend on the reference's length
-        const size_t lds_min = 4096;                 // the split path's pre / post kernels keep every array in global scratch
-        size_t arena = (ctx->job_lds_bytes + 15) & ~(size_t)15;
-        size_t lds = arena + ctx->job_stage_bytes;
+        size_t lds = (ctx->job_lds_bytes + 15) & ~(size_t)15;
         A.lds_bytes = (u32)lds;
-        A.arena_lds = (u32)arena;
+        A.arena_lds = (u32)lds;
         // size classes along the (weight-descending) slice: heavy = 16 waves per read, mid = 4 waves, rest = 1 wave
         // (the re-map round leaves most of the chip idle, so it can afford wider workgroups for more of its reads)
         bool remap_round_ = nj && hj.mode[0] != 0;
@@ -733,12 +715,9 @@ lnr_status launch_jobs(lnr_ctx *ctx, JobSet &S, Launch &Lx, const HostJobs &hj, 
         // a populated table (human scale) adds ~1 500 chance anchors to every read's weight, and the 4-wave kernel holds 14 of a CU's 16
         // wave slots while it runs: fewer reads go there (measured on the GRCh38 stand-in: 6144 -> 40.0 ms, 9000 -> 38.6, 12000 -> 38.5, 20000 -> 45)
         if (!remap_round_ && !ctx->mid_cap_env && ctx->info.hs_len >= (1ULL << 25)) mcap = 9000;
-        u64 scap = remap_round_ ? ctx->dp_split_cap_r1 : ctx->dp_split_cap;
-        u32 gh = g0;
+        u32 gh = g0;                                    // [g0, gh): 16 waves per read
         while (gh < g1 && w[order[gh]] >= hcap) gh++;
-        u32 gs = gh;                                    // [gh, gs): split path (pre -> 16-wave DP -> post)
-        while (gs < g1 && w[order[gs]] >= scap) gs++;
-        u32 gm = gs;                                    // [gs, gm): 4 waves per read
+        u32 gm = gh;                                    // [gh, gm): 4 (or 2) waves per read
         while (gm < g1 && w[order[gm]] >= mcap) gm++;
 #ifdef LNR_PROF
         if (!ctx->prof.p) { if (!ctx->prof.ensure(192 * 8)) return LNR_ERR_NOMEM; (void)hipMemsetAsync(ctx->prof.p, 0, 192 * 8, sm); }
@@ -748,77 +727,46 @@ lnr_status launch_jobs(lnr_ctx *ctx, JobSet &S, Launch &Lx, const HostJobs &hj, 
         if (ctx->tl_round < 4 && g1 <= (1u << 20)) { A.tl = ctx->tl.as<unsigned long long>() + (size_t)ctx->tl_round * (1u << 20) * 4; ctx->tl_n[ctx->tl_round] = g1; ctx->tl_nh[ctx->tl_round] = gm; }
         ctx->tl_round++;
 #endif
-        // streams: the 16-wave kernel gets the spare stream when the batch runs as one lane (kernels on one stream would
-        // run back to back), the 4-wave kernel the lane's main stream, the single-wave kernel the lane's bulk stream
-        // streams: kernels on one stream run back to back.  The 16-wave kernel stays on the lane's main stream (no event wait,
-        // it reaches the GPU first); the split-path chain and the 4-wave kernel take the spare stream when the 16-wave class
-        // is present and the batch runs as one lane, else the main stream; the single-wave kernel goes to the lane's bulk stream.
-        bool wide2 = gm > gh;                                   // split and / or 4-wave class present
-        bool one_lane = ctx->split_cap == 0xffffffffu;
-        // stream of the split / 4-wave class when the 16-wave class is present too: the spare stream when the batch runs as
-        // one lane; with two lanes the other lane owns that stream, so the class queues behind this lane's (short) bulk kernel
-        hipStream_t s4 = (gh > g0 && wide2) ? ((lane == 1 && one_lane) ? ctx->s_multi[0] : sb) : sm;
-        bool after_bulk = s4 == sb && sb != sm;
-        bool fork_m = wide2 && s4 != sm, fork_b = g1 > gm && sb != sm && gm > g0;
-        if (fork_m || fork_b) HIPCK(hipEventRecord(ctx->ev_fork[lane], sm));    // before any launch: nobody waits for another kernel
+        // streams: kernels on one stream run back to back.  The 16-wave kernel stays on the main stream (no event wait, it reaches
+        // the GPU first); the 4/2-wave kernel takes the spare stream when the 16-wave class is present, else the main stream; the
+        // single-wave kernel goes to the bulk stream when a multi-wave class is present, else the main stream.
+        hipStream_t smid = gh > g0 ? ctx->s_spare : sm;
+        bool fork_m = gm > gh && gh > g0, fork_b = g1 > gm && gm > g0;
+        if (fork_m || fork_b) HIPCK(hipEventRecord(ctx->ev_fork, sm));    // before any launch: nobody waits for another kernel
         if (gh > g0) {
             JobArgs H = A;
             size_t hl = (size_t)ctx->heavy_lds_kb * 1024;
             H.grp_lo = g0; H.grp_hi = gh; H.lds_bytes = (u32)hl; H.arena_lds = (u32)hl;
-            if (split) {
-                hipLaunchKernelGGL(k_job_heavy_a, dim3(gh - g0), dim3(1024), hl, sm, H);
-                KCHECK();
-                hipLaunchKernelGGL(k_post, dim3((gh - g0 + 63) / 64), dim3(64), 0, sm, H);
-            } else hipLaunchKernelGGL(k_job_heavy, dim3(gh - g0), dim3(1024), hl, sm, H);
+            hipLaunchKernelGGL(k_job_heavy, dim3(gh - g0), dim3(1024), hl, sm, H);
             KCHECK();
         }
-        auto launch_bulk = [&]() -> lnr_status {
-            if (g1 <= gm) return LNR_OK;
-            hipStream_t bulk = fork_b ? sb : sm;
-            if (fork_b) HIPCK(hipStreamWaitEvent(sb, ctx->ev_fork[lane], 0));
-            if (gm > g0 && bulk != sm && !after_bulk) { hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, bulk, ctx->bulk_delay_ticks); KCHECK(); }
-            JobArgs K = A;
-            K.grp_lo = gm; K.grp_hi = g1;
-            if (split) {
-                hipLaunchKernelGGL(k_job_a, dim3(g1 - gm), dim3(64), lds, bulk, K);
-                KCHECK();
-                hipLaunchKernelGGL(k_post, dim3((g1 - gm + 63) / 64), dim3(64), 0, bulk, K);
-            } else hipLaunchKernelGGL(k_job, dim3(g1 - gm), dim3(64), lds, bulk, K);
-            KCHECK();
-            return LNR_OK;
-        };
-        if (after_bulk && (s = launch_bulk()) != LNR_OK) return s;
-        if (fork_m && !after_bulk) HIPCK(hipStreamWaitEvent(s4, ctx->ev_fork[lane], 0));
-        if (fork_m && after_bulk && !(g1 > gm)) HIPCK(hipStreamWaitEvent(s4, ctx->ev_fork[lane], 0));
-        if (gs > gh) {
-            JobArgs P = A;
-            P.grp_lo = gh; P.grp_hi = gs; P.lds_bytes = (u32)lds_min; P.arena_lds = 0;   // global scratch only: pointers must replay
-            hipLaunchKernelGGL(k_job_pre, dim3(gs - gh), dim3(64), lds_min, s4, P);
-            KCHECK();
-            hipLaunchKernelGGL(k_job_dp, dim3(gs - gh), dim3(64 * DP_SPLIT_WAVES), 0, s4, P);
-            KCHECK();
-            hipLaunchKernelGGL(k_job_post, dim3(gs - gh), dim3(64), lds_min, s4, P);
-            KCHECK();
-        }
-        if (gm > gs) {
+        if (gm > gh) {
+            if (fork_m) HIPCK(hipStreamWaitEvent(smid, ctx->ev_fork, 0));
             JobArgs M = A;
             size_t ml = (size_t)ctx->mid_lds_kb * 1024;
-            M.grp_lo = gs; M.grp_hi = gm; M.lds_bytes = (u32)ml; M.arena_lds = (u32)ml;
-            if (split) {
-                hipLaunchKernelGGL(k_job_mid_a, dim3(gm - gs), dim3(256), ml, s4, M);
-                KCHECK();
-                hipLaunchKernelGGL(k_post, dim3((gm - gs + 63) / 64), dim3(64), 0, s4, M);
-            } else if (ctx->mid_waves == 2 || (ctx->mid_waves == 0 && !remap_round_ && ctx->info.hs_len >= (1ULL << 25)))
+            M.grp_lo = gh; M.grp_hi = gm; M.lds_bytes = (u32)ml; M.arena_lds = (u32)ml;
+            if (ctx->mid_waves == 2 || (ctx->mid_waves == 0 && !remap_round_ && ctx->info.hs_len >= (1ULL << 25)))
                 // round 0 at human scale is bound by wave slots (16 per CU at 128 VGPRs): two waves per read of this class hold half the slots of
                 // four for a little longer (GRCh38 stand-in: 45.2 vs 47.0 ms per step)
-                hipLaunchKernelGGL(k_job_mid2, dim3(gm - gs), dim3(128), ml, s4, M);
-            else hipLaunchKernelGGL(k_job_mid, dim3(gm - gs), dim3(256), ml, s4, M);
+                hipLaunchKernelGGL(k_job_mid2, dim3(gm - gh), dim3(128), ml, smid, M);
+            else hipLaunchKernelGGL(k_job_mid, dim3(gm - gh), dim3(256), ml, smid, M);
+            KCHECK();
+            if (fork_m) HIPCK(hipEventRecord(ctx->ev_join_spare, smid));
+        }
+        if (g1 > gm) {
+            hipStream_t bulk = fork_b ? sb : sm;
+            if (fork_b) {
+                HIPCK(hipStreamWaitEvent(sb, ctx->ev_fork, 0));
+                hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, sb, ctx->bulk_delay_ticks);
+                KCHECK();
+            }
+            JobArgs K = A;
+            K.grp_lo = gm; K.grp_hi = g1;
+            hipLaunchKernelGGL(k_job, dim3(g1 - gm), dim3(64), lds, bulk, K);
             KCHECK();
         }
-        if (fork_m && !after_bulk) HIPCK(hipEventRecord(ctx->ev_join[0], s4));
-        if (!after_bulk && (s = launch_bulk()) != LNR_OK) return s;
-        if (fork_b || (after_bulk && fork_m)) { HIPCK(hipEventRecord(ctx->ev_join[lane], sb)); HIPCK(hipStreamWaitEvent(sm, ctx->ev_join[lane], 0)); }
-        if (fork_m && !after_bulk) HIPCK(hipStreamWaitEvent(sm, ctx->ev_join[0], 0));
+        if (fork_b) { HIPCK(hipEventRecord(ctx->ev_join_bulk, sb)); HIPCK(hipStreamWaitEvent(sm, ctx->ev_join_bulk, 0)); }
+        if (fork_m) HIPCK(hipStreamWaitEvent(sm, ctx->ev_join_spare, 0));
         laps.lap("launches");
         ctx->stats.job_launches++;
         g0 = g1;
@@ -899,10 +847,10 @@ lnr_status tail_prepare(lnr_ctx *ctx, const BatchHost &B, TailBuf &tb, const std
     std::vector<u32> ncords(n);
     {
         Readback rb;
-        PinBuf &pb = ctx->h_rb[st == ctx->s_tail ? 2 : (st == ctx->stream ? 1 : 3)];
+        PinBuf &pb = ctx->h_rb[st == ctx->s_tail ? 2 : 1];
         if (!rb.begin(pb, (size_t)n * 4)) { ctx->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
         HIPCK(rb.add(ncords.data(), ctx->ncords.p, (size_t)n * 4, st));
-        HIPCK(hipStreamSynchronize(st));   // (counts of reads another lane is still working on are not used)
+        HIPCK(hipStreamSynchronize(st));   // (on s_tail: counts of the reads the re-map round is still working on are not used)
         rb.finish();
     }
     tb.h_off.assign(n, 0); tb.h_cap.assign(n, 0);
@@ -938,16 +886,16 @@ void finish_stats(lnr_ctx *ctx, const BatchHost &B) {
     ctx->stats.seed_bytes = rb + ctx->stats.lookups * 8 + ctx->stats.bucket_entries * 8 + ctx->stats.anchors * 8;
 }
 
-// Tail A + re-map round of the reads in `list` (whose round 0 has completed on the lane's s_multi): clean / gather /
-// gaps decide the remap loop (pmpfinder.cpp:2744-2749); every gap of a poorly covered read is then re-seeded with
-// step 7 / score0 (pmpfinder.cpp:2749-2767).  Uses job set S and launch state Lx; returns with the launches enqueued.
-lnr_status remap_round(lnr_ctx *ctx, const BatchHost &B, const std::vector<u32> &list, int lane, JobSet &S, Launch &Lx, TailBuf &tb, HostJobs &j1) {
-    if (list.empty()) return LNR_OK;
-    hipStream_t st = ctx->s_multi[lane];
+// Tail A + re-map round of every read (round 0 has completed on the main stream): clean / gather / gaps decide the remap
+// loop (pmpfinder.cpp:2744-2749); every gap of a poorly covered read is then re-seeded with step 7 / score0
+// (pmpfinder.cpp:2749-2767) into job set 1 (j1).  Returns with the launches enqueued.
+lnr_status remap_round(lnr_ctx *ctx, const BatchHost &B, HostJobs &j1) {
+    hipStream_t st = ctx->stream;
+    JobSet &S = ctx->js[1];
     u32 n = B.n;
     TailArgs T;
     lnr_status s;
-    if ((s = tail_prepare(ctx, B, tb, &list, st, T)) != LNR_OK) return s;
+    if ((s = tail_prepare(ctx, B, ctx->tb_remap, nullptr, st, T)) != LNR_OK) return s;
     Laps laps;
     laps.lap("tail_prepare");
     HIPCK(hipMemsetAsync(ctx->gcursor.p, 0, 4, st));
@@ -972,7 +920,7 @@ lnr_status remap_round(lnr_ctx *ctx, const BatchHost &B, const std::vector<u32> 
     UP *gaps = ctx->h_gaps.as<UP>();
     HIPCK(words_out(gaps, ctx->gdense.p, gtot * sizeof(UP) / 4));
     HIPCK(hipStreamSynchronize(st));
-    for (u32 i : list) {
+    for (u32 i = 0; i < n; i++) {
         if (!(remap[i] && ngaps[i])) continue;
         ctx->stats.remap_reads++;
         j1.grp_beg.push_back(j1.size());
@@ -985,21 +933,7 @@ lnr_status remap_round(lnr_ctx *ctx, const BatchHost &B, const std::vector<u32> 
     laps.lap("gaps-copy+build");
     if ((s = seed_jobs(ctx, S, j1, st)) != LNR_OK) return s;
     laps.lap("seed1(sync)");
-    if (getenv("LNR_DEBUG_R1") && !ctx->dbg_r0w.empty()) {   // diagnostic: round-0 anchors of the reads that own the heavy re-map groups
-        std::vector<std::pair<u64, u64> > v;
-        for (u32 g = 0; g + 1 < j1.grp_beg.size(); g++) {
-            u64 w = 0;
-            for (u32 j = j1.grp_beg[g]; j < j1.grp_beg[g + 1]; j++) w += S.nanc[j];
-            if (w >= 2048) v.push_back(std::make_pair(w, (u64)ctx->dbg_r0w[j1.read[j1.grp_beg[g]]]));
-        }
-        std::sort(v.begin(), v.end());
-        fprintf(stderr, "[lnr] lane %d: %zu re-map groups with >= 2048 anchors; (r1 anchors, r0 anchors of the read):", lane, v.size());
-        for (size_t k = 0; k < v.size(); k += std::max<size_t>(1, v.size() / 40)) fprintf(stderr, " (%llu,%llu)", (unsigned long long)v[k].first, (unsigned long long)v[k].second);
-        fprintf(stderr, "\n");
-    }
-    std::vector<u32> all((size_t)j1.grp_beg.size() - 1);
-    for (u32 g = 0; g < all.size(); g++) all[g] = g;
-    s = launch_jobs(ctx, S, Lx, j1, all, lane);
+    s = launch_jobs(ctx, S, j1);
     laps.lap("launch1");
     laps.done();
     return s;
@@ -1030,80 +964,46 @@ lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, 
         if (B.len[i] > 200) { j0.grp_beg.push_back(j0.size()); j0.add(i, 0, B.len[i], 0); }
     }
     j0.grp_beg.push_back(j0.size());
-    JobSet &S0 = ctx->js[0], &S1 = ctx->js[1];
-    if ((s = seed_jobs(ctx, S0, j0, ctx->stream, n)) != LNR_OK) return s;
+    if ((s = seed_jobs(ctx, ctx->js[0], j0, ctx->stream, n)) != LNR_OK) return s;
     laps.lap("seed0(sync)");
-    // Two lanes.  Lane 0 = the reads with many anchors (they hold the long chaining jobs of both rounds), lane 1 = the bulk.
-    // The reference maps read by read, so any interleaving of reads is the same computation; here lane 0 goes through
-    // round 0 -> tail A -> re-map round while lane 1 is still in round 0, instead of a batch-wide barrier per round.
-    u32 ngrp0 = (u32)j0.grp_beg.size() - 1;
-    std::vector<u32> grp[2], reads[2];
-    std::vector<char> in_heavy(n, 0);
-    const bool dbg_r1 = getenv("LNR_DEBUG_R1") != nullptr;
-    if (dbg_r1) ctx->dbg_r0w.assign(n, 0);
-    for (u32 g = 0; g < ngrp0; g++) {
-        u64 w = 0;
-        for (u32 j = j0.grp_beg[g]; j < j0.grp_beg[g + 1]; j++) w += S0.nanc[j];
-        int lane = w >= ctx->split_cap ? 0 : 1;
-        if (dbg_r1) ctx->dbg_r0w[j0.read[j0.grp_beg[g]]] = (u32)w;
-        grp[lane].push_back(g);
-        if (lane == 0) in_heavy[j0.read[j0.grp_beg[g]]] = 1;
-    }
-    for (u32 i = 0; i < n; i++) reads[in_heavy[i] ? 0 : 1].push_back(i);   // reads without a job go with the bulk
-    laps.lap("partition");
     HIPCK(hipStreamWaitEvent(ctx->stream, ctx->ev_f1, 0));   // read features ready (k_f1 ran beside the seed kernel)
     ctx->t_job.start(ctx->stream);
     HIPCK(hipEventRecord(ctx->ev_start, ctx->stream));
-    HIPCK(hipStreamWaitEvent(ctx->s_multi[0], ctx->ev_start, 0));
-    HIPCK(hipStreamWaitEvent(ctx->s_bulk[1], ctx->ev_start, 0));
+    HIPCK(hipStreamWaitEvent(ctx->s_spare, ctx->ev_start, 0));
+    HIPCK(hipStreamWaitEvent(ctx->s_bulk, ctx->ev_start, 0));
     laps.lap("events");
-    if ((s = launch_jobs(ctx, S0, ctx->ln[0], j0, grp[0], 0)) != LNR_OK) return s;
-    if ((s = launch_jobs(ctx, S0, ctx->ln[1], j0, grp[1], 1)) != LNR_OK) return s;
+    if ((s = launch_jobs(ctx, ctx->js[0], j0)) != LNR_OK) return s;
     laps.lap("launch0");
-    // Whichever lane finishes round 0 first goes through tail A and the re-map round while the other is still in round 0
-    // (job set 1: the other lane still reads job set 0); the second lane follows, by then nobody reads job set 0 any more.
-    // With LNR_SPLIT_CAP at a few thousand anchors lane 0 holds the long single-wave and the 4-wave jobs -- the tail of
-    // round 0 -- and the bulk lane is through first (LNR_LANE_ORDER=bulk, the default); the heavy-first order is kept for
-    // large split values where lane 0 is a handful of reads.
-    HostJobs j1h, j1b;
-    bool bulk_first = ctx->lane_bulk_first;
-    int first = bulk_first ? 1 : 0, second = 1 - first;
-    if (bulk_first) HIPCK(hipStreamSynchronize(ctx->s_multi[1]));
-    if ((s = remap_round(ctx, B, reads[first], first, S1, ctx->ln[first], ctx->tb[first], first ? j1b : j1h)) != LNR_OK) return s;
-    laps.lap("lane-a");
+    HIPCK(hipStreamSynchronize(ctx->stream));
+    HostJobs j1;
+    if ((s = remap_round(ctx, B, j1)) != LNR_OK) return s;
+    laps.lap("tailA+seed1+launch1");
     // Tail B (block chaining on both strands, flags, cords_end; pmpfinder.cpp:2764-2801) of the reads that do not go through
     // the re-map round is final after tail A: it runs on its own stream while the re-map jobs (a few long reads) are busy.
     std::vector<u32> late_list, early_list;
-    bool early = ctx->split_cap == 0xffffffffu && j1b.size() > 0;
+    bool early = j1.size() > 0;
     if (early) {
         std::vector<char> in_r1(n, 0);
-        for (u32 q = 0; q < j1b.size(); q++) in_r1[j1b.read[q]] = 1;
+        for (u32 q = 0; q < j1.size(); q++) in_r1[j1.read[q]] = 1;
         for (u32 i = 0; i < n; i++) (in_r1[i] ? late_list : early_list).push_back(i);
         TailArgs TE;
-        if ((s = tail_prepare(ctx, B, ctx->tb[2], &early_list, ctx->s_tail, TE)) != LNR_OK) return s;
+        if ((s = tail_prepare(ctx, B, ctx->tb_early, &early_list, ctx->s_tail, TE)) != LNR_OK) return s;
         if (TE.n) { hipLaunchKernelGGL(k_tail_b, dim3((TE.n + 63) / 64), dim3(64), 0, ctx->s_tail, TE); KCHECK(); }   // (every read may be in the re-map round)
         HIPCK(hipEventRecord(ctx->ev_prep, ctx->s_tail));
     }
-    HIPCK(hipStreamSynchronize(ctx->s_multi[0]));
-    HIPCK(hipStreamSynchronize(ctx->s_multi[1]));
-    laps.lap("wait-r0");
-    if ((s = remap_round(ctx, B, reads[second], second, S0, ctx->ln[second], ctx->tb[second], second ? j1b : j1h)) != LNR_OK) return s;
-    laps.lap("tailA+seed1+launch1");
-    HIPCK(hipEventRecord(ctx->ev_lane[0], ctx->s_multi[0]));
-    HIPCK(hipStreamWaitEvent(ctx->stream, ctx->ev_lane[0], 0));   // (lane 1's multi stream is the main stream)
     ctx->t_job.stop(ctx->stream);
     HIPCK(hipStreamSynchronize(ctx->stream));
     ctx->stats.job_ms += ctx->t_job.ms();
     laps.lap("wait-r1");
     TailArgs T;
-    if ((s = tail_prepare(ctx, B, ctx->tb[0], early ? &late_list : nullptr, ctx->stream, T)) != LNR_OK) return s;
+    if ((s = tail_prepare(ctx, B, ctx->tb_late, early ? &late_list : nullptr, ctx->stream, T)) != LNR_OK) return s;
     ctx->t_tail.start(ctx->stream);
     if (T.n) { hipLaunchKernelGGL(k_tail_b, dim3((T.n + 63) / 64), dim3(64), 0, ctx->stream, T); KCHECK(); }
     ctx->t_tail.stop(ctx->stream);
     if (early) HIPCK(hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
     int ext_state_out = ctx->gap_ext;
     if (ctx->opts.gap_len) {
-        // the gap re-mapper on the final cords (k_gap): every read with small arenas, then the flagged reads with large ones
+        // the gap re-mapper on the final cords: every read in the fused first stage (k_gap_all), then the flagged reads with the largest arena (k_gap_team)
         u32 maxlen = 0;
         for (u32 i = 0; i < n; i++) maxlen = std::max(maxlen, B.len[i]);
         // arena budget of the gap re-mapper's workers: 48 GiB of the 288, never more than lnr_opts.scratch_budget (when given) nor than 80 % of what
@@ -1115,14 +1015,10 @@ lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, 
         u64 arena1 = align_up(((u64)512 << 10) * ctx->cap_scale + 16ULL * maxlen + sizeof(LeaderScratch) + 65536, 256);
         u64 arena2 = std::max<u64>(((u64)ctx->gap_arena2_mb << 20) * ctx->cap_scale, arena1 * 2);
         u64 arena3 = std::max<u64>(((u64)64 << 20) * ctx->cap_scale, arena2 * 2);
-        u32 w1 = (u32)std::min<u64>(align_up(n, 64), std::max<u64>(64, (budget / arena1) / 64 * 64));   // workers: lanes, or waves with LNR_GAP_MODE=1
-        if (ctx->gap_mode) w1 = std::min<u32>(w1, ctx->gap_waves);
-        u32 w2 = (u32)std::min<u64>(std::min<u64>(n, ctx->gap_waves), std::max<u64>(1, budget / arena2));   // waves of the second launch
-        u32 w3 = (u32)std::min<u64>(n, std::max<u64>(1, (budget / 2) / arena3));
-        const bool fused = ctx->gap_fused && ctx->gap_mode && ctx->gap_team;
+        u32 w3 = (u32)std::min<u64>(n, std::max<u64>(1, (budget / 2) / arena3));   // workgroups of the last launch
         const u32 ncu = ctx->ncu ? ctx->ncu : 256, nteams = std::min<u32>(ctx->gap_teams, ncu / 2);
-        u64 fused_bytes = fused ? (u64)nteams * arena2 + (u64)ncu * K_GAP_TEAM * arena1 : 0;     // (a small chunk runs fewer teams and more single waves: bounded by every CU full of single waves)
-        ENSURE(ctx->gap_arena, std::max(std::max(std::max((u64)w1 * arena1, (u64)w2 * arena2), (u64)w3 * arena3), fused_bytes));
+        u64 fused_bytes = (u64)nteams * arena2 + (u64)ncu * K_GAP_TEAM * arena1;     // (a small chunk runs fewer teams and more single waves: bounded by every CU full of single waves)
+        ENSURE(ctx->gap_arena, std::max((u64)w3 * arena3, fused_bytes));
         ENSURE(ctx->gap_flag, (size_t)n * 4);
         ENSURE(ctx->gap_next, 256);
         HIPCK(hipMemsetAsync(ctx->gap_next.p, 0, 256, ctx->stream));
@@ -1149,7 +1045,7 @@ lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, 
         ENSURE(ctx->gap_weight, ((size_t)n + 16) * 4);
         ENSURE(ctx->gap_list, ((size_t)n + 16) * 4);
         G.list = ctx->gap_list.as<u32>() + 16; G.list_n = ctx->gap_list.as<u32>();
-        // one "ladder" = the three launches (small arenas for every read of [lo, hi), then the flagged reads with larger ones)
+        // one "ladder" over the reads of [lo, hi): the fused first stage, then the reads it flagged with the largest arena
         auto ladder = [&](u32 lo, u32 hi, u32 ext_from, int probe) -> hipError_t {
             hipError_t e = hipMemsetAsync(ctx->gap_next.p, 0, 256, ctx->stream);
             if (e != hipSuccess) return e;
@@ -1159,30 +1055,18 @@ lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, 
             if ((e = launch_gap_weight(G.reads, G.off, G.out_str, G.cords_off, G.nout, lo, hi, ctx->gap_weight.as<u32>(), ctx->stream)) != hipSuccess) return e;
             if ((e = launch_gap_rank(ctx->gap_weight.as<u32>(), lo, hi, ctx->gap_rank.as<u32>() + 16, ctx->gap_rank.as<u32>(), ctx->gap_heavy_w, ctx->stream)) != hipSuccess) return e;
             G.order = ctx->gap_rank.as<u32>() + 16;
-            G.cap_ticks = (u64)ctx->gap_cap_ms * 100000ULL;
-            G.next = ctx->gap_next.as<u32>(); G.big = 0; G.last = 0; G.coop = ctx->gap_mode;
-            if (fused) {
-                // one launch: teams on the reads expected to be heavy + on what the single waves hand over, single waves on the rest
-                if ((e = hipMemsetAsync(ctx->gap_list.p, 0, ((size_t)n + 16) * 4, ctx->stream)) != hipSuccess) return e;
-                G.nteams = std::min<u32>(nteams, std::max<u32>(1, m / 8));
-                u32 bulk_wg = std::min<u32>(ncu > G.nteams ? ncu - G.nteams : 1, (m + K_GAP_TEAM - 1) / K_GAP_TEAM);
-                G.nbulk_waves = bulk_wg * K_GAP_TEAM; G.arena_bytes = arena1; G.arena2_bytes = arena2;
-                G.n_heavy = ctx->gap_rank.as<u32>(); G.q = ctx->gap_list.as<u32>() + 16;
-                G.coop = 1;
-                if ((e = launch_gap_all(G, G.nteams + bulk_wg, ctx->stream)) != hipSuccess) return e;
-            } else {
-                G.arena_bytes = arena1;
-                u32 v1 = std::min<u32>(w1, (u32)align_up(m, 64));
-                if ((e = launch_gap(G, 0, ctx->gap_mode ? v1 : v1 / 64, ctx->stream)) != hipSuccess) return e;
-                G.work_cap = ~0ULL; G.cap_ticks = 0;
-                if ((e = launch_gap_order(G.gap_flag, lo, hi, ctx->gap_list.as<u32>() + 16, ctx->gap_list.as<u32>(), ctx->stream)) != hipSuccess) return e;
-                G.arena_bytes = arena2; G.next = ctx->gap_next.as<u32>() + 8; G.big = 1; G.coop = 1;
-                if ((e = launch_gap(G, ctx->gap_team, std::min(w2, m), ctx->stream)) != hipSuccess) return e;
-            }
-            G.work_cap = ~0ULL; G.cap_ticks = 0; G.big = 1; G.coop = 1;
+            G.next = ctx->gap_next.as<u32>(); G.last = 0;
+            // one launch: teams on the reads expected to be heavy + on what the single waves hand over, single waves on the rest
+            if ((e = hipMemsetAsync(ctx->gap_list.p, 0, ((size_t)n + 16) * 4, ctx->stream)) != hipSuccess) return e;
+            G.nteams = std::min<u32>(nteams, std::max<u32>(1, m / 8));
+            u32 bulk_wg = std::min<u32>(ncu > G.nteams ? ncu - G.nteams : 1, (m + K_GAP_TEAM - 1) / K_GAP_TEAM);
+            G.nbulk_waves = bulk_wg * K_GAP_TEAM; G.arena_bytes = arena1; G.arena2_bytes = arena2;
+            G.n_heavy = ctx->gap_rank.as<u32>(); G.q = ctx->gap_list.as<u32>() + 16;
+            if ((e = launch_gap_all(G, G.nteams + bulk_wg, ctx->stream)) != hipSuccess) return e;
+            G.work_cap = ~0ULL;
             if ((e = launch_gap_order(G.gap_flag, lo, hi, ctx->gap_list.as<u32>() + 16, ctx->gap_list.as<u32>(), ctx->stream)) != hipSuccess) return e;
             G.arena_bytes = arena3; G.next = ctx->gap_next.as<u32>() + 24; G.last = 1;
-            return launch_gap(G, ctx->gap_team, std::min(w3, m), ctx->stream);
+            return launch_gap_team(G, std::min(w3, m), ctx->stream);
         };
         // The stream state (GapArgs): once a read of the stream has extended, every later read starts "extended" -- one ladder over the batch.
         // Until then the batch is taken in growing chunks: a probe ladder finds the chunk's first extending read r* (all reads started "not
@@ -1489,55 +1373,37 @@ lnr_status lnr_create(const lnr_opts *opts, lnr_ctx **out) {
     ctx->device = dev;
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return LNR_ERR_HIP; }
     if (const char *e = getenv("LNR_CAP_SHRINK")) { long v = atol(e); if (v >= 1 && v <= 4096) ctx->cap_shrink = (u32)v; }
-    if (const char *e = getenv("LNR_GAP_MODE")) ctx->gap_mode = atoi(e) ? 1 : 0;
-    if (const char *e = getenv("LNR_GAP_FUSED")) ctx->gap_fused = atoi(e) ? 1 : 0;
     if (const char *e = getenv("LNR_GAP_TEAMS")) { long v = atol(e); if (v >= 1 && v <= 4096) ctx->gap_teams = (u32)v; }
     { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, ctx->device) == hipSuccess) ctx->ncu = (u32)pr.multiProcessorCount; else (void)hipGetLastError(); }
     if (const char *e = getenv("LNR_GAP_HEAVY_W")) { long v = atol(e); if (v >= 1) ctx->gap_heavy_w = (u32)v; }
-    if (const char *e = getenv("LNR_GAP_CAP_MS")) { long v = atol(e); if (v >= 0 && v <= 100000) ctx->gap_cap_ms = (u32)v; }
-    if (const char *e = getenv("LNR_SEED_BH")) ctx->use_bh = atoi(e) ? 1 : 0;
-    if (const char *e = getenv("LNR_GAP_WAVES")) { long v = atol(e); if (v >= 1 && v <= (1 << 20)) ctx->gap_waves = (u32)v; }
     if (const char *e = getenv("LNR_GAP_ARENA2_MB")) { long v = atol(e); if (v >= 1 && v <= 1024) ctx->gap_arena2_mb = (u32)v; }
-    if (const char *e = getenv("LNR_GAP_TEAM")) ctx->gap_team = atoi(e) ? 1 : 0;
     if (const char *e = getenv("LNR_GAP_WORK_CAP")) { long long v = atoll(e); if (v >= 0) ctx->gap_work_cap = (u64)v; }
     if (const char *e = getenv("LNR_SEED_LDS_PAD")) { long v = atol(e); if (v >= 0 && v <= 100000) ctx->seed_lds_pad = (u32)v; }
     if (const char *e = getenv("LNR_JOB_LDS_KB")) { long kb = atol(e); if (kb >= 1 && kb <= 156) ctx->job_lds_bytes = (size_t)kb * 1024; }
-    if (const char *e = getenv("LNR_JOB_STAGE_KB")) { long kb = atol(e); if (kb >= 0 && kb <= 60) ctx->job_stage_bytes = (size_t)kb * 1024; }
     if (const char *e = getenv("LNR_HEAVY_CAP")) { long v = atol(e); if (v >= 64) { ctx->heavy_cap = (u32)std::min<long>(v, 0xffffffffL); ctx->heavy_cap_r1 = ctx->heavy_cap; } }
     if (const char *e = getenv("LNR_HEAVY_LDS_KB")) { long v = atol(e); if (v >= 1 && v <= 56) ctx->heavy_lds_kb = (u32)v; }
     if (const char *e = getenv("LNR_MID_CAP")) { long v = atol(e); if (v >= 64) { ctx->mid_cap_env = true; ctx->mid_cap = (u32)std::min<long>(v, 0xffffffffL); ctx->mid_cap_r1 = ctx->mid_cap; } }
     if (const char *e = getenv("LNR_MID_LDS_KB")) { long v = atol(e); if (v >= 1 && v <= 56) ctx->mid_lds_kb = (u32)v; }
     if (const char *e = getenv("LNR_HEAVY_CAP_R1")) { long v = atol(e); if (v >= 64) ctx->heavy_cap_r1 = (u32)std::min<long>(v, 0xffffffffL); }
     if (const char *e = getenv("LNR_MID_CAP_R1")) { long v = atol(e); if (v >= 64) ctx->mid_cap_r1 = (u32)std::min<long>(v, 0xffffffffL); }
-    if (const char *e = getenv("LNR_DP_SPLIT_CAP")) { long v = atol(e); if (v >= 64) { ctx->dp_split_cap = (u32)std::min<long>(v, 0xffffffffL); ctx->dp_split_cap_r1 = ctx->dp_split_cap; } }
-    if (const char *e = getenv("LNR_DP_SPLIT_CAP_R1")) { long v = atol(e); if (v >= 64) ctx->dp_split_cap_r1 = (u32)std::min<long>(v, 0xffffffffL); }
     if (const char *e = getenv("LNR_MID_WAVES")) ctx->mid_waves = atoi(e) == 2 ? 2 : 4;
-    if (const char *e = getenv("LNR_POST_SPLIT")) ctx->post_split = atoi(e) != 0;
     if (const char *e = getenv("LNR_SEED_BM")) ctx->seed_bm = atoi(e) ? 1 : 0;
     if (const char *e = getenv("LNR_STOP_AFTER")) { long v = atol(e); if (v >= 0 && v < 16) ctx->stop_after = (u32)v; }
     if (const char *e = getenv("LNR_PREP_GRID")) { long v = atol(e); if (v > 0) ctx->prep_grid = (u32)v; }
     if (const char *e = getenv("LNR_PREP_THREADS")) { long v = atol(e); if (v == 64 || v == 128 || v == 256) ctx->prep_threads = (u32)v; }
     if (const char *e = getenv("LNR_BULK_DELAY_US")) { long v = atol(e); if (v >= 0 && v <= 5000) ctx->bulk_delay_ticks = (u32)v * 100; }
-    if (const char *e = getenv("LNR_LANE_ORDER")) ctx->lane_bulk_first = e[0] != 'h';
-    if (const char *e = getenv("LNR_SPLIT_CAP")) { long v = atol(e); if (v >= 1) ctx->split_cap = (u32)std::min<long>(v, 0xffffffffL); }
-    // Three streams in all: the runtime multiplexes streams onto a few hardware queues (4 by default) and two streams on
-    // one queue run their kernels back to back (measured: the bulk kernel waited for the 4-wave kernel).  Lane 1 (bulk)
-    // uses the main stream for its multi-wave kernels, seeds and tails and one side stream for the single-wave kernel;
-    // lane 0 (heavy reads, nearly all multi-wave) runs everything on one stream.
+    // Six streams in all (main, spare, bulk, tail, copy, down): the runtime multiplexes streams onto a few hardware queues (4 by
+    // default) and two streams on one queue run their kernels back to back (measured: the bulk kernel waited for the 4-wave kernel).
     bool ok = hipEventCreateWithFlags(&ctx->ev_start, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&ctx->ev_f1, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&ctx->s_multi[0], hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&ctx->s_bulk[1], hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipStreamCreateWithFlags(&ctx->s_spare, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&ctx->s_bulk, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipStreamCreateWithFlags(&ctx->s_tail, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipStreamCreateWithFlags(&ctx->s_copy, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipStreamCreateWithFlags(&ctx->s_down, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->ev_down, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming) == hipSuccess;
     for (int k = 0; k < 3 && ok; k++) ok = hipEventCreateWithFlags(&ctx->ev_in[k], hipEventDisableTiming) == hipSuccess;
-    ctx->s_bulk[0] = ctx->s_multi[0];
-    if (getenv("LNR_LANE0_BULK_STREAM")) ok = ok && hipStreamCreateWithFlags(&ctx->s_bulk[0], hipStreamNonBlocking) == hipSuccess;   // experiment: own stream for lane 0's single-wave kernel
-    ctx->s_multi[1] = ctx->stream;
-    for (int l = 0; l < 2 && ok; l++)
-        ok = hipEventCreateWithFlags(&ctx->ev_fork[l], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ctx->ev_join[l], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&ctx->ev_lane[l], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ctx->ev_join_spare, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&ctx->ev_join_bulk, hipEventDisableTiming) == hipSuccess;
     if (!ok) { lnr_destroy(ctx); return LNR_ERR_HIP; }
     ctx->t_prep.init(); ctx->t_job.init(); ctx->t_tail.init(); ctx->t_total.init(); ctx->t_gap.init();
     *out = ctx;
@@ -1548,26 +1414,21 @@ void lnr_destroy(lnr_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (int l = 0; l < 2; l++) {
-        if (ctx->s_multi[l]) (void)hipStreamSynchronize(ctx->s_multi[l]);
-        if (ctx->s_bulk[l]) (void)hipStreamSynchronize(ctx->s_bulk[l]);
-    }
+    if (ctx->s_spare) (void)hipStreamSynchronize(ctx->s_spare);
+    if (ctx->s_bulk) (void)hipStreamSynchronize(ctx->s_bulk);
     ctx->t_prep.destroy(); ctx->t_job.destroy(); ctx->t_tail.destroy(); ctx->t_total.destroy();
-    for (int l = 0; l < 2; l++) {
-        ctx->js[l].t_seed.destroy();
-        if (ctx->ev_fork[l]) (void)hipEventDestroy(ctx->ev_fork[l]);
-        if (ctx->ev_join[l]) (void)hipEventDestroy(ctx->ev_join[l]);
-        if (ctx->ev_lane[l]) (void)hipEventDestroy(ctx->ev_lane[l]);
-    }
+    for (int l = 0; l < 2; l++) ctx->js[l].t_seed.destroy();
+    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+    if (ctx->ev_join_spare) (void)hipEventDestroy(ctx->ev_join_spare);
+    if (ctx->ev_join_bulk) (void)hipEventDestroy(ctx->ev_join_bulk);
     if (ctx->s_tail) { (void)hipStreamSynchronize(ctx->s_tail); (void)hipStreamDestroy(ctx->s_tail); }
     if (ctx->s_copy) { (void)hipStreamSynchronize(ctx->s_copy); (void)hipStreamDestroy(ctx->s_copy); }
     if (ctx->s_down) { (void)hipStreamSynchronize(ctx->s_down); (void)hipStreamDestroy(ctx->s_down); }
     if (ctx->ev_down) (void)hipEventDestroy(ctx->ev_down);
     if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
     for (int k = 0; k < 3; k++) if (ctx->ev_in[k]) (void)hipEventDestroy(ctx->ev_in[k]);
-    if (ctx->s_bulk[0] && ctx->s_bulk[0] != ctx->s_multi[0]) (void)hipStreamDestroy(ctx->s_bulk[0]);
-    if (ctx->s_multi[0]) (void)hipStreamDestroy(ctx->s_multi[0]);
-    if (ctx->s_bulk[1]) (void)hipStreamDestroy(ctx->s_bulk[1]);
+    if (ctx->s_spare) (void)hipStreamDestroy(ctx->s_spare);
+    if (ctx->s_bulk) (void)hipStreamDestroy(ctx->s_bulk);
     for (int k = 0; k < 2; k++) if (ctx->ev_up[k]) (void)hipEventDestroy(ctx->ev_up[k]);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);

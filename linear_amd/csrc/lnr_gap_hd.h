@@ -1,8 +1,8 @@
 // lnr_gap_hd.h -- the gap re-mapper (mapGaps / reformCords, gap.cpp / gap_util.cpp / cords.cpp:504-687) as host + device
 // functions of the product, in the idiom of lnr_hd.h: arrays from a per-read arena (mark / release per gap), the tie-sensitive sorts
 // through ref_sort.h, the chain traceback and the block chaining through the forms lnr_hd.h already has.  One read is one serial walk
-// over its gaps (the tiles of a gap are inserted into the cord list before the next gap is looked at).  k_gap (lnr_kernels.hip) runs
-// it with one wave per read: every lane executes this code on the same data, and the loops marked `coop` deal their iterations over
+// over its gaps (the tiles of a gap are inserted into the cord list before the next gap is looked at).  The gap kernels
+// (lnr_gap_kernels.hip) run it with one wave per read: every lane executes this code on the same data, and the loops marked `coop` deal their iterations over
 // the 64 lanes (chain DP, k-mer join).  The same source compiled by g++ (tests/host_shim.cpp) is what the CPU tests check function
 // by function against the oracle (tests/test_gap_shim_cpu.py).  Every function cites the reference lines it follows.  DESIGN.md 5c.
 #pragma once
@@ -116,8 +116,7 @@ struct GapCtx {                                           // one read
     FeatView f1[2]; GenomeFeat gf;
     GapParms gp;
     u64 work = 0, work_cap = ~0ULL;                       // pair evaluations of the chain DPs so far / the budget (over it: ar->ovf = 2)
-    u64 deadline = 0;                                     // device, first launch: wall_clock64() after which the read is given up and left to the team launch (ovf = 2); 0 = none
-    int coop = 0;                                         // device: all 64 lanes of the wave run this read together (k_gap, second launch)
+    int coop = 0;                                         // device: all 64 lanes of the wave run this read together (every gap kernel; 0 on the host)
     int team = 0; struct GapTeam *tm = nullptr;           // device: helper waves of the workgroup for the long rows of the chain DP (k_gap_team)
     int hand = 0;                                         // device: a single wave of the first stage -- a later stage (teams, larger arenas) redoes what it gives up
 #ifdef LNR_GAP_DEVPROF
@@ -127,15 +126,6 @@ struct GapCtx {                                           // one read
     LNR_HD GSeq ref(u64 id) const { GSeq s; s.p = g + seq_off[id]; s.len = seq_len[id]; return s; }
 };
 
-// The first launch runs one wave per read and ends when its slowest read does: a read that is still busy after the deadline is abandoned there
-// (like one that outgrew its arena: ovf = 2, its apxMap cords stay) and redone by the team launch, which has idle CUs to spare while the handful
-// of truly heavy reads set its duration.  Which launch a read ends up in does not change its result.
-LNR_HD inline bool gap_late(GapCtx &X) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (X.deadline && !X.ar->ovf && wall_clock64() > X.deadline) X.ar->ovf = 2;
-#endif
-    return X.ar->ovf != 0;
-}
 #if defined(LNR_GAP_DEVPROF) && defined(__HIP_DEVICE_COMPILE__)
 struct GpScope { GapCtx &X; int i; unsigned long long t0; __device__ GpScope(GapCtx &x, int k) : X(x), i(k), t0(wall_clock64()) {} __device__ ~GpScope() { X.prof[i] += wall_clock64() - t0; } };
 #define GP(X, k) GpScope _gp_scope(X, k)
@@ -1174,7 +1164,7 @@ LNR_HD inline void gap_chain_anchors(const u64 *anchors, u32 n, GVec<u64> &out, 
         i32 ws = 0, wl = 0, wr = 0;
         u32 far_prev = 0;
         for (int i = 0; i < (int)n; i++) {
-            if ((i & 1023) == 0 && gap_late(X)) return;
+            if ((i & 1023) == 0 && X.ar->ovf) return;
             if ((i & 63) == 0) blk = (u32)(i + lane) < n ? anchors[i + lane] : 0;
             int j_str = i - (int)depth < 0 ? 0 : i - (int)depth;
             u64 ai = __shfl(blk, i & 63), xi = ganc_x(ai), key = 0;
@@ -2167,7 +2157,7 @@ LNR_HD inline int gap_map_gaps(GVec<u64> &cs, GVec<u64> &ce, GArena &keep, GapCt
     gather_blocks(cs.p, cs.n, &str_ends, sep, 1, cs.n, L, (u64)cord_gap, (u64)block_size, 0);
     gather_gaps_y(str_ends.p, str_ends.n, gaps, L, (u64)cord_gap, *X.ls);
     for (u32 i = 1; i < cs.n; i++) {
-        if (gap_late(X)) return 1;
+        if (X.ar->ovf) return 1;
         u64 slen = X.seq_len[cord_id(cs[i])];
         gp.read_len = L; gp.ref_len = slen;
         if (is_end(cs[i - 1])) {                                                                 // the block's first cord: towards the read's start

@@ -1,4 +1,4 @@
-// lnr_gap_kernels.hip -- the kernels of the gap re-mapper (mapGaps + reformCords behind apxMap, `-g > 0`): k_gap / k_gap_team
+// lnr_gap_kernels.hip -- the kernels of the gap re-mapper (mapGaps + reformCords behind apxMap, `-g > 0`): k_gap_all / k_gap_team
 // around the per-read code of lnr_gap_hd.h, the wave-parallel exact introsort of that code, and the host-side launcher.  A translation unit
 // of its own (compiled beside lnr_api.hip, linked into the same library): the two halves build in parallel.
 #include <hip/hip_runtime.h>
@@ -143,7 +143,7 @@ template <class T, class Comp> __device__ void gap_sort_wave(T *a, u32 n, Comp c
         ref_sort(a, (long)n, comp, X.ls->st);
         return;
     }
-    if (gap_late(X)) return;
+    if (X.ar->ovf) return;
     int lg = 0;
     for (u32 t = n; t > 1; t >>= 1) lg++;
     if (!GapSortTeam<T, Comp>::run(a, n, comp, X, Lbuf, Rbuf, tasks, lg))
@@ -151,12 +151,9 @@ template <class T, class Comp> __device__ void gap_sort_wave(T *a, u32 n, Comp c
     X.ar->release(m0);
 }
 
-#ifndef K_GAP_WAVES
-#define K_GAP_WAVES 4
-#endif
 // one read: mapGaps + reformCords on its cords in the per-read output slot, with the arena [mine, mine + arena_bytes).  Returns true when the read
-// could not be done here (arena, cord slot, deadline): its apxMap cords stay and gap_flag[r] = 1 + (the request that did not fit, KiB).
-// lvl: 0 first pass (one wave), 1 team with the middle arena, 2 team with the large one (statistics / profile only).
+// could not be done here (arena, cord slot, work budget): its apxMap cords stay and gap_flag[r] = 1 + (the request that did not fit, KiB).
+// lvl: 0 single wave of the first stage, 1 team with the middle arena, 2 team with the large one (statistics / profile only).
 // hands_off: the caller passes a read it could not do on to another workgroup OF THE SAME LAUNCH (k_gap_all), which then owns gap_flag[r]: two
 // workgroups may sit on different XCDs, whose L2s are written back in no particular order at the end of the kernel, so only one of them may
 // store to the word.
@@ -179,14 +176,10 @@ __device__ bool gap_do_read(const GapArgs &A, u32 r, char *mine, u64 arena_bytes
     u64 ar_want = 0;
     if (!bad) {
         const u8 *src = A.reads + A.off[r];
-        if (A.coop) {                                            // (the wave's lanes share the copy; every lane reads the arrays afterwards)
-            for (u64 k = threadIdx.x & 63; k < L; k += 64) { u8 b = src[k]; b = b > 4 ? 4 : b; rd[k] = b; rc[L - 1 - k] = b == 4 ? 4 : 3 - b; }
-            rd[L + (threadIdx.x & 63)] = 0; rc[L + (threadIdx.x & 63)] = 0;
-            WSYNC();
-        } else {
-            for (u64 k = 0; k < L; k++) { u8 b = src[k]; b = b > 4 ? 4 : b; rd[k] = b; rc[L - 1 - k] = b == 4 ? 4 : 3 - b; }
-            for (u32 k = 0; k < 64; k++) { rd[L + k] = 0; rc[L + k] = 0; }
-        }
+        // (the wave's lanes share the copy; every lane reads the arrays afterwards)
+        for (u64 k = threadIdx.x & 63; k < L; k += 64) { u8 b = src[k]; b = b > 4 ? 4 : b; rd[k] = b; rc[L - 1 - k] = b == 4 ? 4 : 3 - b; }
+        rd[L + (threadIdx.x & 63)] = 0; rc[L + (threadIdx.x & 63)] = 0;
+        WSYNC();
         GArena keep; keep.init(kp, keep_bytes);
         GArena ar; ar.init(mine + all.off, arena_bytes - all.off);
         GapCtx X;
@@ -198,8 +191,7 @@ __device__ bool gap_do_read(const GapArgs &A, u32 r, char *mine, u64 arena_bytes
         X.gp.f_dup = A.f_dup; X.gp.thd_gap_len_min = A.gap_len_min;
         const bool ext_in = r >= A.ext_from;
         if (ext_in) X.gp.thd_cts_major_limit = 3;
-        X.coop = A.coop; X.work_cap = A.work_cap; X.team = team; X.tm = tm; X.hand = (A.coop && !A.big && team <= 1) ? 1 : 0;
-        X.deadline = (A.cap_ticks && !flagged_only) ? wall_clock64() + A.cap_ticks : 0;
+        X.coop = 1; X.work_cap = A.work_cap; X.team = team; X.tm = tm; X.hand = team <= 1 ? 1 : 0;
         u64 *os = A.out_str + A.cords_off[r], *oe = A.out_end + A.cords_off[r];
         GVec<u64> cs, ce; cs.init(&keep, nc * 2 + 64); ce.init(&keep, nc * 2 + 64);
         for (u32 i = 0; i < nc; i++) { cs.push(os[i]); ce.push(oe[i]); }
@@ -209,7 +201,7 @@ __device__ bool gap_do_read(const GapArgs &A, u32 r, char *mine, u64 arena_bytes
         int rc_ = gap_map_gaps(cs, ce, keep, X);
         gap_reform_cords(cs, ce);
 #ifdef LNR_GAP_DEVPROF
-        if (A.prof && (A.coop ? (threadIdx.x & 63) == 0 : true)) {
+        if (A.prof && (threadIdx.x & 63) == 0) {
             unsigned long long *pp = A.prof + 16 * (lvl);
             t_read = wall_clock64() - t_read;
             for (int k = 0; k < 10; k++) atomicAdd(pp + k, X.prof[k]);
@@ -223,7 +215,7 @@ __device__ bool gap_do_read(const GapArgs &A, u32 r, char *mine, u64 arena_bytes
         bad = rc_ != 0 || ar.ovf || keep.ovf || cs.n > A.cords_cap[r] || cs.n != ce.n;
         ar_want = ar.want > keep.want ? ar.want : keep.want;
         if (!bad) {
-            if (!ext_in && X.gp.thd_cts_major_limit == 3 && (A.coop ? (threadIdx.x & 63) == 0 : true)) atomicMin(A.first_ext, r);
+            if (!ext_in && X.gp.thd_cts_major_limit == 3 && (threadIdx.x & 63) == 0) atomicMin(A.first_ext, r);
             if (!A.probe) {
                 for (u32 i = 0; i < cs.n; i++) { os[i] = cs[i]; oe[i] = ce[i]; }
                 A.nout[r] = cs.n;
@@ -235,46 +227,32 @@ __device__ bool gap_do_read(const GapArgs &A, u32 r, char *mine, u64 arena_bytes
     if (A.last && bad) A.read_err[r] = 5;
     return bad;
 }
-__device__ void gap_worker(const GapArgs &A, GapTeam *tm, int team) {
-    u32 worker = A.coop ? blockIdx.x : blockIdx.x * blockDim.x + threadIdx.x;
-#ifdef LNR_GAP_DEVPROF
-    if (A.prof && threadIdx.x == 0 && !A.big) { unsigned long long c = atomicAdd(A.prof + 94, 1ULL) + 1; atomicMax(A.prof + 95, c); }   // workers of the first launch alive at once
-#endif
-    char *mine = A.arena + (u64)worker * A.arena_bytes;
-    for (;;) {
-        u32 r;
-        if (A.coop) { r = threadIdx.x == 0 ? atomicAdd(A.next, 1u) : 0u; r = (u32)__shfl((int)r, 0); }
-        else r = atomicAdd(A.next, 1u);
-        if (A.big) {                                                 // the flagged reads, heaviest first
-            if (r >= *A.list_n) break;
-            r = A.list[r];
-        } else { if (r >= A.n - A.lo) break; r = A.order ? A.order[r] : r + A.lo; }
-        if (r >= A.n) break;
-        if (A.big && !A.gap_flag[r]) continue;
-        if (A.big && threadIdx.x == 0) atomicAdd(A.next + 8, 1u);   // (statistics: reads of the second launch)
-        gap_do_read(A, r, mine, A.arena_bytes, tm, team, A.big != 0, A.big + A.last);
-    }
-#ifdef LNR_GAP_DEVPROF
-    if (A.prof && threadIdx.x == 0 && !A.big) atomicAdd(A.prof + 94, ~0ULL);
-#endif
-}
-__global__ void __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(K_GAP_WAVES, K_GAP_WAVES))) k_gap(GapArgs A) { gap_worker(A, nullptr, 1); }
-// The launches for the flagged reads: K_GAP_TEAM waves per read.  Wave 0 is the worker; the others only serve the long rows of its
-// chain DPs (gap_team_helper_loop) and leave when wave 0 has run out of reads.
+// The last launch: the reads still flagged after the first stage (the list k_gap_order made, heaviest first), K_GAP_TEAM waves per read with
+// the large arena.  Wave 0 is the worker; the others only serve the long rows of its chain DPs (gap_team_helper_loop) and leave when wave 0
+// has run out of reads.
 __global__ void __attribute__((amdgpu_flat_work_group_size(64 * K_GAP_TEAM, 64 * K_GAP_TEAM))) k_gap_team(GapArgs A) {
     __shared__ GapTeam tm;
     if (threadIdx.x >= 64) { gap_team_helper_loop(&tm, (int)(threadIdx.x >> 6), K_GAP_TEAM); return; }
-    gap_worker(A, &tm, K_GAP_TEAM);
+    char *mine = A.arena + (u64)blockIdx.x * A.arena_bytes;
+    for (;;) {
+        u32 r = threadIdx.x == 0 ? atomicAdd(A.next, 1u) : 0u;
+        r = (u32)__shfl((int)r, 0);
+        if (r >= *A.list_n) break;
+        r = A.list[r];
+        if (r >= A.n) break;
+        if (!A.gap_flag[r]) continue;
+        if (threadIdx.x == 0) atomicAdd(A.next + 8, 1u);   // (statistics: reads of this launch)
+        gap_do_read(A, r, mine, A.arena_bytes, &tm, K_GAP_TEAM, true, 2);
+    }
     if (threadIdx.x == 0) tm.cmd = 0;
     __syncthreads();                                             // (A) with the exit command: the helpers leave
 }
-
 
 // ---- the fused first stage.  One launch, workgroups of 16 waves: the first A.nteams are TEAMS (wave 0 runs reads, the others serve its DPs,
 // sorts and joins), every other workgroup is 16 independent single-wave workers.  Workgroups are placed in index order, so the teams hold their
 // CUs before the single waves flood the rest of the chip.  The reads come ordered by weight (k_gap_weight / k_gap_rank): teams start on the ones
 // expected to be heavy at once -- their critical path, not the work, is what the stage waits for -- while the single waves take the light end;
-// a single wave that cannot finish a read (arena, deadline) posts it in the queue and a team picks it up.  The stage ends when the single waves
+// a single wave that cannot finish a read (arena, work budget) posts it in the queue and a team picks it up.  The stage ends when the single waves
 // are through and the queue is empty.  Which worker a read ends up with does not change its result.
 __global__ void __attribute__((amdgpu_flat_work_group_size(64 * K_GAP_TEAM, 64 * K_GAP_TEAM))) k_gap_all(GapArgs A) {
     __shared__ GapTeam tm;
@@ -451,9 +429,8 @@ hipError_t launch_gap_order(const u32 *gap_flag, unsigned lo, unsigned n, u32 *l
     hipLaunchKernelGGL(k_gap_order, dim3(1), dim3(1024), 0, stream, gap_flag, lo, n, list, list_n);
     return hipGetLastError();
 }
-hipError_t launch_gap(const GapArgs &A, int team, unsigned grid, hipStream_t stream) {
-    if (team) hipLaunchKernelGGL(k_gap_team, dim3(grid), dim3(64 * K_GAP_TEAM), 0, stream, A);
-    else hipLaunchKernelGGL(k_gap, dim3(grid), dim3(64), 0, stream, A);
+hipError_t launch_gap_team(const GapArgs &A, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(k_gap_team, dim3(grid), dim3(64 * K_GAP_TEAM), 0, stream, A);
     return hipGetLastError();
 }
 

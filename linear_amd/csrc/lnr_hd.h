@@ -75,11 +75,6 @@ LNR_HD inline void lnr_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #endif
 }
-// Two ways the device runs the per-read stages: COOP = all 64 lanes of a wave execute the code together for ONE read (the leader
-// stores, the others track the counts; the job kernels), or one lane per read (k_post: every lane is its own leader and nothing
-// is shared between lanes).  The stage functions that differ take the mode as a template argument.
-template <bool COOP> LNR_HD inline bool lnr_leader() { return COOP ? lnr_is_leader() : true; }
-template <bool COOP> LNR_HD inline void lnr_sync() { if (COOP) lnr_wave_sync(); }
 // A value every lane of the wave holds identically, moved to scalar registers: what is computed from it afterwards runs on the scalar unit
 // instead of occupying the vector ALU for all 64 lanes (the SIMT-uniform phases are bound by VALU issue, not by memory).  Host: identity.
 LNR_HD inline u32 lnr_uni32(u32 v) {
@@ -90,7 +85,6 @@ LNR_HD inline u32 lnr_uni32(u32 v) {
 #endif
 }
 LNR_HD inline u64 lnr_uni64(u64 v) { return ((u64)lnr_uni32((u32)(v >> 32)) << 32) | (u64)lnr_uni32((u32)v); }
-template <bool COOP> LNR_HD inline u64 lnr_u64(u64 v) { return COOP ? lnr_uni64(v) : v; }
 // bounded vector view over caller-provided storage; overflow is recorded, never written past cap
 template <class T>
 struct Vec {
@@ -101,10 +95,6 @@ struct Vec {
     LNR_HD void push_u(const T &v) {
         if (n < cap) { if (lnr_is_leader()) p[n] = v; n++; }
         else if (lnr_is_leader()) *ovf = 1;
-    }
-    template <bool COOP> LNR_HD void push_m(const T &v) {
-        if (n < cap) { if (lnr_leader<COOP>()) p[n] = v; n++; }
-        else if (lnr_leader<COOP>()) *ovf = 1;
     }
     LNR_HD T &operator[](u32 i) { return p[i]; }
     LNR_HD T &back() { return p[n - 1]; }
@@ -995,54 +985,30 @@ LNR_HD inline u32 window_best3(FeatView f1, FeatView f2, u64 y, u64 x0, u64 &x_m
     return mn;
 #endif
 }
-template <bool COOP = true>
 LNR_HD inline u64 previous_window(FeatView f1, FeatView f2, u64 cord) {   // pmpfinder.cpp:883-945
     u64 gid = cord_id(cord), strand = cord_strand(cord);
     u64 x_suf = cord_x(cord) >> 4, y_suf = cord_y(cord) >> 4, x_min = 0;
     if (y_suf < 5 || x_suf < 6) return 0;
     u64 y = y_suf - 5;
-    u32 mn = window_best3<COOP>(f1, f2, y, x_suf - 6, x_min);
+    u32 mn = window_best3(f1, f2, y, x_suf - 6, x_min);
     if (mn > 36) return 0;
     if (x_suf - x_min > 5) return mk_cord((gid << 30) + ((x_suf - 5) << 4), (x_suf - x_min - 5 + y) << 4, strand);
     return mk_cord((gid << 30) + (x_min << 4), y << 4, strand);
 }
-template <bool COOP = true>
 LNR_HD inline u64 next_window(FeatView f1, FeatView f2, u64 cord) {   // pmpfinder.cpp:1079-1150
     u64 gid = cord_id(cord), strand = cord_strand(cord);
     u64 x_pre = cord_x(cord) >> 4, y_pre = cord_y(cord) >> 4, x_min = 0;
     if (y_pre + 12 > f1.n || x_pre + 12 > f2.n) return 0;
     u64 y = y_pre + 5;
-    u32 mn = window_best3<COOP>(f1, f2, y, x_pre + 3, x_min);
+    u32 mn = window_best3(f1, f2, y, x_pre + 3, x_min);
     if (mn > 36) return 0;
     if (x_min - x_pre > 5) return mk_cord((gid << 30) + ((x_pre + 5) << 4), (x_pre + 5 - x_min + y) << 4, strand);
     return mk_cord((gid << 30) + (x_min << 4), y << 4, strand);
 }
-// SIMT-uniform: on the device every lane of the wave executes this with the same arguments (see window_best3);
-// `tail` is the value of cords.back(), carried in a register so that no lane has to re-read the leader's store.
-template <bool COOP = true>
-LNR_HD inline bool extend_window_serial(FeatView f1, FeatView f2, Vec<u64> &cords, u64 &tail, u64 cordy_str, u64 cordy_end) {   // pmpfinder.cpp:1152-1178
-    u32 p_str = cords.n - 1;
-    u64 nc;
-    while ((nc = previous_window<COOP>(f1, f2, tail)) && cord_y(nc) >= cordy_str) {
-        if (cords.n >= cords.cap) { if (lnr_leader<COOP>()) *cords.ovf = 1; return false; }
-        cords.template push_m<COOP>(nc); tail = nc;
-    }
-    u32 p_end = cords.n;
-    if (p_end - p_str > 1) {
-        lnr_sync<COOP>();
-        if (lnr_leader<COOP>())
-            for (u32 k = p_str; k < (p_str + p_end) / 2; k++) rs_swap(cords[k], cords[cords.n - k + p_str - 1]);
-        lnr_sync<COOP>();
-        tail = cords[cords.n - 1];
-    }
-    while ((nc = next_window<COOP>(f1, f2, tail)) && cord_y(nc) + 96 < cordy_end) {
-        if (cords.n >= cords.cap) { if (lnr_leader<COOP>()) *cords.ovf = 1; return false; }
-        cords.template push_m<COOP>(nc); tail = nc;
-    }
-    return true;
-}
 #if defined(__HIP_DEVICE_COMPILE__)
-// The same walk with the window distances of several steps evaluated at once.  A step only chooses among three
+// extend_window (pmpfinder.cpp:1152-1178): SIMT-uniform, every lane of the wave executes it with the same arguments; `tail` is the value of
+// cords.back(), carried in a register so that no lane has to re-read the leader's store.  The device form evaluates the window distances
+// of several steps at once.  A step only chooses among three
 // neighbouring windows, so the windows reachable within the next few steps form a small frontier: its distances are
 // independent loads (one per lane), and the walk through them is register work.  One memory round trip per frontier instead
 // of one per step; the choices, stop conditions and emitted cords are those of previous_window / next_window.
@@ -1162,8 +1128,24 @@ LNR_HD inline bool extend_window(FeatView f1, FeatView f2, Vec<u64> &cords, u64 
     return true;
 }
 #else
+// host form: the serial walk
 LNR_HD inline bool extend_window(FeatView f1, FeatView f2, Vec<u64> &cords, u64 &tail, u64 cordy_str, u64 cordy_end) {
-    return extend_window_serial(f1, f2, cords, tail, cordy_str, cordy_end);
+    u32 p_str = cords.n - 1;
+    u64 nc;
+    while ((nc = previous_window(f1, f2, tail)) && cord_y(nc) >= cordy_str) {
+        if (cords.n >= cords.cap) { *cords.ovf = 1; return false; }
+        cords.push(nc); tail = nc;
+    }
+    u32 p_end = cords.n;
+    if (p_end - p_str > 1) {
+        for (u32 k = p_str; k < (p_str + p_end) / 2; k++) rs_swap(cords[k], cords[cords.n - k + p_str - 1]);
+        tail = cords[cords.n - 1];
+    }
+    while ((nc = next_window(f1, f2, tail)) && cord_y(nc) + 96 < cordy_end) {
+        if (cords.n >= cords.cap) { *cords.ovf = 1; return false; }
+        cords.push(nc); tail = nc;
+    }
+    return true;
 }
 #endif
 struct GenomeFeat { const F96 *base; const u64 *off; u32 nseq; };   // f2 of all sequences, off[nseq+1] in entries
@@ -1191,7 +1173,6 @@ LNR_HD inline u32 filter_hits_apply(u64 *hits, u32 nhits, const i32 *keep) {
     return nhits - mv;
 }
 // SIMT-uniform (all lanes execute it together on the device; hits are read-only, cords are written by the leader).
-template <bool COOP = true>
 LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2], GenomeFeat g, Vec<u64> &cords_, u64 read_str, u64 read_end, u64 L) {   // pmpfinder.cpp:1309-1410
     i64 hitBegin = 1, hitEnd = (i64)nhits;
     if (hitBegin >= hitEnd - 1) return;
@@ -1199,16 +1180,14 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2],
     Vec<u64> cords = cords_;
     struct NBack { Vec<u64> &dst; Vec<u64> &src; LNR_HD ~NBack() { dst.n = src.n; } } nback_{cords_, cords};
     FeatView f1[2] = {f1_[0], f1_[1]};
-    if (COOP) {
-        cords.p = (u64 *)lnr_uni64((u64)cords.p); cords.n = lnr_uni32(cords.n); cords.cap = lnr_uni32(cords.cap); cords.ovf = (int *)lnr_uni64((u64)cords.ovf);
-        for (int k = 0; k < 2; k++) { f1[k].p = (const F96 *)lnr_uni64((u64)f1[k].p); f1[k].n = lnr_uni32(f1[k].n); }
-        g.base = (const F96 *)lnr_uni64((u64)g.base); g.off = (const u64 *)lnr_uni64((u64)g.off); g.nseq = lnr_uni32(g.nseq);
-        read_str = lnr_uni64(read_str); read_end = lnr_uni64(read_end); L = lnr_uni64(L);
-        hitEnd = (i64)lnr_uni32(nhits);
-    }
+    cords.p = (u64 *)lnr_uni64((u64)cords.p); cords.n = lnr_uni32(cords.n); cords.cap = lnr_uni32(cords.cap); cords.ovf = (int *)lnr_uni64((u64)cords.ovf);
+    for (int k = 0; k < 2; k++) { f1[k].p = (const F96 *)lnr_uni64((u64)f1[k].p); f1[k].n = lnr_uni32(f1[k].n); }
+    g.base = (const F96 *)lnr_uni64((u64)g.base); g.off = (const u64 *)lnr_uni64((u64)g.off); g.nseq = lnr_uni32(g.nseq);
+    read_str = lnr_uni64(read_str); read_end = lnr_uni64(read_end); L = lnr_uni64(L);
+    hitEnd = (i64)lnr_uni32(nhits);
     u64 tail;
-    if (cords.n == 0) { cords.template push_m<COOP>(F_END); tail = F_END; }   // initCords
-    else tail = lnr_u64<COOP>(cords[cords.n - 1]);
+    if (cords.n == 0) { cords.push_u(F_END); tail = F_END; }   // initCords
+    else tail = lnr_uni64(cords[cords.n - 1]);
     u64 ready_str, ready_end, cordy_str = 0, cordy_end = 0;
     bool f_sp_l, f_sp_r = false, f_block_end = false, f_append;
     i64 itt_next = hitBegin + 1, itt_first = hitBegin;
@@ -1222,13 +1201,9 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2],
     // the device the first 128 hits live in two registers per lane and are read with v_readlane (the index is wave-uniform); longer lists fall
     // back to memory beyond that.  The genome-feature view (two dependent loads of the offset table) is kept while the sequence id stays.
 #if defined(__HIP_DEVICE_COMPILE__)
-    u64 hreg0 = 0, hreg1 = 0;
-    if (COOP) {
-        const u32 ln_ = threadIdx.x & 63;
-        hreg0 = ln_ < nhits ? hits[ln_] : 0; hreg1 = ln_ + 64 < nhits ? hits[ln_ + 64] : 0;
-    }
+    const u32 ln_ = threadIdx.x & 63;
+    const u64 hreg0 = ln_ < nhits ? hits[ln_] : 0, hreg1 = ln_ + 64 < nhits ? hits[ln_ + 64] : 0;
     auto HIT = [&](i64 i) -> u64 {
-        if (!COOP) return hits[i];
         if (i < 128) {
             const u64 r = i < 64 ? hreg0 : hreg1;
             const int l_ = (int)(i & 63);
@@ -1260,8 +1235,8 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2],
         if (!f_sp_r && !f_block_end) {
             cordy_str = f_sp_l ? hi : (first_i ? ready_str : cord_y(tail));
             cordy_end = cord_y(HIT(itt_next));
-            if (cords.n >= cords.cap) { if (lnr_leader<COOP>()) *cords.ovf = 1; return; }
-            cords.template push_m<COOP>(hi & ~F_END); tail = hi & ~F_END;
+            if (cords.n >= cords.cap) { if (lnr_is_leader()) *cords.ovf = 1; return; }
+            cords.push_u(hi & ~F_END); tail = hi & ~F_END;
             f_append = true;
         } else {
             const u64 hl = HIT(itt_next - 1);
@@ -1269,8 +1244,8 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2],
                 u64 nc = shift_cord(hl, -96, -96);
                 cordy_str = first_i ? read_str : cord_y(nc);
                 cordy_end = cord_y(hl);
-                if (cords.n >= cords.cap) { if (lnr_leader<COOP>()) *cords.ovf = 1; return; }
-                cords.template push_m<COOP>(nc & ~F_END); tail = nc & ~F_END;
+                if (cords.n >= cords.cap) { if (lnr_is_leader()) *cords.ovf = 1; return; }
+                cords.push_u(nc & ~F_END); tail = nc & ~F_END;
                 f_append = true;
             }
         }
@@ -1278,14 +1253,12 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2],
         if (f_append && cord_id(hi) != view_id) { view_id = cord_id(hi); view_f2 = f2_view(g, view_id); }
 #if defined(LNR_PROF) && defined(__HIP_DEVICE_COMPILE__)
         { unsigned long long t_ = clock64(); pdc_[9] += t_ - pdt_; pdt_ = t_; pdc_[0] += f_append ? 1 : 0; pdc_[10]++; }
-        if (f_append && !(COOP ? extend_window(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end, pdc_)
-                               : extend_window_serial<false>(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end))) return;
+        if (f_append && !extend_window(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end, pdc_)) return;
         pdt_ = clock64();
         if (0)
 #endif
-        if (f_append && !(COOP ? extend_window(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end)
-                               : extend_window_serial<false>(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end))) return;
-        if (f_block_end) { tail |= F_END; if (lnr_leader<COOP>()) cords[cords.n - 1] = tail; }
+        if (f_append && !extend_window(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end)) return;
+        if (f_block_end) { tail |= F_END; if (lnr_is_leader()) cords[cords.n - 1] = tail; }
         itt_next = f_block_end ? itt_first : itt_next;
         f_sp_r = false; f_block_end = false;
     }

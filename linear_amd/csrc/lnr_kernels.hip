@@ -515,7 +515,7 @@ __global__ void __launch_bounds__(256) k_ix_ovcount(const i32 *dir, u64 nbuckets
     u32 dl = b < nbuckets ? (u32)(dir[b + 1] - dir[b]) : 0u;
     novl[b] = dl > BL_INLINE ? (i32)((dl - BL_INLINE + 15) >> 4) : 0;
 }
-__global__ void __launch_bounds__(256) k_ix_lines(const i32 *dir, const u64 *hs, const i32 *ovoff, u64 nbuckets, ulonglong2 *bl, u64 *ov, u64 *bh) {
+__global__ void __launch_bounds__(256) k_ix_lines(const i32 *dir, const u64 *hs, const i32 *ovoff, u64 nbuckets, ulonglong2 *bl, u64 *ov) {
     u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;     // one thread per 16-byte part of a line
     u64 b = t >> 3;
     if (b >= nbuckets) return;
@@ -531,7 +531,6 @@ __global__ void __launch_bounds__(256) k_ix_lines(const i32 *dir, const u64 *hs,
         else w[k] = slot - 1 < dl ? hs[(i64)ds + (i64)(slot - 1)] : 0ULL;
     }
     bl[t] = make_ulonglong2(w[0], w[1]);
-    if (part == 0 && bh) bh[b] = w[0];                       // the header words on their own: what the seed kernel looks at one chunk ahead
     if (dl > BL_INLINE) {                                    // the eight threads of the bucket copy its overflow run
         u32 m = dl - BL_INLINE, mpad = ((m + 15) >> 4) << 4;
         for (u32 i = part; i < mpad; i += 8) ov[(u64)o0 * 16 + i] = i < m ? hs[(i64)ds + BL_INLINE + (i64)i] : 0ULL;
@@ -579,7 +578,7 @@ __device__ inline u32 y_nomatch_push(u32 acc, u32 word, u32 Y) {
     return __builtin_amdgcn_alignbit(acc, d, 31);
 }
 __global__ void __launch_bounds__(64) k_seed_fused(JobArrays J, ReadArrays R, const ulonglong2 *bl, const u32 *bm /* null: table too dense to pay */, const u64 *ov, u32 njobs,
-                                                   SeedOutArrays O, u32 est_per_sample_x16, const u64 *bh /* header words of the bucket lines, densely (null: read them from bl) */) {
+                                                   SeedOutArrays O, u32 est_per_sample_x16) {
     __shared__ uint4 s_rec[64];                // per sample: X, bucket start, bucket length, Y | strand << 8
     __shared__ u32 s_mk[64];                   // sample (lane + 1) whose first line has this number within the round
     __shared__ u64 s_src[64];                  // source address of the round's 64 lines (for the lanes that fetch them)
@@ -657,10 +656,9 @@ __global__ void __launch_bounds__(64) k_seed_fused(JobArrays J, ReadArrays R, co
         looks += (u32)__popcll(__ballot(look));
         u32 xg = o.X >> BM_GROUP_LOG2;
         bool fetch = look && (!bm || ((bm[xg >> 5] >> (xg & 31)) & 1));
-        // the header comes from the dense table `bh` (8 bytes per bucket): read out of the bucket line itself it brought the whole 128-byte line
-        // on chip one chunk early, and at GRCh38 scale that line was gone from L2 again when the LDS-DMA of step 2 asked for it -- every
-        // bucket line crossed the fabric twice (round 2: 1.78 x the algorithmic bytes)
-        hdr = fetch ? (bh ? bh[o.X] : bl[(u64)o.X * 8].x) : 0ULL;
+        // the header is read out of the bucket line itself: that brings the whole 128-byte line on chip one chunk early, which warms L2 / MALL
+        // for the LDS-DMA of step 2 (a dense table of the header words was measured slower on the GRCh38 stand-in: 3.07 - 3.12 vs 2.97 - 3.00 ms)
+        hdr = fetch ? bl[(u64)o.X * 8].x : 0ULL;
     };
 #ifndef SEED_PREFETCH
 #define SEED_PREFETCH 1
@@ -1110,7 +1108,6 @@ struct JobArgs {
     u32 lds_bytes;          // dynamic LDS per block: binning histogram (swept in passes of lds_bytes bins) first, then the fast half of the job arena
     u32 arena_lds;          // bytes of that LDS the job arena may use
     u32 stop_after;         // diagnostic (LNR_STOP_AFTER, single-wave kernel only): leave the job after phase stop_after - 1; 0 = run everything
-    u32 *jstate;            // split path: per job {anchors after binning, anchors after the list filter | ok << 31} handed from the pre to the DP / post kernel
     unsigned long long *prof;   // diagnostic build (-DLNR_PROF) only: per-phase cycle sums of lane 0
     unsigned long long *tl;     // diagnostic build only: per launch position {start, end (100 MHz ticks), hw id, anchors in the DP}
 };
@@ -2173,7 +2170,9 @@ __device__ JOB_INLINE u32 gather_blocks_wave(const u64 *hits, u32 nh, UP *sep, u
     return nb;
 }
 // chain_blocks_prepare (f_sort = 1) with all lanes: keys, the tie-sensitive sort, the two gathers
-__device__ JOB_INLINE void chain_blocks_prepare_wave(const u64 *records, const UP *sep, const i32 *sep_score, u32 nb, BlockScratch s) {
+// (this and best_chains2_wave inlined by force, radix_sort_block of the 4- and 16-wave kernels called: the inlining the job kernels were
+// measured with -- left to the compiler it moves with the number of kernels that share these functions, and the bulk kernel ran 2-3 % slower)
+__device__ __forceinline__ void chain_blocks_prepare_wave(const u64 *records, const UP *sep, const i32 *sep_score, u32 nb, BlockScratch s) {
     int lane = lane_id();
     u64 *e = (u64 *)s.sep_tmp;
     for (u32 i = lane; i < nb; i += 64) e[i] = (cord_x40(records[sep[i].first]) << 24) | (u64)i;
@@ -2333,7 +2332,7 @@ __device__ JOB_INLINE u32 prefilter_chains2_wave(u64 *hits, u32 nhits, Vec<UP> &
 }
 // wave-parallel twin of best_chains2 with getApxChainScore2 (cluster_util.cpp:469-526,586-631): serial over blocks, lanes
 // over the <= 20 predecessors; among equal totals the LAST predecessor wins (ascending scan with >=).
-__device__ void best_chains2_wave(const u64 *hits, const UP *sep, const i32 *sep_score, u32 nb, Rec r, unsigned long long *dbg = nullptr) {
+__device__ __forceinline__ void best_chains2_wave(const u64 *hits, const UP *sep, const i32 *sep_score, u32 nb, Rec r, unsigned long long *dbg = nullptr) {
     int lane = lane_id();
     unsigned long long ta = 0, tb = 0, tc = 0, t0_ = 0, t1_ = 0, t2_ = 0;
     (void)ta; (void)tb; (void)tc; (void)t0_; (void)t1_; (void)t2_;
@@ -2467,31 +2466,6 @@ __device__ void best_chains_block(const u32 *xs, const u32 *ys, u32 m, Rec r, in
     }
 }
 
-// Where a job's chained hits wait for k_post: the last 12 x cap bytes (16-byte aligned) of its global scratch region.  The
-// region holds 160 x cap + 1 KB (job_scratch_bytes); the job kernel's own carving stays below 140 x cap and k_post's below
-// 124 x cap, both from the front.
-#ifndef POST_MAX_HITS
-#define POST_MAX_HITS 128
-#endif
-struct PostIn { u64 *hits; i32 *hscore; };
-__device__ __forceinline__ PostIn post_in_of(char *region, u32 cap) {
-    u64 bytes = (job_scratch_bytes(cap) + 255) & ~255ULL;
-    u64 need = ((u64)cap * 12 + 15) & ~15ULL;
-    PostIn p; p.hits = (u64 *)(region + bytes - need); p.hscore = (i32 *)(p.hits + cap);
-    return p;
-}
-// Replays the allocation sequence of the pre phase (global scratch only) from the two counts it left in jstate: n1 = anchors
-// after binning, m = anchors after the list filter.  Same calls in the same order -> same pointers.
-__device__ __forceinline__ void job_replay(const JobArgs &A, u32 j, u32 n1, u32 m, u32 *dyn_lds, Arena &slow, Arena &ar, u64 *&a, JobScratch &S, int *ovf) {
-    u32 cap = A.n_anchors[j] + 2;
-    slow.init(A.scratch + A.scr_off[j], job_scratch_bytes(cap));
-    ar.init((void *)dyn_lds, A.arena_lds); ar.next = &slow;
-    a = A.anchors + A.anc_off[j];
-    (void)slow.get<u64>(cap);
-    if (n1 > 1) a = ar.get<u64>((u64)n1 + 2);
-    if (m > 1) (void)slow.get<u64>((u64)m + 2);
-    (void)job_carve(ar, m, S, ovf);
-}
 // One workgroup per read: runs the read's jobs in order (round 0: the whole read; remap round: its gaps), appending
 // cords to the read's cord list exactly like consecutive apxMap_ calls do.
 //   NW == 1 : one wave does everything (the bulk of the reads).
@@ -2507,10 +2481,7 @@ struct SortShare { u64 *a; u32 *L, *R; u64 *tasks, *stg; u32 stg_cap, n; };
 #ifndef SORT_BLOCK_MIN
 #define SORT_BLOCK_MIN 2048
 #endif
-// PHASE: 0 = the whole job; 1 = up to the filled x / y arrays (state -> A.jstate); 2 = from the traceback on (the DP ran
-// in k_job_dp).  Phases 1 and 2 are launched with arena_lds = 0: every array then lives in the job's global scratch and
-// the allocation sequence, replayed from the two counts in jstate, yields the same pointers in all three kernels.
-template <int NW, int PHASE = 0>
+template <int NW>
 __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
     __shared__ u32 s_m;
     __shared__ int s_ovf, s_flag[4];
@@ -2536,7 +2507,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
     if (jb >= je) return;
     u32 r = A.J.read[jb];
     u64 L = A.read_len[r];
-    if (threadIdx.x == 0) { s_ovf = 0; s_flag[3] = 0; }
+    if (threadIdx.x == 0) s_ovf = 0;
     if (NW == 1) WSYNC(); else __syncthreads();
     Vec<u64> cords;
     cords.init(A.cords + A.cords_off[r], A.cords_cap[r], &s_ovf);
@@ -2567,7 +2538,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
         u64 *ag = nullptr, *s_alt = nullptr;
         u32 n = 0, cap = 0;
         u32 *so_L = nullptr, *so_R = nullptr; u64 *so_tasks = nullptr, *so_stg = nullptr; u32 so_stg_cap = 0;   // scratch of the x-descending sort
-        if (lead && PHASE != 2) {
+        if (lead) {
             ag = A.anchors + A.anc_off[j];
             n = A.n_anchors[j];
             cap = n + 2;   // scratch is sized by the anchors that passed the Y filter (known before the launch), not by the bucket entries
@@ -2589,15 +2560,18 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
                 if (NW == 1) radix_sort_wave(ag, alt, n, hist);
             }
         }
-        if (NW > 1 && PHASE != 2) {
+        if (NW > 1) {
             // the radix sort of a multi-wave workgroup is dealt over its waves (long arrays only: five barriers per pass)
             if (threadIdx.x == 0) { s_rs.a = ag; s_rs.alt = s_alt; s_rs.n = (n > 1 && n >= RADIX_BLOCK_MIN) ? n : 0; }
             __syncthreads();
             RadixShare rs = s_rs;
-            if (rs.n) radix_sort_block<NW>(rs.a, rs.alt, rs.n, s_rhist, s_rtot, &s_rflag);   // ends with a workgroup barrier
+            if (rs.n) {                                // ends with a workgroup barrier (call / inline: see chain_blocks_prepare_wave)
+                if (NW >= 4) { [[clang::noinline]] radix_sort_block<NW>(rs.a, rs.alt, rs.n, s_rhist, s_rtot, &s_rflag); }
+                else radix_sort_block<NW>(rs.a, rs.alt, rs.n, s_rhist, s_rtot, &s_rflag);
+            }
             else if (lead && n > 1) radix_sort_wave(ag, s_alt, n, hist);
         }
-        if (lead && PHASE != 2) {
+        if (lead) {
             if (n > 1) {
                 for (u32 i = lane; i < n; i += 64) a[i] = ag[i];
                 WSYNC();
@@ -2621,7 +2595,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
                 if (NW == 1) introsort_xdesc_wave(a, m, so_L, so_R, so_tasks, &s_ls, so_stg, so_stg_cap);
             }
         }
-        if (NW > 1 && PHASE != 2) {
+        if (NW > 1) {
             // the x-descending sort of a multi-wave workgroup: wave 0 partitions from the top, all waves finish the sub-ranges
             if (threadIdx.x == 0) { s_so.a = a; s_so.L = so_L; s_so.R = so_R; s_so.tasks = so_tasks; s_so.stg = so_stg; s_so.stg_cap = so_stg_cap; s_so.n = (m > 1 && m >= SORT_BLOCK_MIN) ? m : 0; }
             __syncthreads();
@@ -2629,7 +2603,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             if (so.n) introsort_xdesc_block<NW>(so.a, so.n, so.L, so.R, so.tasks, s_sstk, &s_sq, so.stg, so.stg_cap);   // ends with a workgroup barrier
             else if (lead && m > 1) introsort_xdesc_wave(a, m, so_L, so_R, so_tasks, &s_ls, so_stg, so_stg_cap);
         }
-        if (lead && PHASE != 2) {
+        if (lead) {
             LNR_TICK(prof, 15, tk_);
             if (NW == 1 && A.stop_after == 4) break;
             ok = job_carve(ar, m, S, &s_ovf) && !slow.ovf;
@@ -2638,18 +2612,6 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
                 WSYNC();
             } else if (lane == 0) s_ovf = 1;
             LNR_TICK(prof, 3, tk_);
-            if (PHASE == 1) {
-                if (lane == 0) { A.jstate[2 * j] = n; A.jstate[2 * j + 1] = m | (ok ? 0x80000000u : 0u); }
-                continue;                                 // the DP and everything behind it run in the next kernels
-            }
-        }
-        if (lead && PHASE == 2) {
-            u32 n1 = A.jstate[2 * j], mm = A.jstate[2 * j + 1];
-            job_replay(A, j, n1, mm & 0x7fffffffu, dyn_lds, slow, ar, a, S, &s_ovf);
-            m = mm & 0x7fffffffu;
-            ok = (mm >> 31) != 0;
-            if (!ok && lane == 0) s_ovf = 1;
-            WSYNC();
         }
 #ifdef LNR_PROF
         if (prof) {   // job count, anchors entering the DP, predecessor pairs
@@ -2664,7 +2626,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
         // ---------------- chaining DP
         if (NW == 1) {
             if (!ok) break;
-            if ((PHASE == 0 || PHASE == 3) && m >= 2) {
+            if (m >= 2) {
                 best_chains_wave(S.xs, S.ys, m, S.rec, job_parm(mode).score_type, S.cnt, s_tile.tleaf);
             }
         } else {
@@ -2687,22 +2649,6 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             if (m >= 2) traceback_anchor_wave(S.rec, m, sink, S.chain, S.chain_sc, S.cnt, s_flag, &s_ls);
             LNR_TICK(prof, 5, tk_);
             if (NW == 1 && A.stop_after == 6) break;
-            bool handed = false;
-            if (PHASE == 3 && je - jb == 1) {
-                // hand-off to k_post (one lane per read runs the stages a11-a16, which are chains of dependent steps per read).
-                // Only reads with few chained hits go: the block pre-filter is quadratic in the number of hit blocks, fine on one lane
-                // for a typical read and hopeless for a repeat-rich one (those keep the wave-parallel forms below).  Groups of
-                // several jobs (re-map round) stay here too: their jobs append to one cord list in order.
-                u32 nh = S.hits.n;
-                handed = nh <= POST_MAX_HITS && !s_ovf;
-                if (handed) {
-                    WSYNC();
-                    PostIn pi = post_in_of(A.scratch + A.scr_off[j], A.n_anchors[j] + 2);
-                    for (u32 i = (u32)lane; i < nh; i += 64) { pi.hits[i] = S.hits.p[i]; pi.hscore[i] = S.hscore.p[i]; }
-                    if (lane == 0) { A.jstate[2 * j] = m; A.jstate[2 * j + 1] = nh | 0x80000000u; s_flag[3] = 1; }
-                }
-            }
-            if (!handed) {
             JobCtx c;
             c.traceback_done = 1;
             c.L = L; c.read_str = A.J.str[j]; c.read_end = A.J.end[j]; c.mode = mode;
@@ -2724,7 +2670,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             const JobScratch S0 = S;
             u32 nb = 0;
             bool in_lds = false;
-            if (PHASE != 2 && A.arena_lds) {
+            if (A.arena_lds) {
                 Arena pl; pl.init((void *)dyn_lds, A.arena_lds);
                 const u32 nh = S.hits.n;
                 u64 *lh = pl.get<u64>((u64)nh + 2), *lH = pl.get<u64>((u64)nh + 2);
@@ -2817,7 +2763,6 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
                     LNR_TICK(prof, 9, tk_);
                 }
             }
-            }   // !handed
             WSYNC();
 #ifdef LNR_PROF
             if (A.prof && lane == 0) {   // phase cycles of the job with the most anchors in the DP (per launch class of 4: A.prof + 128 + 16 * class)
@@ -2834,7 +2779,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             if (s_ovf) break;             // uniform
         }
     }
-    if (lead && lane == 0) { if (PHASE != 1 && !(PHASE == 3 && s_flag[3])) A.ncords[r] = cords.n; if (s_ovf) A.read_err[r] = 1; }
+    if (lead && lane == 0) { A.ncords[r] = cords.n; if (s_ovf) A.read_err[r] = 1; }
 #ifdef LNR_PROF
     if (tl) tl[1] = wall_clock64();
 #endif
@@ -2851,39 +2796,6 @@ __global__ void __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
     job_group_run<1>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
 }
-// Split path for reads with many anchors: k_job_pre (one wave: binning .. x/y arrays) -> k_job_dp (16 waves: the chaining DP
-// and nothing else, so no wave idles through the serial phases) -> k_job_post (one wave: traceback .. cords), on one stream.
-__global__ void __launch_bounds__(64, 4) k_job_pre(JobArgs A) {
-    extern __shared__ u32 dyn_lds[];
-    if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<1, 1>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
-}
-__global__ void __launch_bounds__(64, 4) k_job_post(JobArgs A) {
-    extern __shared__ u32 dyn_lds[];
-    if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<1, 2>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
-}
-#define DP_SPLIT_WAVES 4
-__global__ void __launch_bounds__(64 * DP_SPLIT_WAVES) k_job_dp(JobArgs A) {
-    __shared__ DpTile<DP_SPLIT_WAVES> s_tile;
-    __shared__ DpShare s_dp;
-    if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    u32 grp = A.grp_order[A.grp_lo + blockIdx.x];
-    for (u32 j = A.grp_beg[grp]; j < A.grp_beg[grp + 1]; j++) {
-        if (threadIdx.x == 0) {
-            u32 n1 = A.jstate[2 * j], mm = A.jstate[2 * j + 1];
-            u32 m = mm & 0x7fffffffu;
-            Arena slow, ar; u64 *a; JobScratch S; int ovf = 0;
-            job_replay(A, j, n1, m, nullptr, slow, ar, a, S, &ovf);
-            s_dp.xs = S.xs; s_dp.ys = S.ys; s_dp.rec = S.rec; s_dp.jlo = S.cnt; s_dp.m = (mm >> 31) ? m : 0;
-            s_dp.score_type = job_parm((int)A.J.mode[j]).score_type; s_dp.abort = 0;
-        }
-        __syncthreads();
-        DpShare d = s_dp;
-        if (d.m >= 2) best_chains_block<DP_SPLIT_WAVES>(d.xs, d.ys, d.m, d.rec, d.score_type, d.jlo, s_tile);
-        __syncthreads();
-    }
-}
 __global__ void __launch_bounds__(1024) k_job_heavy(JobArgs A) {
     extern __shared__ u32 dyn_lds[];
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
@@ -2899,74 +2811,6 @@ __global__ void __launch_bounds__(128, 4) k_job_mid2(JobArgs A) {
     extern __shared__ u32 dyn_lds[];
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
     job_group_run<2>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
-}
-
-// ---- split form (default): the wave-parallel stages a8-a10 (binning .. chaining DP .. traceback) per read in k_job*_a, then
-// k_post with ONE LANE PER READ for the stages that are chains of dependent steps per read (a11-a16: block gathering, block
-// pre-filter, block chaining, window filter, window extension).  In the fused kernels those ran one lane of 64 for 70-80 % of a
-// read's time (phase stamps: extension 37 %, block chaining 19 %, gather + pre-filter 16 % at human scale) while the wave's
-// other lanes idled; here 64 reads share a wave, every read of the batch is resident at once, and the stage is over when its
-// longest chain is.
-__global__ void __launch_bounds__(64, 4) k_job_a(JobArgs A) {
-    extern __shared__ u32 dyn_lds[];
-    if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<1, 3>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
-}
-__global__ void __launch_bounds__(256, 4) k_job_mid_a(JobArgs A) {
-    extern __shared__ u32 dyn_lds[];
-    if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<4, 3>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
-}
-__global__ void __launch_bounds__(1024) k_job_heavy_a(JobArgs A) {
-    extern __shared__ u32 dyn_lds[];
-    if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<16, 3>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
-}
-__global__ void __launch_bounds__(64) k_post(JobArgs A) {
-    u32 pos = A.grp_lo + blockIdx.x * 64 + threadIdx.x;
-    if (pos >= A.grp_hi) return;
-    u32 grp = A.grp_order[pos];
-    u32 jb = A.grp_beg[grp], je = A.grp_beg[grp + 1];
-    if (jb >= je) return;
-    u32 r = A.J.read[jb];
-    if (A.read_err[r]) return;
-    u64 L = A.read_len[r];
-    int ovf = 0;
-    Vec<u64> cords;
-    cords.init(A.cords + A.cords_off[r], A.cords_cap[r], &ovf);
-    cords.n = A.ncords[r];
-    LeaderScratch ls;
-    for (u32 j = jb; j < je && !ovf; j++) {
-        u32 m = A.jstate[2 * j], st = A.jstate[2 * j + 1];
-        if (!(st >> 31)) return;                        // not handed over: the job kernel ran these stages itself (or flagged the read)
-        u32 nh = st & 0x7fffffffu;
-        u32 cap = A.n_anchors[j] + 2;
-        char *region = A.scratch + A.scr_off[j];
-        PostIn pi = post_in_of(region, cap);
-        Arena ar; ar.init(region, (u64)((char *)pi.hits - region));
-        JobScratch S;
-        if (!job_carve(ar, m, S, &ovf)) { ovf = 1; break; }
-        u64 *a2 = ar.get<u64>((u64)m + 2);              // output of _filterBlocksHits (the fused kernel reuses the dead anchor array)
-        if (ar.ovf) { ovf = 1; break; }
-        S.hits.init(pi.hits, cap, &ovf); S.hits.n = nh;
-        S.hscore.init(pi.hscore, cap, &ovf); S.hscore.n = nh;
-        JobCtx c;
-        c.traceback_done = 1;
-        c.L = L; c.read_str = A.J.str[j]; c.read_end = A.J.end[j]; c.mode = (int)A.J.mode[j];
-        u32 nf = A.nf[r];
-        c.f1[0].p = A.f1 + A.f1_off[r]; c.f1[0].n = nf;
-        c.f1[1].p = A.f1 + A.f1_off[r] + nf; c.f1[1].n = nf;
-        c.g = A.g; c.bins = nullptr; c.nbins = 0; c.pair_evals = nullptr; c.prof = nullptr;
-        u64 *H = nullptr; u32 nH = 0;
-        if (job_phase3a(a2, m, S, c, nullptr, H, nH, ls)) { ovf = 1; break; }
-        if (nH >= 2) {
-            filter_hits_flags(H, nH, c.f1, c.g, S.cnt, 0, 1);
-            nH = filter_hits_apply(H, nH, S.cnt);
-            path_dst_2<false>(H, nH, c.f1, c.g, cords, c.read_str, c.read_end, L);
-        }
-    }
-    A.ncords[r] = cords.n;
-    if (ovf) A.read_err[r] = 1;
 }
 
 // Placed on the bulk stream ahead of k_job when multi-wave kernels were launched beside it: a 4- or 16-wave workgroup

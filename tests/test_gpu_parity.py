@@ -101,12 +101,15 @@ def test_gpu_scratch_slicing(oracle_lib):
     f.close()
 
 
-@pytest.mark.parametrize("var,val", [("LNR_MID_CAP", "64"), ("LNR_DP_SPLIT_CAP", "64"), ("LNR_SPLIT_CAP", "300"), ("LNR_POST_SPLIT", "1")])
-def test_gpu_other_size_class_paths(case_inputs, monkeypatch, var, val):
-    """Force the reads through the 4-wave kernel, the split path (pre -> 16-wave DP kernel -> post) and the two-lane
-    orchestration, and the k_post split (serial stages with one lane per read): same cords as the reference."""
+@pytest.mark.parametrize("env", [{"LNR_MID_CAP": "64"}, {"LNR_HEAVY_CAP": "900", "LNR_MID_CAP": "300"}],
+                         ids=["LNR_MID_CAP-64", "LNR_HEAVY_CAP-900-LNR_MID_CAP-300"])
+def test_gpu_other_size_class_paths(case_inputs, monkeypatch, env):
+    """Force the reads through the 4-wave kernel, and through the 16-wave and the 4-wave kernel in one launch (the 4-wave
+    kernel then runs on the spare stream beside the 16-wave one, the single-wave kernel on the bulk stream): same cords
+    as the reference."""
     from linear_amd import Filter
-    monkeypatch.setenv(var, val)
+    for var, val in env.items():
+        monkeypatch.setenv(var, val)
     f = Filter(device=0)
     for name, T in (("rep", 1), ("edge", 3), ("ont", 4)):
         refs, reads, off = case_inputs(name)

@@ -1,4 +1,4 @@
-# kernel trace of the last batch of the GRCh38 probe: start / duration of every lnr kernel (env passes through, e.g. LNR_POST_SPLIT)
+# kernel trace of the last batch of the GRCh38 probe: start / duration of every lnr kernel (env passes through, e.g. LNR_HEAVY_CAP)
 OUT=gpurun_out/${1:-ptrace}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p $OUT && rm -rf $OUT/prof
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof -- python3 tools/grch38_probe.py --batches 1 ${PROBE_ARGS} > $OUT/probe.log 2>&1 || { tail -5 $OUT/probe.log; exit 1; }
