@@ -155,6 +155,19 @@ lnr_status lnr_filter_batch(lnr_ctx *ctx, const uint8_t *reads_concat, const uin
  * until the lnr_filter_wait that RETURNS its batch has returned; the host arrays of a result stay valid until the SECOND next result of the
  * context (two result slots taken in turn: another thread may format batch k while the context runs on).  lnr_last_stats reports the batch
  * handed out last.  lnr_gap_stream(set >= 0) and lnr_set_gap need an idle context (nothing in flight).
+ * Two lanes (gap_len == 0; LNR_LANES=1 in the environment of lnr_create switches them off): the submitted batches are dealt in turn to
+ * two lanes of the context that COMPUTE side by side -- each lane has a worker thread of the library that runs a batch as soon as it is
+ * uploaded, so lnr_filter_wait only waits for the oldest batch, downloads and returns it.  The re-map round of batch k (a few long reads,
+ * the chip nearly empty) then runs under the seed lookup and the first job round of batch k + 1.  Lane 0 is the context itself; lane 1 is
+ * made when a second batch is first in flight, shares the index (views, no copy) and owns a second set of per-batch buffers (about what
+ * one batch needs; the bench process peaks at 162 GiB instead of 103); where that memory cannot be had -- at creation, for the input, or
+ * LNR_ERR_NOMEM inside a batch on lane 1 -- that batch is run again on lane 0 and the context goes on with one lane, no error reported.  Everything above
+ * holds unchanged: submission order, three in flight, lifetimes, errors reported by the lnr_filter_wait of the batch they belong to.  The
+ * event-timed stage times in lnr_stats (seed_count_ms, job_ms, total_ms ...) of a batch then include time in which the chip was shared
+ * with the neighbouring batch: they add up to more than the step time.  With gap_len > 0 batches run one at a time in submission order
+ * (the gap re-mapper's stream state goes from batch to batch), computed inside lnr_filter_wait as before.  While batches are in flight the
+ * index calls, lnr_filter_batch*, lnr_seed_lookup_batch*, lnr_last_gaps and lnr_cords_to_host return LNR_ERR_ARG; lnr_destroy gives
+ * the batches in flight up and returns.
  * A read buffer in pinned host memory (lnr_host_alloc, or the caller's own hipHostMalloc / hipHostRegister) is uploaded by one
  * DMA at link rate; a pageable one goes through the context's pinned staging buffers first. */
 lnr_status lnr_filter_submit(lnr_ctx *ctx, const uint8_t *reads_concat, const uint64_t *off, uint32_t n);

@@ -15,6 +15,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
+#include <condition_variable>
+#include <deque>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -23,11 +28,23 @@ using namespace lnr;
 
 namespace {
 
+// Counter of the (re)allocations of the thread's current batch: filter_dev points it at its context's counter, so that with two lanes
+// every lane counts its own (an allocation in a timed step is a device-wide stall; LNR_DEBUG_TIMES prints the count)
+thread_local std::atomic<unsigned> *t_allocs = nullptr;
+struct AllocCount {     // (nests: the capacity re-run calls filter_dev from inside filter_dev)
+    std::atomic<unsigned> *prev;
+    explicit AllocCount(std::atomic<unsigned> *c) : prev(t_allocs) { t_allocs = c; }
+    ~AllocCount() { t_allocs = prev; }
+};
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    bool owned = true;      // false: a view of another context's buffer (the index a lane shares with its parent), never freed or grown here
     bool ensure(size_t bytes) {
         if (bytes <= cap && p) return true;
+        if (!owned) return false;
+        if (t_allocs) ++*t_allocs;
         bool grown = p != nullptr;          // a buffer that had to grow once gets half as much again: batch-dependent sizes creep, and
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }   // re-allocating GBs in the middle of a run costs hundreds of ms
         size_t nc = bytes + (grown ? bytes / 2 : bytes / 8) + 4096;
@@ -41,19 +58,21 @@ struct DevBuf {
     size_t hcap = 0;
     void *host_stage(size_t bytes) {
         if (bytes <= hcap && hp) return hp;
+        if (t_allocs) ++*t_allocs;
         if (hp) { (void)hipHostFree(hp); hp = nullptr; hcap = 0; }
         size_t nc = bytes + bytes / 8 + 4096;
         if (hipHostMalloc(&hp, nc, hipHostMallocDefault) != hipSuccess) { hp = nullptr; hcap = 0; (void)hipGetLastError(); return nullptr; }
         hcap = nc;
         return hp;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; if (hp) (void)hipHostFree(hp); hp = nullptr; hcap = 0; }
+    void release() { if (p && owned) (void)hipFree(p); p = nullptr; cap = 0; owned = true; if (hp) (void)hipHostFree(hp); hp = nullptr; hcap = 0; }
+    void alias(const DevBuf &o) { release(); p = o.p; cap = o.cap; owned = false; }
     ~DevBuf() { release(); }
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
     template <class T> T *as() const { return (T *)p; }
-    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(hp, o.hp); std::swap(hcap, o.hcap); }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(owned, o.owned); std::swap(hp, o.hp); std::swap(hcap, o.hcap); }
 };
 
 // pinned host staging (device-to-host copies from pageable memory run at a fraction of the link rate)
@@ -63,6 +82,7 @@ struct PinBuf {
     bool ensure(size_t bytes) {
         if (bytes <= cap && p) return true;
         bool grown = p != nullptr;
+        if (t_allocs) ++*t_allocs;
         if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
         size_t nc = bytes + (grown ? bytes / 2 : bytes / 8) + 4096;
         if (hipHostMalloc(&p, nc, hipHostMallocDefault) != hipSuccess) { p = nullptr; cap = 0; (void)hipGetLastError(); return false; }
@@ -110,6 +130,17 @@ static inline hipError_t words_in(void *d_dst, const void *h_pinned, size_t byte
 static const u64 SEQ_PAD = 64;
 static inline u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
 
+// The context's error text.  With two lanes a worker thread writes it (lane 0 is the context itself) while the caller's thread may
+// write or read it: assignments are serialised, and lnr_last_error hands out a copy that only the caller's thread touches.
+struct ErrText {
+    std::mutex m;
+    std::string s, shown;
+    ErrText &operator=(const std::string &v) { std::lock_guard<std::mutex> g(m); s = v; return *this; }
+    ErrText &operator=(const char *v) { std::lock_guard<std::mutex> g(m); s = v; return *this; }
+    std::string get() { std::lock_guard<std::mutex> g(m); return s; }
+    const char *show() { std::lock_guard<std::mutex> g(m); shown = s; return shown.c_str(); }
+};
+
 struct Timer {
     hipEvent_t a = nullptr, b = nullptr;
     void init() { (void)hipEventCreate(&a); (void)hipEventCreate(&b); }
@@ -125,7 +156,7 @@ struct lnr_ctx {
     lnr_opts opts;
     int device = 0;
     hipStream_t stream = nullptr;
-    std::string err;
+    ErrText err;
     // ---- index
     bool has_index = false;
     lnr_index_info info{};
@@ -166,6 +197,35 @@ struct lnr_ctx {
     // one it returns travel to the host), and the second set of device result buffers it lives in
     struct Pre { bool valid = false; lnr_status st = LNR_OK; u32 n = 0; u64 tot = 0; lnr_stats stats; std::vector<u64> coff; const void *d_str = nullptr, *d_end = nullptr; std::string err; } pre;
     DevBuf rB_off, rB_str, rB_end;
+    // ---- lanes: with gap_len == 0 the batches of lnr_filter_submit are dealt in turn to two lanes that compute side by side (the re-map
+    // round of batch k leaves the chip almost empty; seed lookup and round 0 of batch k + 1 fill it).  Lane 0 is this context, lane 1 a
+    // private context (made on first use) whose index buffers are views of this one's; everything per batch -- streams, events, input
+    // slots, job sets, scratch, result buffers, stats -- is the lane's own.  One worker thread per lane runs the synchronous filter_dev
+    // as soon as the lane has an uploaded batch and a free result set; lnr_filter_wait only waits, downloads and hands out.
+    // `mu` guards tickets' `done`, the lanes' queues and counters; a Ticket's other fields belong to the worker from push to `done`.
+    struct Ticket { int lane = 0, slot = 0, res_lane = 0, res_set = 0; bool done = false; Pre pre; };   // lane: whose input slot; res_lane: whose result set (differs after a fallback)
+    struct Lane {
+        lnr_ctx *c = nullptr;
+        std::thread th;
+        std::deque<Ticket *> work;      // uploaded, not computed yet (submission order)
+        bool slot_busy[3] = {false, false, false};
+        u32 pending = 0;                // submitted and not computed to the end
+        u32 unhanded = 0;               // computed and not handed out: each holds one of the lane's two result sets
+        bool busy = false;              // a worker is inside filter_dev on this lane's state
+        bool set_used[2] = {false, false};   // result sets that hold a batch not handed out yet; set_cur: the one r_off / r_str / r_end are now
+        int set_cur = 0;
+    } lane[2];
+    u32 nlanes = 2;                     // LNR_LANES=1|2
+    int lane1_prio = 1;                 // stream priority of lane 1's kernel streams: 1 = low (diagnostic: LNR_LANE1_PRIO=-1|0|1; see lane_create)
+    std::atomic<bool> lane1_off{false}; // lane 1 could not be set up or ran out of memory: everything is computed on lane 0 from now on
+    bool lane1_nomem_test = false;      // diagnostic (LNR_LANE1_NOMEM=1): lane 1's first batch fails as if the device were full, to exercise that fallback
+    bool is_lane = false;               // a lane's private context: index buffers are views, no copy streams
+    int lane_id = 0;
+    std::deque<std::unique_ptr<Ticket>> tickets;   // in flight, submission order (caller's thread only)
+    std::mutex mu;
+    std::condition_variable cv;
+    bool quit = false;
+    std::atomic<unsigned> allocs{0};    // device / pinned (re)allocations made for this lane's batches
     lnr_stats stats_pub;                 // statistics of the batch handed out last (what lnr_last_stats reports)
     u32 in_n[3] = {0, 0, 0};
     int in_head = 0, in_count = 0;
@@ -942,6 +1002,7 @@ lnr_status remap_round(lnr_ctx *ctx, const BatchHost &B, HostJobs &j1) {
 lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, lnr_cords_dev *out, const u64 *h_off = nullptr, int attempt = 0) {
     if (!ctx->has_index) { ctx->err = "no index: call lnr_index_build or lnr_index_adopt first"; return LNR_ERR_NO_INDEX; }
     reset_stats(ctx);
+    AllocCount count_(&ctx->allocs);
     ctx->last_n = n; ctx->last_ncords = 0;
     if (out) { out->n_reads = n; out->n_cords = 0; out->d_cord_off = nullptr; out->d_cords_str = nullptr; out->d_cords_end = nullptr; }
     ENSURE(ctx->r_off, ((size_t)n + 1) * 8);
@@ -1201,6 +1262,7 @@ lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, 
     ctx->t_total.stop(ctx->stream);
     HIPCK(hipStreamSynchronize(ctx->stream));
     laps.lap("tailB+gather");
+    if (laps.on) { char b[64]; snprintf(b, sizeof b, " | lane %d allocations so far %u", ctx->lane_id, ctx->allocs.load()); laps.out += b; }
     laps.done();
     ctx->stats.prep_ms = ctx->t_prep.ms();
     ctx->stats.total_ms = ctx->t_total.ms();
@@ -1273,16 +1335,18 @@ void par_memcpy(void *dst, const void *src, size_t len) {
 }
 
 // Upload of one batch into input slot `slot`, asynchronously on the copy stream; ev_in[slot] marks its end.
-lnr_status submit_reads(lnr_ctx *ctx, int slot, const u8 *reads, const u64 *off, u32 n) {
+// (L: the lane whose slot it is -- the copy stream, the staging ring and the error text are the context's)
+lnr_status submit_reads(lnr_ctx *ctx, lnr_ctx *L, int slot, const u8 *reads, const u64 *off, u32 n) {
     if (!off || (n && !reads)) { ctx->err = "null read buffer"; return LNR_ERR_ARG; }
     for (u32 i = 0; i < n; i++)
         if (off[i + 1] < off[i]) { ctx->err = "read offsets not monotone"; return LNR_ERR_ARG; }   // (before anything is sized by them)
     u64 base = off[0], total = off[n] - off[0];
-    DevBuf &dr = ctx->in_reads[slot], &dof = ctx->in_off[slot];
+    DevBuf &dr = L->in_reads[slot], &dof = L->in_off[slot];
+    AllocCount count_(&L->allocs);
     ENSURE(dr, std::max<u64>(total, 16));
     ENSURE(dof, ((size_t)n + 1) * 8);
-    if (!ctx->h_off[slot].ensure(((size_t)n + 1) * 8)) { ctx->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
-    u64 *o = ctx->h_off[slot].as<u64>();
+    if (!L->h_off[slot].ensure(((size_t)n + 1) * 8)) { ctx->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+    u64 *o = L->h_off[slot].as<u64>();
     for (u32 i = 0; i <= n; i++) o[i] = off[i] - base;
     hipStream_t sc = ctx->s_copy;
     if (total) {
@@ -1312,8 +1376,8 @@ lnr_status submit_reads(lnr_ctx *ctx, int slot, const u8 *reads, const u64 *off,
         }
     }
     HIPCK(hipMemcpyAsync(dof.p, o, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, sc));
-    HIPCK(hipEventRecord(ctx->ev_in[slot], sc));
-    ctx->in_n[slot] = n;
+    HIPCK(hipEventRecord(L->ev_in[slot], sc));
+    L->in_n[slot] = n;
     return LNR_OK;
 }
 
@@ -1350,9 +1414,13 @@ const char *lnr_strerror(lnr_status s) {
     }
     return "unknown status";
 }
-const char *lnr_last_error(const lnr_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+const char *lnr_last_error(const lnr_ctx *ctx) { return ctx ? const_cast<lnr_ctx *>(ctx)->err.show() : "null context"; }
 
-lnr_status lnr_create(const lnr_opts *opts, lnr_ctx **out) {
+}  // extern "C"
+namespace {
+// A context; stream_prio / as_lane: lane 1 of another context (lane_create), whose kernel streams get a priority of their own and
+// which needs no copy streams (uploads and downloads of every lane run on the parent's).
+lnr_status ctx_create(const lnr_opts *opts, int stream_prio, bool as_lane, lnr_ctx **out) {
     if (!out) return LNR_ERR_ARG;
     *out = nullptr;
     lnr_opts o;
@@ -1371,7 +1439,15 @@ lnr_status lnr_create(const lnr_opts *opts, lnr_ctx **out) {
     if (!ctx) return LNR_ERR_NOMEM;
     ctx->opts = o;
     ctx->device = dev;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return LNR_ERR_HIP; }
+    ctx->is_lane = as_lane;
+    ctx->lane[0].c = ctx;
+    auto mk_stream = [stream_prio](hipStream_t *st) {
+        return stream_prio ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, stream_prio) : hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+    };
+    if (mk_stream(&ctx->stream) != hipSuccess) { delete ctx; return LNR_ERR_HIP; }
+    if (const char *e = getenv("LNR_LANES")) { long v = atol(e); if (v == 1 || v == 2) ctx->nlanes = (u32)v; }
+    if (const char *e = getenv("LNR_LANE1_NOMEM")) ctx->lane1_nomem_test = atoi(e) != 0;
+    if (const char *e = getenv("LNR_LANE1_PRIO")) { long v = atol(e); if (v >= -1 && v <= 1) ctx->lane1_prio = (int)v; }
     if (const char *e = getenv("LNR_CAP_SHRINK")) { long v = atol(e); if (v >= 1 && v <= 4096) ctx->cap_shrink = (u32)v; }
     if (const char *e = getenv("LNR_GAP_TEAMS")) { long v = atol(e); if (v >= 1 && v <= 4096) ctx->gap_teams = (u32)v; }
     { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, ctx->device) == hipSuccess) ctx->ncu = (u32)pr.multiProcessorCount; else (void)hipGetLastError(); }
@@ -1396,10 +1472,10 @@ lnr_status lnr_create(const lnr_opts *opts, lnr_ctx **out) {
     // default) and two streams on one queue run their kernels back to back (measured: the bulk kernel waited for the 4-wave kernel).
     bool ok = hipEventCreateWithFlags(&ctx->ev_start, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&ctx->ev_f1, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&ctx->s_spare, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&ctx->s_bulk, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&ctx->s_tail, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&ctx->s_copy, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&ctx->s_down, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && mk_stream(&ctx->s_spare) == hipSuccess && mk_stream(&ctx->s_bulk) == hipSuccess;
+    ok = ok && mk_stream(&ctx->s_tail) == hipSuccess;
+    ok = ok && (as_lane || hipStreamCreateWithFlags(&ctx->s_copy, hipStreamNonBlocking) == hipSuccess);
+    ok = ok && (as_lane || hipStreamCreateWithFlags(&ctx->s_down, hipStreamNonBlocking) == hipSuccess);
     ok = ok && hipEventCreateWithFlags(&ctx->ev_down, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming) == hipSuccess;
     for (int k = 0; k < 3 && ok; k++) ok = hipEventCreateWithFlags(&ctx->ev_in[k], hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ctx->ev_join_spare, hipEventDisableTiming) == hipSuccess &&
@@ -1410,9 +1486,135 @@ lnr_status lnr_create(const lnr_opts *opts, lnr_ctx **out) {
     return LNR_OK;
 }
 
+// What a lane shares with its parent: the index (device buffers as views -- 9 GB at human scale are neither copied nor made to compete
+// with themselves for the Infinity Cache), its host mirrors, the options and the tuning knobs.  Called with lane 1 idle.
+void lane_mirror(lnr_ctx *L, lnr_ctx *P) {
+    L->g.alias(P->g); L->dir.alias(P->dir); L->hs.alias(P->hs); L->f2.alias(P->f2); L->d_seq_off.alias(P->d_seq_off); L->d_f2_off.alias(P->d_f2_off);
+    L->bm.alias(P->bm); L->bl.alias(P->bl); L->ov.alias(P->ov); L->hx_nkeys.alias(P->hx_nkeys); L->hx_nvals.alias(P->hx_nvals); L->d_seq_len.alias(P->d_seq_len);
+    L->hx_nnodes = P->hx_nnodes; L->hx_empty_dir = P->hx_empty_dir;
+    L->has_index = P->has_index; L->info = P->info; L->seq_len = P->seq_len; L->seq_off = P->seq_off; L->f2_off = P->f2_off; L->nbins = P->nbins;
+    L->opts = P->opts;
+    L->job_lds_bytes = P->job_lds_bytes; L->heavy_lds_kb = P->heavy_lds_kb; L->mid_cap = P->mid_cap; L->mid_lds_kb = P->mid_lds_kb; L->heavy_cap = P->heavy_cap;
+    L->heavy_cap_r1 = P->heavy_cap_r1; L->mid_cap_r1 = P->mid_cap_r1; L->stop_after = P->stop_after; L->mid_waves = P->mid_waves; L->mid_cap_env = P->mid_cap_env;
+    L->seed_bm = P->seed_bm; L->prep_threads = P->prep_threads; L->prep_grid = P->prep_grid; L->bulk_delay_ticks = P->bulk_delay_ticks;
+    L->cap_shrink = P->cap_shrink; L->seed_lds_pad = P->seed_lds_pad; L->ncu = P->ncu;
+}
+
+lnr_status compute_slot(lnr_ctx *C, lnr_ctx *In, int slot, lnr_ctx::Pre &P);
+
+// gives back the large per-batch device buffers of a lane that is switched off (its input slots and result sets stay: batches
+// uploaded or computed there are still to be run / handed out)
+void lane_release_batch(lnr_ctx *L) {
+    for (int k = 0; k < 2; k++) { L->js[k].anchors.release(); L->js[k].cap_slots = 0; }
+    L->ln.job_scr.release(); L->tb_remap.scr.release(); L->tb_early.scr.release(); L->tb_late.scr.release();
+    L->pk.release(); L->nm.release(); L->f1.release(); L->cords.release(); L->out_str.release(); L->out_end.release(); L->gaps.release(); L->gdense.release();
+}
+
+// One lane's worker: takes the lane's uploaded batches in submission order and runs each to the end (filter_dev is synchronous; the
+// thread sleeps in its stream syncs).  A batch that fails parks its status in its ticket; the worker goes on with the next.
+void lane_worker(lnr_ctx *top, int li) {
+    lnr_ctx::Lane &Ln = top->lane[li], &L0 = top->lane[0];
+    lnr_ctx *L = Ln.c;
+    (void)hipSetDevice(top->device);
+    std::unique_lock<std::mutex> lk(top->mu);
+    auto take_set = [](lnr_ctx::Lane &R, lnr_ctx::Ticket *T) {   // (under the lock; R.unhanded < 2, so one of the two is free)
+        T->res_set = R.set_used[0] ? 1 : 0;
+        R.set_used[T->res_set] = true;
+    };
+    auto run = [&](lnr_ctx::Lane &R, lnr_ctx::Ticket *T) {     // T on lane R's state, with the lock released; R.busy is set
+        lnr_ctx *C = R.c;
+        // into a free one of the lane's two result sets: the batch computed before this one may still be waiting for its download
+        if (T->res_set != R.set_cur) { C->r_off.swap(C->rB_off); C->r_str.swap(C->rB_str); C->r_end.swap(C->rB_end); R.set_cur = T->res_set; }
+        compute_slot(C, L, T->slot, T->pre);
+        if (T->pre.st == LNR_OK && !C->rB_str.p) {
+            // the lane's first batch: size the other result set now, not in the lane's second batch (with two lanes that one is already
+            // past a caller's two warm-up batches, and an allocation stalls the whole device)
+            AllocCount count_(&C->allocs);
+            (void)C->rB_off.ensure(C->r_off.cap); (void)C->rB_off.host_stage(C->r_off.hcap); (void)C->rB_str.ensure(C->r_str.cap); (void)C->rB_end.ensure(C->r_end.cap);
+        }
+    };
+    for (;;) {
+        // (lane 0 leaves its state to a batch that lane 1 could not hold: that batch is older than anything lane 0 has left to do
+        //  but one, and lnr_filter_wait hands out in submission order)
+        top->cv.wait(lk, [&] { return top->quit || (!Ln.work.empty() && (li == 1 || (Ln.unhanded < 2 && !Ln.busy && !(top->lane1_off && top->lane[1].pending > 0))) && (li == 0 || top->lane1_off || Ln.unhanded < 2)); });
+        if (top->quit) return;
+        lnr_ctx::Ticket *T = Ln.work.front();
+        Ln.work.pop_front();
+        bool on_own = li == 0 || !top->lane1_off;
+        if (on_own) {
+            Ln.busy = true;
+            take_set(Ln, T);
+            lk.unlock();
+            if (li == 1 && top->lane1_nomem_test) { top->lane1_nomem_test = false; T->pre = lnr_ctx::Pre(); T->pre.valid = true; T->pre.st = LNR_ERR_NOMEM; T->pre.err = "LNR_LANE1_NOMEM: allocation failure injected"; }
+            else run(Ln, T);
+            lk.lock();
+            Ln.busy = false;
+            if (li == 1 && T->pre.st == LNR_ERR_NOMEM) {
+                Ln.set_used[T->res_set] = false;
+                // No room for a second lane's batch state (a workload that fits once, not twice): one lane from now on.  Lane 1's
+                // buffers are given back and the batch is run again on lane 0; its input stays where it was uploaded.
+                top->lane1_off = true;
+                on_own = false;
+                lk.unlock();
+                (void)hipStreamSynchronize(L->stream); (void)hipStreamSynchronize(L->s_spare); (void)hipStreamSynchronize(L->s_bulk); (void)hipStreamSynchronize(L->s_tail);
+                lane_release_batch(L);
+                if (getenv("LNR_DEBUG_TIMES")) fprintf(stderr, "[lnr] lane 1 out of memory: its batch runs again on lane 0, one lane from now on\n");
+                lk.lock();
+                top->cv.notify_all();
+            }
+        }
+        if (!on_own) {
+            top->cv.wait(lk, [&] { return top->quit || (!L0.busy && L0.unhanded < 2); });
+            if (top->quit) return;
+            L0.busy = true;
+            take_set(L0, T);
+            lk.unlock();
+            run(L0, T);
+            lk.lock();
+            L0.busy = false;
+        }
+        lnr_ctx::Lane &R = on_own ? Ln : L0;
+        T->res_lane = on_own ? li : 0;
+        T->done = true;
+        Ln.slot_busy[T->slot] = false; Ln.pending--; R.unhanded++;
+        top->cv.notify_all();
+    }
+}
+
+// Lane 1 of ctx.  Stream priority: the runtime keeps a pool of hardware queues per priority, so kernel streams of another priority
+// than lane 0's do not share a queue with them (two streams on one queue run back to back: lane 1's seed lookup would wait behind
+// lane 0's 26 ms bulk kernel and the overlap would be gone).  Measured on the bench workload (ms per step; one lane: 43.4):
+// same priority 46.8 -- slower than one lane --, lane 1 high 37.9, lane 1 low 35.2.  Low is the default.
+lnr_status lane_create(lnr_ctx *ctx) {
+    lnr_opts o = ctx->opts;
+    o.device = ctx->device;
+    lnr_ctx *L = nullptr;
+    lnr_status s = ctx_create(&o, ctx->lane1_prio, true, &L);
+    if (s != LNR_OK) return s;
+    L->lane_id = 1; L->nlanes = 1;
+    ctx->lane[1].c = L;
+    return LNR_OK;
+}
+
+bool in_flight(const lnr_ctx *ctx) { return ctx->in_count || ctx->pre.valid || !ctx->tickets.empty(); }
+bool two_lanes(const lnr_ctx *ctx) { return ctx->nlanes == 2 && ctx->opts.gap_len == 0 && !ctx->is_lane; }
+}  // namespace
+extern "C" {
+
+lnr_status lnr_create(const lnr_opts *opts, lnr_ctx **out) { return ctx_create(opts, 0, false, out); }
+
 void lnr_destroy(lnr_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
+    // batches still in flight are given up: a worker finishes the batch it is in (tens of ms) and leaves the rest
+    { std::lock_guard<std::mutex> g(ctx->mu); ctx->quit = true; }
+    ctx->cv.notify_all();
+    for (int l = 0; l < 2; l++) if (ctx->lane[l].th.joinable()) ctx->lane[l].th.join();
+    ctx->tickets.clear();
+    // (an upload into a lane's input slot, or a download out of its result set, may still be queued on this context's copy streams)
+    if (ctx->s_copy) (void)hipStreamSynchronize(ctx->s_copy);
+    if (ctx->s_down) (void)hipStreamSynchronize(ctx->s_down);
+    if (ctx->lane[1].c) { lnr_destroy(ctx->lane[1].c); ctx->lane[1].c = nullptr; }
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->s_spare) (void)hipStreamSynchronize(ctx->s_spare);
     if (ctx->s_bulk) (void)hipStreamSynchronize(ctx->s_bulk);
@@ -1446,6 +1648,7 @@ lnr_status lnr_index_build(lnr_ctx *ctx, const uint8_t *const *seq, const uint64
         if (!seq[i]) { ctx->err = "null sequence pointer"; return LNR_ERR_ARG; }
         if (len[i] >= (1ULL << 30) - (1ULL << 20)) { ctx->err = "sequence too long for the 30-bit x field (cords.cpp:13-14)"; return LNR_ERR_LIMIT; }
     }
+    if (in_flight(ctx)) { ctx->err = "lnr_index_build: batches are in flight"; return LNR_ERR_ARG; }
     DevGuard dg_(ctx->device);
     ctx->has_index = false;
     set_index_layout(ctx, len, nseq);
@@ -1592,6 +1795,7 @@ lnr_status lnr_index_export(lnr_ctx *ctx, int32_t *dir, uint64_t *hs, int32_t *f
 
 lnr_status lnr_index_alloc(lnr_ctx *ctx, const lnr_index_info *info, const uint64_t *seq_len) {
     if (!ctx || !info || !seq_len || info->nseq == 0 || info->nseq >= 1024) return LNR_ERR_ARG;
+    if (in_flight(ctx)) { ctx->err = "lnr_index_alloc: batches are in flight"; return LNR_ERR_ARG; }
     DevGuard dg_(ctx->device);
     ctx->has_index = false;
     set_index_layout(ctx, seq_len, info->nseq);
@@ -1624,6 +1828,7 @@ lnr_status lnr_index_blob(lnr_ctx *ctx, uint32_t which, void **d_ptr, uint64_t *
 lnr_status lnr_index_adopt(lnr_ctx *ctx) {
     if (!ctx) return LNR_ERR_ARG;
     if (!ctx->g.p || !ctx->dir.p || !ctx->hs.p || !ctx->f2.p) return LNR_ERR_NO_INDEX;
+    if (in_flight(ctx)) { ctx->err = "lnr_index_adopt: batches are in flight"; return LNR_ERR_ARG; }
     DevGuard dg_(ctx->device);
     { lnr_status st_ = ctx->opts.index_type == 2 ? hx_derive(ctx) : build_seed_view(ctx); if (st_ != LNR_OK) return st_; }   // derived structures: rebuilt from the received dir / hs (ysa)
     HIPCK(hipStreamSynchronize(ctx->stream));
@@ -1722,7 +1927,7 @@ lnr_status lnr_index_broadcast(lnr_ctx *const *ctxs, uint32_t n, uint32_t root, 
 lnr_status lnr_filter_batch_dev(lnr_ctx *ctx, const uint8_t *d_reads, const uint64_t *d_off, uint32_t n, lnr_cords_dev *out) {
     if (!ctx || !d_off || (n && !d_reads)) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
-    if (ctx->in_count || ctx->pre.valid) { ctx->err = "batches submitted with lnr_filter_submit are still in flight"; return LNR_ERR_ARG; }
+    if (in_flight(ctx)) { ctx->err = "batches submitted with lnr_filter_submit are still in flight"; return LNR_ERR_ARG; }
     lnr_status st_ = filter_dev(ctx, d_reads, d_off, n, out);
     ctx->stats_pub = ctx->stats;
     return st_;
@@ -1730,6 +1935,7 @@ lnr_status lnr_filter_batch_dev(lnr_ctx *ctx, const uint8_t *d_reads, const uint
 lnr_status lnr_last_gaps(lnr_ctx *ctx, lnr_gaps *out) {
     if (!ctx || !out) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
+    if (!ctx->tickets.empty()) { ctx->err = "lnr_last_gaps: batches are in flight (a worker is writing the per-read arrays)"; return LNR_ERR_ARG; }
     u32 n = ctx->last_n;
     out->n_reads = n; out->n_gaps = 0; out->gap_off = nullptr; out->gaps = nullptr;
     ctx->h_gap_off.assign((size_t)n + 1, 0);
@@ -1765,6 +1971,7 @@ lnr_status lnr_last_gaps(lnr_ctx *ctx, lnr_gaps *out) {
 lnr_status lnr_cords_to_host(lnr_ctx *ctx, lnr_cords *out) {
     if (!ctx || !out) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
+    if (!ctx->tickets.empty()) { ctx->err = "lnr_cords_to_host: batches are in flight"; return LNR_ERR_ARG; }
     u64 tot = ctx->last_ncords;
     const int rs = ctx->res_slot;
     ctx->res_slot ^= 1;
@@ -1792,23 +1999,53 @@ lnr_status lnr_filter_submit(lnr_ctx *ctx, const uint8_t *reads, const uint64_t 
     if (!ctx) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
     if (!ctx->has_index) { ctx->err = "no index"; return LNR_ERR_NO_INDEX; }
-    if (ctx->in_count + (ctx->pre.valid ? 1 : 0) >= 3) { ctx->err = "three batches already in flight: call lnr_filter_wait first"; return LNR_ERR_ARG; }
+    if (ctx->in_count + (ctx->pre.valid ? 1 : 0) + ctx->tickets.size() >= 3) { ctx->err = "three batches already in flight: call lnr_filter_wait first"; return LNR_ERR_ARG; }
+    if (two_lanes(ctx)) {
+        // the lanes take the batches in turn; an idle context starts with lane 0, so one batch at a time (lnr_filter_batch) never touches lane 1
+        int li = (ctx->tickets.empty() || ctx->lane1_off) ? 0 : (ctx->tickets.back()->lane ^ 1);
+        if (li == 1 && !ctx->lane[1].c && lane_create(ctx) != LNR_OK) { ctx->lane1_off = true; li = 0; }
+        int slot = 0;
+        for (;;) {
+            lnr_ctx::Lane &Ln = ctx->lane[li];
+            bool idle;
+            { std::lock_guard<std::mutex> g(ctx->mu); idle = Ln.pending == 0; slot = 0; while (slot < 2 && Ln.slot_busy[slot]) slot++; }
+            if (li == 1 && idle) lane_mirror(Ln.c, ctx);       // (the index can only have changed with nothing in flight)
+            lnr_status s = submit_reads(ctx, Ln.c, slot, reads, off, n);
+            if (s == LNR_ERR_NOMEM && li == 1) { ctx->lane1_off = true; li = 0; continue; }   // no room for a second lane's input: one lane from now on
+            if (s != LNR_OK) return s;
+            break;
+        }
+        lnr_ctx::Lane &Ln = ctx->lane[li];
+        if (!Ln.th.joinable()) {
+            try { Ln.th = std::thread(lane_worker, ctx, li); }
+            catch (...) { ctx->err = "worker thread could not be started"; return LNR_ERR_INTERNAL; }
+        }
+        std::unique_ptr<lnr_ctx::Ticket> T(new lnr_ctx::Ticket());
+        T->lane = li; T->slot = slot;
+        {
+            std::lock_guard<std::mutex> g(ctx->mu);
+            Ln.slot_busy[slot] = true; Ln.pending++;
+            Ln.work.push_back(T.get());
+        }
+        ctx->tickets.push_back(std::move(T));
+        ctx->cv.notify_all();
+        return LNR_OK;
+    }
     int slot = (ctx->in_head + ctx->in_count) % 3;
-    lnr_status s = submit_reads(ctx, slot, reads, off, n);
+    lnr_status s = submit_reads(ctx, ctx, slot, reads, off, n);
     if (s != LNR_OK) return s;
     ctx->in_count++;
     return LNR_OK;
 }
 namespace {
-// runs the oldest submitted batch; its results stay on the device (ctx->pre) until lnr_filter_wait hands them out
-lnr_status compute_submitted(lnr_ctx *ctx) {
-    int slot = ctx->in_head;
-    ctx->in_head = (ctx->in_head + 1) % 3; ctx->in_count--;
-    lnr_ctx::Pre &P = ctx->pre;
-    P.valid = true; P.tot = 0; P.n = ctx->in_n[slot];
-    hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev_in[slot], 0);
-    P.st = e == hipSuccess ? filter_dev(ctx, ctx->in_reads[slot].as<u8>(), ctx->in_off[slot].as<u64>(), ctx->in_n[slot], nullptr, ctx->h_off[slot].as<u64>()) : LNR_ERR_HIP;
-    P.err = ctx->err;
+// runs the batch in input slot `slot` of lane In on the state of lane ctx (the same lane, but for a batch lane 1 could not hold); its
+// results stay on the device (P) until lnr_filter_wait hands them out
+lnr_status compute_slot(lnr_ctx *ctx, lnr_ctx *In, int slot, lnr_ctx::Pre &P) {
+    P = lnr_ctx::Pre();
+    P.valid = true; P.tot = 0; P.n = In->in_n[slot];
+    hipError_t e = hipStreamWaitEvent(ctx->stream, In->ev_in[slot], 0);
+    P.st = e == hipSuccess ? filter_dev(ctx, In->in_reads[slot].as<u8>(), In->in_off[slot].as<u64>(), In->in_n[slot], nullptr, In->h_off[slot].as<u64>()) : LNR_ERR_HIP;
+    P.err = ctx->err.get();
     P.stats = ctx->stats;
     if (P.st == LNR_OK) {
         P.tot = ctx->last_ncords;
@@ -1818,10 +2055,42 @@ lnr_status compute_submitted(lnr_ctx *ctx) {
     }
     return P.st;
 }
+// (one lane, -g > 0: the oldest submitted batch, computed on the caller's thread from inside lnr_filter_wait)
+lnr_status compute_submitted(lnr_ctx *ctx) {
+    int slot = ctx->in_head;
+    ctx->in_head = (ctx->in_head + 1) % 3; ctx->in_count--;
+    return compute_slot(ctx, ctx, slot, ctx->pre);
+}
 }  // namespace
 lnr_status lnr_filter_wait(lnr_ctx *ctx, lnr_cords *out) {
     if (!ctx || !out) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
+    if (!ctx->tickets.empty()) {
+        // two lanes: the oldest batch in flight is being computed (or was) by its lane's worker; wait for it, download, hand out
+        lnr_ctx::Ticket *T = ctx->tickets.front().get();
+        { std::unique_lock<std::mutex> lk(ctx->mu); ctx->cv.wait(lk, [&] { return T->done; }); }
+        lnr_ctx::Pre P = std::move(T->pre);
+        lnr_ctx::Lane &Ln = ctx->lane[T->res_lane];
+        const int T_set = T->res_set;
+        ctx->tickets.pop_front();
+        // (the lane's result set is free again once the download has finished, or at once when there is nothing to download)
+        struct Free { lnr_ctx *c; lnr_ctx::Lane &l; int set; ~Free() { { std::lock_guard<std::mutex> g(c->mu); l.unhanded--; l.set_used[set] = false; } c->cv.notify_all(); } } free_{ctx, Ln, T_set};
+        if (P.st != LNR_OK) { ctx->err = P.err; return P.st; }
+        const int rs = ctx->res_slot;
+        ctx->res_slot ^= 1;
+        PinBuf &hs_ = ctx->h_cords_str2[rs], &he_ = ctx->h_cords_end2[rs];
+        if (!hs_.ensure(std::max<u64>(P.tot * 8, 16)) || !he_.ensure(std::max<u64>(P.tot * 8, 16))) { ctx->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+        ctx->h_cord_off2[rs].swap(P.coff);
+        if (P.tot) {      // (filter_dev returned with the lane's streams idle: the result is complete)
+            HIPCK(hipMemcpyAsync(hs_.p, P.d_str, P.tot * 8, hipMemcpyDeviceToHost, ctx->s_down));
+            HIPCK(hipMemcpyAsync(he_.p, P.d_end, P.tot * 8, hipMemcpyDeviceToHost, ctx->s_down));
+            HIPCK(hipStreamSynchronize(ctx->s_down));
+        }
+        ctx->stats_pub = P.stats;
+        out->n_reads = P.n; out->n_cords = P.tot;
+        out->cord_off = ctx->h_cord_off2[rs].data(); out->cords_str = hs_.as<u64>(); out->cords_end = he_.as<u64>();
+        return LNR_OK;
+    }
     if (!ctx->pre.valid) {
         if (ctx->in_count == 0) { ctx->err = "no batch in flight"; return LNR_ERR_ARG; }
         compute_submitted(ctx);
@@ -1855,7 +2124,7 @@ lnr_status lnr_filter_wait(lnr_ctx *ctx, lnr_cords *out) {
 }
 lnr_status lnr_filter_batch(lnr_ctx *ctx, const uint8_t *reads, const uint64_t *off, uint32_t n, lnr_cords *out) {
     if (!ctx || !out) return LNR_ERR_ARG;
-    if (ctx->in_count || ctx->pre.valid) { ctx->err = "batches submitted with lnr_filter_submit are still in flight"; return LNR_ERR_ARG; }
+    if (in_flight(ctx)) { ctx->err = "batches submitted with lnr_filter_submit are still in flight"; return LNR_ERR_ARG; }
     lnr_status s = lnr_filter_submit(ctx, reads, off, n);
     if (s != LNR_OK) return s;
     return lnr_filter_wait(ctx, out);
@@ -1864,6 +2133,7 @@ lnr_status lnr_filter_batch(lnr_ctx *ctx, const uint8_t *reads, const uint64_t *
 lnr_status lnr_seed_lookup_batch_dev(lnr_ctx *ctx, const uint8_t *d_reads, const uint64_t *d_off, uint32_t n) {
     if (!ctx || !d_off || (n && !d_reads)) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
+    if (in_flight(ctx)) { ctx->err = "batches submitted with lnr_filter_submit are still in flight"; return LNR_ERR_ARG; }
     lnr_status st_ = seed_dev(ctx, d_reads, d_off, n, false);
     ctx->stats_pub = ctx->stats;
     return st_;
@@ -1872,8 +2142,8 @@ lnr_status lnr_seed_lookup_batch(lnr_ctx *ctx, const uint8_t *reads, const uint6
     if (!ctx || !out) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
     if (!ctx->has_index) { ctx->err = "no index"; return LNR_ERR_NO_INDEX; }
-    if (ctx->in_count || ctx->pre.valid) { ctx->err = "batches submitted with lnr_filter_submit are still in flight"; return LNR_ERR_ARG; }
-    lnr_status s = submit_reads(ctx, 0, reads, off, n);
+    if (in_flight(ctx)) { ctx->err = "batches submitted with lnr_filter_submit are still in flight"; return LNR_ERR_ARG; }
+    lnr_status s = submit_reads(ctx, ctx, 0, reads, off, n);
     if (s != LNR_OK) return s;
     HIPCK(hipStreamWaitEvent(ctx->stream, ctx->ev_in[0], 0));
     if ((s = seed_dev(ctx, ctx->in_reads[0].as<u8>(), ctx->in_off[0].as<u64>(), n, true)) != LNR_OK) return s;
@@ -1904,7 +2174,7 @@ lnr_status lnr_prof_read(lnr_ctx *ctx, unsigned long long *out16) {
 
 lnr_status lnr_gap_stream(lnr_ctx *ctx, int set, int *state) {
     if (!ctx || set > 1) return LNR_ERR_ARG;
-    if (set >= 0 && (ctx->in_count || ctx->pre.valid)) { ctx->err = "lnr_gap_stream: batches are in flight (the next one may have been computed already)"; return LNR_ERR_ARG; }
+    if (set >= 0 && in_flight(ctx)) { ctx->err = "lnr_gap_stream: batches are in flight (the next one may have been computed already)"; return LNR_ERR_ARG; }
     if (set >= 0) ctx->gap_ext = set;
     if (state) *state = ctx->gap_ext;
     return LNR_OK;
@@ -1912,7 +2182,7 @@ lnr_status lnr_gap_stream(lnr_ctx *ctx, int set, int *state) {
 
 lnr_status lnr_set_gap(lnr_ctx *ctx, uint32_t gap_len, uint32_t dup) {
     if (!ctx || dup > 1) return LNR_ERR_ARG;
-    if (ctx->in_count || ctx->pre.valid) { ctx->err = "lnr_set_gap: batches are in flight"; return LNR_ERR_ARG; }
+    if (in_flight(ctx)) { ctx->err = "lnr_set_gap: batches are in flight"; return LNR_ERR_ARG; }
     ctx->opts.gap_len = gap_len; ctx->opts.dup = dup; ctx->gap_ext = 0;
     return LNR_OK;
 }
