@@ -1104,7 +1104,11 @@ lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, 
         G.first_ext = ctx->gap_first.as<u32>();
         ENSURE(ctx->gap_rank, ((size_t)n + 16) * 4);
         ENSURE(ctx->gap_weight, ((size_t)n + 16) * 4);
-        ENSURE(ctx->gap_list, ((size_t)n + 16) * 4);
+        // list / hand-over queue: n entries + one per team.  A team of k_gap_all looks at queue entry k before it knows whether the single waves
+        // are through, for k up to (reads handed over) + (teams) - 1; every entry it can look at is zeroed before the launch.  (With n entries
+        // only, a batch of one read that was handed over had its team read entry 1: stale words of an earlier batch, taken for a read index.)
+        const size_t list_words = (size_t)n + 16 + nteams + 16;
+        ENSURE(ctx->gap_list, list_words * 4);
         G.list = ctx->gap_list.as<u32>() + 16; G.list_n = ctx->gap_list.as<u32>();
         // one "ladder" over the reads of [lo, hi): the fused first stage, then the reads it flagged with the largest arena
         auto ladder = [&](u32 lo, u32 hi, u32 ext_from, int probe) -> hipError_t {
@@ -1118,7 +1122,7 @@ lnr_status filter_dev(lnr_ctx *ctx, const u8 *d_reads, const u64 *d_off, u32 n, 
             G.order = ctx->gap_rank.as<u32>() + 16;
             G.next = ctx->gap_next.as<u32>(); G.last = 0;
             // one launch: teams on the reads expected to be heavy + on what the single waves hand over, single waves on the rest
-            if ((e = hipMemsetAsync(ctx->gap_list.p, 0, ((size_t)n + 16) * 4, ctx->stream)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(ctx->gap_list.p, 0, list_words * 4, ctx->stream)) != hipSuccess) return e;
             G.nteams = std::min<u32>(nteams, std::max<u32>(1, m / 8));
             u32 bulk_wg = std::min<u32>(ncu > G.nteams ? ncu - G.nteams : 1, (m + K_GAP_TEAM - 1) / K_GAP_TEAM);
             G.nbulk_waves = bulk_wg * K_GAP_TEAM; G.arena_bytes = arena1; G.arena2_bytes = arena2;
@@ -1325,7 +1329,7 @@ void par_memcpy(void *dst, const void *src, size_t len) {
     unsigned T = (unsigned)std::min<size_t>(4, len / MIN);
     if (T < 2) { memcpy(dst, src, len); return; }
     std::vector<std::thread> th;
-    size_t per = (len / T + 63) & ~(size_t)63;
+    size_t per = ((len + T - 1) / T + 63) & ~(size_t)63;          // (rounded UP before the alignment: T shares of len / T rounded down can end up to T - 1 bytes short of len)
     for (unsigned t = 1; t < T; t++) {
         size_t o = (size_t)t * per, l = o < len ? std::min(per, len - o) : 0;
         if (l) th.emplace_back([=]() { memcpy((char *)dst + o, (const char *)src + o, l); });

@@ -123,8 +123,33 @@ struct GapCtx {                                           // one read
     unsigned long long prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // ticks per phase (diagnostic build, tools/measure/gap_prof.sh)
     unsigned long long dp_t = 0, dp_n = 0, dp_mode = 0, dp_fn = 0;          // the read's longest chain DP: ticks, anchors, 1 = by columns, score function
 #endif
+#ifdef LNR_GAP_TRACE
+    int trace = 0;                                        // diagnostic build: this read prints the stations of its gaps (host and device print the same lines)
+#endif
     LNR_HD GSeq ref(u64 id) const { GSeq s; s.p = g + seq_off[id]; s.len = seq_len[id]; return s; }
 };
+#ifdef LNR_GAP_TRACE
+// Diagnostic build (-DLNR_GAP_TRACE): one read (device: the last of the launch; host shim: LNR_GAP_TRACE in the environment) prints sizes and
+// checksums of the vectors at the stations of every gap, so that a host run and a device run of the same read can be compared line by line.
+LNR_HD inline bool gap_trace_on(const GapCtx &X) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return X.trace && (threadIdx.x & 63) == 0;
+#else
+    return X.trace != 0;
+#endif
+}
+LNR_HD inline void gap_trace_vec(const GapCtx &X, const char *name, const GVec<u64> &v) {
+    if (!gap_trace_on(X)) return;
+    u64 h = 1469598103934665603ULL;
+    for (u32 i = 0; i < v.n; i++) h = (h ^ v.p[i]) * 1099511628211ULL;
+    printf("[gt] %s n %u h %016llx first %016llx last %016llx\n", name, v.n, (unsigned long long)h, (unsigned long long)(v.n ? v.p[0] : 0), (unsigned long long)(v.n ? v.p[v.n - 1] : 0));
+}
+#define GT_VEC(X, name, v) gap_trace_vec(X, name, v)
+#define GT_W(X, name, a, b, c) do { if (gap_trace_on(X)) printf("[gt] %s %016llx %016llx %lld\n", name, (unsigned long long)(a), (unsigned long long)(b), (long long)(c)); } while (0)
+#else
+#define GT_VEC(X, name, v) do {} while (0)
+#define GT_W(X, name, a, b, c) do {} while (0)
+#endif
 
 #if defined(LNR_GAP_DEVPROF) && defined(__HIP_DEVICE_COMPILE__)
 struct GpScope { GapCtx &X; int i; unsigned long long t0; __device__ GpScope(GapCtx &x, int k) : X(x), i(k), t0(wall_clock64()) {} __device__ ~GpScope() { X.prof[i] += wall_clock64() - t0; } };
@@ -1659,15 +1684,20 @@ LNR_HD inline int gap_map_along_chain(const GSeq &ref, const GSeq &seq2, const G
         GP(X, 10);
         c_stream(ref, hs, cord_x(a), cord_x(b), step1, shape_len, 0, X.coop);
         c_stream(seq2, hs, cord_y(a), cord_y(b), step2, shape_len, 1, X.coop);
+        GT_W(X, "along a b", a, b, i_end - i_str); GT_VEC(X, "along hs", hs);
         c_create_anchors2(hs, anc, (as < ae ? as : ae) - 30, (as > ae ? as : ae) + 30, X.ls->st, &X);
+        GT_VEC(X, "along anchors", anc);
         gap_sort(anc.p, (long)anc.n, GapCmp{2, 0}, X);
+        GT_VEC(X, "along sorted", anc);
     }
     GP2(X, 11);
     stick_main_chain(anc, ch, X.gp.thd_smcn_danchor);
+    GT_VEC(X, "along stuck", anc);
     GVec<u64> first; first.init(X.ar, anc.n + 16);
     // bestn 1: only the first chain is wanted; it is collected as anchors and turned into tiles below (chn_ext_clip_metric1: min length 1, abort 0)
     gap_chain_anchors(anc.p, anc.n, first, false, 15, 30, 1, 1, 0, [](u64 p, u64 q) { return gap_clip_score(p, q); }, X, 5);
     int f_strand = (int)tile_strand(ch[0]);
+    GT_VEC(X, "along first chain", first);
     for (u32 i = 0; i < first.n; i++) { u64 t = ganc_tile(first[i]); if (f_strand) t |= 1ULL << 61; tiles.push(t); }
     return 0;
 }
@@ -1735,7 +1765,9 @@ LNR_HD inline void gap_remap_chain_one_end(const GSeq &ref, GVec<u64> &ch, int s
     if (direction <= 0) { i_str = (int)ch.n - remap_num > 0 ? (int)ch.n - remap_num : 0; i_end = (int)ch.n; }
     else { i_str = 0; i_end = (int)ch.n < remap_num ? (int)ch.n : remap_num; }
     gap_map_along_chain(ref, seq2, ch, re, i_str, i_end, shape_len, step1, step2, X);
+    GT_VEC(X, "remap along", re);
     gap_clip_chain(re, shape_len, direction, true, gtx, gty, X);
+    GT_VEC(X, "remap clipped", re);
     if (direction <= 0) { ch.erase(0, (u32)i_end); ch.insert(0, re.p, re.n); }
     else if (!re.empty()) { ch.n = (u32)i_str; ch.append(re); }
 }
@@ -1758,7 +1790,9 @@ LNR_HD inline int gap_reextend_chain_one_side(const GSeq &ref, GVec<u64> &ch, in
         re.back() = shift_cord(ch[(u32)ipe], d, d);
         i_str = ii; i_end = ipe + 1;
     }
+    GT_W(X, "reextend lower upper dir", lower, upper, direction); GT_VEC(X, "reextend in", re);
     gap_remap_chain_one_end(ref, re, shape_len, step1, step2, (int)re.n, direction, X);
+    GT_VEC(X, "reextend out", re);
     ch.erase((u32)i_str, (u32)i_end);
     ch.insert((u32)i_str, re.p, re.n);
     return (int)ch.n - len;
@@ -1770,12 +1804,19 @@ LNR_HD inline void gap_extend_interval_one_side(const GSeq &ref, GVec<u64> &tile
     gp.direction = direction;
     GVec<u64> g_hs, anc, chain; g_hs.init(X.ar, 2048); anc.init(X.ar, 2048); chain.init(X.ar, 256);
     { GP(X, 2); g_stream(ref, X.read, g_hs, gap_str, gap_end, (u32)gp.thd_eis_shape_len, gp.thd_eis_step1, gp.thd_eis_step2, X.coop); }
+    GT_W(X, "extend", gap_str, gap_end, direction); GT_VEC(X, "extend g_hs", g_hs);
     g_create_anchors(g_hs, anc, gp.thd_eis_shape_len, direction, 0, 0, X.read.len - 1, gap_str, gap_end, X);
+    GT_VEC(X, "extend anchors", anc);
     g_chains_from_anchors(anc, chain, X.read.len, X);
+    GT_VEC(X, "extend chain", chain);
     closest_extension_chain(chain, gap_str, gap_end, true, gp);
+    GT_VEC(X, "extend closest", chain);
     gap_remap_chain_one_end(ref, chain, gp.thd_etfas_shape_len, gp.thd_etfas_step1, gp.thd_etfas_step2, 50, direction, X);
+    GT_VEC(X, "extend remapped", chain);
     tiles_from_chain(chain, tiles, gap_str, gap_end, 0, (int)chain.n, X);
+    GT_VEC(X, "extend tiles", tiles);
     gap_trim_tiles(tiles, gap_str, gap_end, X.read.len - 1, direction, X);
+    GT_VEC(X, "extend trimmed", tiles);
     gp.direction = od;
 }
 LNR_HD inline void gap_extend_result_filter(GVec<u64> &ts, GVec<u64> &te, u64 gap_str, u64 gap_end, int direction, const GapParms &gp) {   // mapExtendResultFilter_ :3986-4031
@@ -1857,6 +1898,7 @@ LNR_HD inline int gap_reextend_clip_one_side(const GSeq &ref, GVec<u64> &ch, u64
 LNR_HD inline void gap_tiles_from_anchors2(const GSeq &ref, GVec<u64> &anchors, GVec<u64> &ts, GVec<u64> &te, u64 gap_str, u64 gap_end, u64 read_len, GapCtx &X) {   // createTilesFromAnchors2_ :4171-4247
     GVec<u64> tmp; tmp.init(X.ar, 256);
     g_chains_from_anchors(anchors, tmp, read_len, X);
+    GT_VEC(X, "anchors2 sorted", anchors); GT_VEC(X, "anchors2 chains", tmp);
     int pre_i = 0;
     for (int i = 0; i < (int)tmp.n; i++) {
         bool blk_end = is_tile_end(tmp[(u32)i]) != 0;
@@ -1865,7 +1907,9 @@ LNR_HD inline void gap_tiles_from_anchors2(const GSeq &ref, GVec<u64> &anchors, 
         u32 len0 = ts.n;
         u64 head = tmp[(u32)pre_i], tail = tmp[(u32)i];
         i += gap_reextend_clip_one_side(ref, tmp, gap_str, gap_end, pre_i, i, -1, X);
+        GT_VEC(X, "anchors2 clip-", tmp);
         i += gap_reextend_clip_one_side(ref, tmp, gap_str, gap_end, pre_i, i, 1, X);
+        GT_VEC(X, "anchors2 clip+", tmp);
         if (!(tmp.empty() || pre_i < 0 || i < 0)) {
             copy_tile_sgn(head, tmp[(u32)pre_i]);
             copy_tile_sgn(tail, tmp[(u32)i]);
@@ -1999,12 +2043,18 @@ LNR_HD inline void gap_map_generic(const GSeq &ref, GVec<u64> &ts, GVec<u64> &te
     X.gp.f_rfts_clip = 0;
     if (!cord_strand(gap_str ^ gap_end)) {
         GVec<u64> g_hs, anc; g_hs.init(X.ar, 2048); anc.init(X.ar, 2048);
+        GT_W(X, "generic", gap_str, gap_end, ref.len);
         { GP(X, 2); g_stream(ref, X.read, g_hs, gap_str, gap_end, 9, 5, 1, X.coop); }
+        GT_VEC(X, "generic g_hs", g_hs);
         g_create_anchors(g_hs, anc, 9, 0, -(((i64)1 << 62) - 1), ((i64)1 << 62) - 1, X.read.len - 1, gap_str, gap_end, X);
+        GT_VEC(X, "generic anchors", anc);
         if (anc.n > 1000) gap_filter_anchors(anc, X);
+        GT_VEC(X, "generic anchors filtered", anc);
         gap_tiles_from_anchors2(ref, anc, ts, te, gap_str, gap_end, X.read.len - 1, X);
+        GT_VEC(X, "generic tiles_str", ts); GT_VEC(X, "generic tiles_end", te);
     }
     gap_reform_tiles(ts, te, gap_str, gap_end, 0, X.gp);
+    GT_VEC(X, "generic reformed_str", ts); GT_VEC(X, "generic reformed_end", te);
     X.gp.f_rfts_clip = oclip;
 }
 
@@ -2125,6 +2175,7 @@ LNR_HD inline int gap_map_gap(u64 gap_str, u64 gap_end, GVec<u64> &tiles_str, GV
     }
     for (int i = 1; i < (int)tiles_str.n - 1; i++) { tiles_str[(u32)i - 1] = tiles_str[(u32)i]; tiles_end[(u32)i - 1] = tiles_end[(u32)i]; }
     tiles_str.n = tiles_str.n >= 2 ? tiles_str.n - 2 : 0; tiles_end.n = tiles_end.n >= 2 ? tiles_end.n - 2 : 0;
+    GT_W(X, "gap", gap_str, gap_end, direction); GT_VEC(X, "gap tiles_str", tiles_str); GT_VEC(X, "gap tiles_end", tiles_end);
     return 0;
 }
 LNR_HD inline i64 gap_max_gapsy_overlap(const UP *gapsy, u32 n, u64 gap_str, u64 gap_end) {   // _getMaxGapsyOverlap gap_util.cpp:343-362
@@ -2156,6 +2207,7 @@ LNR_HD inline int gap_map_gaps(GVec<u64> &cs, GVec<u64> &ce, GArena &keep, GapCt
     if (keep.ovf) return 1;
     gather_blocks(cs.p, cs.n, &str_ends, sep, 1, cs.n, L, (u64)cord_gap, (u64)block_size, 0);
     gather_gaps_y(str_ends.p, str_ends.n, gaps, L, (u64)cord_gap, *X.ls);
+    GT_VEC(X, "cords_str in", cs); GT_VEC(X, "cords_end in", ce); GT_W(X, "blocks gaps", str_ends.n, gaps.n, L);
     for (u32 i = 1; i < cs.n; i++) {
         if (X.ar->ovf) return 1;
         u64 slen = X.seq_len[cord_id(cs[i])];
@@ -2206,6 +2258,7 @@ LNR_HD inline int gap_map_gaps(GVec<u64> &cs, GVec<u64> &ce, GArena &keep, GapCt
         }
         if (X.ar->ovf || keep.ovf) return 1;
     }
+    GT_VEC(X, "cords_str", cs); GT_VEC(X, "cords_end", ce);
     return ovf;
 }
 // ---- reformCords with reformCordsDxDy1 (cords.cpp:504-687)

@@ -192,6 +192,18 @@ __device__ bool gap_do_read(const GapArgs &A, u32 r, char *mine, u64 arena_bytes
         const bool ext_in = r >= A.ext_from;
         if (ext_in) X.gp.thd_cts_major_limit = 3;
         X.coop = 1; X.work_cap = A.work_cap; X.team = team; X.tm = tm; X.hand = team <= 1 ? 1 : 0;
+#ifdef LNR_GAP_TRACE
+        X.trace = r + 1 == A.n && !A.probe;
+        if (gap_trace_on(X)) {
+            u64 h[5];
+            for (int q = 0; q < 5; q++) h[q] = 1469598103934665603ULL;
+            for (u64 k = 0; k < L; k++) { h[0] = (h[0] ^ rd[k]) * 1099511628211ULL; h[1] = (h[1] ^ rc[k]) * 1099511628211ULL; }
+            for (u32 k = 0; k < 2 * nf; k++) { F96 v = X.f1[0].p[k]; int s_ = k >= nf ? 3 : 2; h[s_] = (h[s_] ^ (u32)v.v0) * 1099511628211ULL; h[s_] = (h[s_] ^ (u32)v.v1) * 1099511628211ULL; h[s_] = (h[s_] ^ (u32)v.v2) * 1099511628211ULL; }
+            for (u32 k = 0; k < 64; k++) h[4] = (h[4] ^ rd[L + k] ^ ((u64)rc[L + k] << 8)) * 1099511628211ULL;
+            printf("[gt] read %u L %llu nout %u cap %u cords_off %llu nf %u f1_off %llu ext_from %u lo %u lvl %d team %d arena %llu\n", r, (unsigned long long)L, nc, A.cords_cap[r], (unsigned long long)A.cords_off[r], nf, (unsigned long long)A.f1_off[r], A.ext_from, A.lo, lvl, team, (unsigned long long)arena_bytes);
+            printf("[gt] inputs rd %016llx rc %016llx f1+ %016llx f1- %016llx pad %016llx\n", (unsigned long long)h[0], (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3], (unsigned long long)h[4]);
+        }
+#endif
         u64 *os = A.out_str + A.cords_off[r], *oe = A.out_end + A.cords_off[r];
         GVec<u64> cs, ce; cs.init(&keep, nc * 2 + 64); ce.init(&keep, nc * 2 + 64);
         for (u32 i = 0; i < nc; i++) { cs.push(os[i]); ce.push(oe[i]); }

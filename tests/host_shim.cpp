@@ -7,6 +7,8 @@
 #include <vector>
 #include <algorithm>
 #include <cstring>
+#include <cstdio>
+#include <cstdlib>
 #include "../linear_amd/csrc/lnr_hd.h"
 #include "../linear_amd/csrc/lnr_gap_hd.h"
 
@@ -363,6 +365,9 @@ static i64 map_read_g_lim(void *h, const u8 *read, u64 len, u32 gap_len, int f_d
     H.X.gp.f_dup = f_dup;
     H.X.gp.thd_gap_len_min = gap_len == 1 ? 50 : (gap_len < 10 ? 10 : gap_len);
     if (ext_state && *ext_state) H.X.gp.thd_cts_major_limit = 3;
+#ifdef LNR_GAP_TRACE
+    H.X.trace = getenv("LNR_GAP_TRACE") != nullptr;
+#endif
     GVec<u64> cs, ce; cs.init(&H.keep, (u32)S.cs.size() * 2 + 64); ce.init(&H.keep, (u32)S.cs.size() * 2 + 64);
     for (u64 v : S.cs) cs.push(v);
     for (u64 v : S.ce) ce.push(v);

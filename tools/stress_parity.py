@@ -48,17 +48,38 @@ def plant_svs(reads, off, refs, rng):
     return (np.concatenate(out) if out else np.zeros(0, np.uint8)), o2
 
 
-def main():
-    ncfg = int(sys.argv[1]) if len(sys.argv) > 1 else 12
-    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    lb.build()
-    pyorc.build(ref=False)
+class Config:
+    """configuration k of a seed: what was drawn, and build() for its references and reads (made on demand: a configuration that is only
+    looked at costs nothing)"""
+
+    def __init__(self, k, s, kind, T, L, err, nreads, jitter, opt, gap_len, dup, ref_sizes, n_families, lead, with_gap):
+        self.k, self.s, self.kind, self.T, self.L, self.err, self.nreads, self.jitter = k, s, kind, T, L, err, nreads, jitter
+        self.opt, self.gap_len, self.dup, self.ref_sizes, self.n_families, self.lead, self.with_gap = opt, gap_len, dup, ref_sizes, n_families, lead, with_gap
+
+    def params(self) -> dict:
+        return {"k": self.k, "s": self.s, "kind": self.kind, "T": self.T, "L": self.L, "err": self.err, "nreads": self.nreads, "jitter": self.jitter,
+                "opts": self.opt, "gap_len": self.gap_len, "dup": self.dup, "ref_sizes": self.ref_sizes}
+
+    def build(self):
+        """-> (refs, reads, off)"""
+        s = self.s
+        if self.kind == 0:
+            refs = [synth.random_ref(self.ref_sizes[0], s)]
+        elif self.kind == 1:
+            refs = [synth.repeat_ref(self.ref_sizes[0], s, n_families=self.n_families)]
+        else:
+            refs = [synth.repeat_ref(400_000, s), synth.add_n_runs(synth.random_ref(250_000, s + 1), s + 2, lead=self.lead),
+                    synth.repeat_ref(150_000, s + 3, n_families=4)]
+        reads, off, _ = synth.sample_reads(refs, self.nreads, self.L, self.err, s + 7, "random", len_jitter=self.jitter)
+        if self.with_gap:
+            reads, off = plant_svs(reads, off, refs, np.random.default_rng(s + 11))
+        return refs, reads, off
+
+
+def configs(seed0: int, ncfg: int, with_gap: bool):
+    """The configurations 0 .. ncfg-1 that `stress_parity.py ncfg seed0` runs (LNR_STRESS_GAP=1: with_gap), in order.  Every draw is made here and in
+    one fixed order, whether a configuration is then used or not: configuration k of a seed is the same whatever is done with the others."""
     rng = np.random.default_rng(seed0)
-    bad = 0
-    only = {int(x) for x in os.environ.get("LNR_STRESS_ONLY", "").split(",") if x}
-    libs = [x for x in os.environ.get("LNR_STRESS_LIBS", "").split(",") if x]
-    itype = int(os.environ.get("LNR_STRESS_INDEX_TYPE", "1"))   # the reference's -i: 1 DIndex, 2 HIndex
-    with_gap = os.environ.get("LNR_STRESS_GAP", "0") == "1"
     for k in range(ncfg):
         s = int(rng.integers(1, 1 << 30))
         kind = int(rng.integers(0, 3))
@@ -66,24 +87,39 @@ def main():
         L = int(rng.choice([201, 260, 700, 3000, 9000, 20000, 40000, 120000]))
         err = float(rng.choice([0.0, 0.03, 0.1, 0.15]))
         nreads = int(rng.choice([1, 7, 64, 300, 1500]))
+        n_families, lead = 0, 0
         if kind == 0:
-            refs = [synth.random_ref(int(rng.integers(200_000, 900_000)), s)]
+            ref_sizes = [int(rng.integers(200_000, 900_000))]
         elif kind == 1:
-            refs = [synth.repeat_ref(int(rng.integers(300_000, 1_500_000)), s, n_families=int(rng.integers(3, 20)))]
+            ref_sizes = [int(rng.integers(300_000, 1_500_000))]
+            n_families = int(rng.integers(3, 20))
         else:
-            refs = [synth.repeat_ref(400_000, s), synth.add_n_runs(synth.random_ref(250_000, s + 1), s + 2, lead=int(rng.integers(0, 5000))),
-                    synth.repeat_ref(150_000, s + 3, n_families=4)]
+            ref_sizes = [400_000, 250_000, 150_000]                # (add_n_runs replaces bases: the length stays)
+            lead = int(rng.integers(0, 5000))
         jitter = float(rng.choice([0.0, 0.5]))
         # library options (read at lnr_create): exercise the other size classes and orchestration modes now and then
         opt = OPTION_SETS[int(rng.integers(0, len(OPTION_SETS)))]
         gap_len, dup = 0, 0
         if with_gap:                                  # (drawn before a configuration is skipped: LNR_STRESS_ONLY re-runs exactly the configuration of the full run)
             gap_len, dup = int(rng.choice([1, 5, 50, 200])), int(rng.integers(0, 2))
+        yield Config(k, s, kind, T, L, err, nreads, jitter, opt, gap_len, dup, ref_sizes, n_families, lead, with_gap)
+
+
+def main():
+    ncfg = int(sys.argv[1]) if len(sys.argv) > 1 else 12
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    lb.build()
+    pyorc.build(ref=False)
+    bad = 0
+    only = {int(x) for x in os.environ.get("LNR_STRESS_ONLY", "").split(",") if x}
+    libs = [x for x in os.environ.get("LNR_STRESS_LIBS", "").split(",") if x]
+    itype = int(os.environ.get("LNR_STRESS_INDEX_TYPE", "1"))   # the reference's -i: 1 DIndex, 2 HIndex
+    with_gap = os.environ.get("LNR_STRESS_GAP", "0") == "1"
+    for c in configs(seed0, ncfg, with_gap):
+        k, kind, T, L, err, nreads, opt, gap_len, dup = c.k, c.kind, c.T, c.L, c.err, c.nreads, c.opt, c.gap_len, c.dup
         if only and k not in only:
             continue
-        reads, off, _ = synth.sample_reads(refs, nreads, L, err, s + 7, "random", len_jitter=jitter)
-        if with_gap:
-            reads, off = plant_svs(reads, off, refs, np.random.default_rng(s + 11))
+        refs, reads, off = c.build()
         for kv in ALL_KEYS:
             os.environ.pop(kv, None)
         os.environ.update(opt)
