@@ -225,7 +225,7 @@ lnr_status lnr_reader_ids(const lnr_reader *r, const char **ids, const uint64_t 
 const char *lnr_reader_error(const lnr_reader *r);
 void lnr_reader_close(lnr_reader *r);
 
-/* Output side (host threads; replaces, for this path, the calculator's tail cords2BamLink + fillBamRecords, src/mapper.cpp:463-470,
+/* Output side (host threads, and a GPU twin below; replaces, for this path, the calculator's tail cords2BamLink + fillBamRecords, src/mapper.cpp:463-470,
  * src/f_io.cpp:758-1011, src/align_util.cpp:301-343,452-744, and the printer's writeSam / print_cords_apf, src/f_io.cpp:100-207,
  * 313-412): the cords of a batch as SAM records (what = 1) or APF text (what = 2), byte for byte what the reference prints for
  * the same cords with -g 0 (MAPQ 255, flag 16 / 2048, SA:Z of the read's other lines; APF: a blank line before every '@' record
@@ -241,6 +241,21 @@ lnr_status lnr_writer_sam_header(lnr_writer *w, const char *command_line, const 
 lnr_status lnr_writer_set_preset(lnr_writer *w, uint32_t preset);
 lnr_status lnr_writer_set_read_group(lnr_writer *w, const char *read_group, const char *sample_name);
 void lnr_writer_destroy(lnr_writer *w);
+/* GPU twin of lnr_writer_format: the same bytes, formatted on `device`.  A writer with a GPU side owns a stream and its buffers there, is
+ * independent of any lnr_ctx (may run while a context computes on the same device) and is used by one thread at a time.  The text lands in
+ * pinned host memory owned by the writer, valid until the writer's next format call; lnr_writer_set_preset applies to both sides.
+ * lnr_writer_format_dev takes what lnr_filter_batch_dev hands out (the caller has waited for that call) and the batch's d_off;
+ * lnr_writer_format_gpu uploads host cords and goes the same way.  Before lnr_writer_gpu_open both return LNR_ERR_ARG;
+ * lnr_writer_destroy releases the GPU side.  Every entry leaves the caller's current device as it found it.  lnr_writer_error: detail of
+ * the writer's last failure.  lnr_writer_gpu_times: wall / device milliseconds of the last GPU format call -- upload (wall), measure, scan,
+ * emit (HIP events), download (wall). */
+lnr_status lnr_writer_gpu_open(lnr_writer *w, int32_t device);              /* LNR_ERR_NO_DEVICE without a usable device */
+lnr_status lnr_writer_format_gpu(lnr_writer *w, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids,
+                                 const uint64_t *id_off, int what, const char **text, uint64_t *size);   /* host cords in (uploaded), host text out */
+lnr_status lnr_writer_format_dev(lnr_writer *w, const lnr_cords_dev *cords, const uint64_t *d_read_off /* n + 1, the batch's d_off */,
+                                 const char *read_ids, const uint64_t *id_off, int what, const char **text, uint64_t *size);
+lnr_status lnr_writer_gpu_times(const lnr_writer *w, double *ms5);
+const char *lnr_writer_error(const lnr_writer *w);
 
 #ifdef __cplusplus
 }

@@ -58,7 +58,8 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_index_export", "lnr_index_alloc", "lnr_index_blob", "lnr_index_adopt", "lnr_filter_batch", "lnr_filter_batch_dev",
            "lnr_cords_to_host", "lnr_seed_lookup_batch", "lnr_seed_lookup_batch_dev", "lnr_last_stats", "lnr_filter_submit", "lnr_filter_wait",
            "lnr_host_alloc", "lnr_host_free", "lnr_reader_open", "lnr_reader_next", "lnr_reader_ids", "lnr_reader_error", "lnr_reader_close",
-           "lnr_writer_create", "lnr_writer_format", "lnr_writer_sam_header", "lnr_writer_destroy", "lnr_last_gaps", "lnr_gap_stream", "lnr_set_gap", "lnr_index_broadcast", "lnr_writer_set_preset", "lnr_writer_set_read_group"]
+           "lnr_writer_create", "lnr_writer_format", "lnr_writer_sam_header", "lnr_writer_destroy", "lnr_last_gaps", "lnr_gap_stream", "lnr_set_gap", "lnr_index_broadcast", "lnr_writer_set_preset", "lnr_writer_set_read_group",
+           "lnr_writer_gpu_open", "lnr_writer_format_gpu", "lnr_writer_format_dev", "lnr_writer_gpu_times", "lnr_writer_error"]
 
 
 def load_library() -> C.CDLL:
@@ -102,6 +103,13 @@ def load_library() -> C.CDLL:
     lib.lnr_writer_sam_header.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_destroy.argtypes = [C.c_void_p]
     lib.lnr_last_gaps.argtypes = [C.c_void_p, C.POINTER(LnrGaps)]
+    lib.lnr_writer_set_preset.argtypes = [C.c_void_p, C.c_uint32]
+    lib.lnr_writer_gpu_open.argtypes = [C.c_void_p, C.c_int32]
+    lib.lnr_writer_format_gpu.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u64p, C.c_char_p, _u64p, C.c_int, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev), C.c_void_p, C.c_char_p, _u64p, C.c_int, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_gpu_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.lnr_writer_error.restype = C.c_char_p
+    lib.lnr_writer_error.argtypes = [C.c_void_p]
     return lib
 
 
@@ -338,7 +346,7 @@ class Reader:
 
 
 class Writer:
-    """Cords of a batch -> SAM records / APF text (host code; no GPU needed)."""
+    """Cords of a batch -> SAM records / APF text: format() on host threads (no GPU needed), format_gpu() / format_dev() on the GPU."""
 
     def __init__(self, genome_ids: list[str], genome_len: list[int]):
         self.lib = load_library()
@@ -366,6 +374,53 @@ class Writer:
         if st != 0:
             raise LnrError(st, self.lib.lnr_strerror(st).decode())
         return C.string_at(text, size.value)
+
+    def set_preset(self, preset: int) -> None:
+        st = self.lib.lnr_writer_set_preset(self.h, preset)
+        if st != 0:
+            raise LnrError(st, self.lib.lnr_strerror(st).decode())
+
+    def _check(self, st: int) -> None:
+        if st != 0:
+            raise LnrError(st, self.lib.lnr_strerror(st).decode(), self.lib.lnr_writer_error(self.h).decode())
+
+    @staticmethod
+    def _ids(read_ids: list[str]):
+        blob = b"".join(i.encode() + b"\0" for i in read_ids)
+        ido = np.zeros(len(read_ids) + 1, np.uint64)
+        ido[1:] = np.cumsum([len(i.encode()) + 1 for i in read_ids])
+        return blob, ido
+
+    def gpu_open(self, device: int = 0) -> None:
+        """Gives the writer its GPU side (a stream and buffers on `device`); format_gpu / format_dev need it."""
+        self._check(self.lib.lnr_writer_gpu_open(self.h, device))
+
+    def format_gpu(self, cord_off: np.ndarray, cords_str: np.ndarray, cords_end: np.ndarray, read_len: np.ndarray, read_ids: list[str], what: str, copy: bool = True):
+        """The bytes of format(), formatted on the GPU.  copy=False: (address, size) of the writer's pinned text instead of a bytes object."""
+        cord_off = np.ascontiguousarray(cord_off, dtype=np.uint64)
+        cs = np.ascontiguousarray(cords_str, dtype=np.uint64)
+        ce = np.ascontiguousarray(cords_end, dtype=np.uint64)
+        rl = np.ascontiguousarray(read_len, dtype=np.uint64)
+        c = LnrCords()
+        c.n_reads, c.n_cords = cord_off.size - 1, cs.size
+        c.cord_off, c.cords_str, c.cords_end = _p(cord_off, _u64p), _p(cs, _u64p), _p(ce, _u64p)
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_gpu(self.h, C.byref(c), _p(rl, _u64p), blob, _p(ido, _u64p), {"sam": 1, "apf": 2}[what], C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value) if copy else (text.value, size.value)
+
+    def format_dev(self, cords_dev: "LnrCordsDev", d_off_ptr: int, read_ids: list[str], what: str, copy: bool = True):
+        """Device form: the result of Filter.filter_batch_dev and the batch's device read offsets (n + 1)."""
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_dev(self.h, C.byref(cords_dev), d_off_ptr, blob, _p(ido, _u64p), {"sam": 1, "apf": 2}[what], C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value) if copy else (text.value, size.value)
+
+    def gpu_times(self) -> dict:
+        """Milliseconds of the last GPU format call: upload and download (wall), measure / scan / emit (HIP events)."""
+        ms = (C.c_double * 5)()
+        self._check(self.lib.lnr_writer_gpu_times(self.h, ms))
+        return dict(zip(("upload_ms", "measure_ms", "scan_ms", "emit_ms", "download_ms"), ms))
 
     def sam_header(self, command_line: str) -> bytes:
         text, size = C.c_void_p(), C.c_uint64()

@@ -40,7 +40,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0;
     std::vector<int> devices;
 };
 
@@ -55,7 +55,8 @@ static void usage() {
             "    -ss, --sequence_sam INT    0 {DEFAULT} (1 not built here)\nMore options\n    -dup, --duplication INT    0 {DEFAULT} | 1\n    -b,  --bal_flag INT        1 {DEFAULT}\n"
             "    -p,  --preset INT          1 {DEFAULT} | 2   (0 not built here)\n    -i,  --index_type INT      1 {DEFAULT} | 2\n    -c,  --apx_c_flag INT      1 {DEFAULT}\n    -f,  --feature_type INT    2 {DEFAULT}\n"
             "    -r,  --reform_ccs_cigar_flag INT   0 {DEFAULT}\nMI355X front-end\n    --gpus INT                 GPUs to use {1}\n    --devices LIST             their HIP ordinals, e.g. 0,1,2,3\n"
-            "    --block-reads INT          reads per block {65536}\n    --index-mode bcast|build   several GPUs: RCCL broadcast of the index {DEFAULT} or every GPU builds its own\n");
+            "    --block-reads INT          reads per block {65536}\n    --index-mode bcast|build   several GPUs: RCCL broadcast of the index {DEFAULT} or every GPU builds its own\n"
+            "    --gpu-writer               format .sam / .apf text on the first GPU in use instead of the writer's host threads {off}\n");
 }
 
 // returns 0 ok, 1 error, 2 help shown
@@ -80,6 +81,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         if (s.size() < 2 || s[0] != '-' || is_number(s.substr(1))) { pos.push_back(s); continue; }
         std::string name = s.substr(s[1] == '-' ? 2 : 1), val;
         bool has_val = false;
+        if (name == "gpu-writer") { o.gpu_writer = 1; continue; }                                  // a switch: takes no value
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         const Opt *op = nullptr;
@@ -230,6 +232,12 @@ int main(int argc, char **argv) {
     if (lnr_writer_create(gn.data(), gl.data(), (uint32_t)gn.size(), &wr) != LNR_OK) { fprintf(stderr, "E: writer\n"); return 1; }
     lnr_writer_set_preset(wr, o.sensitivity);
     lnr_writer_set_read_group(wr, o.read_group.c_str(), o.sample_name.c_str());
+    if (o.gpu_writer && lnr_writer_gpu_open(wr, o.devices[0]) != LNR_OK) {                       // before any output file is opened
+        fprintf(stderr, "\033[1;31mE:\033[0m --gpu-writer: %s\n", lnr_writer_error(wr));
+        lnr_writer_destroy(wr);
+        for (auto *c : ctx) lnr_destroy(c);
+        return 1;
+    }
 
     // ---- the pipeline
     Shared sh;
@@ -353,8 +361,12 @@ int main(int argc, char **argv) {
                 }
             }
             double tw0 = now();
-            if (fsam) { lnr_writer_format(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), 1, o.thread, &text, &size); if (fwrite(text, 1, size, fsam) != size) { sh.fail("write error (.sam)"); break; } }
-            if (fapf) { lnr_writer_format(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), 2, o.thread, &text, &size); if (fwrite(text, 1, size, fapf) != size) { sh.fail("write error (.apf)"); break; } }
+            auto format = [&](int what) {
+                return o.gpu_writer ? lnr_writer_format_gpu(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), what, &text, &size)
+                                    : lnr_writer_format(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), what, o.thread, &text, &size);
+            };
+            if (fsam) { if (format(1) != LNR_OK) { sh.fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fsam) != size) { sh.fail("write error (.sam)"); break; } }
+            if (fapf) { if (format(2) != LNR_OK) { sh.fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fapf) != size) { sh.fail("write error (.apf)"); break; } }
             us_writer += (uint64_t)((now() - tw0) * 1e6);
             total_reads += b->n;
             { std::lock_guard<std::mutex> l(sh.m); sh.written_upto[(size_t)b->worker]++; }

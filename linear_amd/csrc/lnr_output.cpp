@@ -13,6 +13,7 @@
 // Parity: byte-identical to the reference's own functions on the goldens (tests/test_output_cpu.py; APF blank lines follow the
 // reference's rule for a block = one call).
 #include "../../include/linear_amd.h"
+#include "lnr_output_hook.h"
 
 #include <cmath>
 #include <cstdio>
@@ -213,7 +214,7 @@ void apf_read(const Writer &w, const u64 *c, u64 n, u64 L, const char *rid, bool
 
 }  // namespace
 
-struct lnr_writer { Writer w; };
+struct lnr_writer { Writer w; lnr_outgpu *gpu = nullptr; char err[256] = ""; };
 
 extern "C" {
 
@@ -225,7 +226,50 @@ lnr_status lnr_writer_create(const char *const *genome_ids, const uint64_t *geno
     *out = p;
     return LNR_OK;
 }
-void lnr_writer_destroy(lnr_writer *w) { delete w; }
+void lnr_writer_destroy(lnr_writer *w) {
+    if (w && w->gpu && lnr_outgpu_close) lnr_outgpu_close(w->gpu);
+    delete w;
+}
+
+// ---- the GPU twin of lnr_writer_format: the entry points live here (host code), the work behind the weak hook of lnr_output_hook.h
+const char *lnr_writer_error(const lnr_writer *w) { return w ? w->err : "null writer"; }
+
+lnr_status lnr_writer_gpu_open(lnr_writer *wr, int32_t device) {
+    if (!wr) return LNR_ERR_ARG;
+    if (wr->gpu) return LNR_OK;
+    if (!lnr_outgpu_open) {
+        snprintf(wr->err, sizeof wr->err, "no usable device: this build of the writer has no GPU side (device %d asked for)", (int)device);
+        return LNR_ERR_NO_DEVICE;
+    }
+    std::string blob; std::vector<u64> goff;
+    for (const std::string &g : wr->w.gid) { goff.push_back(blob.size()); blob += g; blob += '\0'; }
+    wr->err[0] = 0;
+    return (lnr_status)lnr_outgpu_open(device, blob.data(), blob.size(), goff.data(), wr->w.glen.data(), (uint32_t)wr->w.gid.size(), &wr->gpu, wr->err, sizeof wr->err);
+}
+
+static lnr_status format_on_gpu(lnr_writer *wr, lnr_outgpu_batch &b, const char **text, uint64_t *size) {
+    if (!wr->gpu) { snprintf(wr->err, sizeof wr->err, "lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
+    b.thd_large_X = wr->w.thd_large_X; b.thd_DI = wr->w.thd_DI; b.thd_X = wr->w.thd_X;
+    wr->err[0] = 0;
+    return (lnr_status)lnr_outgpu_format(wr->gpu, &b, text, size, wr->err, sizeof wr->err);
+}
+lnr_status lnr_writer_format_gpu(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
+                                 int what, const char **text, uint64_t *size) {
+    if (!wr || !cords || !read_len || !read_ids || !id_off || !text || !size || (what != 1 && what != 2)) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{0, cords->n_reads, cords->n_cords, cords->cord_off, cords->cords_str, cords->cords_end, read_len, read_ids, id_off, what, 0, 0, 0};
+    return format_on_gpu(wr, b, text, size);
+}
+lnr_status lnr_writer_format_dev(lnr_writer *wr, const lnr_cords_dev *cords, const uint64_t *d_read_off, const char *read_ids, const uint64_t *id_off,
+                                 int what, const char **text, uint64_t *size) {
+    if (!wr || !cords || !read_ids || !id_off || !text || !size || (what != 1 && what != 2) || (cords->n_reads && !d_read_off)) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, what, 0, 0, 0};
+    return format_on_gpu(wr, b, text, size);
+}
+lnr_status lnr_writer_gpu_times(const lnr_writer *wr, double *ms5) {
+    if (!wr || !ms5 || !wr->gpu) return LNR_ERR_ARG;
+    lnr_outgpu_times(wr->gpu, ms5);
+    return LNR_OK;
+}
 
 // what: 1 = SAM records, 2 = APF.  Reads are formatted on `threads` host threads and concatenated in read order.
 lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,

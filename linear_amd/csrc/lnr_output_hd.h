@@ -1,0 +1,228 @@
+// lnr_output_hd.h -- the two per-read formatters of lnr_output.cpp (SAM records, APF text) as __host__ __device__ code over raw arrays.
+//
+// PRODUCT code: the kernels of lnr_output_kernels.hip call these functions on the device; tests/output_shim.cpp compiles the same text
+// with g++ so that every byte is pinned on a machine without a GPU (tests/test_output_hd_cpu.py).  The host writer lnr_writer_format keeps
+// its own std::string form in lnr_output.cpp and is the yardstick this file is compared with.
+//
+// Unit of work: the ITEM = one cord j (1 <= j < n) of a read.
+//   APF  item j = the '@' header when cord j - 1 ends a block, then the '|' line of cord j          (print_cords_apf f_io.cpp:100-207)
+//   SAM  item j = the whole record line when cord j starts a record (j == 1 or ifCreateNew_ between j - 1 and j), else nothing
+//                                                                                                 (cords2BamLink f_io.cpp:899-1011)
+// An item is written through a SINK with put(char): CountSink measures, a byte sink emits, one body serves both, so size and content
+// cannot disagree.  No std::string / std::vector: a record's CIGAR is streamed through a one-element merge window (appendCigarShrink
+// only ever looks at the last element), the SA:Z summary of a record is a second walk over its cords.
+#pragma once
+#include <stdint.h>
+#include <math.h>
+#include "ref_sort.h"      // LNR_HD
+
+namespace lnr_out {
+
+typedef uint64_t u64;
+typedef int64_t i64;
+typedef uint32_t u32;
+
+struct Params {                 // plain data: what the writer knows about the genome and the preset
+    const char *gblob;          // genome names, '\0'-separated
+    const u64 *goff;            // nseq: start of name g in gblob
+    const u64 *glen;            // nseq
+    u32 nseq;
+    u64 thd_large_X;
+    i64 thd_DI, thd_X;
+};
+
+LNR_HD inline u64 cx(u64 v) { return (v >> 20) & ((1ULL << 30) - 1); }
+LNR_HD inline u64 cy(u64 v) { return v & 0xfffffULL; }
+LNR_HD inline u64 cid(u64 v) { return (v >> 50) & 1023ULL; }
+LNR_HD inline u64 cstrand(u64 v) { return (v >> 61) & 1ULL; }
+LNR_HD inline bool cend(u64 v) { return (v >> 60) & 1ULL; }
+LNR_HD inline u64 shift_cord(u64 v, i64 x, i64 y) { return (u64)((i64)v + (x << 20) + y); }
+LNR_HD inline i64 iabs(i64 v) { return v < 0 ? -v : v; }
+
+// ---- sinks and text primitives
+struct CountSink { u64 n = 0; LNR_HD void put(char) { n++; } };
+struct ByteSink { char *p; LNR_HD void put(char c) { *p++ = c; } };
+
+template <class S> LNR_HD inline void put_str(S &s, const char *z) { for (; *z; z++) s.put(*z); }
+// decimal by hand: digits are taken low to high into 4-bit slots of one register (no array, no scratch) and handed out high to low;
+// 16 digits per register, the 4 more a 64-bit value may have go first
+template <class S> LNR_HD inline void put_dec16(S &s, u64 v, int min_digits) {
+    u64 acc = 0; int k = 0;
+    do { acc = (acc << 4) | (v % 10); v /= 10; k++; } while (v || k < min_digits);
+    while (k--) { s.put((char)('0' + (acc & 15))); acc >>= 4; }
+}
+template <class S> LNR_HD inline void put_u(S &s, u64 v) {
+    const u64 P16 = 10000000000000000ULL;
+    if (v >= P16) { put_dec16(s, v / P16, 1); put_dec16(s, v % P16, 16); }
+    else put_dec16(s, v, 1);
+}
+template <class S> LNR_HD inline void put_i(S &s, i64 v) {
+    if (v < 0) { s.put('-'); put_u(s, (u64)0 - (u64)v); }
+    else put_u(s, (u64)v);
+}
+LNR_HD inline const char *gname(const Params &P, u64 g) { return g < P.nseq ? P.gblob + P.goff[g] : "*"; }
+
+// ---- APF
+template <class S> LNR_HD inline void apf_item(S &out, const Params &P, const u64 *c, u64 n, u64 j, u64 L, const char *rid, bool blank_before) {
+    bool head = cend(c[j - 1]);
+    if (head) {
+        u64 m = j; int main_cnt = 0, block_len = 0;
+        while (m < n && !cend(c[m])) { if (cstrand(c[m])) main_cnt++; block_len++; m++; }
+        char main_icon = main_cnt > block_len / 2 ? '-' : (main_cnt == block_len / 2 ? (cstrand(c[j]) ? '-' : '+') : '+');
+        u64 e = m < n ? m : n - 1;                    // the block's last cord: its end flag, or the read's last cord
+        u64 r_end = cy(c[e]) + 96, s_end = cx(c[e]) + 96;
+        if (blank_before) out.put('\n');
+        u64 g = cid(c[j]);
+        out.put('@'); out.put(' '); put_str(out, rid); out.put(' ');
+        put_u(out, L); out.put(' ');
+        put_u(out, cy(c[j])); out.put(' ');
+        put_u(out, r_end < L ? r_end : L); out.put(' ');
+        out.put(main_icon); out.put(' ');
+        put_str(out, gname(P, g)); out.put(' ');
+        put_u(out, g < P.nseq ? P.glen[g] : 0); out.put(' ');
+        put_u(out, cx(c[j])); out.put(' ');
+        put_u(out, s_end); out.put('\n');
+    }
+    i64 d1 = 0, d2 = 0;
+    if (!head) { d1 = (i64)(cx(c[j]) - cx(c[j - 1])); d2 = (i64)(cy(c[j]) - cy(c[j - 1])); }
+    out.put('|'); out.put(' ');
+    put_u(out, cy(c[j])); out.put(' ');
+    put_u(out, cx(c[j])); out.put(' ');
+    put_i(out, d2); out.put(' ');
+    put_i(out, d1); out.put(' ');
+    out.put(cstrand(c[j]) ? '-' : '+');
+    out.put('\n');
+}
+
+// ---- SAM
+LNR_HD inline int if_create_new(u64 c1s, u64 c1e, u64 c2s, u64 thd_large_X) {      // ifCreateNew_ f_io.cpp:674-692
+    u64 x11 = cx(c1s), y11 = cy(c1s), x12 = cx(c1e), y12 = cy(c1e), x21 = cx(c2s), y21 = cy(c2s);
+    return cend(c1s) || x11 > x21 || y11 > y21 || ((i64)(x21 - x12) > (i64)thd_large_X && (i64)(y21 - y12) > (i64)thd_large_X) || cstrand(c1s ^ c2s);
+}
+// cord i is the last of its record
+LNR_HD inline bool rec_last(const u64 *cs, const u64 *ce, u64 n, u64 i, u64 thd_large_X) { return i == n - 1 || if_create_new(cs[i], ce[i], cs[i + 1], thd_large_X); }
+// cord j is the first of a record
+LNR_HD inline bool rec_first(const u64 *cs, const u64 *ce, u64 j, u64 thd_large_X) { return j == 1 || if_create_new(cs[j - 1], ce[j - 1], cs[j], thd_large_X); }
+
+// (float)|DI| / (float)thd_DI, correctly rounded and never fused: 160 / 80 must stay 2, an approximate reciprocal makes it 2.0000002 -> 3 pieces
+LNR_HD inline float div_rn(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+
+// The CIGAR of one record as a stream of merged elements: Ops::op(char, u32 count, index of the element)
+template <class Ops> struct Merge {                   // appendCigarShrink f_io.cpp:659-669 with a window of one element
+    Ops &ops; char op = 0; u32 cnt = 0; u32 idx = 0; bool have = false;
+    LNR_HD explicit Merge(Ops &o) : ops(o) {}
+    LNR_HD void flush() { if (have) { ops.op(op, cnt, idx); idx++; have = false; } }
+    LNR_HD void push(char o, u32 k) { flush(); op = o; cnt = k; have = true; }               // push_back
+    LNR_HD void shrink(char o, u32 k) { if (have && op == o) cnt += k; else push(o, k); }
+};
+template <class M> LNR_HD inline void rect(M &m, u64 a, u64 b, int f_m) {                     // createRectangleCigarPair f_io.cpp:697-718
+    u64 dx = cx(b) - cx(a), dy = cy(b) - cy(a);
+    char o1 = f_m ? 'X' : '=', o2; u32 n1, n2;
+    if (dx >= dy) { o2 = 'D'; n1 = (u32)dy; n2 = (u32)(dx - dy); }
+    else { o2 = 'I'; n1 = (u32)dx; n2 = (u32)(dy - dx); }
+    if (n1) m.shrink(o1, n1);
+    if (n2) m.shrink(o2, n2);
+}
+template <class M> LNR_HD inline void cord2cigar(M &m, u64 c1s, u64 c1e, u64 c2s, i64 thd_DI, i64 thd_X) {   // cord2cigar_ f_io.cpp:758-875
+    // (its diagonal check against the previous cord's return value cannot fail here: that value IS c1s, by construction of the caller)
+    u64 x12 = cx(c1e), y12 = cy(c1e), x21 = cx(c2s), y21 = cy(c2s);
+    if (x12 < x21 && y12 < y21) {
+        rect(m, c1s, c1e, 0);
+        i64 DI = (i64)(x21 - x12 - y21 + y12);
+        i64 X = (i64)(x21 - x12 < y21 - y12 ? x21 - x12 : y21 - y12);
+        if (iabs(DI) > thd_DI && X > thd_X) {
+            i64 split_n = (i64)ceilf(div_rn((float)iabs(DI), (float)thd_DI));
+            if (X < split_n) split_n = X;
+            i64 split_DI = thd_DI, split_X = X / split_n;
+            u64 s = c1e;
+            for (i64 i = 0; i < split_n - 1; i++) {
+                u64 e = DI < 0 ? shift_cord(s, split_X, split_X + split_DI) : shift_cord(s, split_X + split_DI, split_X);
+                rect(m, s, e, 0);
+                s = e;
+            }
+            rect(m, s, c2s, 1);
+        } else rect(m, c1e, c2s, 1);
+    } else rect(m, c1s, c2s, 0);
+}
+// every element of the record whose first cord is lo, in order; returns the record's last cord
+template <class Ops> LNR_HD inline u64 record_ops(Ops &ops, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L) {
+    Merge<Ops> m(ops);
+    if (cy(cs[lo]) != 0) m.push('S', (u32)cy(cs[lo]));                       // insertNewBamRecord align_util.cpp:325-333
+    u64 i = lo;
+    for (;; i++) {
+        bool last = rec_last(cs, ce, n, i, P.thd_large_X);
+        cord2cigar(m, cs[i], ce[i], last ? ce[i] : cs[i + 1], P.thd_DI, P.thd_X);
+        if (last) break;
+    }
+    i64 clipped = (i64)(int)(L - cy(ce[i]));
+    if (clipped > 0) m.push('S', (u32)clipped);
+    m.flush();
+    return i;
+}
+template <class S> struct TextOps { S &out; u32 k = 0; LNR_HD explicit TextOps(S &o) : out(o) {} LNR_HD void op(char o, u32 c, u32) { put_u(out, c); out.put(o); k++; } };
+struct SazOps {                                                               // createSAZTagCigar align_util.cpp:452-520
+    u64 s0 = 0, cm = 0, nm = 0; i64 ci = 0;
+    LNR_HD void op(char o, u32 c, u32 idx) {
+        if (idx == 0 && o == 'S') s0 = c;
+        else if (o == '=') cm += c;
+        else if (o == 'X') { cm += c; nm += c; }
+        else if (o == 'I') { ci -= c; nm += c; }
+        else if (o == 'D') { ci += c; nm += c; }
+    }
+};
+LNR_HD inline unsigned rec_flag(const u64 *cs, u64 lo) { return (lo == 1 ? 0u : 2048u) | (cstrand(cs[lo]) ? 16u : 0u); }
+
+// the line of record number `it` (of n_rec) whose first cord is lo
+template <class S> LNR_HD inline void sam_item(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname, u64 it, u64 n_rec) {
+    put_str(out, qname); out.put('\t');
+    put_u(out, rec_flag(cs, lo)); out.put('\t');
+    put_str(out, gname(P, (u64)(int)cid(cs[lo]))); out.put('\t');
+    put_i(out, (i64)cx(cs[lo]) + 1); put_str(out, "\t255\t");
+    TextOps<S> t(out);
+    record_ops(t, P, cs, ce, n, lo, L);
+    if (t.k == 0) out.put('*');
+    put_str(out, "\t*\t0\t0\t*\t*");
+    if (n_rec > 1) {                                   // SA:Z: every other record of the read, in record order
+        put_str(out, "\tSA:Z:");
+        u64 a = 1;
+        for (u64 jr = 0; a < n; jr++) {
+            SazOps z;
+            u64 b = record_ops(z, P, cs, ce, n, a, L);
+            if (jr != it) {
+                // NM cache (createSAZTagCigarOneChimeric align_util.cpp:642-678): a record's NM is summed the first time any line lists it --
+                // line 0 lists all others first, line 1 lists record 0 first; every later listing prints 0
+                bool first_visit = it == 0 || (it == 1 && jr == 0);
+                put_str(out, gname(P, (u64)(int)cid(cs[a]))); out.put(',');
+                put_i(out, (i64)cx(cs[a]) + 1); out.put(',');
+                out.put(cstrand(cs[a]) ? '-' : '+'); out.put(',');
+                put_u(out, z.s0); out.put('S');
+                put_u(out, (unsigned)z.cm); out.put('M');
+                put_u(out, (unsigned)iabs(z.ci)); out.put(z.ci < 0 ? 'I' : 'D');
+                put_str(out, "0S,255,");
+                put_i(out, first_visit ? (int)z.nm : 0); out.put(';');
+            }
+            a = b + 1;
+        }
+    }
+    out.put('\n');
+}
+
+// ---- one read, item after item (what the host shim runs; the kernels deal the items of a read to the lanes of a wave instead)
+template <class S> LNR_HD inline void apf_read(S &out, const Params &P, const u64 *c, u64 n, u64 L, const char *rid, bool blank_before) {
+    for (u64 j = 1; j < n; j++) apf_item(out, P, c, n, j, L, rid, blank_before);
+}
+template <class S> LNR_HD inline void sam_read(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 L, const char *qname) {
+    u64 n_rec = 0;
+    for (u64 j = 1; j < n; j++) n_rec += rec_first(cs, ce, j, P.thd_large_X);
+    u64 it = 0;
+    for (u64 j = 1; j < n; j++)
+        if (rec_first(cs, ce, j, P.thd_large_X)) sam_item(out, P, cs, ce, n, j, L, qname, it++, n_rec);
+}
+
+}  // namespace lnr_out

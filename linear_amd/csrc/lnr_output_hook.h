@@ -1,0 +1,24 @@
+// lnr_output_hook.h -- the seam between the writer's C ABI (lnr_output.cpp, host code by g++) and its GPU side (lnr_output_kernels.hip).
+// lnr_output.cpp is also linked WITHOUT the device half (the front-end's test double, tests/stub_abi.cpp), so it refers to these symbols
+// weakly: where they are absent lnr_writer_gpu_open answers LNR_ERR_NO_DEVICE.  Plain data only crosses here.  Return values are lnr_status.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+extern "C" {
+struct lnr_outgpu;
+struct lnr_outgpu_batch {
+    int dev_form;                    // 0: the arrays below are host memory and get uploaded; 1: device memory, used in place
+    uint32_t n_reads; uint64_t n_cords;
+    const uint64_t *cord_off, *cords_str, *cords_end;
+    const uint64_t *read_len;        // dev_form 0: n lengths (host); dev_form 1: n + 1 read offsets (device), length k = off[k + 1] - off[k]
+    const char *read_ids; const uint64_t *id_off;      // host, id_off[k] = start of id k; the blob ends with the '\0' of the last id
+    int what;                        // 1 SAM, 2 APF
+    uint64_t thd_large_X; int64_t thd_DI, thd_X;
+};
+int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, const uint64_t *goff, const uint64_t *glen, uint32_t nseq,
+                    lnr_outgpu **out, char *err, size_t err_cap) __attribute__((weak));
+int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **text, uint64_t *size, char *err, size_t err_cap) __attribute__((weak));
+void lnr_outgpu_times(const lnr_outgpu *g, double *ms5) __attribute__((weak));   // last call: upload, measure, scan, emit, download
+void lnr_outgpu_close(lnr_outgpu *g) __attribute__((weak));
+}

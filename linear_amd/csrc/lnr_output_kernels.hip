@@ -1,0 +1,282 @@
+// lnr_output_kernels.hip -- the GPU side of the writer (lnr_writer_format_gpu / _dev): the cords of a batch -> SAM records or APF text in
+// HBM, then one copy into pinned host memory.  gfx950, wave64.  Every byte comes from lnr_output_hd.h, the same text the CPU test pins.
+//
+// Three steps on the writer's own stream:
+//   k_out_measure  bytes of text per read                      (one wave per read)
+//   k_out_scan     exclusive scan -> 64-bit text offsets, total read back through pinned memory
+//   k_out_emit     every read writes its text at its offset     (one wave per read; placement by the scan alone, no atomics)
+// Tiling: workgroup = one wave = one read, lane = item (cord j of the read, lnr_output_hd.h) in tiles of 64 cords.  Per tile the lanes size
+// their items with the counting sink, a wave scan turns sizes into positions, the lanes format again into an LDS window that mirrors the
+// 4-byte-aligned destination, and the wave copies the window out as coalesced dword stores (single bytes only in the first and last dword
+// of a tile, which neighbouring tiles / reads share).  Text longer than the window takes more rounds: a lane formats once per window its item
+// touches and the sink drops what lies outside.  The block header of an APF item and the record of a SAM item look ahead along the read
+// inside one lane; read index, pointers, counts and the read's text offset are wave-uniform (blockIdx), so the compiler keeps them scalar.
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <new>
+
+#include "lnr_output_hd.h"
+#include "lnr_output_hook.h"
+
+namespace {
+
+using namespace lnr_out;
+
+constexpr u32 OUT_WIN = 8192;                 // bytes of LDS window per wave (a tile of 64 APF lines is about 2 KiB)
+
+struct LdsSink {                              // writes the bytes that fall into the window, counts on past the others
+    char *lds; u64 rel;                       // position relative to the window start (wraps below it: "negative" is huge)
+    __device__ void put(char c) { if (rel < OUT_WIN) lds[rel] = c; rel++; }
+};
+
+__device__ __forceinline__ u64 wave_incl_scan_u64(u64 v) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) { u64 t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
+    return v;
+}
+
+struct ReadArgs {
+    Params P;
+    const u64 *coff, *cs, *ce, *len; int len_is_off;
+    const char *ids; const u64 *idoff;
+    int what;
+};
+
+template <class S> __device__ __forceinline__ void item_text(S &s, const ReadArgs &A, const u64 *cs, const u64 *ce, u64 nc, u64 j, u64 L, const char *id, bool blank,
+                                                             u64 it, u64 n_rec) {
+    if (A.what == 2) apf_item(s, A.P, cs, nc, j, L, id, blank);
+    else sam_item(s, A.P, cs, ce, nc, j, L, id, it, n_rec);
+}
+
+// one wave = read k.  EMIT false: returns the bytes of its text.  EMIT true: writes them to text + toff.
+template <bool EMIT> __device__ u64 format_read(const ReadArgs &A, u32 k, char *text, u64 toff, char *lds) {
+    const int lane = threadIdx.x & 63;
+    const u64 a = A.coff[k], nc = A.coff[k + 1] - a;
+    const u64 *cs = A.cs + a, *ce = A.ce + a;
+    const u64 L = A.len_is_off ? A.len[k + 1] - A.len[k] : A.len[k];
+    const char *id = A.ids + A.idoff[k];
+    const bool blank = k > 0;
+    u64 n_rec = 0;
+    if (A.what == 1)
+        for (u64 base = 1; base < nc; base += 64) {
+            u64 j = base + lane;
+            n_rec += (u64)__popcll(__ballot(j < nc && rec_first(cs, ce, j, A.P.thd_large_X)));
+        }
+    const u32 mis = (u32)(toff & 3);           // the LDS window mirrors the destination from a 4-byte boundary on
+    char *dst = text + (toff - mis);           // staged position p of the read's text <-> dst[p]
+    u64 pos = 0, rec_carry = 0;
+    for (u64 base = 1; base < nc; base += 64) {
+        const u64 j = base + lane;
+        const bool item = j < nc && (A.what == 2 || rec_first(cs, ce, j, A.P.thd_large_X));
+        const u64 bal = __ballot(item);
+        const u64 it = rec_carry + (u64)__popcll(bal & ((1ULL << lane) - 1ULL));
+        u64 sz = 0;
+        if (item) { CountSink c; item_text(c, A, cs, ce, nc, j, L, id, blank, it, n_rec); sz = c.n; }
+        const u64 incl = wave_incl_scan_u64(sz);
+        const u64 tile_total = __shfl(incl, 63, 64);
+        if constexpr (EMIT) {
+            const u64 s0 = mis + pos, s1 = s0 + tile_total, mine = s0 + incl - sz;
+            for (u64 wlo = s0 & ~3ULL; wlo < s1; wlo += OUT_WIN) {
+                if (sz && mine < wlo + OUT_WIN && mine + sz > wlo) { LdsSink s{lds, mine - wlo}; item_text(s, A, cs, ce, nc, j, L, id, blank, it, n_rec); }
+                __syncthreads();               // (the workgroup is this one wave; all loop bounds here are wave-uniform)
+                const u64 lo = wlo > s0 ? wlo : s0, hi = wlo + OUT_WIN < s1 ? wlo + OUT_WIN : s1;
+                for (u32 d = lane; d < OUT_WIN / 4; d += 64) {
+                    const u64 p = wlo + 4ULL * d;
+                    if (p >= hi) break;
+                    if (p + 4 <= lo) continue;
+                    if (p >= lo && p + 4 <= hi) *reinterpret_cast<u32 *>(dst + p) = reinterpret_cast<const u32 *>(lds)[d];
+                    else for (u32 b = 0; b < 4; b++) if (p + b >= lo && p + b < hi) dst[p + b] = lds[4 * d + b];
+                }
+                __syncthreads();
+            }
+        }
+        pos += tile_total;
+        rec_carry += (u64)__popcll(bal);
+    }
+    return pos;
+}
+
+__global__ __launch_bounds__(64) void k_out_measure(ReadArgs A, u64 *sizes) {
+    u64 s = format_read<false>(A, blockIdx.x, nullptr, 0, nullptr);
+    if (threadIdx.x == 0) sizes[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(64) void k_out_emit(ReadArgs A, const u64 *toff, char *text) {
+    __shared__ __attribute__((aligned(16))) char lds[OUT_WIN];
+    format_read<true>(A, blockIdx.x, text, toff[blockIdx.x], lds);
+}
+// in place: a[0 .. n) sizes -> exclusive offsets, a[n] = total.  One workgroup: n is the reads of a batch.
+__global__ __launch_bounds__(1024) void k_out_scan(u64 *a, u32 n) {
+    __shared__ u64 part[1024];
+    const u32 t = threadIdx.x, chunk = (n + 1023) / 1024;
+    const u64 lo = (u64)t * chunk < n ? (u64)t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
+    u64 s = 0;
+    for (u64 i = lo; i < hi; i++) s += a[i];
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) { u64 run = 0; for (u32 i = 0; i < 1024; i++) { u64 v = part[i]; part[i] = run; run += v; } a[n] = run; }
+    __syncthreads();
+    u64 run = part[t];
+    for (u64 i = lo; i < hi; i++) { u64 v = a[i]; a[i] = run; run += v; }
+}
+
+double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct Buf { void *p = nullptr; u64 cap = 0; };
+
+}  // namespace
+
+struct lnr_outgpu {
+    int device = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    Buf gblob, goff, glen, ids, idoff, coff, cs, ce, len, sizes, text;
+    u32 nseq = 0;
+    char *h_text = nullptr; u64 h_cap = 0;      // pinned
+    u64 *h_total = nullptr;                     // pinned
+    double ms[5] = {0, 0, 0, 0, 0};
+};
+
+namespace {
+
+struct DeviceGuard {                            // every entry leaves the caller's current device as it found it
+    int prev = -1;
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+#define OUT_CK(call, status)                                                                                              \
+    do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, err_cap, "%s: %s", #call, hipGetErrorString(e_)); return (status); } } while (0)
+
+int dev_need(Buf &b, u64 bytes, char *err, size_t err_cap) {
+    if (bytes <= b.cap) return 0;
+    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    u64 want = bytes + bytes / 4 + 256;
+    OUT_CK(hipMalloc(&b.p, want), -4);
+    b.cap = want;
+    return 0;
+}
+void free_all(lnr_outgpu *g) {
+    for (Buf *b : {&g->gblob, &g->goff, &g->glen, &g->ids, &g->idoff, &g->coff, &g->cs, &g->ce, &g->len, &g->sizes, &g->text}) if (b->p) (void)hipFree(b->p);
+    if (g->h_text) (void)hipHostFree(g->h_text);
+    if (g->h_total) (void)hipHostFree(g->h_total);
+    for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
+    if (g->st) (void)hipStreamDestroy(g->st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, const uint64_t *goff, const uint64_t *glen, uint32_t nseq,
+                    lnr_outgpu **out, char *err, size_t err_cap) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) { snprintf(err, err_cap, "no usable HIP device for the GPU writer"); return -2; }
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    if (device < 0) device = dg.prev < 0 ? 0 : dg.prev;
+    if (device >= count) { snprintf(err, err_cap, "no usable HIP device %d for the GPU writer (%d present)", (int)device, count); return -2; }
+    lnr_outgpu *g = new (std::nothrow) lnr_outgpu();
+    if (!g) return -4;
+    g->device = device; g->nseq = nseq;
+    auto fail = [&](int s) { free_all(g); delete g; return s; };
+    if (hipSetDevice(device) != hipSuccess) { snprintf(err, err_cap, "hipSetDevice(%d) failed", (int)device); return fail(-2); }
+    int s = 0;
+    auto step = [&]() -> int {
+        OUT_CK(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking), -3);
+        for (hipEvent_t &e : g->ev) OUT_CK(hipEventCreate(&e), -3);
+        OUT_CK(hipHostMalloc((void **)&g->h_total, sizeof(u64), hipHostMallocDefault), -4);
+        if ((s = dev_need(g->gblob, gblob_bytes + 1, err, err_cap)) || (s = dev_need(g->goff, 8ULL * nseq + 8, err, err_cap)) || (s = dev_need(g->glen, 8ULL * nseq + 8, err, err_cap))) return s;
+        if (nseq) {
+            OUT_CK(hipMemcpyAsync(g->gblob.p, gblob, gblob_bytes, hipMemcpyHostToDevice, g->st), -3);
+            OUT_CK(hipMemcpyAsync(g->goff.p, goff, 8ULL * nseq, hipMemcpyHostToDevice, g->st), -3);
+            OUT_CK(hipMemcpyAsync(g->glen.p, glen, 8ULL * nseq, hipMemcpyHostToDevice, g->st), -3);
+        }
+        OUT_CK(hipStreamSynchronize(g->st), -3);
+        return 0;
+    };
+    if ((s = step())) return fail(s);
+    *out = g;
+    return 0;
+}
+
+int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **text, uint64_t *size, char *err, size_t err_cap) {
+    static const char empty[1] = "";
+    for (double &m : g->ms) m = 0;
+    const u32 n = b->n_reads;
+    if (n == 0) { *text = empty; *size = 0; return 0; }
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    OUT_CK(hipSetDevice(g->device), -3);
+    int s;
+    ReadArgs A;
+    A.P.gblob = (const char *)g->gblob.p; A.P.goff = (const u64 *)g->goff.p; A.P.glen = (const u64 *)g->glen.p; A.P.nseq = g->nseq;
+    A.P.thd_large_X = b->thd_large_X; A.P.thd_DI = b->thd_DI; A.P.thd_X = b->thd_X;
+    A.what = b->what;
+    // read ids: once per call, '\0'-separated blob + offsets
+    double t0 = wall_ms();
+    const u64 id_bytes = b->id_off[n - 1] + strlen(b->read_ids + b->id_off[n - 1]) + 1;
+    if ((s = dev_need(g->ids, id_bytes, err, err_cap)) || (s = dev_need(g->idoff, 8ULL * n, err, err_cap)) || (s = dev_need(g->sizes, 8ULL * (n + 1ULL), err, err_cap))) return s;
+    OUT_CK(hipMemcpyAsync(g->ids.p, b->read_ids, id_bytes, hipMemcpyHostToDevice, g->st), -3);
+    OUT_CK(hipMemcpyAsync(g->idoff.p, b->id_off, 8ULL * n, hipMemcpyHostToDevice, g->st), -3);
+    A.ids = (const char *)g->ids.p; A.idoff = (const u64 *)g->idoff.p;
+    if (b->dev_form) {
+        A.coff = b->cord_off; A.cs = b->cords_str; A.ce = b->cords_end; A.len = b->read_len; A.len_is_off = 1;
+    } else {
+        if ((s = dev_need(g->coff, 8ULL * (n + 1ULL), err, err_cap)) || (s = dev_need(g->cs, 8ULL * b->n_cords + 8, err, err_cap)) ||
+            (s = dev_need(g->ce, 8ULL * b->n_cords + 8, err, err_cap)) || (s = dev_need(g->len, 8ULL * n, err, err_cap))) return s;
+        OUT_CK(hipMemcpyAsync(g->coff.p, b->cord_off, 8ULL * (n + 1ULL), hipMemcpyHostToDevice, g->st), -3);
+        if (b->n_cords) {
+            OUT_CK(hipMemcpyAsync(g->cs.p, b->cords_str, 8ULL * b->n_cords, hipMemcpyHostToDevice, g->st), -3);
+            OUT_CK(hipMemcpyAsync(g->ce.p, b->cords_end, 8ULL * b->n_cords, hipMemcpyHostToDevice, g->st), -3);
+        }
+        OUT_CK(hipMemcpyAsync(g->len.p, b->read_len, 8ULL * n, hipMemcpyHostToDevice, g->st), -3);
+        A.coff = (const u64 *)g->coff.p; A.cs = (const u64 *)g->cs.p; A.ce = (const u64 *)g->ce.p; A.len = (const u64 *)g->len.p; A.len_is_off = 0;
+    }
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    g->ms[0] = wall_ms() - t0;
+    u64 *sizes = (u64 *)g->sizes.p;
+    OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
+    hipLaunchKernelGGL(k_out_measure, dim3(n), dim3(64), 0, g->st, A, sizes);
+    OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
+    hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, g->st, sizes, n);
+    OUT_CK(hipEventRecord(g->ev[2], g->st), -3);
+    OUT_CK(hipMemcpyAsync(g->h_total, sizes + n, sizeof(u64), hipMemcpyDeviceToHost, g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    OUT_CK(hipGetLastError(), -3);
+    const u64 total = *g->h_total;
+    if ((s = dev_need(g->text, total + 8, err, err_cap))) return s;
+    if (total + 8 > g->h_cap) {
+        if (g->h_text) { (void)hipHostFree(g->h_text); g->h_text = nullptr; g->h_cap = 0; }
+        u64 want = total + total / 4 + 4096;
+        OUT_CK(hipHostMalloc((void **)&g->h_text, want, hipHostMallocDefault), -4);
+        g->h_cap = want;
+    }
+    OUT_CK(hipEventRecord(g->ev[3], g->st), -3);
+    hipLaunchKernelGGL(k_out_emit, dim3(n), dim3(64), 0, g->st, A, (const u64 *)sizes, (char *)g->text.p);
+    OUT_CK(hipEventRecord(g->ev[4], g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    OUT_CK(hipGetLastError(), -3);
+    t0 = wall_ms();
+    if (total) OUT_CK(hipMemcpyAsync(g->h_text, g->text.p, total, hipMemcpyDeviceToHost, g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    g->ms[4] = wall_ms() - t0;
+    float f = 0;
+    OUT_CK(hipEventElapsedTime(&f, g->ev[0], g->ev[1]), -3); g->ms[1] = f;
+    OUT_CK(hipEventElapsedTime(&f, g->ev[1], g->ev[2]), -3); g->ms[2] = f;
+    OUT_CK(hipEventElapsedTime(&f, g->ev[3], g->ev[4]), -3); g->ms[3] = f;
+    *text = g->h_text; *size = total;
+    return 0;
+}
+
+void lnr_outgpu_times(const lnr_outgpu *g, double *ms5) { for (int i = 0; i < 5; i++) ms5[i] = g->ms[i]; }
+
+void lnr_outgpu_close(lnr_outgpu *g) {
+    if (!g) return;
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    (void)hipSetDevice(g->device);
+    free_all(g);
+    delete g;
+}
+
+}  // extern "C"

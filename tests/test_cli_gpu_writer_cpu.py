@@ -1,0 +1,53 @@
+"""CPU: the front-end's --gpu-writer switch against the test double of the device half (tests/stub_abi.cpp + the real reader and writer,
+as tests/test_cli_frontend_cpu.py links them): the double has no GPU side, so the switch must be refused with a message that names the
+missing device before any output file exists; without the switch nothing changes; the usage text lists it."""
+import os
+import subprocess
+
+import pytest
+
+from tests.test_cli_frontend_cpu import write_inputs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = os.path.join(ROOT, "tests", "_build")
+CSRC = os.path.join(ROOT, "linear_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def cli():
+    os.makedirs(BUILD, exist_ok=True)
+    so, exe = os.path.join(BUILD, "libstub_gpuw_linear_amd.so"), os.path.join(BUILD, "linear_filter_stub_gpuw")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", os.path.join(ROOT, "tests", "stub_abi.cpp"), os.path.join(CSRC, "lnr_reader.cpp"),
+                           os.path.join(CSRC, "lnr_output.cpp"), "-o", so, "-lz", "-lpthread"])
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", os.path.join(CSRC, "linear_filter_main.cpp"), "-o", exe, so, "-Wl,-rpath," + BUILD, "-lpthread"])
+    return exe
+
+
+def run(cli, args, cwd):
+    return subprocess.run([cli] + args, cwd=str(cwd), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+
+
+def test_gpu_writer_switch_without_a_gpu_side(cli, tmp_path):
+    reads, ref = write_inputs(tmp_path, n_reads=60)
+    base = run(cli, ["filter", reads[0], ref, "-t", "2", "-ot", "3", "-o", str(tmp_path / "plain"), "--block-reads", "7"], tmp_path)
+    assert base.returncode == 0, base.stderr.decode()
+    for extra in (["--gpu-writer"], ["--gpu-writer", "--devices", "3"]):
+        p = run(cli, ["filter", reads[0], ref, "-t", "2", "-ot", "3", "-o", str(tmp_path / "gw"), "--block-reads", "7"] + extra, tmp_path)
+        assert p.returncode == 1, p.stderr.decode()
+        assert b"--gpu-writer" in p.stderr and b"no usable device" in p.stderr and (b"device %d" % (3 if "3" in extra else 0)) in p.stderr
+        assert not os.path.exists(tmp_path / "gw.sam") and not os.path.exists(tmp_path / "gw.apf")      # nothing half written
+    # the switch takes no value: what follows it is still read as an argument, in any position
+    p = run(cli, ["filter", "--gpu-writer", reads[0], ref, "-ot", "2", "-o", str(tmp_path / "gw2")], tmp_path)
+    assert p.returncode == 1 and b"no usable device" in p.stderr and not os.path.exists(tmp_path / "gw2.sam")
+    # without it: the same run gives the same files again
+    again = run(cli, ["filter", reads[0], ref, "-t", "2", "-ot", "3", "-o", str(tmp_path / "plain2"), "--block-reads", "7"], tmp_path)
+    assert again.returncode == 0
+    for ext in (".sam", ".apf"):
+        a, b = open(tmp_path / ("plain" + ext), "rb").read(), open(tmp_path / ("plain2" + ext), "rb").read()
+        assert a == b and len(a) > 500
+
+
+def test_usage_lists_the_switch(cli, tmp_path):
+    p = run(cli, ["filter", "-h", "x", "y"], tmp_path)
+    assert p.returncode == 0 and b"MI355X front-end" in p.stderr
+    assert b"--gpu-writer" in p.stderr.split(b"MI355X front-end")[1]
