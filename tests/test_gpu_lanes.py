@@ -110,6 +110,48 @@ def test_gpu_two_lanes_equal_one_batch_at_a_time(case_inputs, oracle_lib, monkey
     f.close()
 
 
+def test_gpu_lane_1_follows_an_index_rebuilt_between_pipelines(case_inputs, oracle_lib, monkeypatch, capfd):
+    """Both lanes read the one index of their context: after lane 1 has computed on a first index, lnr_index_build with nothing in flight
+    on another, larger reference set (the index buffers are sized anew) must reach lane 1 as well -- sizes, offsets, device pointers.
+    Every batch of a pipeline on the second index equals the same batch through lnr_filter_batch on a fresh one-lane context."""
+    from linear_amd import Filter, synth
+    refs, batches = _batches(case_inputs)
+    monkeypatch.setenv("LNR_DEBUG_TIMES", "1")
+    f = Filter(device=0)
+    f.build_index(refs, 3)
+    capfd.readouterr()
+    first = _pipeline(f, [batches[k] for k in (0, 3, 4, 6)])
+    err = capfd.readouterr().err
+    assert err.count("| lane 1 allocations") >= 1 and err.count("| lane 0 allocations") >= 1, "both lanes must have computed on the first index"
+    g = np.load(os.path.join(GOLD, "edge_T3.npz"))
+    assert np.array_equal(first[0][0], g["cord_off"]) and np.array_equal(first[0][1], g["cords_str"]) and np.array_equal(first[0][2], g["cords_end"])
+    refs2 = case_inputs("rep")[0]
+    assert sum(r.size for r in refs2) != sum(r.size for r in refs) and max(r.size for r in refs2) > max(r.size for r in refs)
+    batches2 = [synth.sample_reads(refs2, 40, 8000, 0.10, 9100 + k, "random")[:2] for k in range(4)]
+    batches2 = [(np.ascontiguousarray(r, np.uint8), np.ascontiguousarray(o, np.uint64)) for r, o in batches2]
+    f.build_index(refs2, 1)
+    capfd.readouterr()
+    got = _pipeline(f, batches2)
+    err = capfd.readouterr().err
+    assert err.count("| lane 1 allocations") >= 1 and err.count("| lane 0 allocations") >= 1, "both lanes must have computed on the second index"
+    assert "lane 1 out of memory" not in err
+    f.close()
+    monkeypatch.delenv("LNR_DEBUG_TIMES")
+    monkeypatch.setenv("LNR_LANES", "1")
+    one = Filter(device=0)
+    monkeypatch.delenv("LNR_LANES")
+    one.build_index(refs2, 1)
+    want = [one.filter_batch(*b) for b in batches2]
+    one.close()
+    assert all(w[1].size > 0 for w in want)
+    for k, (w, c) in enumerate(zip(want, got)):
+        assert _same(w, c), k
+    o = oracle_lib.Checker("oracle", refs2, 1)
+    ooff, ocs, oce, _ = o.map_batch(*batches2[1], threads=8)
+    o.close()
+    assert np.array_equal(got[1][0], ooff) and np.array_equal(got[1][1], ocs) and np.array_equal(got[1][2], oce)
+
+
 def test_gpu_lane_1_out_of_memory_falls_back_to_one_lane(case_inputs, monkeypatch, capfd):
     """A workload that fits once but not twice: LNR_LANE1_NOMEM=1 makes lane 1's first batch fail with LNR_ERR_NOMEM, as a full device would.
     The batch is run again on lane 0 and handed out in its place, no batch reports an error, and every later batch runs on lane 0."""

@@ -1,6 +1,6 @@
 """GPU (-m gpu): a read's cords must not depend on where the read sits in its batch, on the batch's size, on what lies around the
 batch in host memory or on what the context ran before -- and, while the gap re-mapper's stream state is still 0, on how the batch
-falls onto the chunks of the probe ladder (lnr_api.hip filter_dev: 256, 1 024, 4 096 ... reads).  The oracle is the checker
+falls onto the chunks of the probe ladder (lnr_gap_stage.h gap_stage: 256, 1 024, 4 096 ... reads).  The oracle is the checker
 throughout (pinned to the real program by tests/test_oracle_golden.py); every value is an integer word, so every comparison is exact,
 and no read is left out of one."""
 import os
