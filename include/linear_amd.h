@@ -256,6 +256,24 @@ lnr_status lnr_writer_format_dev(lnr_writer *w, const lnr_cords_dev *cords, cons
                                  const char *read_ids, const uint64_t *id_off, int what, const char **text, uint64_t *size);
 lnr_status lnr_writer_gpu_times(const lnr_writer *w, double *ms5);
 const char *lnr_writer_error(const lnr_writer *w);
+/* SAM with the SEQ column, as the reference prints it with -ss 1 (fillBamRecordLinkRecords align_util.cpp:745-808, cigar2SamSeq :1434-1500):
+ * the record's CIGAR is walked with the genome at (RNAME, POS) and the read at its first base (flag 16: at the first base of its reverse
+ * complement); S and I print the read's bases, '=' prints the GENOME's, X prints the read's base where it differs from the genome's and N
+ * where it does not, D prints nothing; an empty SEQ prints '*'.  Every other byte of the line is that of lnr_writer_format(what = 1).
+ * A source position outside its sequence (undefined behaviour in the reference) reads as ordinal 0 ('A'), ordinals above 4 read as N.
+ * lnr_writer_set_genome: nseq host pointers (Dna5 ordinals, lengths as given to lnr_writer_create), borrowed until lnr_writer_destroy or the
+ * next call; NULL = off.  Without it the three format calls return LNR_ERR_ARG (lnr_writer_error says so); the two GPU forms also before
+ * lnr_writer_gpu_open.  The GPU side uploads ITS OWN byte-per-base copy of the genome in the first SEQ call after set_genome + gpu_open
+ * (either order) and again only after another set_genome: 3.1 GB of HBM for a human genome, next to whatever a lnr_ctx holds -- the
+ * writer stays independent of any context.  reads_concat / read_off[n + 1]: the layout lnr_filter_batch takes (device memory for _dev).
+ * Text lifetime, current device and lnr_writer_gpu_times as for the calls above. */
+lnr_status lnr_writer_set_genome(lnr_writer *w, const uint8_t *const *seq);
+lnr_status lnr_writer_format_seq(lnr_writer *w, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_off,
+                                 const char *read_ids, const uint64_t *id_off, uint32_t threads, const char **text, uint64_t *size);
+lnr_status lnr_writer_format_seq_gpu(lnr_writer *w, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_off,
+                                     const char *read_ids, const uint64_t *id_off, const char **text, uint64_t *size);
+lnr_status lnr_writer_format_seq_dev(lnr_writer *w, const lnr_cords_dev *cords, const uint8_t *d_reads_concat, const uint64_t *d_read_off,
+                                     const char *read_ids, const uint64_t *id_off, const char **text, uint64_t *size);
 
 #ifdef __cplusplus
 }

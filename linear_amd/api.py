@@ -59,7 +59,8 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_cords_to_host", "lnr_seed_lookup_batch", "lnr_seed_lookup_batch_dev", "lnr_last_stats", "lnr_filter_submit", "lnr_filter_wait",
            "lnr_host_alloc", "lnr_host_free", "lnr_reader_open", "lnr_reader_next", "lnr_reader_ids", "lnr_reader_error", "lnr_reader_close",
            "lnr_writer_create", "lnr_writer_format", "lnr_writer_sam_header", "lnr_writer_destroy", "lnr_last_gaps", "lnr_gap_stream", "lnr_set_gap", "lnr_index_broadcast", "lnr_writer_set_preset", "lnr_writer_set_read_group",
-           "lnr_writer_gpu_open", "lnr_writer_format_gpu", "lnr_writer_format_dev", "lnr_writer_gpu_times", "lnr_writer_error"]
+           "lnr_writer_gpu_open", "lnr_writer_format_gpu", "lnr_writer_format_dev", "lnr_writer_gpu_times", "lnr_writer_error",
+           "lnr_writer_set_genome", "lnr_writer_format_seq", "lnr_writer_format_seq_gpu", "lnr_writer_format_seq_dev"]
 
 
 def load_library() -> C.CDLL:
@@ -110,6 +111,10 @@ def load_library() -> C.CDLL:
     lib.lnr_writer_gpu_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.lnr_writer_error.restype = C.c_char_p
     lib.lnr_writer_error.argtypes = [C.c_void_p]
+    lib.lnr_writer_set_genome.argtypes = [C.c_void_p, C.POINTER(_u8p)]
+    lib.lnr_writer_format_seq.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.c_uint32, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_seq_gpu.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_seq_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev), C.c_void_p, C.c_void_p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
     return lib
 
 
@@ -414,6 +419,56 @@ class Writer:
         blob, ido = self._ids(read_ids)
         text, size = C.c_void_p(), C.c_uint64()
         self._check(self.lib.lnr_writer_format_dev(self.h, C.byref(cords_dev), d_off_ptr, blob, _p(ido, _u64p), {"sam": 1, "apf": 2}[what], C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value) if copy else (text.value, size.value)
+
+    def set_genome(self, seqs) -> None:
+        """The genome's bases (one uint8 array of Dna5 ordinals per sequence, lengths as given to the constructor) for the SEQ column of
+        format_seq*; None = off.  The arrays are kept alive by the writer."""
+        if seqs is None:
+            self._genome = None
+            self._check(self.lib.lnr_writer_set_genome(self.h, None))
+            return
+        keep = [np.ascontiguousarray(s, dtype=np.uint8) for s in seqs]
+        keep = [s if s.size else np.zeros(1, np.uint8) for s in keep]
+        arr = (_u8p * max(len(keep), 1))(*[_p(s, _u8p) for s in keep])
+        self._genome = (keep, arr)
+        self._check(self.lib.lnr_writer_set_genome(self.h, arr))
+
+    @staticmethod
+    def _seq_args(cord_off, cords_str, cords_end, reads, read_off):
+        cord_off = np.ascontiguousarray(cord_off, dtype=np.uint64)
+        cs = np.ascontiguousarray(cords_str, dtype=np.uint64)
+        ce = np.ascontiguousarray(cords_end, dtype=np.uint64)
+        reads = np.ascontiguousarray(reads, dtype=np.uint8)
+        if reads.size == 0:
+            reads = np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        c = LnrCords()
+        c.n_reads, c.n_cords = cord_off.size - 1, cs.size
+        c.cord_off, c.cords_str, c.cords_end = _p(cord_off, _u64p), _p(cs, _u64p), _p(ce, _u64p)
+        return c, reads, off, (cord_off, cs, ce)
+
+    def format_seq(self, cord_off: np.ndarray, cords_str: np.ndarray, cords_end: np.ndarray, reads: np.ndarray, read_off: np.ndarray, read_ids: list[str], threads: int = 4) -> bytes:
+        """SAM records with the SEQ column (the reference's -ss 1) on host threads; reads / read_off[n + 1] as filter_batch takes them."""
+        c, reads, off, _keep = self._seq_args(cord_off, cords_str, cords_end, reads, read_off)
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_seq(self.h, C.byref(c), _p(reads, _u8p), _p(off, _u64p), blob, _p(ido, _u64p), threads, C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value)
+
+    def format_seq_gpu(self, cord_off: np.ndarray, cords_str: np.ndarray, cords_end: np.ndarray, reads: np.ndarray, read_off: np.ndarray, read_ids: list[str], copy: bool = True):
+        """The bytes of format_seq(), formatted on the GPU."""
+        c, reads, off, _keep = self._seq_args(cord_off, cords_str, cords_end, reads, read_off)
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_seq_gpu(self.h, C.byref(c), _p(reads, _u8p), _p(off, _u64p), blob, _p(ido, _u64p), C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value) if copy else (text.value, size.value)
+
+    def format_seq_dev(self, cords_dev: "LnrCordsDev", d_reads_ptr: int, d_off_ptr: int, read_ids: list[str], copy: bool = True):
+        """Device form of format_seq_gpu: the result of Filter.filter_batch_dev with the batch's device bases and read offsets (n + 1)."""
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_seq_dev(self.h, C.byref(cords_dev), d_reads_ptr, d_off_ptr, blob, _p(ido, _u64p), C.byref(text), C.byref(size)))
         return C.string_at(text, size.value) if copy else (text.value, size.value)
 
     def gpu_times(self) -> dict:

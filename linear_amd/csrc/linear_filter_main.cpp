@@ -14,7 +14,9 @@
 //   gap stream     with -g > 0 the reference's result depends on the order reads meet a thread's GapParms (lnr_gap_stream in the header): the blocks
 //                  are taken strictly in file order until a block reports the stream "extended"; from then on every GPU runs freely with that state.
 //                  The result is the reference's `-t 1` result whatever --gpus is.
-// Not built (exit 1 with a message, never a silently different result): BAM output (-ot 4 / 8), -ss 1 (SEQ printing), -c 0, -f 1, -r 1, -p 0, -b 0
+//   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
+//                  option -ss itself stays refused.
+// Not built (exit 1 with a message, never a silently different result): BAM output (-ot 4 / 8), -ss 1 (use --sam-seq), -c 0, -f 1, -r 1, -p 0, -b 0
 // (the reference's -b 0 path writes a header-only SAM: SURVEY App. C.7).
 #include "../../include/linear_amd.h"
 
@@ -40,7 +42,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0;
     std::vector<int> devices;
 };
 
@@ -52,11 +54,12 @@ static void usage() {
             "Basic options\n    -o,  --output STR          prefix of the output (default: the read file's name up to its first '.')\n"
             "    -ot, --output_type INT     1 .apf, 2 .sam {DEFAULT}, 3 both (4 / 8: BAM, not built here)\n    -t,  --thread INT          threads: the index layout of the reference's -t and the host threads of the writer {16}\n"
             "    -g,  --gap_len INT         minimal length of gaps to re-map; -g 0 off; bare -g or 1 = 50 {DEFAULT}\n    -rg, --read_group STR      @RG ID\n    -sn, --sample_name STR     @RG SM\n"
-            "    -ss, --sequence_sam INT    0 {DEFAULT} (1 not built here)\nMore options\n    -dup, --duplication INT    0 {DEFAULT} | 1\n    -b,  --bal_flag INT        1 {DEFAULT}\n"
+            "    -ss, --sequence_sam INT    0 {DEFAULT} (1 not built here: --sam-seq prints what the reference prints with -ss 1)\nMore options\n    -dup, --duplication INT    0 {DEFAULT} | 1\n    -b,  --bal_flag INT        1 {DEFAULT}\n"
             "    -p,  --preset INT          1 {DEFAULT} | 2   (0 not built here)\n    -i,  --index_type INT      1 {DEFAULT} | 2\n    -c,  --apx_c_flag INT      1 {DEFAULT}\n    -f,  --feature_type INT    2 {DEFAULT}\n"
             "    -r,  --reform_ccs_cigar_flag INT   0 {DEFAULT}\nMI355X front-end\n    --gpus INT                 GPUs to use {1}\n    --devices LIST             their HIP ordinals, e.g. 0,1,2,3\n"
             "    --block-reads INT          reads per block {65536}\n    --index-mode bcast|build   several GPUs: RCCL broadcast of the index {DEFAULT} or every GPU builds its own\n"
-            "    --gpu-writer               format .sam / .apf text on the first GPU in use instead of the writer's host threads {off}\n");
+            "    --gpu-writer               format .sam / .apf text on the first GPU in use instead of the writer's host threads {off}\n"
+            "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n");
 }
 
 // returns 0 ok, 1 error, 2 help shown
@@ -82,6 +85,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         std::string name = s.substr(s[1] == '-' ? 2 : 1), val;
         bool has_val = false;
         if (name == "gpu-writer") { o.gpu_writer = 1; continue; }                                  // a switch: takes no value
+        if (name == "sam-seq") { o.sam_seq = 1; continue; }
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         const Opt *op = nullptr;
@@ -232,6 +236,7 @@ int main(int argc, char **argv) {
     if (lnr_writer_create(gn.data(), gl.data(), (uint32_t)gn.size(), &wr) != LNR_OK) { fprintf(stderr, "E: writer\n"); return 1; }
     lnr_writer_set_preset(wr, o.sensitivity);
     lnr_writer_set_read_group(wr, o.read_group.c_str(), o.sample_name.c_str());
+    if (o.sam_seq) lnr_writer_set_genome(wr, gp.data());                                         // (the genome vectors outlive the writer)
     if (o.gpu_writer && lnr_writer_gpu_open(wr, o.devices[0]) != LNR_OK) {                       // before any output file is opened
         fprintf(stderr, "\033[1;31mE:\033[0m --gpu-writer: %s\n", lnr_writer_error(wr));
         lnr_writer_destroy(wr);
@@ -362,6 +367,9 @@ int main(int argc, char **argv) {
             }
             double tw0 = now();
             auto format = [&](int what) {
+                if (what == 1 && o.sam_seq)                              // the block's bases are alive: it is recycled below, after the writer is through
+                    return o.gpu_writer ? lnr_writer_format_seq_gpu(wr, &b->cords, b->bases, b->off.data(), b->ids.data(), b->id_off.data(), &text, &size)
+                                        : lnr_writer_format_seq(wr, &b->cords, b->bases, b->off.data(), b->ids.data(), b->id_off.data(), o.thread, &text, &size);
                 return o.gpu_writer ? lnr_writer_format_gpu(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), what, &text, &size)
                                     : lnr_writer_format(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), what, o.thread, &text, &size);
             };

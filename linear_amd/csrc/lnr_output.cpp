@@ -148,9 +148,37 @@ struct Writer {
     std::string text;
     u64 thd_large_X = 8000; i64 thd_DI = 80, thd_X = 200;      // mapper.cpp:465,185-186 (preset 1)
     std::string rg, sn;                                        // -rg / -sn
+    const uint8_t *const *genome = nullptr;                    // lnr_writer_set_genome: gid.size() borrowed sequences (Dna5 ordinals), or off
 };
 
-void sam_read(const Writer &w, const u64 *cs, const u64 *ce, u64 n, u64 L, const char *qname, std::string &out, std::vector<Rec> &recs) {
+// SEQ of one record as `-ss 1` prints it (fillBamRecordLinkRecords align_util.cpp:745-808 with f_is_align == 0, cigar2SamSeq :1434-1500): the
+// genome walks on from (rid, pos), the read from its first base -- flag 16: from the first base of its reverse complement (_compltRvseStr).
+// S and I print the read, '=' prints the GENOME, X prints the read's base where it differs from the genome's and N where it does not, D moves
+// the genome on.  Defined here where the reference reads out of range: a position outside its sequence is ordinal 0; ordinals above 4 are N.
+void sam_seq(const Writer &w, const Rec &r, const uint8_t *read, u64 L, std::string &out) {
+    const bool rev = (r.flag & 16) != 0;
+    const uint8_t *g = (size_t)r.rid < w.gid.size() ? w.genome[r.rid] : nullptr;
+    const u64 gl = g ? w.glen[(size_t)r.rid] : 0;
+    auto rd = [&](u64 p) -> unsigned { if (p >= L) return 0; unsigned b = rev ? read[L - 1 - p] : read[p]; return b > 3 ? 4u : (rev ? 3u - b : b); };
+    auto gn = [&](u64 x) -> unsigned { if (x >= gl) return 0; unsigned b = g[x]; return b > 4 ? 4u : b; };
+    u64 x = (u64)r.pos, y = 0;
+    const size_t before = out.size();
+    for (const Cig &c : r.cigar) {
+        if (c.op == 'D') { x += c.n; continue; }
+        for (uint32_t i = 0; i < c.n; i++) {
+            unsigned o;
+            if (c.op == '=') o = gn(x + i);
+            else { o = rd(y + i); if (c.op == 'X' && o == gn(x + i)) o = 4; }
+            out += "ACGTN"[o];
+        }
+        y += c.n;
+        if (c.op == '=' || c.op == 'X') x += c.n;
+    }
+    if (out.size() == before) out += '*';
+}
+
+// read != nullptr: SEQ is printed (lnr_writer_format_seq)
+void sam_read(const Writer &w, const u64 *cs, const u64 *ce, u64 n, u64 L, const char *qname, std::string &out, std::vector<Rec> &recs, const uint8_t *read = nullptr) {
     cords_to_records(cs, ce, n, L, recs, w.thd_large_X, w.thd_DI, w.thd_X);
     std::vector<char> saz_done(recs.size(), 0);       // "saz_cigar not empty" per record (fillBamRecordLinkRecords walks the heads in record order)
     for (size_t it = 0; it < recs.size(); it++) {
@@ -162,7 +190,9 @@ void sam_read(const Writer &w, const u64 *cs, const u64 *ce, u64 n, u64 L, const
         put_i(out, r.pos + 1); out += "\t255\t";
         if (r.cigar.empty()) out += '*';
         for (const Cig &c : r.cigar) { put_u(out, c.n); out += c.op; }
-        out += "\t*\t0\t0\t*\t*";
+        out += "\t*\t0\t0\t";
+        if (read) sam_seq(w, r, read, L, out); else out += '*';
+        out += "\t*";
         if (recs.size() > 1) {                         // SA:Z: every other line of the read, in record order (createSAZTagOneLine)
             out += "\tSA:Z:";
             for (size_t j = 0; j < recs.size(); j++)
@@ -214,7 +244,7 @@ void apf_read(const Writer &w, const u64 *c, u64 n, u64 L, const char *rid, bool
 
 }  // namespace
 
-struct lnr_writer { Writer w; lnr_outgpu *gpu = nullptr; char err[256] = ""; };
+struct lnr_writer { Writer w; lnr_outgpu *gpu = nullptr; bool genome_on_gpu = false; char err[256] = ""; };
 
 extern "C" {
 
@@ -256,13 +286,13 @@ static lnr_status format_on_gpu(lnr_writer *wr, lnr_outgpu_batch &b, const char 
 lnr_status lnr_writer_format_gpu(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
                                  int what, const char **text, uint64_t *size) {
     if (!wr || !cords || !read_len || !read_ids || !id_off || !text || !size || (what != 1 && what != 2)) return LNR_ERR_ARG;
-    lnr_outgpu_batch b{0, cords->n_reads, cords->n_cords, cords->cord_off, cords->cords_str, cords->cords_end, read_len, read_ids, id_off, what, 0, 0, 0};
+    lnr_outgpu_batch b{0, cords->n_reads, cords->n_cords, cords->cord_off, cords->cords_str, cords->cords_end, read_len, read_ids, id_off, what, 0, 0, 0, nullptr};
     return format_on_gpu(wr, b, text, size);
 }
 lnr_status lnr_writer_format_dev(lnr_writer *wr, const lnr_cords_dev *cords, const uint64_t *d_read_off, const char *read_ids, const uint64_t *id_off,
                                  int what, const char **text, uint64_t *size) {
     if (!wr || !cords || !read_ids || !id_off || !text || !size || (what != 1 && what != 2) || (cords->n_reads && !d_read_off)) return LNR_ERR_ARG;
-    lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, what, 0, 0, 0};
+    lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, what, 0, 0, 0, nullptr};
     return format_on_gpu(wr, b, text, size);
 }
 lnr_status lnr_writer_gpu_times(const lnr_writer *wr, double *ms5) {
@@ -272,9 +302,9 @@ lnr_status lnr_writer_gpu_times(const lnr_writer *wr, double *ms5) {
 }
 
 // what: 1 = SAM records, 2 = APF.  Reads are formatted on `threads` host threads and concatenated in read order.
-lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
-                             int what, uint32_t threads, const char **text, uint64_t *size) {
-    if (!wr || !cords || !read_len || !read_ids || !id_off || !text || !size || (what != 1 && what != 2)) return LNR_ERR_ARG;
+// reads_concat != nullptr (SAM only): read_len holds n + 1 read offsets instead of n lengths, and SEQ is printed
+static lnr_status format_on_host(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_len, const char *read_ids,
+                                 const uint64_t *id_off, int what, uint32_t threads, const char **text, uint64_t *size) {
     const Writer &w = wr->w;
     uint32_t n = cords->n_reads;
     if (threads < 1) threads = 1;
@@ -287,7 +317,8 @@ lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint6
         for (uint32_t k = lo; k < hi; k++) {
             u64 a = cords->cord_off[k], e = cords->cord_off[k + 1];
             const char *id = read_ids + id_off[k];
-            if (what == 1) sam_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k], id, o, recs);
+            if (reads_concat) sam_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k + 1] - read_len[k], id, o, recs, reads_concat + read_len[k]);
+            else if (what == 1) sam_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k], id, o, recs);
             else apf_read(w, cords->cords_str + a, e - a, read_len[k], id, k > 0, o);
         }
     };
@@ -300,6 +331,52 @@ lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint6
     *text = wr->w.text.data();
     *size = wr->w.text.size();
     return LNR_OK;
+}
+lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
+                             int what, uint32_t threads, const char **text, uint64_t *size) {
+    if (!wr || !cords || !read_len || !read_ids || !id_off || !text || !size || (what != 1 && what != 2)) return LNR_ERR_ARG;
+    return format_on_host(wr, cords, nullptr, read_len, read_ids, id_off, what, threads, text, size);
+}
+
+// ---- SAM with the SEQ column (what the reference prints with -ss 1): host, GPU with host cords, GPU with device cords
+lnr_status lnr_writer_set_genome(lnr_writer *wr, const uint8_t *const *seq) {
+    if (!wr) return LNR_ERR_ARG;
+    wr->w.genome = seq;
+    wr->genome_on_gpu = false;                         // the GPU side takes its copy in the next SEQ call
+    return LNR_OK;
+}
+static bool seq_ready(lnr_writer *wr) {
+    if (wr->w.genome) return true;
+    snprintf(wr->err, sizeof wr->err, "lnr_writer_set_genome has not been called on this writer: no bases for SEQ");
+    return false;
+}
+lnr_status lnr_writer_format_seq(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_off, const char *read_ids,
+                                 const uint64_t *id_off, uint32_t threads, const char **text, uint64_t *size) {
+    if (!wr || !cords || !reads_concat || !read_off || !read_ids || !id_off || !text || !size || !seq_ready(wr)) return LNR_ERR_ARG;
+    return format_on_host(wr, cords, reads_concat, read_off, read_ids, id_off, 1, threads, text, size);
+}
+static lnr_status format_seq_on_gpu(lnr_writer *wr, lnr_outgpu_batch &b, const char **text, uint64_t *size) {
+    if (!seq_ready(wr)) return LNR_ERR_ARG;
+    if (!wr->gpu) { snprintf(wr->err, sizeof wr->err, "lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
+    if (!wr->genome_on_gpu) {
+        wr->err[0] = 0;
+        lnr_status s = (lnr_status)lnr_outgpu_set_genome(wr->gpu, wr->w.genome, wr->w.glen.data(), (uint32_t)wr->w.glen.size(), wr->err, sizeof wr->err);
+        if (s != LNR_OK) return s;
+        wr->genome_on_gpu = true;
+    }
+    return format_on_gpu(wr, b, text, size);
+}
+lnr_status lnr_writer_format_seq_gpu(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_off, const char *read_ids,
+                                     const uint64_t *id_off, const char **text, uint64_t *size) {
+    if (!wr || !cords || !reads_concat || !read_off || !read_ids || !id_off || !text || !size) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{0, cords->n_reads, cords->n_cords, cords->cord_off, cords->cords_str, cords->cords_end, read_off, read_ids, id_off, 1, 0, 0, 0, reads_concat};
+    return format_seq_on_gpu(wr, b, text, size);
+}
+lnr_status lnr_writer_format_seq_dev(lnr_writer *wr, const lnr_cords_dev *cords, const uint8_t *d_reads_concat, const uint64_t *d_read_off, const char *read_ids,
+                                     const uint64_t *id_off, const char **text, uint64_t *size) {
+    if (!wr || !cords || !read_ids || !id_off || !text || !size || (cords->n_reads && (!d_read_off || !d_reads_concat))) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, 1, 0, 0, 0, d_reads_concat};
+    return format_seq_on_gpu(wr, b, text, size);
 }
 
 // SAM header as `linear filter` writes it: @SQ per reference sequence, then @RG and @PG (no @HD)

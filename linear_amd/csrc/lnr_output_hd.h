@@ -11,6 +11,8 @@
 // An item is written through a SINK with put(char): CountSink measures, a byte sink emits, one body serves both, so size and content
 // cannot disagree.  No std::string / std::vector: a record's CIGAR is streamed through a one-element merge window (appendCigarShrink
 // only ever looks at the last element), the SA:Z summary of a record is a second walk over its cords.
+// With SEQ (sam_item_seq) a record line is head, SEQ, tail; the SEQ is a stream of SEGMENTS (bases of the genome, of the read, or the per-base
+// comparison of an X element) that comes off the walk that prints the CIGAR: serially through the sink here, dealt to a wave in the kernels.
 #pragma once
 #include <stdint.h>
 #include <math.h>
@@ -165,7 +167,12 @@ template <class Ops> LNR_HD inline u64 record_ops(Ops &ops, const Params &P, con
     m.flush();
     return i;
 }
-template <class S> struct TextOps { S &out; u32 k = 0; LNR_HD explicit TextOps(S &o) : out(o) {} LNR_HD void op(char o, u32 c, u32) { put_u(out, c); out.put(o); k++; } };
+// prints the elements; `seq` = bases the record's SEQ has (S I = X take one from the read or the genome each, D none)
+template <class S> struct TextOps {
+    S &out; u32 k = 0; u64 seq = 0;
+    LNR_HD explicit TextOps(S &o) : out(o) {}
+    LNR_HD void op(char o, u32 c, u32) { put_u(out, c); out.put(o); k++; if (o != 'D') seq += c; }
+};
 struct SazOps {                                                               // createSAZTagCigar align_util.cpp:452-520
     u64 s0 = 0, cm = 0, nm = 0; i64 ci = 0;
     LNR_HD void op(char o, u32 c, u32 idx) {
@@ -178,8 +185,9 @@ struct SazOps {                                                               //
 };
 LNR_HD inline unsigned rec_flag(const u64 *cs, u64 lo) { return (lo == 1 ? 0u : 2048u) | (cstrand(cs[lo]) ? 16u : 0u); }
 
-// the line of record number `it` (of n_rec) whose first cord is lo
-template <class S> LNR_HD inline void sam_item(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname, u64 it, u64 n_rec) {
+// the line of record number `it` (of n_rec) whose first cord is lo = head, SEQ, tail
+// head: QNAME .. TLEN and the tab before SEQ; returns the bases of the record's SEQ
+template <class S> LNR_HD inline u64 sam_head(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname) {
     put_str(out, qname); out.put('\t');
     put_u(out, rec_flag(cs, lo)); out.put('\t');
     put_str(out, gname(P, (u64)(int)cid(cs[lo]))); out.put('\t');
@@ -187,7 +195,12 @@ template <class S> LNR_HD inline void sam_item(S &out, const Params &P, const u6
     TextOps<S> t(out);
     record_ops(t, P, cs, ce, n, lo, L);
     if (t.k == 0) out.put('*');
-    put_str(out, "\t*\t0\t0\t*\t*");
+    put_str(out, "\t*\t0\t0\t");
+    return t.seq;
+}
+// tail: the tab after SEQ, QUAL, SA:Z, end of line
+template <class S> LNR_HD inline void sam_tail(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 L, u64 it, u64 n_rec) {
+    put_str(out, "\t*");
     if (n_rec > 1) {                                   // SA:Z: every other record of the read, in record order
         put_str(out, "\tSA:Z:");
         u64 a = 1;
@@ -212,6 +225,77 @@ template <class S> LNR_HD inline void sam_item(S &out, const Params &P, const u6
     }
     out.put('\n');
 }
+template <class S> LNR_HD inline void sam_item(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname, u64 it, u64 n_rec) {
+    sam_head(out, P, cs, ce, n, lo, L, qname);
+    out.put('*');                                      // SEQ not printed
+    sam_tail(out, P, cs, ce, n, L, it, n_rec);
+}
+
+// ---- SEQ of a record (-ss 1: fillBamRecordLinkRecords align_util.cpp:745-808 with f_is_align == 0, cigar2SamSeq :1434-1500)
+// Two iterators walk the record's CIGAR: the genome from (sequence id, POS), the read from its first base -- for flag 16 from the first base
+// of its reverse complement.  S and I take their bases from the read, '=' takes them from the GENOME, X prints the read's base where it
+// differs from the genome's and N where it does not, D only moves the genome on.  A source position outside its sequence (undefined in the
+// reference) reads as ordinal 0 here; ordinals above 4 read as N.
+struct SeqSrc {                 // plain data: where the bases of one read's records come from
+    const uint8_t *genome;      // every sequence back to back, one Dna5 ordinal per byte
+    const u64 *gstart;          // nseq: first base of sequence g in genome
+    const u64 *glen;            // nseq
+    u32 nseq;
+    const uint8_t *read;        // the read, forward
+    u64 L;
+};
+struct RecSrc { const uint8_t *g; u64 gl; const uint8_t *read; u64 L; bool rev; };     // the two sources of ONE record: its genome sequence, the read and its strand
+LNR_HD inline RecSrc rec_src(const SeqSrc &q, const u64 *cs, u64 lo) {
+    const u64 g = (u64)(int)cid(cs[lo]);
+    const bool ok = g < q.nseq;
+    return RecSrc{ok ? q.genome + q.gstart[g] : nullptr, ok ? q.glen[g] : 0, q.read, q.L, cstrand(cs[lo]) != 0};
+}
+enum { SEG_READ = 0, SEG_GENOME = 1, SEG_X = 2 };
+LNR_HD inline u32 seq_read_ord(const RecSrc &r, u64 y) {                           // base y of the read, or of its reverse complement
+    if (y >= r.L) return 0;
+    u32 b = r.rev ? r.read[r.L - 1 - y] : r.read[y];
+    return b > 3 ? 4u : (r.rev ? 3u - b : b);
+}
+LNR_HD inline u32 seq_genome_ord(const RecSrc &r, u64 x) {
+    if (x >= r.gl) return 0;
+    u32 b = r.g[x];
+    return b > 4 ? 4u : b;
+}
+LNR_HD inline char seq_char(const RecSrc &r, u32 kind, u64 x, u64 y) {
+    u32 o;
+    if (kind == SEG_GENOME) o = seq_genome_ord(r, x);
+    else {
+        o = seq_read_ord(r, y);
+        if (kind == SEG_X && o == seq_genome_ord(r, x)) o = 4;
+    }
+    return (char)((0x4e54474341ULL >> (8 * o)) & 0xff);                            // "ACGTN"
+}
+// The SEQ as a stream of SEGMENTS off the walk that prints the CIGAR: F::seg(number, kind, position in SEQ, genome x, read y, bases)
+template <class F> struct SegOps {
+    F &f; u64 x, y = 0, p = 0; u32 k = 0;
+    LNR_HD SegOps(F &f_, u64 x0) : f(f_), x(x0) {}
+    LNR_HD void op(char o, u32 c, u32) {
+        if (o == 'D') { x += c; return; }
+        const u32 kind = o == '=' ? SEG_GENOME : (o == 'X' ? SEG_X : SEG_READ);
+        f.seg(k++, kind, p, x, y, c);
+        p += c; y += c;
+        if (kind != SEG_READ) x += c;
+    }
+};
+template <class F> LNR_HD inline void record_segs(F &f, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L) {
+    SegOps<F> s(f, cx(cs[lo]));
+    record_ops(s, P, cs, ce, n, lo, L);
+}
+template <class S> struct SeqPrint {              // the serial form: base after base through the sink
+    S &out; RecSrc r;
+    LNR_HD void seg(u32, u32 kind, u64, u64 x, u64 y, u32 c) { for (u32 i = 0; i < c; i++) out.put(seq_char(r, kind, x + i, y + i)); }
+};
+template <class S> LNR_HD inline void sam_item_seq(S &out, const Params &P, const SeqSrc &q, const u64 *cs, const u64 *ce, u64 n, u64 lo, const char *qname, u64 it, u64 n_rec) {
+    u64 bases = sam_head(out, P, cs, ce, n, lo, q.L, qname);
+    if (bases == 0) out.put('*');
+    else { SeqPrint<S> sp{out, rec_src(q, cs, lo)}; record_segs(sp, P, cs, ce, n, lo, q.L); }
+    sam_tail(out, P, cs, ce, n, q.L, it, n_rec);
+}
 
 // ---- one read, item after item (what the host shim runs; the kernels deal the items of a read to the lanes of a wave instead)
 template <class S> LNR_HD inline void apf_read(S &out, const Params &P, const u64 *c, u64 n, u64 L, const char *rid, bool blank_before) {
@@ -223,6 +307,13 @@ template <class S> LNR_HD inline void sam_read(S &out, const Params &P, const u6
     u64 it = 0;
     for (u64 j = 1; j < n; j++)
         if (rec_first(cs, ce, j, P.thd_large_X)) sam_item(out, P, cs, ce, n, j, L, qname, it++, n_rec);
+}
+template <class S> LNR_HD inline void sam_read_seq(S &out, const Params &P, const SeqSrc &q, const u64 *cs, const u64 *ce, u64 n, const char *qname) {
+    u64 n_rec = 0;
+    for (u64 j = 1; j < n; j++) n_rec += rec_first(cs, ce, j, P.thd_large_X);
+    u64 it = 0;
+    for (u64 j = 1; j < n; j++)
+        if (rec_first(cs, ce, j, P.thd_large_X)) sam_item_seq(out, P, q, cs, ce, n, j, qname, it++, n_rec);
 }
 
 }  // namespace lnr_out

@@ -15,10 +15,14 @@ struct lnr_outgpu_batch {
     const char *read_ids; const uint64_t *id_off;      // host, id_off[k] = start of id k; the blob ends with the '\0' of the last id
     int what;                        // 1 SAM, 2 APF
     uint64_t thd_large_X; int64_t thd_DI, thd_X;
+    const uint8_t *reads;            // SAM with SEQ: the reads' bases back to back (host or device as dev_form says), and read_len then holds n + 1
+                                     // read offsets in both forms; NULL: SEQ prints as '*'
 };
 int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, const uint64_t *goff, const uint64_t *glen, uint32_t nseq,
                     lnr_outgpu **out, char *err, size_t err_cap) __attribute__((weak));
 int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **text, uint64_t *size, char *err, size_t err_cap) __attribute__((weak));
+// the GPU side's own copy of the genome for SEQ: nseq host sequences, one Dna5 ordinal per byte; replaces an earlier copy
+int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) __attribute__((weak));
 void lnr_outgpu_times(const lnr_outgpu *g, double *ms5) __attribute__((weak));   // last call: upload, measure, scan, emit, download
 void lnr_outgpu_close(lnr_outgpu *g) __attribute__((weak));
 }

@@ -11,6 +11,15 @@
 // of a tile, which neighbouring tiles / reads share).  Text longer than the window takes more rounds: a lane formats once per window its item
 // touches and the sink drops what lies outside.  The block header of an APF item and the record of a SAM item look ahead along the read
 // inside one lane; read index, pointers, counts and the read's text offset are wave-uniform (blockIdx), so the compiler keeps them scalar.
+//
+// SAM with SEQ (lnr_writer_format_seq_gpu / _dev: k_out_measure_seq, k_out_emit_seq): a record line is head, SEQ, tail, and the SEQ is 10-20 kB
+// where head and tail are some hundred bytes.  Head and tail go the way above, lane = item, through the LDS window; the window starts out
+// as zeros, which no text holds, so the copy stores what was formatted and leaves the SEQ bytes between them alone.  The SEQ bytes are
+// written by the whole wave, record after record of the tile: the owning lane walks its record once more and streams the SEGMENTS of the
+// SEQ (lnr_output_hd.h) into an LDS table, SEG_CAP at a time, then every lane produces destination-aligned dwords -- finds its segment
+// by bisection over the table's SEQ positions, loads the source bytes (genome forward; read forward, or backward and complemented for
+// flag 16), maps them through ACGTN.  Single-byte stores: the first and last dword of a SEQ, which it shares with head and tail, and a
+// dword that straddles a refill of the table.  The measure kernel sums element counts and touches no base.
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>
@@ -98,6 +107,123 @@ template <bool EMIT> __device__ u64 format_read(const ReadArgs &A, u32 k, char *
     return pos;
 }
 
+// ---- SAM with SEQ
+constexpr u32 SEG_CAP = 256;                   // segments of a record in LDS at a time
+struct SeqArgs { const uint8_t *genome; const u64 *gstart; const uint8_t *reads; };       // (A.len holds read offsets here: read k = reads + len[k])
+struct SegTable { u64 pos[SEG_CAP + 1], x[SEG_CAP], y[SEG_CAP]; u32 kind[SEG_CAP]; };       // pos: SEQ position of segment i, pos[i + 1] its end
+struct SegFill {                               // keeps segments skip .. skip + SEG_CAP - 1 of the walk, counts on past the others
+    SegTable *t; u32 skip;
+    __device__ void seg(u32 k, u32 kind, u64 p, u64 x, u64 y, u32 c) {
+        const u32 i = k - skip;
+        if (i < SEG_CAP) { t->pos[i] = p; t->pos[i + 1] = p + c; t->x[i] = x; t->y[i] = y; t->kind[i] = kind; }
+    }
+};
+
+// the wave writes SEQ positions [tab.pos[0], tab.pos[cnt]) of one record; staged position of SEQ position p = q0 + p
+__device__ __forceinline__ void seq_copy(const SegTable *tab, u32 cnt, const RecSrc &r, char *dst, u64 q0) {
+    const int lane = threadIdx.x & 63;
+    const u64 e0 = q0 + tab->pos[0], e1 = q0 + tab->pos[cnt];
+    for (u64 p = (e0 & ~3ULL) + 4ULL * lane; p < e1; p += 256) {
+        const u64 first = (p > e0 ? p : e0) - q0;
+        u32 s = 0, hi = cnt;                   // the last segment that starts at or before `first`
+        while (hi - s > 1) { const u32 mid = (s + hi) >> 1; if (tab->pos[mid] <= first) s = mid; else hi = mid; }
+        u64 s_lo = tab->pos[s], s_hi = tab->pos[s + 1];
+        u32 word = 0;
+        for (u32 b = 0; b < 4; b++) {
+            const u64 pb = p + b;
+            if (pb < e0 || pb >= e1) continue;
+            const u64 sp = pb - q0;
+            while (sp >= s_hi) { s++; s_lo = s_hi; s_hi = tab->pos[s + 1]; }
+            const u64 o = sp - s_lo;
+            word |= (u32)(uint8_t)seq_char(r, tab->kind[s], tab->x[s] + o, tab->y[s] + o) << (8 * b);
+        }
+        if (p >= e0 && p + 4 <= e1) *reinterpret_cast<u32 *>(dst + p) = word;
+        else for (u32 b = 0; b < 4; b++) if (p + b >= e0 && p + b < e1) dst[p + b] = (char)(word >> (8 * b));
+    }
+}
+
+// one wave = read k, as format_read
+template <bool EMIT> __device__ u64 format_read_seq(const ReadArgs &A, const SeqArgs &Q, u32 k, char *text, u64 toff, char *lds, SegTable *tab) {
+    const int lane = threadIdx.x & 63;
+    const u64 a = A.coff[k], nc = A.coff[k + 1] - a;
+    const u64 *cs = A.cs + a, *ce = A.ce + a;
+    const u64 L = A.len[k + 1] - A.len[k];
+    const SeqSrc q{Q.genome, Q.gstart, A.P.glen, A.P.nseq, Q.reads + A.len[k], L};
+    const char *id = A.ids + A.idoff[k];
+    u64 n_rec = 0;
+    for (u64 base = 1; base < nc; base += 64) {
+        u64 j = base + lane;
+        n_rec += (u64)__popcll(__ballot(j < nc && rec_first(cs, ce, j, A.P.thd_large_X)));
+    }
+    const u32 mis = (u32)(toff & 3);
+    char *dst = text + (toff - mis);
+    u64 pos = 0, rec_carry = 0;
+    for (u64 base = 1; base < nc; base += 64) {
+        const u64 j = base + lane;
+        const bool item = j < nc && rec_first(cs, ce, j, A.P.thd_large_X);
+        const u64 bal = __ballot(item);
+        const u64 it = rec_carry + (u64)__popcll(bal & ((1ULL << lane) - 1ULL));
+        u64 hsz = 0, bases = 0, tsz = 0;       // head (with the '*' of an empty SEQ), SEQ, tail
+        if (item) {
+            CountSink h; bases = sam_head(h, A.P, cs, ce, nc, j, L, id); hsz = h.n + (bases == 0);
+            CountSink t; sam_tail(t, A.P, cs, ce, nc, L, it, n_rec); tsz = t.n;
+        }
+        const u64 sz = hsz + bases + tsz;
+        const u64 incl = wave_incl_scan_u64(sz);
+        const u64 tile_total = __shfl(incl, 63, 64);
+        if constexpr (EMIT) {
+            const u64 s0 = mis + pos, s1 = s0 + tile_total, mine = s0 + incl - sz, tpos = mine + hsz + bases;
+            for (u64 wlo = s0 & ~3ULL; wlo < s1; wlo += OUT_WIN) {
+                const bool hin = item && mine < wlo + OUT_WIN && mine + hsz > wlo, tin = item && tpos < wlo + OUT_WIN && tpos + tsz > wlo;
+                if (!__ballot(hin || tin)) continue;               // a window inside one SEQ
+                for (u32 d = lane; d < OUT_WIN / 4; d += 64) reinterpret_cast<u32 *>(lds)[d] = 0;
+                __syncthreads();
+                if (hin) { LdsSink s{lds, mine - wlo}; if (sam_head(s, A.P, cs, ce, nc, j, L, id) == 0) s.put('*'); }
+                if (tin) { LdsSink s{lds, tpos - wlo}; sam_tail(s, A.P, cs, ce, nc, L, it, n_rec); }
+                __syncthreads();
+                for (u32 d = lane; d < OUT_WIN / 4; d += 64) {     // zero bytes: outside the tile, or SEQ
+                    const u32 v = reinterpret_cast<const u32 *>(lds)[d];
+                    const u64 p = wlo + 4ULL * d;
+                    if (v == 0) continue;
+                    if (((v - 0x01010101u) & ~v & 0x80808080u) == 0) *reinterpret_cast<u32 *>(dst + p) = v;
+                    else for (u32 b = 0; b < 4; b++) if ((v >> (8 * b)) & 0xff) dst[p + b] = (char)(v >> (8 * b));
+                }
+                __syncthreads();
+            }
+            for (u64 todo = __ballot(item && bases > 0); todo; todo &= todo - 1) {        // the records of the tile, one after the other
+                const int own = __ffsll((unsigned long long)todo) - 1;
+                const u64 lo = base + (u64)own;                    // its first cord: wave-uniform
+                const u64 q0 = __shfl(mine + hsz, own, 64);
+                const RecSrc r = rec_src(q, cs, lo);
+                u32 done = 0, total;
+                do {
+                    u32 seen = 0;
+                    if (lane == own) { SegFill f{tab, done}; SegOps<SegFill> so(f, cx(cs[lo])); record_ops(so, A.P, cs, ce, nc, lo, L); seen = so.k; }
+                    __syncthreads();
+                    total = (u32)__builtin_amdgcn_readfirstlane((int)__shfl(seen, own, 64));
+                    const u32 cnt = total - done < SEG_CAP ? total - done : SEG_CAP;
+                    if (cnt) seq_copy(tab, cnt, r, dst, q0);
+                    done += cnt;
+                    __syncthreads();
+                } while (done < total);
+            }
+        }
+        pos += tile_total;
+        rec_carry += (u64)__popcll(bal);
+    }
+    return pos;
+}
+
+__global__ __launch_bounds__(64) void k_out_measure_seq(ReadArgs A, SeqArgs Q, u64 *sizes) {
+    u64 s = format_read_seq<false>(A, Q, blockIdx.x, nullptr, 0, nullptr, nullptr);
+    if (threadIdx.x == 0) sizes[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(64) void k_out_emit_seq(ReadArgs A, SeqArgs Q, const u64 *toff, char *text) {
+    __shared__ __attribute__((aligned(16))) char lds[OUT_WIN];
+    __shared__ SegTable tab;
+    format_read_seq<true>(A, Q, blockIdx.x, text, toff[blockIdx.x], lds, &tab);
+}
+
 __global__ __launch_bounds__(64) void k_out_measure(ReadArgs A, u64 *sizes) {
     u64 s = format_read<false>(A, blockIdx.x, nullptr, 0, nullptr);
     if (threadIdx.x == 0) sizes[blockIdx.x] = s;
@@ -132,6 +258,7 @@ struct lnr_outgpu {
     hipStream_t st = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     Buf gblob, goff, glen, ids, idoff, coff, cs, ce, len, sizes, text;
+    Buf genome, gstart, reads;                  // SEQ: the writer's own copy of the genome (lnr_outgpu_set_genome), the reads of a host-form call
     u32 nseq = 0;
     char *h_text = nullptr; u64 h_cap = 0;      // pinned
     u64 *h_total = nullptr;                     // pinned
@@ -156,7 +283,7 @@ int dev_need(Buf &b, u64 bytes, char *err, size_t err_cap) {
     return 0;
 }
 void free_all(lnr_outgpu *g) {
-    for (Buf *b : {&g->gblob, &g->goff, &g->glen, &g->ids, &g->idoff, &g->coff, &g->cs, &g->ce, &g->len, &g->sizes, &g->text}) if (b->p) (void)hipFree(b->p);
+    for (Buf *b : {&g->gblob, &g->goff, &g->glen, &g->ids, &g->idoff, &g->coff, &g->cs, &g->ce, &g->len, &g->sizes, &g->text, &g->genome, &g->gstart, &g->reads}) if (b->p) (void)hipFree(b->p);
     if (g->h_text) (void)hipHostFree(g->h_text);
     if (g->h_total) (void)hipHostFree(g->h_total);
     for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
@@ -199,6 +326,29 @@ int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, con
     return 0;
 }
 
+int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) {
+    if (nseq != g->nseq) { snprintf(err, err_cap, "the genome has %u sequences, the writer was opened with %u", nseq, g->nseq); return -1; }
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    OUT_CK(hipSetDevice(g->device), -3);
+    u64 *start = new (std::nothrow) u64[nseq + 1ULL];
+    if (!start) return -4;
+    start[0] = 0;
+    for (u32 i = 0; i < nseq; i++) start[i + 1] = start[i] + glen[i];
+    int s = 0;
+    auto step = [&]() -> int {
+        if ((s = dev_need(g->genome, start[nseq] + 1, err, err_cap)) || (s = dev_need(g->gstart, 8ULL * nseq + 8, err, err_cap))) return s;
+        for (u32 i = 0; i < nseq; i++)
+            if (glen[i]) OUT_CK(hipMemcpyAsync((char *)g->genome.p + start[i], seq[i], glen[i], hipMemcpyHostToDevice, g->st), -3);
+        OUT_CK(hipMemcpyAsync(g->gstart.p, start, 8ULL * nseq + 8, hipMemcpyHostToDevice, g->st), -3);
+        OUT_CK(hipStreamSynchronize(g->st), -3);
+        return 0;
+    };
+    s = step();
+    delete[] start;
+    return s;
+}
+
 int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **text, uint64_t *size, char *err, size_t err_cap) {
     static const char empty[1] = "";
     for (double &m : g->ms) m = 0;
@@ -212,6 +362,8 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     A.P.gblob = (const char *)g->gblob.p; A.P.goff = (const u64 *)g->goff.p; A.P.glen = (const u64 *)g->glen.p; A.P.nseq = g->nseq;
     A.P.thd_large_X = b->thd_large_X; A.P.thd_DI = b->thd_DI; A.P.thd_X = b->thd_X;
     A.what = b->what;
+    const bool seq = b->reads != nullptr;      // SAM with SEQ: b->read_len holds n + 1 offsets in both forms
+    SeqArgs Q{(const uint8_t *)g->genome.p, (const u64 *)g->gstart.p, b->reads};
     // read ids: once per call, '\0'-separated blob + offsets
     double t0 = wall_ms();
     const u64 id_bytes = b->id_off[n - 1] + strlen(b->read_ids + b->id_off[n - 1]) + 1;
@@ -223,20 +375,27 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
         A.coff = b->cord_off; A.cs = b->cords_str; A.ce = b->cords_end; A.len = b->read_len; A.len_is_off = 1;
     } else {
         if ((s = dev_need(g->coff, 8ULL * (n + 1ULL), err, err_cap)) || (s = dev_need(g->cs, 8ULL * b->n_cords + 8, err, err_cap)) ||
-            (s = dev_need(g->ce, 8ULL * b->n_cords + 8, err, err_cap)) || (s = dev_need(g->len, 8ULL * n, err, err_cap))) return s;
+            (s = dev_need(g->ce, 8ULL * b->n_cords + 8, err, err_cap)) || (s = dev_need(g->len, 8ULL * (n + 1ULL), err, err_cap))) return s;
         OUT_CK(hipMemcpyAsync(g->coff.p, b->cord_off, 8ULL * (n + 1ULL), hipMemcpyHostToDevice, g->st), -3);
         if (b->n_cords) {
             OUT_CK(hipMemcpyAsync(g->cs.p, b->cords_str, 8ULL * b->n_cords, hipMemcpyHostToDevice, g->st), -3);
             OUT_CK(hipMemcpyAsync(g->ce.p, b->cords_end, 8ULL * b->n_cords, hipMemcpyHostToDevice, g->st), -3);
         }
-        OUT_CK(hipMemcpyAsync(g->len.p, b->read_len, 8ULL * n, hipMemcpyHostToDevice, g->st), -3);
-        A.coff = (const u64 *)g->coff.p; A.cs = (const u64 *)g->cs.p; A.ce = (const u64 *)g->ce.p; A.len = (const u64 *)g->len.p; A.len_is_off = 0;
+        OUT_CK(hipMemcpyAsync(g->len.p, b->read_len, 8ULL * (n + (seq ? 1ULL : 0ULL)), hipMemcpyHostToDevice, g->st), -3);
+        if (seq) {
+            const u64 bases = b->read_len[n];
+            if ((s = dev_need(g->reads, bases + 1, err, err_cap))) return s;
+            if (bases) OUT_CK(hipMemcpyAsync(g->reads.p, b->reads, bases, hipMemcpyHostToDevice, g->st), -3);
+            Q.reads = (const uint8_t *)g->reads.p;
+        }
+        A.coff = (const u64 *)g->coff.p; A.cs = (const u64 *)g->cs.p; A.ce = (const u64 *)g->ce.p; A.len = (const u64 *)g->len.p; A.len_is_off = seq ? 1 : 0;
     }
     OUT_CK(hipStreamSynchronize(g->st), -3);
     g->ms[0] = wall_ms() - t0;
     u64 *sizes = (u64 *)g->sizes.p;
     OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
-    hipLaunchKernelGGL(k_out_measure, dim3(n), dim3(64), 0, g->st, A, sizes);
+    if (seq) hipLaunchKernelGGL(k_out_measure_seq, dim3(n), dim3(64), 0, g->st, A, Q, sizes);
+    else hipLaunchKernelGGL(k_out_measure, dim3(n), dim3(64), 0, g->st, A, sizes);
     OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
     hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, g->st, sizes, n);
     OUT_CK(hipEventRecord(g->ev[2], g->st), -3);
@@ -252,7 +411,8 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
         g->h_cap = want;
     }
     OUT_CK(hipEventRecord(g->ev[3], g->st), -3);
-    hipLaunchKernelGGL(k_out_emit, dim3(n), dim3(64), 0, g->st, A, (const u64 *)sizes, (char *)g->text.p);
+    if (seq) hipLaunchKernelGGL(k_out_emit_seq, dim3(n), dim3(64), 0, g->st, A, Q, (const u64 *)sizes, (char *)g->text.p);
+    else hipLaunchKernelGGL(k_out_emit, dim3(n), dim3(64), 0, g->st, A, (const u64 *)sizes, (char *)g->text.p);
     OUT_CK(hipEventRecord(g->ev[4], g->st), -3);
     OUT_CK(hipStreamSynchronize(g->st), -3);
     OUT_CK(hipGetLastError(), -3);
