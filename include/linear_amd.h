@@ -224,6 +224,25 @@ lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64
 lnr_status lnr_reader_ids(const lnr_reader *r, const char **ids, const uint64_t **id_off);
 const char *lnr_reader_error(const lnr_reader *r);
 void lnr_reader_close(lnr_reader *r);
+/* GPU twin of lnr_reader_next: the text goes to `device` (a mapped file through two pinned staging buffers, a gzip file inflated straight into
+ * pinned memory) and is parsed there -- classify, prefix sum, compact -- into device blocks the reader owns, in the layout lnr_filter_batch_dev and
+ * lnr_writer_format_dev / _seq_dev take.  lnr_reader_next_dev delivers the blocks lnr_reader_next would deliver for the same dst_cap / max_reads
+ * on the same file: the same n per call, the same offsets (*d_off on the device, *off the host's copy, n + 1 each), the same ordinals, the same
+ * ids through lnr_reader_ids; no base comes back to the host.  The block is complete on return and stays valid until `slots` further calls.
+ * The reader owns a stream and its buffers, is independent of any lnr_ctx and is used by one thread at a time; every entry leaves the caller's
+ * current device as it found it; lnr_reader_close releases the GPU side.  Where a FASTQ file leaves the four-line form the serial parser takes
+ * over, exactly where the mapped parser hands over, and its records are uploaded.  lnr_reader_next and lnr_reader_next_dev may be mixed on one
+ * reader: both advance the same file position.  Errors: before lnr_reader_gpu_open LNR_ERR_ARG; slots outside 1..8 LNR_ERR_ARG; no usable device,
+ * or a library linked without its device half, LNR_ERR_NO_DEVICE; a record that alone exceeds dst_cap LNR_ERR_LIMIT (lnr_reader_error says so).
+ * lnr_reader_gpu_times: milliseconds of the last lnr_reader_next_dev, summed over its windows -- stage + upload (wall), measure, scan, emit (HIP
+ * events), download of offsets and header spans (wall).  lnr_reader_gpu_tile: bytes of text per workgroup of the kernels (0 without the device
+ * half).  LNR_READER_GPU_WINDOW in the environment: bytes of text per window (default 256 MiB, at most 1 GiB; a window without a whole record is
+ * doubled); block boundaries do not depend on it. */
+lnr_status lnr_reader_gpu_open(lnr_reader *r, int32_t device, uint32_t slots /* 1..8 */);
+lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_reads, const uint8_t **d_reads_concat, const uint64_t **d_off /* n+1, device */,
+                               const uint64_t **off /* n+1, host */, uint32_t *n_out);
+lnr_status lnr_reader_gpu_times(const lnr_reader *r, double *ms5);
+uint32_t lnr_reader_gpu_tile(void);
 
 /* Output side (host threads, and a GPU twin below; replaces, for this path, the calculator's tail cords2BamLink + fillBamRecords, src/mapper.cpp:463-470,
  * src/f_io.cpp:758-1011, src/align_util.cpp:301-343,452-744, and the printer's writeSam / print_cords_apf, src/f_io.cpp:100-207,

@@ -60,7 +60,8 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_host_alloc", "lnr_host_free", "lnr_reader_open", "lnr_reader_next", "lnr_reader_ids", "lnr_reader_error", "lnr_reader_close",
            "lnr_writer_create", "lnr_writer_format", "lnr_writer_sam_header", "lnr_writer_destroy", "lnr_last_gaps", "lnr_gap_stream", "lnr_set_gap", "lnr_index_broadcast", "lnr_writer_set_preset", "lnr_writer_set_read_group",
            "lnr_writer_gpu_open", "lnr_writer_format_gpu", "lnr_writer_format_dev", "lnr_writer_gpu_times", "lnr_writer_error",
-           "lnr_writer_set_genome", "lnr_writer_format_seq", "lnr_writer_format_seq_gpu", "lnr_writer_format_seq_dev"]
+           "lnr_writer_set_genome", "lnr_writer_format_seq", "lnr_writer_format_seq_gpu", "lnr_writer_format_seq_dev",
+           "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile"]
 
 
 def load_library() -> C.CDLL:
@@ -99,6 +100,11 @@ def load_library() -> C.CDLL:
     lib.lnr_reader_error.restype = C.c_char_p
     lib.lnr_reader_error.argtypes = [C.c_void_p]
     lib.lnr_reader_close.argtypes = [C.c_void_p]
+    lib.lnr_reader_gpu_open.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
+    lib.lnr_reader_next_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_u64p), C.POINTER(C.c_uint32)]
+    lib.lnr_reader_gpu_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.lnr_reader_gpu_tile.restype = C.c_uint32
+    lib.lnr_reader_gpu_tile.argtypes = []
     lib.lnr_writer_create.argtypes = [C.POINTER(C.c_char_p), _u64p, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.lnr_writer_format.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u64p, C.c_char_p, _u64p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_sam_header.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), _u64p]
@@ -331,12 +337,40 @@ class Reader:
         st = self.lib.lnr_reader_next(self.h, C.c_void_p(dst.ctypes.data), dst.size, _p(off, _u64p), max_reads, C.byref(n))
         if st != 0:
             raise LnrError(st, self.lib.lnr_strerror(st).decode(), self.lib.lnr_reader_error(self.h).decode())
+        return n.value, off[: n.value + 1].copy(), self._ids(n.value)
+
+    def _ids(self, n: int):
         ids_p, ido_p = C.c_char_p(), _u64p()
         self.lib.lnr_reader_ids(self.h, C.byref(ids_p), C.byref(ido_p))
-        ido = np.ctypeslib.as_array(ido_p, shape=(n.value + 1,)) if n.value else np.zeros(1, np.uint64)
-        raw = C.string_at(C.cast(ids_p, C.c_void_p), int(ido[n.value])) if n.value else b""
-        ids = [raw[int(ido[k]):int(ido[k + 1]) - 1].decode(errors="replace") for k in range(n.value)]
-        return n.value, off[: n.value + 1].copy(), ids
+        ido = np.ctypeslib.as_array(ido_p, shape=(n + 1,)) if n else np.zeros(1, np.uint64)
+        raw = C.string_at(C.cast(ids_p, C.c_void_p), int(ido[n])) if n else b""
+        return [raw[int(ido[k]):int(ido[k + 1]) - 1].decode(errors="replace") for k in range(n)]
+
+    def _ck(self, st: int):
+        if st != 0:
+            raise LnrError(st, self.lib.lnr_strerror(st).decode(), self.lib.lnr_reader_error(self.h).decode())
+
+    def gpu_open(self, device: int = 0, slots: int = 2) -> None:
+        """Gives the reader its GPU side (a stream, staging buffers and `slots` device blocks on `device`); next_dev needs it."""
+        self._ck(self.lib.lnr_reader_gpu_open(self.h, device, slots))
+
+    def next_dev(self, dst_cap: int, max_reads: int):
+        """The block next() would deliver, parsed on the GPU into a device block of the reader: (n, d_reads_ptr, d_off_ptr, off[n+1], ids[n]);
+        n == 0 at end of file.  The device block stays valid until `slots` further calls."""
+        dr, dof, off_p, n = C.c_void_p(), C.c_void_p(), _u64p(), C.c_uint32()
+        self._ck(self.lib.lnr_reader_next_dev(self.h, dst_cap, max_reads, C.byref(dr), C.byref(dof), C.byref(off_p), C.byref(n)))
+        off = np.ctypeslib.as_array(off_p, shape=(n.value + 1,)).copy()
+        return n.value, dr.value, dof.value, off, self._ids(n.value)
+
+    def gpu_times(self) -> dict:
+        """Milliseconds of the last next_dev: stage + upload and download (wall), measure / scan / emit (HIP events)."""
+        ms = (C.c_double * 5)()
+        self._ck(self.lib.lnr_reader_gpu_times(self.h, ms))
+        return dict(zip(("upload_ms", "measure_ms", "scan_ms", "emit_ms", "download_ms"), ms))
+
+    @staticmethod
+    def gpu_tile() -> int:
+        return int(load_library().lnr_reader_gpu_tile())
 
     def close(self):
         if getattr(self, "h", None):

@@ -14,6 +14,10 @@
 //   gap stream     with -g > 0 the reference's result depends on the order reads meet a thread's GapParms (lnr_gap_stream in the header): the blocks
 //                  are taken strictly in file order until a block reports the stream "extended"; from then on every GPU runs freely with that state.
 //                  The result is the reference's `-t 1` result whatever --gpus is.
+//   device chain   --gpu-reader (extension): the reader thread parses the read files on the first GPU (lnr_reader_next_dev, three device blocks), the
+//                  calculator runs lnr_filter_batch_dev on them and the text comes from lnr_cords_to_host + the host writer or, with --gpu-writer,
+//                  from lnr_writer_format_dev / _seq_dev on the same device buffers: no read base crosses PCIe.  One GPU, one batch at a time (the
+//                  device form of the filter has one lane); the same bytes as the default path.
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
 // Not built (exit 1 with a message, never a silently different result): BAM output (-ot 4 / 8), -ss 1 (use --sam-seq), -c 0, -f 1, -r 1, -p 0, -b 0
@@ -34,6 +38,16 @@
 #include <unistd.h>
 #include <vector>
 
+// entry points only --gpu-reader uses: referred to weakly, so that the front-end still links against a library without them (the test double)
+extern "C" {
+lnr_status lnr_filter_batch_dev(lnr_ctx *, const uint8_t *, const uint64_t *, uint32_t, lnr_cords_dev *) __attribute__((weak));
+lnr_status lnr_cords_to_host(lnr_ctx *, lnr_cords *) __attribute__((weak));
+lnr_status lnr_writer_format_dev(lnr_writer *, const lnr_cords_dev *, const uint64_t *, const char *, const uint64_t *, int, const char **, uint64_t *) __attribute__((weak));
+lnr_status lnr_writer_format_seq_dev(lnr_writer *, const lnr_cords_dev *, const uint8_t *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
+lnr_status lnr_reader_gpu_open(lnr_reader *, int32_t, uint32_t) __attribute__((weak));
+lnr_status lnr_reader_next_dev(lnr_reader *, uint64_t, uint32_t, const uint8_t **, const uint64_t **, const uint64_t **, uint32_t *) __attribute__((weak));
+}
+
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Options {
@@ -42,7 +56,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0;
     std::vector<int> devices;
 };
 
@@ -59,6 +73,8 @@ static void usage() {
             "    -r,  --reform_ccs_cigar_flag INT   0 {DEFAULT}\nMI355X front-end\n    --gpus INT                 GPUs to use {1}\n    --devices LIST             their HIP ordinals, e.g. 0,1,2,3\n"
             "    --block-reads INT          reads per block {65536}\n    --index-mode bcast|build   several GPUs: RCCL broadcast of the index {DEFAULT} or every GPU builds its own\n"
             "    --gpu-writer               format .sam / .apf text on the first GPU in use instead of the writer's host threads {off}\n"
+            "    --gpu-reader               parse the read files on the first GPU in use and keep the reads there: reader -> filter -> writer on device buffers {off}\n"
+            "                               (one GPU; with --sam-seq it needs --gpu-writer: the read bases are not on the host)\n"
             "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n");
 }
 
@@ -86,6 +102,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         bool has_val = false;
         if (name == "gpu-writer") { o.gpu_writer = 1; continue; }                                  // a switch: takes no value
         if (name == "sam-seq") { o.sam_seq = 1; continue; }
+        if (name == "gpu-reader") { o.gpu_reader = 1; continue; }
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         const Opt *op = nullptr;
@@ -150,6 +167,27 @@ struct Shared {
     std::atomic<int> failed{0};
     std::string err;
     void fail(const std::string &e) { std::lock_guard<std::mutex> l(m); if (!failed) { err = e; failed = 1; } cv.notify_all(); }
+};
+
+// the output files of the printer (Mapper::p_printResults mapper.cpp:478-509): a new pair when the prefix changes, or once with -o
+struct Outputs {
+    FILE *fsam = nullptr, *fapf = nullptr;
+    std::string cur_prefix; bool any_open = false; int cur_file = -1;
+    // makes the files of read file `file` current; header = the SAM header text.  false: the files cannot be written (err says which)
+    bool turn_to(const Options &o, int file, const std::string &header, std::string &err) {
+        if (file == cur_file) return true;
+        cur_file = file;
+        std::string prefix = o.oPath.empty() ? output_prefix_of(o.r_paths[(size_t)file]) : o.oPath;
+        if (any_open && !(o.oPath.empty() && prefix != cur_prefix)) return true;
+        close();
+        fsam = (o.f_output_type & 2) ? fopen((prefix + ".sam").c_str(), "wb") : nullptr;
+        fapf = (o.f_output_type & 1) ? fopen((prefix + ".apf").c_str(), "wb") : nullptr;
+        if (((o.f_output_type & 2) && !fsam) || ((o.f_output_type & 1) && !fapf)) { err = "can't write output files with prefix " + prefix; return false; }
+        if (fsam) fwrite(header.data(), 1, header.size(), fsam);
+        cur_prefix = prefix; any_open = true;
+        return true;
+    }
+    void close() { if (fsam) fclose(fsam); if (fapf) fclose(fapf); fsam = fapf = nullptr; }
 };
 
 int main(int argc, char **argv) {
@@ -242,6 +280,149 @@ int main(int argc, char **argv) {
         lnr_writer_destroy(wr);
         for (auto *c : ctx) lnr_destroy(c);
         return 1;
+    }
+    if (o.gpu_reader) {                                                                          // before any output file is opened, too
+        std::string why;
+        if (!lnr_filter_batch_dev || !lnr_cords_to_host || !lnr_writer_format_dev || !lnr_writer_format_seq_dev || !lnr_reader_gpu_open || !lnr_reader_next_dev)
+            why = "no usable device: this library has no device form of the filter";
+        else if (G != 1) why = "the device chain runs on one GPU (--gpus 1)";
+        else if (o.sam_seq && !o.gpu_writer) why = "with --sam-seq the reads stay on the device: add --gpu-writer";
+        else {
+            lnr_reader *probe = nullptr;
+            if (lnr_reader_open(o.r_paths[0].c_str(), &probe) != LNR_OK) why = "can't open read file " + o.r_paths[0];
+            else { if (lnr_reader_gpu_open(probe, o.devices[0], 3) != LNR_OK) why = lnr_reader_error(probe); lnr_reader_close(probe); }
+        }
+        if (!why.empty()) {
+            fprintf(stderr, "\033[1;31mE:\033[0m --gpu-reader: %s\n", why.c_str());
+            lnr_writer_destroy(wr);
+            for (auto *c : ctx) lnr_destroy(c);
+            return 1;
+        }
+        // reader thread -> calculator -> writer thread, three device blocks of the reader in flight; one batch at a time in the context
+        struct DBlock {
+            const uint8_t *d_reads = nullptr; const uint64_t *d_off = nullptr;
+            std::vector<uint64_t> off, len, id_off, coff, cs, ce;
+            std::vector<char> ids;
+            std::string sam, apf;
+            uint32_t n = 0; int file = 0;
+        };
+        Queue<DBlock *> freeq, readyq, doneq;
+        std::mutex em; std::string err; std::atomic<int> failed{0};
+        auto fail = [&](const std::string &e) { { std::lock_guard<std::mutex> l(em); if (!failed) { err = e; failed = 1; } } freeq.close(); readyq.close(); doneq.close(); };
+        std::string sam_header;                                  // (taken here: the calculator thread is the writer's only user under --gpu-writer)
+        { const char *t; uint64_t z; lnr_writer_sam_header(wr, "", &t, &z); sam_header.assign(t, z); }
+        std::vector<DBlock> dblocks(3);
+        for (auto &b : dblocks) freeq.push(&b);
+        uint64_t cap = (uint64_t)o.block_reads * 12000 + (1u << 20);
+        if (cap > ((uint64_t)3 << 30)) cap = (uint64_t)3 << 30;
+        lnr_reader *cur = nullptr;                               // the reader of the file in work: its device blocks live until the file's last block is written
+        std::atomic<uint64_t> total_reads{0}, us_reader{0}, us_gpu{0}, us_writer{0};
+        const double t_reads0 = now();
+        std::thread reader([&] {
+            for (size_t f = 0; f < o.r_paths.size() && !failed; f++) {
+                if (lnr_reader_open(o.r_paths[f].c_str(), &cur) != LNR_OK) { cur = nullptr; fail("can't open read file " + o.r_paths[f]); break; }
+                if (lnr_reader_gpu_open(cur, o.devices[0], 3) != LNR_OK) { fail(std::string("--gpu-reader: ") + lnr_reader_error(cur)); break; }
+                for (;;) {
+                    DBlock *b = nullptr;
+                    if (!freeq.pop(b) || failed) break;
+                    const uint64_t *ho = nullptr;
+                    double tr0 = now();
+                    lnr_status rs_ = lnr_reader_next_dev(cur, cap, o.block_reads, &b->d_reads, &b->d_off, &ho, &b->n);
+                    us_reader += (uint64_t)((now() - tr0) * 1e6);
+                    if (rs_ != LNR_OK) { fail(std::string("reads: ") + lnr_reader_error(cur)); break; }
+                    if (!b->n) { freeq.push(b); break; }
+                    const char *ids; const uint64_t *io;
+                    lnr_reader_ids(cur, &ids, &io);
+                    b->off.assign(ho, ho + b->n + 1);
+                    b->id_off.assign(io, io + b->n + 1);
+                    b->ids.assign(ids, ids + io[b->n]);
+                    b->len.resize(b->n);
+                    for (uint32_t i = 0; i < b->n; i++) b->len[i] = b->off[i + 1] - b->off[i];
+                    b->file = (int)f;
+                    readyq.push(b);
+                }
+                // the file is read: once its blocks are back the reader goes, with its device blocks and staging buffers
+                DBlock *back[3]; size_t nb = 0;
+                while (nb < 3 && !failed && freeq.pop(back[nb])) nb++;
+                if (nb < 3) break;
+                lnr_reader_close(cur); cur = nullptr;
+                for (DBlock *b : back) freeq.push(b);
+            }
+            readyq.close();
+        });
+        std::thread calc([&] {
+            DBlock *b = nullptr;
+            while (readyq.pop(b) && !failed) {
+                double tg0 = now();
+                lnr_cords_dev dev{};
+                lnr_status s = lnr_filter_batch_dev(ctx[0], b->d_reads, b->d_off, b->n, &dev);
+                if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
+                if (o.gpu_writer) {                                  // the text of the block, from the device buffers
+                    const char *text; uint64_t size;
+                    b->sam.clear(); b->apf.clear();
+                    if (o.f_output_type & 2) {
+                        s = o.sam_seq ? lnr_writer_format_seq_dev(wr, &dev, b->d_reads, b->d_off, b->ids.data(), b->id_off.data(), &text, &size)
+                                      : lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 1, &text, &size);
+                        if (s != LNR_OK) { fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); break; }
+                        b->sam.assign(text, size);
+                    }
+                    if (o.f_output_type & 1) {
+                        s = lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 2, &text, &size);
+                        if (s != LNR_OK) { fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; }
+                        b->apf.assign(text, size);
+                    }
+                } else {
+                    lnr_cords c{};
+                    s = lnr_cords_to_host(ctx[0], &c);
+                    if (s != LNR_OK) { fail(std::string("cords: ") + lnr_last_error(ctx[0])); break; }
+                    b->coff.assign(c.cord_off, c.cord_off + c.n_reads + 1);
+                    b->cs.assign(c.cords_str, c.cords_str + c.n_cords);
+                    b->ce.assign(c.cords_end, c.cords_end + c.n_cords);
+                }
+                us_gpu += (uint64_t)((now() - tg0) * 1e6);
+                doneq.push(b);
+            }
+            doneq.close();
+        });
+        std::thread writer([&] {
+            Outputs out;
+            FILE *&fsam = out.fsam, *&fapf = out.fapf;
+            const char *text; uint64_t size;
+            DBlock *b = nullptr;
+            while (doneq.pop(b) && !failed) {
+                std::string oe;
+                if (!out.turn_to(o, b->file, sam_header, oe)) { fail(oe); break; }
+                double tw0 = now();
+                bool ok = true;
+                if (o.gpu_writer) {
+                    if (fsam) ok = fwrite(b->sam.data(), 1, b->sam.size(), fsam) == b->sam.size();
+                    if (ok && fapf) ok = fwrite(b->apf.data(), 1, b->apf.size(), fapf) == b->apf.size();
+                    if (!ok) { fail("write error"); break; }
+                } else {
+                    lnr_cords c{b->n, (uint64_t)b->cs.size(), b->coff.data(), b->cs.data(), b->ce.data()};
+                    if (fsam) { if (lnr_writer_format(wr, &c, b->len.data(), b->ids.data(), b->id_off.data(), 1, o.thread, &text, &size) != LNR_OK) { fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fsam) != size) { fail("write error (.sam)"); break; } }
+                    if (fapf) { if (lnr_writer_format(wr, &c, b->len.data(), b->ids.data(), b->id_off.data(), 2, o.thread, &text, &size) != LNR_OK) { fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fapf) != size) { fail("write error (.apf)"); break; } }
+                }
+                us_writer += (uint64_t)((now() - tw0) * 1e6);
+                total_reads += b->n;
+                freeq.push(b);
+            }
+            out.close();
+        });
+        calc.join();
+        writer.join();
+        freeq.close();
+        reader.join();
+        if (cur) lnr_reader_close(cur);
+        lnr_writer_destroy(wr);
+        for (auto *c : ctx) lnr_destroy(c);
+        if (failed) { fprintf(stderr, "\033[1;31mE:\033[0m %s\n", err.c_str()); return 1; }
+        const double t_reads = now() - t_reads0;
+        fprintf(stderr, "  Processed: %llu reads on 1 GPU (device chain); read files in -> output files out: %.3f s = %.0f reads/s\n", (unsigned long long)total_reads.load(), t_reads,
+                total_reads.load() / (t_reads > 0 ? t_reads : 1));
+        fprintf(stderr, "  Stage busy time[s]: reader %.3f, GPU (kernels%s) %.3f, writer %.3f\n", us_reader.load() / 1e6, o.gpu_writer ? " + text" : " + download", us_gpu.load() / 1e6, us_writer.load() / 1e6);
+        fprintf(stderr, "Time in sum[s] %.2f      \n", now() - t_start);
+        return 0;
     }
 
     // ---- the pipeline
@@ -336,10 +517,14 @@ int main(int argc, char **argv) {
     });
     // writer: the one printer, in file order (parallel_io.cpp:522-569)
     std::thread writer([&] {
-        FILE *fsam = nullptr, *fapf = nullptr;
-        std::string cur_prefix; bool any_open = false; int cur_file = -1;
+        Outputs out;
+        FILE *&fsam = out.fsam, *&fapf = out.fapf;
+        // `@PG ... CL:` stays empty: the reference's Options constructor fills cmd_line only `if (length(argv) < 1)` (base.cpp:64-72), i.e. never
+        std::string sam_header;
         uint64_t want = 0;
         const char *text; uint64_t size;
+        lnr_writer_sam_header(wr, "", &text, &size);
+        sam_header.assign(text, size);
         for (;;) {
             Block *b = nullptr;
             {
@@ -350,21 +535,7 @@ int main(int argc, char **argv) {
                 if (it == sh.done.end()) break;
                 b = it->second; sh.done.erase(it);
             }
-            if (b->file != cur_file) {                                   // p_printResults: a new output when the prefix changes (or once with -o)
-                cur_file = b->file;
-                std::string prefix = o.oPath.empty() ? output_prefix_of(o.r_paths[(size_t)b->file]) : o.oPath;
-                bool fresh = !any_open || (o.oPath.empty() && prefix != cur_prefix);
-                if (fresh) {
-                    if (fsam) fclose(fsam);
-                    if (fapf) fclose(fapf);
-                    fsam = (o.f_output_type & 2) ? fopen((prefix + ".sam").c_str(), "wb") : nullptr;
-                    fapf = (o.f_output_type & 1) ? fopen((prefix + ".apf").c_str(), "wb") : nullptr;
-                    if (((o.f_output_type & 2) && !fsam) || ((o.f_output_type & 1) && !fapf)) { sh.fail("can't write output files with prefix " + prefix); break; }
-                    // `@PG ... CL:` stays empty: the reference's Options constructor fills cmd_line only `if (length(argv) < 1)` (base.cpp:64-72), i.e. never
-                    if (fsam) { lnr_writer_sam_header(wr, "", &text, &size); fwrite(text, 1, size, fsam); }
-                    cur_prefix = prefix; any_open = true;
-                }
-            }
+            { std::string oe; if (!out.turn_to(o, b->file, sam_header, oe)) { sh.fail(oe); break; } }
             double tw0 = now();
             auto format = [&](int what) {
                 if (what == 1 && o.sam_seq)                              // the block's bases are alive: it is recycled below, after the writer is through
@@ -382,8 +553,7 @@ int main(int argc, char **argv) {
             sh.free_blocks.push(b);
             want++;
         }
-        if (fsam) fclose(fsam);
-        if (fapf) fclose(fapf);
+        out.close();
     });
     for (auto &t : workers) t.join();
     { std::lock_guard<std::mutex> l(sh.m); sh.workers_done = true; }

@@ -11,6 +11,7 @@
 //     G/g 2, T/t/U/u 3, everything else N = 4; blanks and line ends inside a record are skipped; multi-line FASTA and
 //     multi-line FASTQ (quality length = sequence length) are accepted.
 #include "../../include/linear_amd.h"
+#include "lnr_reader_hook.h"
 
 // Plain (not gzip) files take a PARALLEL path (f4's reason to exist: feed a GPU that filters 2 M reads/s): the file is mapped, one pass of
 // memchr finds the record boundaries of the next block (a FASTA record ends before the next '>' at a line start; a FASTQ record is taken as four
@@ -26,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
@@ -47,6 +49,12 @@ struct lnr_reader {
     unsigned char tab[256];
     // the mapped file of the parallel path (plain files only)
     const unsigned char *map = nullptr; size_t map_len = 0, mpos = 0; bool use_map = false; unsigned threads = 8;
+    // the GPU twin (lnr_reader_gpu_open / lnr_reader_next_dev): its device side, the slot of the next block, "the serial parser has taken over",
+    // "the inflate stream has ended", and the host block the serial parser's records pass through on their way up
+    lnr_rdgpu *gpu = nullptr; uint32_t gslots = 0, gslot = 0; bool gpu_serial = false, gz_done = false;
+    std::unique_ptr<uint8_t[]> hblock; uint64_t hblock_cap = 0;
+    uint64_t g_text = 0, g_recs = 0;     // text bytes and records the windows have used up so far: sizes the next window
+    char gerr[256] = "";
 
     bool fill() {
         if (eof) return false;
@@ -109,6 +117,7 @@ lnr_status lnr_reader_open(const char *path, lnr_reader **out) {
 
 void lnr_reader_close(lnr_reader *r) {
     if (!r) return;
+    if (r->gpu && lnr_rdgpu_close) lnr_rdgpu_close(r->gpu);
     if (r->f) gzclose(r->f);
     if (r->map) munmap((void *)r->map, r->map_len);
     delete r;
@@ -118,13 +127,9 @@ const char *lnr_reader_error(const lnr_reader *r) { return r ? r->err.c_str() : 
 
 // Next block of records: at most max_reads records and never more than dst_cap bases (a record that does not fit any more is left
 // for the next call; one that could never fit is LNR_ERR_LIMIT).  off[0] = 0 .. off[*n_out] written.  *n_out == 0 at end of file.
-lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64_t *off, uint32_t max_reads, uint32_t *n_out) {
-    if (!r || !dst || !off || !n_out) return LNR_ERR_ARG;
-    *n_out = 0;
-    off[0] = 0;
-    r->ids.clear(); r->id_off.assign(1, 0);
-    uint64_t used = 0;
-    uint32_t n = 0;
+// (the body of lnr_reader_next: the block holds n records / `used` bases already when the GPU twin hands the rest of a block to the serial parser)
+static lnr_status next_from(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64_t *off, uint32_t max_reads, uint32_t *n_out, uint32_t n, uint64_t used,
+                            bool serial_only) {
     if (r->have_spill) {
         if (r->spill.size() > dst_cap) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
         memcpy(dst, r->spill.data(), r->spill.size());
@@ -133,7 +138,7 @@ lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64
         n = 1; off[1] = used; r->id_off.push_back(r->ids.size());
         r->have_spill = false; r->spill.clear(); r->spill_id.clear();
     }
-    if (r->use_map && !r->have_spill) {
+    if (r->use_map && !r->have_spill && !serial_only) {
         struct Rec { size_t hdr, hdr_end, seq, seq_end; uint64_t nb; };
         std::vector<Rec> recs;
         const unsigned char *M = r->map;
@@ -304,6 +309,157 @@ lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64
         r->id_off.push_back(r->ids.size());
     }
     *n_out = n;
+    return LNR_OK;
+}
+
+lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64_t *off, uint32_t max_reads, uint32_t *n_out) {
+    if (!r || !dst || !off || !n_out) return LNR_ERR_ARG;
+    *n_out = 0;
+    off[0] = 0;
+    r->ids.clear(); r->id_off.assign(1, 0);
+    return next_from(r, dst, dst_cap, off, max_reads, n_out, 0, 0, false);
+}
+
+// ---- the GPU twin: the same blocks, parsed on the device into device memory (lnr_reader_kernels.hip behind lnr_reader_hook.h)
+lnr_status lnr_reader_gpu_open(lnr_reader *r, int32_t device, uint32_t slots) {
+    if (!r) return LNR_ERR_ARG;
+    if (slots < 1 || slots > 8) { r->err = "lnr_reader_gpu_open: slots must be 1..8"; return LNR_ERR_ARG; }
+    if (r->gpu) { r->err = "lnr_reader_gpu_open: the reader has a GPU side already"; return LNR_ERR_ARG; }
+    if (!lnr_rdgpu_open) {
+        snprintf(r->gerr, sizeof r->gerr, "no usable device %d: this library was linked without its device half", (int)device);
+        r->err = r->gerr;
+        return LNR_ERR_NO_DEVICE;
+    }
+    lnr_status s = (lnr_status)lnr_rdgpu_open(device, slots, &r->gpu, r->gerr, sizeof r->gerr);
+    if (s != LNR_OK) { r->err = r->gerr; return s; }
+    r->gslots = slots; r->gslot = 0;
+    return LNR_OK;
+}
+
+uint32_t lnr_reader_gpu_tile(void) { return lnr_rdgpu_tile ? lnr_rdgpu_tile() : 0; }
+
+lnr_status lnr_reader_gpu_times(const lnr_reader *r, double *ms5) {
+    if (!r || !ms5 || !r->gpu) return LNR_ERR_ARG;
+    lnr_rdgpu_times(r->gpu, ms5);
+    return LNR_OK;
+}
+
+// Windows of text go to the device until the block is full, the file ends or the four-line FASTQ form breaks (hand-over: the serial parser
+// takes the rest of the file, its records are uploaded).  LNR_READER_GPU_WINDOW = bytes of text per window (default 256 MiB; a window that
+// holds no whole record is doubled): block boundaries do not depend on it.
+lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_reads, const uint8_t **d_reads_concat, const uint64_t **d_off,
+                               const uint64_t **off, uint32_t *n_out) {
+    if (!r || !d_reads_concat || !d_off || !off || !n_out) return LNR_ERR_ARG;
+    *n_out = 0;
+    if (!r->gpu) { r->err = "lnr_reader_gpu_open has not been called on this reader"; return LNR_ERR_ARG; }
+    auto gfail = [&](int s) { r->err = r->gerr; return (lnr_status)s; };
+    const uint32_t slot = r->gslot;
+    uint8_t *dr; uint64_t *dof, *ho;
+    if (int s = lnr_rdgpu_block(r->gpu, slot, dst_cap, max_reads, &dr, &dof, &ho, r->gerr, sizeof r->gerr)) return gfail(s);
+    r->gslot = (slot + 1) % r->gslots;
+    lnr_rdgpu_times_reset(r->gpu);
+    r->ids.clear(); r->id_off.assign(1, 0);
+    uint64_t wcap = 256ULL << 20, grow = 1, used = 0;
+    if (const char *e = getenv("LNR_READER_GPU_WINDOW")) { long long v = atoll(e); if (v >= 16) wcap = (uint64_t)v; }
+    if (wcap > (1ULL << 30)) wcap = 1ULL << 30;
+    uint32_t n = 0;
+    bool full = false;
+    auto is_ws = [](unsigned char c) { return c == '\n' || c == '\r' || c == ' ' || c == '\t'; };
+    while (!r->gpu_serial && !r->have_spill && n < max_reads) {
+        const uint64_t freeb = dst_cap - used, allowed = max_reads - n;
+        // the window: what the free bases can take as text, but no more than the records still allowed will probably need -- by the bytes
+        // per record seen so far (a first window guesses 1 KiB per record; a window that runs out is followed by the next one)
+        uint64_t want = freeb * (r->format == 1 ? 1 : 2) + freeb / 50 + allowed * 128 + 65536;
+        const uint64_t per_rec = r->g_recs ? r->g_text / r->g_recs + 1 : 1024;
+        const uint64_t by_recs = allowed * (per_rec + per_rec / 8) + 65536;
+        if (want > by_recs) want = by_recs;
+        if (want > wcap) want = wcap;
+        want *= grow;
+        if (want > (1ULL << 30)) want = 1ULL << 30;
+        lnr_rdgpu_window w{};
+        const unsigned char *text = nullptr;
+        uint64_t len = 0, lead = 0;
+        bool eof = false;
+        if (r->use_map) {
+            while (r->mpos < r->map_len && is_ws(r->map[r->mpos])) r->mpos++;
+            if (r->mpos >= r->map_len) break;
+            text = r->map + r->mpos;
+            len = r->map_len - r->mpos < want ? r->map_len - r->mpos : want;
+            eof = r->mpos + len == r->map_len;
+        } else {                                                  // an inflate stream (or any file the reader does not map): gzread into a pinned buffer
+            const uint64_t have = r->end - r->pos;
+            if (want < have + 16) want = have + 16;
+            uint8_t *S = lnr_rdgpu_stage(r->gpu, want);
+            if (!S) { r->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+            memcpy(S, r->buf.data() + r->pos, have);
+            r->pos = r->end = 0;
+            len = have;
+            while (!r->gz_done && len < want) {
+                const uint64_t ask = want - len < (1u << 30) ? want - len : (1u << 30);
+                int got = gzread(r->f, S + len, (unsigned)ask);
+                if (got < 0) { int e; r->err = gzerror(r->f, &e); return LNR_ERR_ARG; }
+                if (got == 0) r->gz_done = true;
+                len += (uint64_t)got;
+            }
+            eof = r->gz_done;
+            while (lead < len && is_ws(S[lead])) lead++;
+            text = S + lead; len -= lead;
+            w.pinned = 1;
+            if (!len) { if (eof) break; continue; }
+        }
+        if (r->format == 0) r->format = text[0] == '>' ? 1 : (text[0] == '@' ? 2 : -1);
+        uint64_t consumed = 0;
+        bool handover = r->format < 0 || text[0] != (r->format == 1 ? '>' : '@');       // (the serial parser reports it)
+        lnr_rdgpu_result res{};
+        if (!handover) {
+            w.fmt = r->format; w.eof = eof; w.text = text; w.len = len; w.slot = slot; w.threads = r->threads;
+            w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
+            if (int s = lnr_rdgpu_parse(r->gpu, &w, &res, r->gerr, sizeof r->gerr)) return gfail(s);
+            for (uint64_t k = 0; k < res.n; k++) {
+                uint64_t hb = res.hdr[2 * k], he = res.hdr[2 * k + 1];
+                while (he > hb && text[he - 1] == '\r') he--;
+                r->ids.insert(r->ids.end(), (const char *)text + hb, (const char *)text + he);
+                r->ids.push_back('\0');
+                r->id_off.push_back(r->ids.size());
+            }
+            n += (uint32_t)res.n; used += res.bases; consumed = res.consumed;
+            r->records += res.n; r->bases += res.bases;
+            r->g_recs += res.n; r->g_text += res.consumed;
+            handover = res.handover != 0;
+        }
+        if (r->use_map) r->mpos += consumed;
+        else {                                                    // what the window did not use goes back in front of the stream
+            const uint64_t left = len - consumed;
+            if (r->buf.size() < left) r->buf.resize(left);
+            memcpy(r->buf.data(), text + consumed, left);
+            r->pos = 0; r->end = left;
+        }
+        if (handover) {
+            if (r->use_map) { r->use_map = false; gzseek(r->f, (z_off_t)r->mpos, SEEK_SET); r->pos = r->end = 0; r->eof = false; }
+            r->gpu_serial = true;
+            break;
+        }
+        if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
+        if (res.full) { full = true; break; }
+        if (eof && consumed == len) break;
+        if (res.n == 0) {
+            if (len >= (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
+            grow *= 2;
+        }
+    }
+    if ((r->gpu_serial || r->have_spill) && !full && n < max_reads) {   // the serial parser's share of the block, through a host block
+        if (r->hblock_cap < dst_cap) {
+            r->hblock.reset(new (std::nothrow) uint8_t[dst_cap ? dst_cap : 1]);
+            if (!r->hblock) { r->hblock_cap = 0; r->err = "host allocation failed"; return LNR_ERR_NOMEM; }
+            r->hblock_cap = dst_cap;
+        }
+        uint32_t n2 = n;
+        lnr_status s = next_from(r, r->hblock.get(), dst_cap, ho, max_reads, &n2, n, used, true);
+        if (s != LNR_OK) return s;
+        if (int s2 = lnr_rdgpu_append(r->gpu, slot, used, r->hblock.get() + used, ho[n2] - used, n, ho + n, n2 - n, r->gerr, sizeof r->gerr)) return gfail(s2);
+        n = n2;
+    }
+    *d_reads_concat = dr; *d_off = dof; *off = ho; *n_out = n;
     return LNR_OK;
 }
 

@@ -1,0 +1,37 @@
+// lnr_reader_hook.h -- the seam between the reader's C ABI (lnr_reader.cpp, host code by g++) and its GPU side (lnr_reader_kernels.hip).
+// lnr_reader.cpp is also linked WITHOUT the device half (the front-end's test double, tests/stub_abi.cpp), so it refers to these symbols
+// weakly: where they are absent lnr_reader_gpu_open answers LNR_ERR_NO_DEVICE.  Plain data only crosses here.  Return values are lnr_status.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+extern "C" {
+struct lnr_rdgpu;
+struct lnr_rdgpu_window {
+    int fmt;                         // 1 FASTA, 2 FASTQ
+    int eof;                         // the window ends at the end of the file
+    int pinned;                      // text lies in a staging buffer of lnr_rdgpu_stage: copied up as it is
+    const uint8_t *text; uint64_t len;               // host text; byte 0 starts a record
+    uint32_t slot, threads;          // device block to append to; host threads that fill the staging buffers
+    uint64_t rec_base, base_base;    // records and bases already in the block
+    uint64_t allowed, free;          // records still allowed, bases still free
+};
+struct lnr_rdgpu_result {
+    uint64_t n, bases, consumed;     // records taken, their bases, text bytes used up
+    uint32_t handover, full, too_big;                // the serial parser goes on at `consumed`; the next record does not fit; ... and it is the first
+    const uint64_t *hdr;             // n pairs (begin, end) of header spans, window offsets (pinned host memory, valid until the next parse)
+};
+int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, size_t err_cap) __attribute__((weak));
+// makes block `slot` hold dst_cap bases and max_reads + 1 offsets; hands out its device arrays and the host copy of the offsets
+int lnr_rdgpu_block(lnr_rdgpu *g, uint32_t slot, uint64_t dst_cap, uint32_t max_reads, uint8_t **d_reads, uint64_t **d_off, uint64_t **h_off,
+                    char *err, size_t err_cap) __attribute__((weak));
+uint8_t *lnr_rdgpu_stage(lnr_rdgpu *g, uint64_t bytes) __attribute__((weak));   // the pinned buffer a stream is inflated into (contents are not kept when it grows)
+int lnr_rdgpu_parse(lnr_rdgpu *g, const lnr_rdgpu_window *w, lnr_rdgpu_result *r, char *err, size_t err_cap) __attribute__((weak));
+// records of the serial parser: nb bases behind base_base, offsets off[0 .. n] (block coordinates) at rec_base
+int lnr_rdgpu_append(lnr_rdgpu *g, uint32_t slot, uint64_t base_base, const uint8_t *bases, uint64_t nb, uint64_t rec_base, const uint64_t *off, uint64_t n,
+                     char *err, size_t err_cap) __attribute__((weak));
+void lnr_rdgpu_times(const lnr_rdgpu *g, double *ms5) __attribute__((weak));   // last block: stage + upload, measure, scan, emit, download
+void lnr_rdgpu_times_reset(lnr_rdgpu *g) __attribute__((weak));
+uint32_t lnr_rdgpu_tile(void) __attribute__((weak));
+void lnr_rdgpu_close(lnr_rdgpu *g) __attribute__((weak));
+}
