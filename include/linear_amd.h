@@ -109,8 +109,9 @@ typedef struct lnr_stats {
     uint64_t seed_bytes;
     double prep_ms, seed_count_ms, seed_gather_ms, job_ms, tail_ms, total_ms;
     uint32_t seed_count_launches, seed_gather_launches, job_launches;
-    uint32_t gap_second_pass;  /* reads the gap re-mapper ran a second time (a team of waves per read: out of the first launch's arena or cord slot) */
+    uint32_t gap_second_pass;  /* reads of the gap re-mapper that a 16-wave team of the first stage did: ranked heavy, or handed over by a single wave (arena, cord slot, a sort or chain DP too long for one wave) */
     double gap_ms;             /* device time of the gap re-mapper (-g > 0) */
+    uint32_t gap_last_launch;  /* reads the first stage left flagged and the last launch did (a team per read with the largest arena) */
 } lnr_stats;
 
 void lnr_opts_default(lnr_opts *o);

@@ -51,9 +51,29 @@ def stale(obj: str, src: str) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, defines: tuple = (), out: str | None = None) -> str:
-    """defines / out: variant builds for A/B and diagnostic runs (tools/build_variant.sh)"""
+def build(force: bool = False, defines: tuple = (), out: str | None = None, only: tuple | None = None) -> str:
+    """defines / out: variant builds for A/B and diagnostic runs (tools/build_variant.sh).  only: the device translation units that see the
+    defines -- the variant then links the stock objects of every other unit (the stock library is built first when it is stale) and is
+    left alone while it is newer than its sources"""
     so = out or SO
+    if out and only:
+        build()
+        tag = "." + os.path.basename(out).replace(".so", "")
+        stock = [os.path.join(HERE, s.replace(".cpp", ".o")) for s in ("lnr_reader.cpp", "lnr_output.cpp")] + [os.path.join(HERE, s.replace(".hip", ".o")) for s in DEVICE_TUS if s not in only]
+        mine = [(os.path.join(HERE, s.replace(".hip", tag + ".o")), s) for s in only]
+        note, want = out + ".defines", " ".join(defines) + "\n"      # what the variant was built with, beside it: other defines, another build
+        same = os.path.exists(note) and open(note).read() == want
+        if not force and same and os.path.exists(out) and not any(stale(o, s) or os.path.getmtime(o) > os.path.getmtime(out) for o, s in mine) and all(os.path.getmtime(o) <= os.path.getmtime(out) for o in stock):
+            return out
+        for obj, src in mine:
+            cmd = [hipcc_path()] + [f for f in FLAGS if f != "-shared"] + list(defines) + ["-c", os.path.join(CSRC, src), "-o", obj]
+            if subprocess.call(cmd):
+                raise RuntimeError("compile failed: " + " ".join(cmd))
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call([hipcc_path(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out] + ["-Wl," + o for o in stock + [o for o, _ in mine]] + ["-lz", "-lpthread"])
+        with open(note, "w") as f:
+            f.write(want)
+        return out
     if force or out or needs_build():
         from concurrent.futures import ThreadPoolExecutor
         tag = "" if not out else "." + os.path.basename(out).replace(".so", "")
@@ -77,6 +97,28 @@ def build(force: bool = False, defines: tuple = (), out: str | None = None) -> s
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", os.path.join(CSRC, "linear_filter_main.cpp"), "-o", CLI, SO,
                                    "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lpthread"])
     return so
+
+
+# The gap re-mapper's team forms with their size thresholds pulled down (tests/test_gpu_gap_variants.py): the same device code as the stock
+# library, selected by small inputs.  Only lnr_gap_kernels.hip sees these macros.
+VARIANT_DIR = os.path.join(HERE, "..", "tools", "_variants")
+GAP_VARIANTS = {
+    "columns": ("-DK_GAP_COL_MIN=64", "-DK_GAP_COL_MEAN=1", "-DK_GAP_YB_MIN=64", "-DK_GAP_SORT_TEAM_MIN=128", "-DK_GAP_JOIN_TEAM_MIN=256"),
+    # every column DP by the x-window scan: no DP is long enough for the y buckets
+    "scan": ("-DK_GAP_COL_MIN=64", "-DK_GAP_COL_MEAN=1", "-DK_GAP_YB_MIN=1000000000", "-DK_GAP_SORT_TEAM_MIN=128", "-DK_GAP_JOIN_TEAM_MIN=256"),
+    "rows": ("-DK_GAP_COL_MIN=1000000000", "-DK_GAP_TEAM_ROW=256", "-DK_GAP_SINGLE_MAX=1024", "-DK_GAP_SORT_TEAM_MIN=128", "-DK_GAP_JOIN_TEAM_MIN=256"),
+}
+
+
+def gap_variant_path(name: str) -> str:
+    return os.path.abspath(os.path.join(VARIANT_DIR, "gap_" + name + ".so"))
+
+
+def build_gap_variants() -> list:
+    from concurrent.futures import ThreadPoolExecutor
+    build()
+    with ThreadPoolExecutor(len(GAP_VARIANTS)) as ex:
+        return list(ex.map(lambda kv: build(defines=kv[1], out=gap_variant_path(kv[0]), only=("lnr_gap_kernels.hip",)), GAP_VARIANTS.items()))
 
 
 if __name__ == "__main__":

@@ -517,18 +517,19 @@ lnr_status filter_dev(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, lnr_c
     }
     std::vector<u32> nout(n);
     std::vector<i32> rerr(n);
-    u32 gap_second = 0;
+    u32 gap_second = 0, gap_last = 0;
     {
         Readback rb;
         if (!rb.begin(L->h_rb[0], (size_t)n * 8 + 256)) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
         LCK(rb.add(nout.data(), L->nout.p, (size_t)n * 4, L->stream));
         LCK(rb.add(rerr.data(), L->read_err.p, (size_t)n * 4, L->stream));
         if (L->opts->gap_len) LCK(rb.add(&gap_second, L->gap_next.as<u32>() + 16, 4, L->stream));
+        if (L->opts->gap_len) LCK(rb.add(&gap_last, L->gap_next.as<u32>() + 24 + 8, 4, L->stream));   // (k_gap_team's count of the reads it did)
         LCK(hipStreamSynchronize(L->stream));
         rb.finish();
     }
     L->stats.tail_ms += L->t_tail.ms();
-    if (L->opts->gap_len) { L->stats.gap_ms += L->t_gap.ms(); L->stats.gap_second_pass += gap_second; }
+    if (L->opts->gap_len) { L->stats.gap_ms += L->t_gap.ms(); L->stats.gap_second_pass += gap_second; L->stats.gap_last_launch += gap_last; }
     for (u32 i = 0; i < n; i++)
         if (rerr[i]) {
             // A read outgrew a per-read capacity (cords: 16 per 64 bases + 256; gaps: one per 1000 bases + 4 -- heuristics, generous by an

@@ -35,7 +35,7 @@ struct Tuning {
     u32 gap_arena2_mb = 64;    // arena of a team of the first stage of the gap re-mapper (LNR_GAP_ARENA2_MB)
     u32 gap_teams = 96, ncu = 0;   // team workgroups of the first stage (k_gap_all; LNR_GAP_TEAMS); compute units of the device
     u32 gap_heavy_w = 60000;   // weight (k_gap_weight) from which a read is expected to need a team (LNR_GAP_HEAVY_W)
-    u64 gap_work_cap = 3000000;   // pair evaluations of the chain DPs a worker of the first stage spends on a read before it gives the read up to a team / the last launch (LNR_GAP_WORK_CAP)
+    u64 gap_work_cap = 3000000;   // LNR_GAP_WORK_CAP: passed to the kernels, but without effect there -- GapCtx::work is counted only by the serial host loop of gap_chain_anchors, and the kernels always take its coop branch
     u32 nlanes = 2;                     // LNR_LANES=1|2
     int lane1_prio = 1;                 // stream priority of lane 1's kernel streams: 1 = low (diagnostic: LNR_LANE1_PRIO=-1|0|1; see lane_create)
     bool lane1_nomem = false;           // diagnostic (LNR_LANE1_NOMEM=1): lane 1's first batch fails as if the device were full, to exercise that fallback

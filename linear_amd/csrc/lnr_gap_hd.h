@@ -115,7 +115,7 @@ struct GapCtx {                                           // one read
     const u8 *g; const u64 *seq_off; const u64 *seq_len;  // genome
     FeatView f1[2]; GenomeFeat gf;
     GapParms gp;
-    u64 work = 0, work_cap = ~0ULL;                       // pair evaluations of the chain DPs so far / the budget (over it: ar->ovf = 2)
+    u64 work = 0, work_cap = ~0ULL;                       // pair evaluations of the chain DPs so far / the budget (over it: ar->ovf = 2); counted by the serial host form only
     int coop = 0;                                         // device: all 64 lanes of the wave run this read together (every gap kernel; 0 on the host)
     int team = 0; struct GapTeam *tm = nullptr;           // device: helper waves of the workgroup for the long rows of the chain DP (k_gap_team)
     int hand = 0;                                         // device: a single wave of the first stage -- a later stage (teams, larger arenas) redoes what it gives up
@@ -128,6 +128,24 @@ struct GapCtx {                                           // one read
 #endif
     LNR_HD GSeq ref(u64 id) const { GSeq s; s.p = g + seq_off[id]; s.len = seq_len[id]; return s; }
 };
+#if defined(LNR_GAP_HOST_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+// TEST-ONLY host account (tests/host_shim.cpp defines LNR_GAP_HOST_STATS; no product build does): what the gap stage of one read asks of
+// its worker, measured on the serial forms below, so that a CPU test can say which of the team forms (chain DP by columns with its scan and
+// y-bucket forms, long-row share, team sort, team join) a read would select on the device.  The thresholds are the CALLER's numbers (the
+// shipped ones or a variant's), not the K_GAP_* macros of this file: a retuned macro makes the pinned counts of the test wrong, not right.
+struct GapHostStats {
+    u64 col_min = 1024, col_mean = 12, yb_min = 4096, yb_max = 1024, team_row = 2048, sort_min = 4096, join_min = 65536;
+    u64 dp_n = 0, dp_cols = 0;      // the largest chain DP with a score function id: anchors, distinct x
+    u64 row_max = 0;                // longest predecessor row of any DP (i - 1 - j of the serial scan)
+    u64 sort_max = 0;               // longest GapCmp sort
+    u64 join_max = 0;               // largest (p2 - p1) * (k - p2) of a join block
+    u64 n_yb = 0, n_scan = 0;       // DPs that the column form takes: predecessors from y buckets / from the x-window scan
+    u64 n_row = 0, n_row_rej = 0;   // rows that follow a row of at least team_row + 256 predecessors in a DP the column form does not take (long-row share) / of those, in DPs of at least col_min anchors (the column form looked and declined)
+    u64 n_sort = 0, n_join = 0;     // sorts of at least sort_min elements / join blocks of at least join_min pairs
+    void clear() { dp_n = dp_cols = row_max = sort_max = join_max = n_yb = n_scan = n_row = n_row_rej = n_sort = n_join = 0; }
+};
+inline GapHostStats &gap_host_stats() { static thread_local GapHostStats s; return s; }
+#endif
 #ifdef LNR_GAP_TRACE
 // Diagnostic build (-DLNR_GAP_TRACE): one read (device: the last of the launch; host shim: LNR_GAP_TRACE in the environment) prints sizes and
 // checksums of the vectors at the stations of every gap, so that a host run and a device run of the same read can be compared line by line.
@@ -211,6 +229,9 @@ template <class T, class Comp> LNR_HD inline void gap_sort(T *a, long n, Comp co
     ref_sort(a, n, comp, X.ls->st);
 }
 inline LNR_HD void gap_sort(u64 *a, long n, GapCmp comp, GapCtx &X) {
+#if defined(LNR_GAP_HOST_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+    { GapHostStats &hs_ = gap_host_stats(); if ((u64)n > hs_.sort_max) hs_.sort_max = (u64)n; if ((u64)n >= hs_.sort_min) hs_.n_sort++; }
+#endif
 #if defined(__HIP_DEVICE_COMPILE__)
     if (X.coop && n >= 2 && (n <= 16 || (comp.kind == 4 && n <= 128))) { gap_rank_sort(a, (u32)n, comp); return; }
     if (X.coop && n > 96) { gap_sort_wave(a, (u32)n, comp, X); return; }
@@ -364,6 +385,9 @@ LNR_HD inline void g_set_anchors(const GVec<u64> &g_hs, GVec<u64> &out, int p1, 
     }
 #endif
     (void)coop;
+#if defined(LNR_GAP_HOST_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+    if (Xp && p2 > p1 && k > p2) { GapHostStats &hs_ = gap_host_stats(); u64 np_ = (u64)(p2 - p1) * (u64)(k - p2); if (np_ > hs_.join_max) hs_.join_max = np_; if (np_ >= hs_.join_min) hs_.n_join++; }
+#endif
     for (int i = p1; i < p2; i++) for (int j = p2; j < k; j++) {
         u64 a = ganc_make(g_hs[(u32)i], g_hs[(u32)j], rvcp);
         if (B.keep(a)) out.push(a);
@@ -458,6 +482,9 @@ LNR_HD inline void c_create_anchors2(GVec<u64> &g_hs, GVec<u64> &out, i64 lower,
         if (t == 0) continue;
         if (t == 1) { p2 = k; continue; }
         if (out.ar->ovf) return;
+#if defined(LNR_GAP_HOST_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+        if (Xp && p2 > p1 && k > p2) { GapHostStats &hs_ = gap_host_stats(); u64 np_ = (u64)(p2 - p1) * (u64)(k - p2); if (np_ > hs_.join_max) hs_.join_max = np_; if (np_ >= hs_.join_min) hs_.n_join++; }
+#endif
         for (int i = p1; i < p2; i++) {
             i64 x = (i64)(g_hs[(u32)i] & ((1ULL << 30) - 1));
             for (int j = p2; j < k; j++) {
@@ -1127,6 +1154,30 @@ struct TileSink {
         nchains++;
     }
 };
+#if defined(LNR_GAP_HOST_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+// one chain DP for the host account: which form the device's team would take (the tests of gap_chain_anchors / gap_dp_columns restated with the
+// caller's thresholds) and, row by row, the lengths of the serial scan.  The device has two more exits from the column form that are not
+// restated here -- a column that holds the same anchor twice (tm->dup == 1) and a y list that does not fit the arena --: n_yb and n_scan are
+// upper bounds of what the device does
+struct GapHostDp {
+    bool cols_form = false; u64 n, prev = 0;
+    GapHostDp(const u64 *anchors, u32 n_, int fn_id) : n(n_) {
+        GapHostStats &h = gap_host_stats();
+        if (!fn_id) return;
+        u64 cols = 0, ymin = ~0ULL, ymax = 0;
+        for (u32 i = 0; i < n_; i++) { u64 y = ganc_y(anchors[i]); cols += (i == 0 || ganc_x(anchors[i - 1]) != ganc_x(anchors[i])) ? 1 : 0; ymin = y < ymin ? y : ymin; ymax = y > ymax ? y : ymax; }
+        if (n > h.dp_n) { h.dp_n = n; h.dp_cols = cols; }
+        cols_form = n >= h.col_min && cols * h.col_mean <= n;
+        if (cols_form) { bool yb = n >= h.yb_min && 2 * (((ymax - ymin) >> 6) + 1) <= h.yb_max; if (yb) h.n_yb++; else h.n_scan++; }
+    }
+    void row(u64 len) {
+        GapHostStats &h = gap_host_stats();
+        if (len > h.row_max) h.row_max = len;
+        if (!cols_form && prev >= h.team_row + 256 && len >= 64) { h.n_row++; if (n >= h.col_min) h.n_row_rej++; }
+        prev = len;
+    }
+};
+#endif
 template <class Score>
 LNR_HD inline void gap_chain_anchors(const u64 *anchors, u32 n, GVec<u64> &out, bool to_tiles, u32 depth, u64 dx_depth, int bestn, int min_len, int abort_score, Score score, GapCtx &X, int fn_id = 0) {
     if (n < 2 || X.ar->ovf) return;
@@ -1239,6 +1290,9 @@ LNR_HD inline void gap_chain_anchors(const u64 *anchors, u32 n, GVec<u64> &out, 
         }
     } else
 #endif
+#if defined(LNR_GAP_HOST_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+    GapHostDp hs_dp_(anchors, n, fn_id);
+#endif
     for (int i = 0; i < (int)n; i++) {
         int j_str = i - (int)depth < 0 ? 0 : i - (int)depth, max_j = i, best = -1, j = i - 1;
         for (; j >= 0 && (j >= j_str || ganc_x(anchors[j]) - ganc_x(anchors[i]) < dx_depth); j--) {
@@ -1248,6 +1302,9 @@ LNR_HD inline void gap_chain_anchors(const u64 *anchors, u32 n, GVec<u64> &out, 
         if (best > 0) { r.p2[i] = max_j; r.score[i] = best; r.len[i] = r.len[max_j] + 1; r.score2[i] = best; r.root[i] = r.root[max_j]; r.leaf[i] = 1; r.leaf[max_j] = 0; }
         else { r.p2[i] = -1; r.score[i] = 0; r.len[i] = 1; r.score2[i] = 0; r.root[i] = i; r.leaf[i] = 1; }
         X.work += (u64)(i - 1 - j);
+#if defined(LNR_GAP_HOST_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+        hs_dp_.row((u64)(i - 1 - j));
+#endif
         if (X.work > X.work_cap) { X.ar->ovf = 2; return; }
     }
     }

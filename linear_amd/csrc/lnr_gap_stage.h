@@ -81,6 +81,7 @@ lnr_status gap_stage(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, u32 ma
     if (L->opts->scratch_budget && L->opts->scratch_budget < budget) budget = L->opts->scratch_budget;
     { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) { u64 avail = (u64)(((double)fr + (double)L->gap_arena.cap) * 0.8); if (avail < budget) budget = avail; } else (void)hipGetLastError(); }
     if (budget < ((u64)1 << 30)) budget = (u64)1 << 30;
+    // (tests/host_shim.cpp hs_gap_arena1 restates this formula at cap_scale 1: change both)
     u64 arena1 = align_up(((u64)512 << 10) * L->cap_scale + 16ULL * maxlen + sizeof(LeaderScratch) + 65536, 256);
     u64 arena2 = std::max<u64>(((u64)tun.gap_arena2_mb << 20) * L->cap_scale, arena1 * 2);
     u64 arena3 = std::max<u64>(((u64)64 << 20) * L->cap_scale, arena2 * 2);

@@ -124,6 +124,26 @@ def sample_reads(refs: list[np.ndarray], n_reads: int, read_len: int, err: float
     return np.concatenate(chunks) if chunks else np.zeros(0, np.uint8), off, truth
 
 
+def tandem_array(unit: np.ndarray, copies: int, div: float, rng: np.random.Generator) -> np.ndarray:
+    """`copies` copies of `unit` in a row, each with its own substitutions at rate `div` (a satellite array)."""
+    arr = np.tile(unit, copies)
+    mut = rng.random(arr.size) < div
+    arr[mut] = (arr[mut] + rng.integers(1, 4, size=int(mut.sum()), dtype=np.uint8)) & 3
+    return arr
+
+
+def tandem_expansion_read(ref: np.ndarray, pos: int, array_len: int, unit: np.ndarray, copies: int, div: float, flank: tuple[int, int],
+                          err: float, rng: np.random.Generator, rc: bool = False) -> np.ndarray:
+    """A read across the tandem array at ref[pos, pos + array_len) in which the array has `copies` copies of the unit (an expansion when
+    that is more than the reference carries), flanked by flank[0] / flank[1] bases of the reference on either side, with sequencing
+    errors at rate `err`.  The gap between the flanks then joins every reference copy against every read copy: many anchors per
+    reference position, long sorts, large k-mer blocks."""
+    left = ref[pos - flank[0]:pos]
+    right = ref[pos + array_len:pos + array_len + flank[1]]
+    seg = mutate(np.concatenate([left, tandem_array(unit, copies, div, rng), right]), err, rng)
+    return revcomp(seg) if rc else seg
+
+
 def pack_reads(read_list: list[np.ndarray]) -> tuple[np.ndarray, np.ndarray]:
     off = np.zeros(len(read_list) + 1, dtype=np.uint64)
     off[1:] = np.cumsum([r.size for r in read_list])

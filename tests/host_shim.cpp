@@ -9,6 +9,7 @@
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
+#define LNR_GAP_HOST_STATS 1     // the host account of lnr_gap_hd.h (GapHostStats): this shim alone defines it
 #include "../linear_amd/csrc/lnr_hd.h"
 #include "../linear_amd/csrc/lnr_gap_hd.h"
 
@@ -381,6 +382,25 @@ static i64 map_read_g_lim(void *h, const u8 *read, u64 len, u32 gap_len, int f_d
     S.ce.assign(ce.p, ce.p + ce.n);
     return (i64)S.cs.size();
 }
+// What the gap stage of one read (-g gap_len -dup f_dup, stream state `ext`) asks of its worker (GapHostStats, lnr_gap_hd.h).
+// thr[7]: K_GAP_COL_MIN, K_GAP_COL_MEAN, K_GAP_YB_MIN, K_GAP_YB_MAX, K_GAP_TEAM_ROW, K_GAP_SORT_TEAM_MIN, K_GAP_JOIN_TEAM_MIN as the caller has them.
+// out[13]: largest DP's anchors and columns, longest row, longest sort, largest join block, arena and keep-arena high-water marks, then the
+// counts: DPs by columns from y buckets / by the scan, long-row shares (all / in DPs the column form declined), team sorts, team joins.
+i64 hs_gap_needs(void *h, const u8 *read, u64 len, u32 gap_len, int f_dup, int ext, const u64 *thr, u64 *out) {
+    GapHostStats &g = gap_host_stats();
+    g.col_min = thr[0]; g.col_mean = thr[1]; g.yb_min = thr[2]; g.yb_max = thr[3]; g.team_row = thr[4]; g.sort_min = thr[5]; g.join_min = thr[6];
+    g.clear();
+    Shim &S = *(Shim *)h;
+    S.stats[0] = S.stats[1] = 0;
+    int st = ext;
+    i64 rc = map_read_g_lim(h, read, len, gap_len, f_dup, (u64)256 << 20, (u64)64 << 20, ~0ULL, &st);
+    u64 v[13] = {g.dp_n, g.dp_cols, g.row_max, g.sort_max, g.join_max, rc >= 0 && len > 200 && gap_len ? S.stats[0] : 0, rc >= 0 && len > 200 && gap_len ? S.stats[1] : 0,
+                 g.n_yb, g.n_scan, g.n_row, g.n_row_rej, g.n_sort, g.n_join};
+    memcpy(out, v, sizeof v);
+    return rc;
+}
+// the arena of a single wave of the gap stage's first launch for a batch whose longest read has maxlen bases (lnr_gap_stage.h gap_stage, capacities x 1)
+u64 hs_gap_arena1(u64 maxlen) { return (((u64)512 << 10) + 16ULL * maxlen + sizeof(LeaderScratch) + 65536 + 255) / 256 * 256; }
 // the column DP's (dx, dy) forms against the anchor forms: over x2 = base, x1 = base + dx, y2 = ybase, y1 = ybase + dy for every (dx, dy) of the
 // rectangle, same strand and opposite strands.  Returns the number of pairs where "positive?" or the positive value differ.
 u64 hs_gap_delta_check(int fn, u32 dx_max, i32 dy_lo, i32 dy_hi) {

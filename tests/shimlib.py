@@ -116,6 +116,29 @@ class Shim:
         self.lib.hs_get_cords(self.h, _p(cs, _u64p), _p(ce, _u64p))
         return cs[:n], ce[:n]
 
+    # the thresholds of the team forms as the library ships them (the K_GAP_* macros of lnr_gap_hd.h / lnr_gap_kernels.hip, restated)
+    GAP_THRESHOLDS = dict(col_min=1024, col_mean=12, yb_min=4096, yb_max=1024, team_row=2048, sort_min=4096, join_min=65536)
+    GAP_NEEDS = ("dp_n", "dp_cols", "row_max", "sort_max", "join_max", "arena_hw", "keep_hw", "n_yb", "n_scan", "n_row", "n_row_rej", "n_sort", "n_join")
+
+    def gap_needs(self, read, gap_len=50, dup=0, ext=1, **thr):
+        """What the read's gap stage asks of its worker, and which team forms it selects under the thresholds `thr` (GapHostStats)."""
+        read = np.ascontiguousarray(read, dtype=np.uint8)
+        t = dict(self.GAP_THRESHOLDS)
+        assert set(thr) <= set(t), thr
+        t.update(thr)
+        tv = np.array([t[k] for k in ("col_min", "col_mean", "yb_min", "yb_max", "team_row", "sort_min", "join_min")], np.uint64)
+        out = np.zeros(len(self.GAP_NEEDS), np.uint64)
+        self.lib.hs_gap_needs.restype = C.c_int64
+        self.lib.hs_gap_needs.argtypes = [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, _u64p, _u64p]
+        n = self.lib.hs_gap_needs(self.h, _p(read, _u8p), read.size, gap_len, dup, ext, _p(tv, _u64p), _p(out, _u64p))
+        assert n >= 0, f"shim error {n}"
+        return {k: int(v) for k, v in zip(self.GAP_NEEDS, out)}
+
+    def gap_arena1(self, maxlen):
+        self.lib.hs_gap_arena1.restype = C.c_uint64
+        self.lib.hs_gap_arena1.argtypes = [C.c_uint64]
+        return int(self.lib.hs_gap_arena1(maxlen))
+
     def stage(self, stage):
         n = self.lib.hs_debug_get(self.h, stage, None, 0)
         out = np.zeros(max(int(n), 1), np.uint64)
