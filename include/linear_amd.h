@@ -238,7 +238,27 @@ void lnr_reader_close(lnr_reader *r);
  * lnr_reader_gpu_times: milliseconds of the last lnr_reader_next_dev, summed over its windows -- stage + upload (wall), measure, scan, emit (HIP
  * events), download of offsets and header spans (wall).  lnr_reader_gpu_tile: bytes of text per workgroup of the kernels (0 without the device
  * half).  LNR_READER_GPU_WINDOW in the environment: bytes of text per window (default 256 MiB, at most 1 GiB; a window without a whole record is
- * doubled); block boundaries do not depend on it. */
+ * doubled); block boundaries do not depend on it.
+ *
+ * BGZF input (the blocked gzip of bgzip / htslib) is inflated on the device: only compressed bytes go up, no text byte crosses the bus.  A file
+ * counts as BGZF when its first member has the magic 1f 8b, CM 8, FLG = FEXTRA and, among the subfields of its extra field, one 'B','C' of
+ * length 2 (BSIZE), and lies inside the file.  Its blocks are walked one window at a time; each non-empty block is inflated by k_bgzf_inflate
+ * behind the text the last window did not use, which stays on the device.  The gzread stream takes over -- at that member's offset, through a
+ * fresh inflate stream opened there, never by re-reading the file -- at a member that is not BGZF, where the chain would leave the file or BSIZE
+ * is too small for header and footer, where a FASTQ leaves the four-line form, and at the first lnr_reader_next on the reader.  A block whose
+ * DEFLATE data is invalid, whose text is not ISIZE bytes or whose CRC32 differs from the footer makes the call return LNR_ERR_ARG and deliver
+ * no block; lnr_reader_error names the block's file offset and the reason; the reader can only be closed after that.  LNR_READER_BGZF=0 in
+ * the environment at lnr_reader_open: BGZF files are read like any gzip file (gzread into the pinned staging buffer).  lnr_reader_next
+ * always reads gzip files through gzread.  lnr_reader_gpu_inflate_stats: counts of the last lnr_reader_next_dev and of all calls so far. */
+typedef struct {
+    uint64_t blocks;                 /* BGZF blocks inflated on the device */
+    uint64_t compressed_bytes;       /* bytes of the file uploaded for them */
+    uint64_t text_bytes;             /* text bytes produced on the device */
+    uint64_t gzread_bytes;           /* text bytes that came through gzread instead */
+    double inflate_ms, gather_ms;    /* k_bgzf_inflate and the gather of the header lines (HIP events) */
+} lnr_inflate_counts;
+typedef struct { lnr_inflate_counts last, total; } lnr_inflate_stats;
+lnr_status lnr_reader_gpu_inflate_stats(const lnr_reader *r, lnr_inflate_stats *out);
 lnr_status lnr_reader_gpu_open(lnr_reader *r, int32_t device, uint32_t slots /* 1..8 */);
 lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_reads, const uint8_t **d_reads_concat, const uint64_t **d_off /* n+1, device */,
                                const uint64_t **off /* n+1, host */, uint32_t *n_out);

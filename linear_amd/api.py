@@ -48,6 +48,14 @@ class LnrStats(C.Structure):
                [(k, C.c_uint32) for k in ("seed_count_launches", "seed_gather_launches", "job_launches", "gap_second_pass")] + [("gap_ms", C.c_double), ("gap_last_launch", C.c_uint32)]
 
 
+class LnrInflateCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("blocks", "compressed_bytes", "text_bytes", "gzread_bytes")] + [(k, C.c_double) for k in ("inflate_ms", "gather_ms")]
+
+
+class LnrInflateStats(C.Structure):
+    _fields_ = [("last", LnrInflateCounts), ("total", LnrInflateCounts)]
+
+
 class LnrError(RuntimeError):
     def __init__(self, status: int, msg: str, detail: str = ""):
         super().__init__(f"linear_amd: {msg} (status {status}){': ' + detail if detail else ''}")
@@ -61,7 +69,7 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_writer_create", "lnr_writer_format", "lnr_writer_sam_header", "lnr_writer_destroy", "lnr_last_gaps", "lnr_gap_stream", "lnr_set_gap", "lnr_index_broadcast", "lnr_writer_set_preset", "lnr_writer_set_read_group",
            "lnr_writer_gpu_open", "lnr_writer_format_gpu", "lnr_writer_format_dev", "lnr_writer_gpu_times", "lnr_writer_error",
            "lnr_writer_set_genome", "lnr_writer_format_seq", "lnr_writer_format_seq_gpu", "lnr_writer_format_seq_dev",
-           "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile"]
+           "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats"]
 
 
 def load_library() -> C.CDLL:
@@ -103,6 +111,7 @@ def load_library() -> C.CDLL:
     lib.lnr_reader_gpu_open.argtypes = [C.c_void_p, C.c_int32, C.c_uint32]
     lib.lnr_reader_next_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_u64p), C.POINTER(C.c_uint32)]
     lib.lnr_reader_gpu_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.lnr_reader_gpu_inflate_stats.argtypes = [C.c_void_p, C.POINTER(LnrInflateStats)]
     lib.lnr_reader_gpu_tile.restype = C.c_uint32
     lib.lnr_reader_gpu_tile.argtypes = []
     lib.lnr_writer_create.argtypes = [C.POINTER(C.c_char_p), _u64p, C.c_uint32, C.POINTER(C.c_void_p)]
@@ -367,6 +376,13 @@ class Reader:
         ms = (C.c_double * 5)()
         self._ck(self.lib.lnr_reader_gpu_times(self.h, ms))
         return dict(zip(("upload_ms", "measure_ms", "scan_ms", "emit_ms", "download_ms"), ms))
+
+    def gpu_inflate_stats(self) -> dict:
+        """BGZF input: {"last": counts of the last next_dev, "total": of all calls}; each {blocks, compressed_bytes, text_bytes, gzread_bytes,
+        inflate_ms, gather_ms} -- blocks inflated on the device, bytes uploaded for them, text produced there, text that came through gzread."""
+        st = LnrInflateStats()
+        self._ck(self.lib.lnr_reader_gpu_inflate_stats(self.h, C.byref(st)))
+        return {w: {k: getattr(getattr(st, w), k) for k, _ in LnrInflateCounts._fields_} for w in ("last", "total")}
 
     @staticmethod
     def gpu_tile() -> int:

@@ -12,12 +12,17 @@
 //     multi-line FASTQ (quality length = sequence length) are accepted.
 #include "../../include/linear_amd.h"
 #include "lnr_reader_hook.h"
+#include "lnr_inflate_hd.h"
 
 // Plain (not gzip) files take a PARALLEL path (f4's reason to exist: feed a GPU that filters 2 M reads/s): the file is mapped, one pass of
 // memchr finds the record boundaries of the next block (a FASTA record ends before the next '>' at a line start; a FASTQ record is taken as four
 // lines -- anything else, e.g. multi-line FASTQ, hands the rest of the file to the serial parser below), then `threads` host threads count and
 // convert the bases of their share of the records straight into the caller's (pinned) block.  Same records, same ordinals, same ids as the serial
 // parser (tests/test_reader_cpu.py runs both on every fixture).  A gzip file is one inflate stream and stays serial.
+//
+// A BGZF file (blocked gzip: every member carries its size in a 'BC' extra subfield, lnr_inf::bgzf_member) is mapped too, for
+// lnr_reader_next_dev alone: its blocks go up compressed and are inflated on the device (k_bgzf_inflate).  lnr_reader_next reads it
+// through gzread like any gzip file; bgzf_to_stream() is the one place where the two meet.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -55,6 +60,15 @@ struct lnr_reader {
     std::unique_ptr<uint8_t[]> hblock; uint64_t hblock_cap = 0;
     uint64_t g_text = 0, g_recs = 0;     // text bytes and records the windows have used up so far: sizes the next window
     char gerr[256] = "";
+    // BGZF (device inflate): the file is mapped at `map` with use_map false.  The chain is walked one window at a time from bpos on;
+    // `chain` = the blocks whose text lies on the device and is not used up, byte 0 of the device text = byte bskip of chain[0]'s text
+    struct BBlk { uint64_t off; uint32_t size, isize; };
+    bool bgzf = false, bend = false, bstop = false, bfailed = false;   // live; the chain reached the end of the file; the member at bpos is not BGZF
+    int bfd = -1;
+    uint64_t bpos = 0, bskip = 0, bkeep_from = 0, bcarry = 0;         // device text [bkeep_from, bkeep_from + bcarry) is what the last window left
+    std::vector<BBlk> chain;
+    lnr_inflate_counts ist_last{}, ist_total{};
+    uint64_t gz_bytes = 0;                                            // text bytes that came out of gzread
 
     bool fill() {
         if (eof) return false;
@@ -62,6 +76,7 @@ struct lnr_reader {
         int n = gzread(f, buf.data(), (unsigned)buf.size());
         if (n < 0) { int e; err = gzerror(f, &e); eof = true; return false; }
         if (n == 0) { eof = true; return false; }
+        gz_bytes += (uint64_t)n;
         pos = 0; end = (size_t)n;
         return true;
     }
@@ -84,6 +99,33 @@ struct lnr_reader {
     }
 };
 
+// "Continue the serial stream at the first text byte the device path has not used up": block chain[0] (or the member at bpos), bskip bytes
+// in.  Every BGZF block is a complete gzip member, so a fresh inflate stream may start at its file offset (lseek + gzdopen of a duplicated
+// descriptor; gzseek would inflate the file from its start again).  From here on the reader treats the file as any gzip file.
+static bool bgzf_to_stream(lnr_reader *r) {
+    const uint64_t off = r->chain.empty() ? r->bpos : r->chain[0].off;
+    uint64_t skip = r->chain.empty() ? 0 : r->bskip;
+    r->bgzf = false; r->chain.clear(); r->bskip = r->bcarry = r->bkeep_from = 0;
+    int fd = dup(r->bfd);
+    gzFile nf = nullptr;
+    if (fd < 0 || lseek(fd, (off_t)off, SEEK_SET) < 0 || !(nf = gzdopen(fd, "rb"))) {
+        if (fd >= 0) close(fd);
+        r->err = "cannot reopen the file at BGZF block offset " + std::to_string(off);
+        return false;
+    }
+    if (r->f) gzclose(r->f);
+    r->f = nf;
+    gzbuffer(r->f, 1u << 20);
+    r->pos = r->end = 0; r->eof = false; r->gz_done = false;
+    while (skip) {
+        const unsigned ask = skip < r->buf.size() ? (unsigned)skip : (unsigned)r->buf.size();
+        int got = gzread(r->f, r->buf.data(), ask);
+        if (got <= 0) { int e; r->err = "BGZF block at file offset " + std::to_string(off) + ": " + (got < 0 ? gzerror(r->f, &e) : "unexpected end of file"); return false; }
+        skip -= (uint64_t)got; r->gz_bytes += (uint64_t)got;
+    }
+    return true;
+}
+
 extern "C" {
 
 lnr_status lnr_reader_open(const char *path, lnr_reader **out) {
@@ -102,6 +144,14 @@ lnr_status lnr_reader_open(const char *path, lnr_reader **out) {
         if (fd >= 0 && fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 2 && pread(fd, magic, 2, 0) == 2 && !(magic[0] == 0x1f && magic[1] == 0x8b)) {
             void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
             if (m != MAP_FAILED) { r->map = (const unsigned char *)m; r->map_len = (size_t)st.st_size; r->use_map = true; (void)madvise(m, r->map_len, MADV_SEQUENTIAL); }
+        } else if (fd >= 0 && magic[0] == 0x1f && magic[1] == 0x8b && S_ISREG(st.st_mode) && st.st_size >= 18 && !(getenv("LNR_READER_BGZF") && atoi(getenv("LNR_READER_BGZF")) == 0)) {
+            // gzip: BGZF when the first member says so (the walk of the other members waits for the windows that need them)
+            void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            uint32_t doff = 0;
+            if (m != MAP_FAILED && lnr_inf::bgzf_member((const uint8_t *)m, (uint64_t)st.st_size, doff)) {
+                r->map = (const unsigned char *)m; r->map_len = (size_t)st.st_size; (void)madvise(m, r->map_len, MADV_SEQUENTIAL);
+                r->bgzf = true; r->bfd = fd; fd = -1;                 // (the serial and host paths still read through r->f)
+            } else if (m != MAP_FAILED) munmap(m, (size_t)st.st_size);
         }
         if (fd >= 0) close(fd);
         unsigned hw = std::thread::hardware_concurrency();
@@ -119,6 +169,7 @@ void lnr_reader_close(lnr_reader *r) {
     if (!r) return;
     if (r->gpu && lnr_rdgpu_close) lnr_rdgpu_close(r->gpu);
     if (r->f) gzclose(r->f);
+    if (r->bfd >= 0) close(r->bfd);
     if (r->map) munmap((void *)r->map, r->map_len);
     delete r;
 }
@@ -317,6 +368,10 @@ lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64
     *n_out = 0;
     off[0] = 0;
     r->ids.clear(); r->id_off.assign(1, 0);
+    if (r->bgzf) {
+        if (r->bpos == 0 && r->chain.empty()) r->bgzf = false;       // nothing was read on the device: r->f stands at the start of the file, as ever
+        else if (!bgzf_to_stream(r)) return LNR_ERR_ARG;              // next_dev has read ahead on the device: the stream goes on where it stopped
+    }
     return next_from(r, dst, dst_cap, off, max_reads, n_out, 0, 0, false);
 }
 
@@ -344,6 +399,12 @@ lnr_status lnr_reader_gpu_times(const lnr_reader *r, double *ms5) {
     return LNR_OK;
 }
 
+lnr_status lnr_reader_gpu_inflate_stats(const lnr_reader *r, lnr_inflate_stats *out) {
+    if (!r || !out || !r->gpu) return LNR_ERR_ARG;
+    out->last = r->ist_last; out->total = r->ist_total;
+    return LNR_OK;
+}
+
 // Windows of text go to the device until the block is full, the file ends or the four-line FASTQ form breaks (hand-over: the serial parser
 // takes the rest of the file, its records are uploaded).  LNR_READER_GPU_WINDOW = bytes of text per window (default 256 MiB; a window that
 // holds no whole record is doubled): block boundaries do not depend on it.
@@ -359,6 +420,19 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
     r->gslot = (slot + 1) % r->gslots;
     lnr_rdgpu_times_reset(r->gpu);
     r->ids.clear(); r->id_off.assign(1, 0);
+    r->ist_last = lnr_inflate_counts{};
+    const uint64_t gz0 = r->gz_bytes;
+    struct StatsAtExit {                                          // the counts of this call join the totals however it ends
+        lnr_reader *r; uint64_t gz0;
+        ~StatsAtExit() {
+            lnr_inflate_counts &l = r->ist_last, &t = r->ist_total;
+            double ms2[2] = {0, 0};
+            if (lnr_rdgpu_inflate_times) lnr_rdgpu_inflate_times(r->gpu, ms2);
+            l.gzread_bytes = r->gz_bytes - gz0; l.inflate_ms = ms2[0]; l.gather_ms = ms2[1];
+            t.blocks += l.blocks; t.compressed_bytes += l.compressed_bytes; t.text_bytes += l.text_bytes; t.gzread_bytes += l.gzread_bytes;
+            t.inflate_ms += l.inflate_ms; t.gather_ms += l.gather_ms;
+        }
+    } stats_at_exit{r, gz0};
     uint64_t wcap = 256ULL << 20, grow = 1, used = 0;
     if (const char *e = getenv("LNR_READER_GPU_WINDOW")) { long long v = atoll(e); if (v >= 16) wcap = (uint64_t)v; }
     if (wcap > (1ULL << 30)) wcap = 1ULL << 30;
@@ -380,6 +454,81 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
         const unsigned char *text = nullptr;
         uint64_t len = 0, lead = 0;
         bool eof = false;
+        if (r->bgzf) {                                            // a run of whole BGZF blocks, inflated on the device behind what the last window left
+            if (r->bfailed) { r->err = r->gerr; return LNR_ERR_ARG; }
+            std::vector<lnr_rdgpu_bgzf_blk> tab;
+            const uint64_t c0 = r->bpos, chain0 = r->chain.size();
+            uint64_t fresh = 0, tl = r->bcarry;
+            while (!r->bend && !r->bstop && tl < want && tl + 65536 <= (1ULL << 30) && r->bpos - c0 < (1ULL << 30)) {
+                if (r->bpos >= r->map_len) { r->bend = true; break; }
+                uint32_t doff = 0;
+                const unsigned char *m = r->map + r->bpos;
+                const uint32_t size = lnr_inf::bgzf_member(m, r->map_len - r->bpos, doff);
+                auto le32 = [](const unsigned char *q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24); };
+                const uint32_t isize = size ? le32(m + size - 4) : 0;
+                if (!size || isize > 65536) { r->bstop = true; break; }     // not a BGZF member (or the chain leaves the file): gzread goes on here
+                if (isize) {
+                    tab.push_back(lnr_rdgpu_bgzf_blk{r->bpos + doff - c0, fresh, size - doff - 8, isize, le32(m + size - 8), 0});
+                    r->chain.push_back(lnr_reader::BBlk{r->bpos, size, isize});
+                    fresh += isize; tl += isize;
+                }
+                r->bpos += size;
+            }
+            if (!r->bend && !r->bstop && r->bpos >= r->map_len) r->bend = true;
+            if (!tl) {
+                if (r->bend) break;
+                if (r->bstop) { if (!bgzf_to_stream(r)) return LNR_ERR_ARG; continue; }
+            }
+            if (tl + 65536 > (1ULL << 30) && tl < want) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
+            lnr_rdgpu_bgzf job{};
+            job.comp = r->map + c0; job.comp_len = r->bpos - c0; job.blk = tab.data(); job.nblk = (uint32_t)tab.size();
+            job.keep_from = r->bkeep_from; job.carry = r->bcarry; job.new_text = fresh;
+            lnr_rdgpu_window w{};
+            w.fmt = r->format; w.eof = r->bend; w.slot = slot; w.threads = r->threads;
+            w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
+            lnr_rdgpu_result res{};
+            lnr_rdgpu_bgzf_result br{};
+            if (int s = lnr_rdgpu_parse_bgzf(r->gpu, &job, &w, &res, &br, r->gerr, sizeof r->gerr)) { r->bfailed = true; return gfail(s); }
+            if (br.bad_status) {                                  // a call that meets a bad block delivers no block
+                snprintf(r->gerr, sizeof r->gerr, "BGZF block at file offset %llu: %s", (unsigned long long)r->chain[chain0 + br.bad_blk].off, lnr_inf::status_text(br.bad_status));
+                r->bfailed = true;
+                return gfail(LNR_ERR_ARG);
+            }
+            r->ist_last.blocks += tab.size(); r->ist_last.compressed_bytes += job.comp_len; r->ist_last.text_bytes += fresh;
+            if (r->format == 0 && br.first >= 0) r->format = w.fmt;
+            bool handover = br.first >= 0 && !br.parsed;          // not a record start: the serial parser reports it
+            if (br.parsed) {
+                for (uint64_t k = 0; k < res.n; k++) {
+                    r->ids.insert(r->ids.end(), br.ids + br.id_off[k], br.ids + br.id_off[k] + br.id_len[k]);
+                    r->ids.push_back('\0');
+                    r->id_off.push_back(r->ids.size());
+                }
+                n += (uint32_t)res.n; used += res.bases;
+                r->records += res.n; r->bases += res.bases;
+                r->g_recs += res.n; r->g_text += res.consumed;
+                handover = res.handover != 0;
+            }
+            // what the window used up leaves the chain; the rest stays on the device for the next window
+            const uint64_t adv = br.lead + (br.parsed ? res.consumed : 0);
+            r->bkeep_from = br.parsed ? res.consumed : br.lead;
+            r->bcarry = tl - adv;
+            r->bskip += adv;
+            size_t gone = 0;
+            while (gone < r->chain.size() && r->bskip >= r->chain[gone].isize) r->bskip -= r->chain[gone++].isize;
+            r->chain.erase(r->chain.begin(), r->chain.begin() + (long)gone);
+            if (handover || r->bstop) {                           // the stream goes on at the first byte the device has not used up
+                if (!bgzf_to_stream(r)) return LNR_ERR_ARG;
+                if (handover) { r->gpu_serial = true; break; }
+            }
+            if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
+            if (res.full) { full = true; break; }
+            if (r->bend && r->bcarry == 0) break;
+            if (br.parsed && res.n == 0 && r->bgzf) {
+                if (tl + 65536 > (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
+                grow *= 2;
+            }
+            continue;
+        }
         if (r->use_map) {
             while (r->mpos < r->map_len && is_ws(r->map[r->mpos])) r->mpos++;
             if (r->mpos >= r->map_len) break;
@@ -399,7 +548,7 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
                 int got = gzread(r->f, S + len, (unsigned)ask);
                 if (got < 0) { int e; r->err = gzerror(r->f, &e); return LNR_ERR_ARG; }
                 if (got == 0) r->gz_done = true;
-                len += (uint64_t)got;
+                len += (uint64_t)got; r->gz_bytes += (uint64_t)got;
             }
             eof = r->gz_done;
             while (lead < len && is_ws(S[lead])) lead++;

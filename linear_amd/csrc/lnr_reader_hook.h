@@ -21,6 +21,26 @@ struct lnr_rdgpu_result {
     uint32_t handover, full, too_big;                // the serial parser goes on at `consumed`; the next record does not fit; ... and it is the first
     const uint64_t *hdr;             // n pairs (begin, end) of header spans, window offsets (pinned host memory, valid until the next parse)
 };
+// ---- BGZF input: the blocks of a window are inflated on the device, behind the text the last window left over
+struct lnr_rdgpu_bgzf_blk { uint64_t coff, ooff; uint32_t clen, isize, crc, pad; };   // DEFLATE data at comp + coff; text at (new text) + ooff
+struct lnr_rdgpu_bgzf {
+    const uint8_t *comp; uint64_t comp_len;          // the compressed bytes of the window's blocks (pageable host memory: the mapped file)
+    const lnr_rdgpu_bgzf_blk *blk; uint32_t nblk;    // blocks with ISIZE > 0
+    uint64_t keep_from, carry;                       // device text [keep_from, keep_from + carry) of the last window moves to the front
+    uint64_t new_text;                               // sum of ISIZE: the window's text is carry + new_text bytes
+};
+struct lnr_rdgpu_bgzf_result {
+    uint32_t bad_blk, bad_status;                    // bad_status != 0: block bad_blk did not inflate (lnr_inf::Status); nothing else is valid
+    uint64_t lead;                                   // white space skipped at the front of the text (the parse saw the text behind it)
+    int first;                                       // first byte behind it, -1: the text is white space up to `lead`
+    uint32_t parsed;                                 // 0: no parse ran (format unknown / not a record start: hand-over, or nothing but blanks)
+    const char *ids; const uint64_t *id_off; const uint32_t *id_len;   // header bytes of the taken records, '\r' stripped (pinned, valid until the next parse)
+};
+// stage these compressed bytes, inflate these blocks behind `carry` bytes, then measure / scan / emit over the device text.  w->text is
+// not used, w->len is set here; w->fmt == 0: decided by the first byte.
+int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
+                         char *err, size_t err_cap) __attribute__((weak));
+void lnr_rdgpu_inflate_times(const lnr_rdgpu *g, double *ms2) __attribute__((weak));   // last block: inflate kernel, header gather (HIP events)
 int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, size_t err_cap) __attribute__((weak));
 // makes block `slot` hold dst_cap bases and max_reads + 1 offsets; hands out its device arrays and the host copy of the offsets
 int lnr_rdgpu_block(lnr_rdgpu *g, uint32_t slot, uint64_t dst_cap, uint32_t max_reads, uint8_t **d_reads, uint64_t **d_off, uint64_t **h_off,

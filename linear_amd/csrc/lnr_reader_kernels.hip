@@ -23,6 +23,10 @@
 
 #include "lnr_reader_hd.h"
 #include "lnr_reader_hook.h"
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LNR_INFLATE_UNIFORM(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))      // the decoder's state is the same in every lane
+#endif
+#include "lnr_inflate_hd.h"
 
 namespace {
 
@@ -180,6 +184,56 @@ __global__ __launch_bounds__(64) void k_rd_emit(EmitArgs A) {
     }
 }
 
+// ---- BGZF: one wave inflates one block (lnr_inflate_hd.h) straight into the window's text in global memory.  Every lane runs the decoder
+// with the same values (bit buffer, code tables in LDS); lane 0 stores literals, all lanes copy a match: byte i of it comes from byte
+// (i mod distance) of the source, all of which the wave has stored before.  A workgroup-scope fence stands between those stores and the
+// loads: on gfx950 it needs no vmcnt wait (a CU performs one wave's vector memory operations in issue order through its one L1, so the
+// load sees the store), and it keeps the compiler from reordering them.  Then 64 slices of the text are CRC'd, one per lane, and combined.
+struct WaveSink {
+    u8 *out; u32 lane;
+    __device__ void lit(u32 pos, u8 b) { if (lane == 0) out[pos] = b; }
+    __device__ void match(u32 pos, u32 len, u32 dist) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        const u8 *src = out + (pos - dist);
+        for (u32 i = lane; i < len; i += 64) out[pos + i] = src[dist >= len ? i : i % dist];
+    }
+    __device__ void stored(u32 pos, const u8 *src, u32 n) { for (u32 i = lane; i < n; i += 64) out[pos + i] = src[i]; }
+};
+
+__global__ __launch_bounds__(64) void k_bgzf_inflate(const u8 *comp, u64 comp_len, const lnr_rdgpu_bgzf_blk *tab, u32 nblk, u8 *text, u64 text_cap, u32 *status) {
+    __shared__ lnr_inf::Tables T;
+    const u32 b = blockIdx.x, lane = threadIdx.x;
+    if (b >= nblk) return;
+    const lnr_rdgpu_bgzf_blk B = tab[b];
+    u32 st;
+    if (B.coff > comp_len || B.clen > comp_len - B.coff || B.ooff > text_cap || B.isize > text_cap - B.ooff) st = lnr_inf::E_TABLE;
+    else {
+        WaveSink o{text + B.ooff, lane};
+        st = lnr_inf::inflate_block(comp + B.coff, B.clen, o, B.isize, T);
+        if (st == lnr_inf::OK) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            const u32 S = (B.isize + 63) / 64, a = lane * S < B.isize ? lane * S : B.isize, e = a + S < B.isize ? a + S : B.isize;
+            u32 x = lnr_inf::crc_shift(lnr_inf::crc_of(o.out + a, e - a), B.isize - e);
+            for (int d = 32; d; d >>= 1) x ^= (u32)__shfl_xor((int)x, d, 64);
+            if (x != B.crc) st = lnr_inf::E_CRC;
+        }
+    }
+    if (lane == 0) status[b] = st;
+}
+
+// header bytes of the taken records -> one run of bytes the host reads (one wave per record); trailing '\r' dropped as the host parser does
+__global__ __launch_bounds__(64) void k_rd_gather(const u8 *text, u64 len, const u64 *hdr, const u64 *dst_off, u64 n, u8 *dst, u64 dst_cap, u32 *lens) {
+    const u64 k = blockIdx.x;
+    if (k >= n) return;
+    const u32 lane = threadIdx.x;
+    const u64 hb = hdr[2 * k], o = dst_off[k];
+    u64 he = hdr[2 * k + 1];
+    if (hb > he || he > len || o > dst_cap || he - hb > dst_cap - o) { if (lane == 0) lens[k] = ~0u; return; }
+    while (he > hb && text[he - 1] == '\r') he--;
+    for (u64 i = lane; i < he - hb; i += 64) dst[o + i] = text[hb + i];
+    if (lane == 0) lens[k] = (u32)(he - hb);
+}
+
 double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Buf { void *p = nullptr; u64 cap = 0; };
@@ -198,6 +252,11 @@ struct lnr_rdgpu {
     Pin up[2], stage, h_res, h_hdr;
     Block blk[8];
     double ms[5] = {0, 0, 0, 0, 0};
+    // BGZF: compressed bytes, block table, status per block, a buffer for moves that overlap, the gathered headers
+    Buf comp, btab, bstat, move, idoff, idbytes, idlen;
+    Pin h_btab, h_bstat, h_head, h_idoff, h_idbytes, h_idlen;
+    hipEvent_t ev_i[4] = {nullptr, nullptr, nullptr, nullptr};
+    double ms_inf[2] = {0, 0};
 };
 
 namespace {
@@ -237,14 +296,54 @@ void par_copy(void *dst, const void *src, u64 n, u32 threads) {
     for (auto &x : th) x.join();
 }
 void free_all(lnr_rdgpu *g) {
-    for (Buf *b : {&g->text, &g->sums, &g->carry, &g->hdr, &g->res}) if (b->p) (void)hipFree(b->p);
-    for (Pin *b : {&g->up[0], &g->up[1], &g->stage, &g->h_res, &g->h_hdr}) if (b->p) (void)hipHostFree(b->p);
+    for (Buf *b : {&g->text, &g->sums, &g->carry, &g->hdr, &g->res, &g->comp, &g->btab, &g->bstat, &g->move, &g->idoff, &g->idbytes, &g->idlen}) if (b->p) (void)hipFree(b->p);
+    for (Pin *b : {&g->up[0], &g->up[1], &g->stage, &g->h_res, &g->h_hdr, &g->h_btab, &g->h_bstat, &g->h_head, &g->h_idoff, &g->h_idbytes, &g->h_idlen}) if (b->p) (void)hipHostFree(b->p);
+    for (hipEvent_t e : g->ev_i) if (e) (void)hipEventDestroy(e);
     for (Block &b : g->blk) { if (b.reads.p) (void)hipFree(b.reads.p); if (b.off.p) (void)hipFree(b.off.p); if (b.h_off.p) (void)hipHostFree(b.h_off.p); }
     for (hipEvent_t e : g->ev_up) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->ev_m) if (e) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
     if (g->s_copy) (void)hipStreamDestroy(g->s_copy);
+}
+
+// scan + emit over the window's text in g->text (measured already: nchunk pairs of events), results and header spans to the host
+int scan_emit(lnr_rdgpu *g, const lnr_rdgpu_window *w, u32 nt, u64 nchunk, u64 max_rec, lnr_rdgpu_result *r, char *err, size_t err_cap) {
+    Block &b = g->blk[w->slot];
+    u8 *d_text = (u8 *)g->text.p;
+    double t0;
+    // ---- scan + emit
+    ScanArgs SA;
+    SA.text = d_text; SA.sums = (const Sum *)g->sums.p; SA.carry = (Carry *)g->carry.p; SA.nt = nt;
+    SA.L.fmt = w->fmt; SA.L.eof = w->eof ? 1u : 0u; SA.L.len = w->len; SA.L.allowed = w->allowed; SA.L.free = w->free;
+    SA.res = (Result *)g->res.p; SA.d_off = (u64 *)b.off.p; SA.rec_base = w->rec_base; SA.base_base = w->base_base;
+    EmitArgs EA;
+    EA.text = d_text; EA.len = w->len; EA.fmt = w->fmt; EA.carry = (const Carry *)g->carry.p; EA.res = (Result *)g->res.p;
+    EA.rec_base = w->rec_base; EA.base_base = w->base_base; EA.out = (u8 *)b.reads.p; EA.d_off = (u64 *)b.off.p; EA.hdr = (u64 *)g->hdr.p;
+    RD_CK(hipEventRecord(g->ev[0], g->st), -3);
+    hipLaunchKernelGGL(k_rd_scan, dim3(1), dim3(SCAN_THREADS), 0, g->st, SA);
+    RD_CK(hipEventRecord(g->ev[1], g->st), -3);
+    hipLaunchKernelGGL(k_rd_emit, dim3(nt), dim3(64), 0, g->st, EA);
+    RD_CK(hipEventRecord(g->ev[2], g->st), -3);
+    RD_CK(hipMemcpyAsync(g->h_res.p, g->res.p, sizeof(Result), hipMemcpyDeviceToHost, g->st), -3);
+    RD_CK(hipStreamSynchronize(g->st), -3);
+    RD_CK(hipGetLastError(), -3);
+    t0 = wall_ms();
+    const Result R = *(const Result *)g->h_res.p;
+    if (R.n > max_rec || R.bases > w->free) { snprintf(err, err_cap, "internal: the scan took %llu records", (unsigned long long)R.n); return -8; }
+    u64 *h_off = (u64 *)b.h_off.p;
+    RD_CK(hipMemcpyAsync(h_off + w->rec_base, (u64 *)b.off.p + w->rec_base, 8 * (R.n + 1), hipMemcpyDeviceToHost, g->st), -3);
+    if (R.n) RD_CK(hipMemcpyAsync(g->h_hdr.p, g->hdr.p, 16 * R.n, hipMemcpyDeviceToHost, g->st), -3);
+    RD_CK(hipStreamSynchronize(g->st), -3);
+    g->ms[4] += wall_ms() - t0;
+    float f = 0;
+    for (u64 k = 0; k < nchunk; k++) { RD_CK(hipEventElapsedTime(&f, g->ev_m[2 * k], g->ev_m[2 * k + 1]), -3); g->ms[1] += f; }
+    RD_CK(hipEventElapsedTime(&f, g->ev[0], g->ev[1]), -3); g->ms[2] += f;
+    RD_CK(hipEventElapsedTime(&f, g->ev[1], g->ev[2]), -3); g->ms[3] += f;
+    r->n = R.n; r->bases = R.bases; r->consumed = R.consumed == ~0ULL ? w->len : R.consumed;
+    r->handover = R.handover; r->full = R.full; r->too_big = R.too_big;
+    r->hdr = (const uint64_t *)g->h_hdr.p;
+    return 0;
 }
 
 }  // namespace
@@ -270,6 +369,7 @@ int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, s
         RD_CK(hipStreamCreateWithFlags(&g->s_copy, hipStreamNonBlocking), -3);
         for (hipEvent_t &e : g->ev_up) RD_CK(hipEventCreate(&e), -3);
         for (hipEvent_t &e : g->ev) RD_CK(hipEventCreate(&e), -3);
+        for (hipEvent_t &e : g->ev_i) RD_CK(hipEventCreate(&e), -3);
         if (!pin_need(g->h_res, sizeof(Result))) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
         return dev_need(g->res, sizeof(Result), err, err_cap);
     };
@@ -339,39 +439,148 @@ int lnr_rdgpu_parse(lnr_rdgpu *g, const lnr_rdgpu_window *w, lnr_rdgpu_result *r
     }
     RD_CK(hipStreamSynchronize(g->s_copy), -3);
     g->ms[0] += wall_ms() - t0;
-    // ---- scan + emit
-    ScanArgs SA;
-    SA.text = d_text; SA.sums = (const Sum *)g->sums.p; SA.carry = (Carry *)g->carry.p; SA.nt = nt;
-    SA.L.fmt = w->fmt; SA.L.eof = w->eof ? 1u : 0u; SA.L.len = w->len; SA.L.allowed = w->allowed; SA.L.free = w->free;
-    SA.res = (Result *)g->res.p; SA.d_off = (u64 *)b.off.p; SA.rec_base = w->rec_base; SA.base_base = w->base_base;
-    EmitArgs EA;
-    EA.text = d_text; EA.len = w->len; EA.fmt = w->fmt; EA.carry = (const Carry *)g->carry.p; EA.res = (Result *)g->res.p;
-    EA.rec_base = w->rec_base; EA.base_base = w->base_base; EA.out = (u8 *)b.reads.p; EA.d_off = (u64 *)b.off.p; EA.hdr = (u64 *)g->hdr.p;
-    RD_CK(hipEventRecord(g->ev[0], g->st), -3);
-    hipLaunchKernelGGL(k_rd_scan, dim3(1), dim3(SCAN_THREADS), 0, g->st, SA);
-    RD_CK(hipEventRecord(g->ev[1], g->st), -3);
-    hipLaunchKernelGGL(k_rd_emit, dim3(nt), dim3(64), 0, g->st, EA);
-    RD_CK(hipEventRecord(g->ev[2], g->st), -3);
-    RD_CK(hipMemcpyAsync(g->h_res.p, g->res.p, sizeof(Result), hipMemcpyDeviceToHost, g->st), -3);
-    RD_CK(hipStreamSynchronize(g->st), -3);
-    RD_CK(hipGetLastError(), -3);
-    t0 = wall_ms();
-    const Result R = *(const Result *)g->h_res.p;
-    if (R.n > max_rec || R.bases > w->free) { snprintf(err, err_cap, "internal: the scan took %llu records", (unsigned long long)R.n); return -8; }
-    u64 *h_off = (u64 *)b.h_off.p;
-    RD_CK(hipMemcpyAsync(h_off + w->rec_base, (u64 *)b.off.p + w->rec_base, 8 * (R.n + 1), hipMemcpyDeviceToHost, g->st), -3);
-    if (R.n) RD_CK(hipMemcpyAsync(g->h_hdr.p, g->hdr.p, 16 * R.n, hipMemcpyDeviceToHost, g->st), -3);
-    RD_CK(hipStreamSynchronize(g->st), -3);
-    g->ms[4] += wall_ms() - t0;
-    float f = 0;
-    for (u64 k = 0; k < nchunk; k++) { RD_CK(hipEventElapsedTime(&f, g->ev_m[2 * k], g->ev_m[2 * k + 1]), -3); g->ms[1] += f; }
-    RD_CK(hipEventElapsedTime(&f, g->ev[0], g->ev[1]), -3); g->ms[2] += f;
-    RD_CK(hipEventElapsedTime(&f, g->ev[1], g->ev[2]), -3); g->ms[3] += f;
-    r->n = R.n; r->bases = R.bases; r->consumed = R.consumed == ~0ULL ? w->len : R.consumed;
-    r->handover = R.handover; r->full = R.full; r->too_big = R.too_big;
-    r->hdr = (const uint64_t *)g->h_hdr.p;
+    return scan_emit(g, w, nt, nchunk, max_rec, r, err, err_cap);
+}
+
+// pageable host bytes -> device, through the two pinned staging buffers that host threads fill in turn; g->st waits for the last copy
+static int upload_pageable(lnr_rdgpu *g, u8 *dst, const u8 *src, u64 len, u32 threads, char *err, size_t err_cap) {
+    for (Pin &p : g->up) if (!pin_need(p, RD_CHUNK)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    u64 k = 0;
+    for (u64 o = 0; o < len; o += RD_CHUNK, k++) {
+        const u64 n = len - o < RD_CHUNK ? len - o : RD_CHUNK;
+        RD_CK(hipEventSynchronize(g->ev_up[k & 1]), -3);
+        par_copy(g->up[k & 1].p, src + o, n, threads);
+        RD_CK(hipMemcpyAsync(dst + o, g->up[k & 1].p, n, hipMemcpyHostToDevice, g->s_copy), -3);
+        RD_CK(hipEventRecord(g->ev_up[k & 1], g->s_copy), -3);
+    }
+    if (k) RD_CK(hipStreamWaitEvent(g->st, g->ev_up[(k - 1) & 1], 0), -3);
     return 0;
 }
+
+// device text [from, from + n) -> [to, to + n) on g->st, to < from; through g->move where the two overlap
+static int move_text(lnr_rdgpu *g, u8 *text, u64 to, u64 from, u64 n, char *err, size_t err_cap) {
+    if (!n || to == from) return 0;
+    if (to + n <= from) { RD_CK(hipMemcpyAsync(text + to, text + from, n, hipMemcpyDeviceToDevice, g->st), -3); return 0; }
+    if (int s = dev_need(g->move, n, err, err_cap)) return s;
+    RD_CK(hipMemcpyAsync(g->move.p, text + from, n, hipMemcpyDeviceToDevice, g->st), -3);
+    RD_CK(hipMemcpyAsync(text + to, g->move.p, n, hipMemcpyDeviceToDevice, g->st), -3);
+    return 0;
+}
+
+int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
+                         char *err, size_t err_cap) {
+    *br = lnr_rdgpu_bgzf_result{};
+    br->first = -1;
+    *r = lnr_rdgpu_result{};
+    u64 tlen = job->carry + job->new_text;
+    if (!tlen || tlen > (1ULL << 30) || w->slot >= g->slots || job->comp_len > (1ULL << 31)) { snprintf(err, err_cap, "internal: window of %llu bytes", (unsigned long long)tlen); return -8; }
+    if (job->keep_from + job->carry > g->text.cap) { snprintf(err, err_cap, "internal: carried text outside the buffer"); return -8; }
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    RD_CK(hipSetDevice(g->device), -3);
+    int s;
+    // ---- the text buffer: whole tiles; the carried text moves to its front (into a new buffer where this one is too small)
+    const u64 need = ((tlen + RD_TILE - 1) / RD_TILE) * RD_TILE + 16;
+    if (need > g->text.cap) {
+        Buf nb;
+        if ((s = dev_need(nb, need, err, err_cap))) return s;
+        if (job->carry) {
+            hipError_t e = hipMemcpyAsync(nb.p, (u8 *)g->text.p + job->keep_from, job->carry, hipMemcpyDeviceToDevice, g->st);
+            if (e == hipSuccess) e = hipStreamSynchronize(g->st);
+            if (e != hipSuccess) { (void)hipFree(nb.p); snprintf(err, err_cap, "moving the carried text: %s", hipGetErrorString(e)); return -3; }
+        }
+        if (g->text.p) (void)hipFree(g->text.p);
+        g->text = nb;
+    } else if ((s = move_text(g, (u8 *)g->text.p, 0, job->keep_from, job->carry, err, err_cap))) return s;
+    u8 *d_text = (u8 *)g->text.p;
+    // ---- compressed bytes and the block table up, one wave per block
+    double t0 = wall_ms();
+    const u32 nblk = job->nblk;
+    if (nblk) {
+        const u64 tb = (u64)nblk * sizeof(lnr_rdgpu_bgzf_blk);
+        if ((s = dev_need(g->comp, job->comp_len + 16, err, err_cap)) || (s = dev_need(g->btab, tb, err, err_cap)) || (s = dev_need(g->bstat, 4ULL * nblk, err, err_cap))) return s;
+        if (!pin_need(g->h_btab, tb) || !pin_need(g->h_bstat, 4ULL * nblk)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+        memcpy(g->h_btab.p, job->blk, tb);
+        RD_CK(hipMemcpyAsync(g->btab.p, g->h_btab.p, tb, hipMemcpyHostToDevice, g->st), -3);
+        RD_CK(hipMemsetAsync(g->bstat.p, 0xff, 4ULL * nblk, g->st), -3);
+        if ((s = upload_pageable(g, (u8 *)g->comp.p, job->comp, job->comp_len, w->threads, err, err_cap))) return s;
+        RD_CK(hipEventRecord(g->ev_i[0], g->st), -3);
+        hipLaunchKernelGGL(k_bgzf_inflate, dim3(nblk), dim3(64), 0, g->st, (const u8 *)g->comp.p, (u64)job->comp_len, (const lnr_rdgpu_bgzf_blk *)g->btab.p, nblk,
+                           d_text + job->carry, (u64)job->new_text, (u32 *)g->bstat.p);
+        RD_CK(hipEventRecord(g->ev_i[1], g->st), -3);
+        RD_CK(hipMemcpyAsync(g->h_bstat.p, g->bstat.p, 4ULL * nblk, hipMemcpyDeviceToHost, g->st), -3);
+    }
+    constexpr u64 HEAD = 65536;                                            // (blanks in front of the first record are used up this many per pass)
+    if (!pin_need(g->h_head, HEAD)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    const u64 hl = tlen < HEAD ? tlen : HEAD;
+    RD_CK(hipMemcpyAsync(g->h_head.p, d_text, hl, hipMemcpyDeviceToHost, g->st), -3);
+    RD_CK(hipStreamSynchronize(g->st), -3);
+    RD_CK(hipGetLastError(), -3);
+    g->ms[0] += wall_ms() - t0;
+    float f = 0;
+    if (nblk) {
+        RD_CK(hipEventElapsedTime(&f, g->ev_i[0], g->ev_i[1]), -3); g->ms_inf[0] += f;
+        const u32 *stt = (const u32 *)g->h_bstat.p;
+        for (u32 k = 0; k < nblk; k++) if (stt[k]) { br->bad_blk = k; br->bad_status = stt[k]; return 0; }
+    }
+    // ---- a window starts at a record start: white space in front of it (the start of the file) is skipped
+    const u8 *head = (const u8 *)g->h_head.p;
+    u64 lead = 0;
+    while (lead < hl && is_ws(head[lead])) lead++;
+    br->lead = lead;
+    if (lead == hl) return 0;                                              // nothing but blanks so far: the caller uses them up
+    br->first = head[lead];
+    if (w->fmt == 0) w->fmt = head[lead] == '>' ? FASTA : head[lead] == '@' ? FASTQ : -1;
+    if (w->fmt < 0 || head[lead] != (w->fmt == FASTA ? '>' : '@')) return 0;
+    if (lead) {
+        if ((s = move_text(g, d_text, 0, lead, tlen - lead, err, err_cap))) return s;
+        tlen -= lead;
+    }
+    w->len = tlen; w->text = nullptr; w->pinned = 1;
+    Block &b = g->blk[w->slot];
+    const u32 nt = (u32)((tlen + RD_TILE - 1) / RD_TILE);
+    const u64 max_rec = w->allowed < tlen / 2 + 1 ? w->allowed : tlen / 2 + 1;
+    if ((s = dev_need(g->sums, (u64)nt * sizeof(Sum), err, err_cap)) || (s = dev_need(g->carry, (u64)nt * sizeof(Carry), err, err_cap)) ||
+        (s = dev_need(g->hdr, 16 * max_rec + 16, err, err_cap))) return s;
+    if (!pin_need(g->h_hdr, 16 * max_rec + 16)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    if (w->base_base + w->free + 16 > b.reads.cap || 8 * (w->rec_base + w->allowed + 1) > b.off.cap) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
+    while (g->ev_m.size() < 2) { hipEvent_t e; RD_CK(hipEventCreate(&e), -3); g->ev_m.push_back(e); }
+    RD_CK(hipEventRecord(g->ev_m[0], g->st), -3);
+    hipLaunchKernelGGL(k_rd_measure, dim3(nt), dim3(64), 0, g->st, (const u8 *)d_text, (u64)tlen, w->fmt, 0u, (Sum *)g->sums.p);
+    RD_CK(hipEventRecord(g->ev_m[1], g->st), -3);
+    if ((s = scan_emit(g, w, nt, 1, max_rec, r, err, err_cap))) return s;
+    br->parsed = 1;
+    // ---- the header bytes of the taken records: their places from the spans (host), the bytes by one wave per record
+    const u64 n = r->n;
+    if (!pin_need(g->h_idoff, 8 * n + 8) || !pin_need(g->h_idlen, 4 * n + 4)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    u64 *ido = (u64 *)g->h_idoff.p, total = 0;
+    for (u64 k = 0; k < n; k++) {
+        const u64 hb = r->hdr[2 * k], he = r->hdr[2 * k + 1];
+        if (hb > he || he > tlen) { snprintf(err, err_cap, "internal: header span of record %llu", (unsigned long long)k); return -8; }
+        ido[k] = total; total += he - hb;
+    }
+    br->id_off = ido; br->id_len = (const uint32_t *)g->h_idlen.p;
+    if (!pin_need(g->h_idbytes, total + 1)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    br->ids = (const char *)g->h_idbytes.p;
+    if (n) {
+        if ((s = dev_need(g->idoff, 8 * n, err, err_cap)) || (s = dev_need(g->idlen, 4 * n, err, err_cap)) || (s = dev_need(g->idbytes, total + 1, err, err_cap))) return s;
+        RD_CK(hipMemcpyAsync(g->idoff.p, ido, 8 * n, hipMemcpyHostToDevice, g->st), -3);
+        RD_CK(hipEventRecord(g->ev_i[2], g->st), -3);
+        hipLaunchKernelGGL(k_rd_gather, dim3((u32)n), dim3(64), 0, g->st, (const u8 *)d_text, (u64)tlen, (const u64 *)g->hdr.p, (const u64 *)g->idoff.p, n,
+                           (u8 *)g->idbytes.p, total, (u32 *)g->idlen.p);
+        RD_CK(hipEventRecord(g->ev_i[3], g->st), -3);
+        RD_CK(hipMemcpyAsync(g->h_idlen.p, g->idlen.p, 4 * n, hipMemcpyDeviceToHost, g->st), -3);
+        if (total) RD_CK(hipMemcpyAsync(g->h_idbytes.p, g->idbytes.p, total, hipMemcpyDeviceToHost, g->st), -3);
+        RD_CK(hipStreamSynchronize(g->st), -3);
+        RD_CK(hipGetLastError(), -3);
+        RD_CK(hipEventElapsedTime(&f, g->ev_i[2], g->ev_i[3]), -3); g->ms_inf[1] += f;
+        for (u64 k = 0; k < n; k++)
+            if (br->id_len[k] > r->hdr[2 * k + 1] - r->hdr[2 * k]) { snprintf(err, err_cap, "internal: gathered header of record %llu", (unsigned long long)k); return -8; }
+    }
+    return 0;
+}
+
+void lnr_rdgpu_inflate_times(const lnr_rdgpu *g, double *ms2) { ms2[0] = g->ms_inf[0]; ms2[1] = g->ms_inf[1]; }
 
 int lnr_rdgpu_append(lnr_rdgpu *g, uint32_t slot, uint64_t base_base, const uint8_t *bases, uint64_t nb, uint64_t rec_base, const uint64_t *off, uint64_t n,
                      char *err, size_t err_cap) {
@@ -386,7 +595,7 @@ int lnr_rdgpu_append(lnr_rdgpu *g, uint32_t slot, uint64_t base_base, const uint
 }
 
 void lnr_rdgpu_times(const lnr_rdgpu *g, double *ms5) { for (int i = 0; i < 5; i++) ms5[i] = g->ms[i]; }
-void lnr_rdgpu_times_reset(lnr_rdgpu *g) { for (double &m : g->ms) m = 0; }
+void lnr_rdgpu_times_reset(lnr_rdgpu *g) { for (double &m : g->ms) m = 0; g->ms_inf[0] = g->ms_inf[1] = 0; }
 
 void lnr_rdgpu_close(lnr_rdgpu *g) {
     if (!g) return;
