@@ -314,6 +314,20 @@ lnr_status lnr_writer_format_seq_gpu(lnr_writer *w, const lnr_cords *cords, cons
                                      const char *read_ids, const uint64_t *id_off, const char **text, uint64_t *size);
 lnr_status lnr_writer_format_seq_dev(lnr_writer *w, const lnr_cords_dev *cords, const uint8_t *d_reads_concat, const uint64_t *d_read_off,
                                      const char *read_ids, const uint64_t *id_off, const char **text, uint64_t *size);
+/* BGZF output of the GPU writer.  on != 0: lnr_writer_format_gpu / _dev / _seq_gpu / _seq_dev return, in *text / *size, whole BGZF members
+ * whose inflated concatenation is byte for byte the text the same call returns with it off; block k holds text [k*0xff00, ...); an empty
+ * text gives zero bytes; no EOF marker is added.  Before lnr_writer_gpu_open: LNR_ERR_ARG.  lnr_writer_format / _format_seq are not affected.
+ * The text is compressed where it was formatted (one dynamic-Huffman DEFLATE block per member, a stored block where that is not smaller:
+ * a member is at most its text + 31 bytes) and only the members are downloaded: with the switch on, download_ms of lnr_writer_gpu_times
+ * times that download.  The bytes are a function of the text alone.  Lifetime of the returned bytes: until the writer's next format or
+ * lnr_writer_bgzf_bytes_gpu call. */
+lnr_status lnr_writer_set_bgzf(lnr_writer *w, int on);
+/* Any host bytes (the SAM header) compressed the same way on the writer's device; size 0 gives zero bytes. */
+lnr_status lnr_writer_bgzf_bytes_gpu(lnr_writer *w, const char *bytes, uint64_t size, const char **data, uint64_t *out_size);
+/* The 28-byte empty member that ends a BGZF file (host constant; needs no device). */
+lnr_status lnr_writer_bgzf_eof(const char **data, uint64_t *size);
+typedef struct { uint64_t blocks, stored_blocks, text_bytes, compressed_bytes; double deflate_ms, pack_ms; } lnr_bgzf_stats;   /* last GPU call */
+lnr_status lnr_writer_bgzf_stats(const lnr_writer *w, lnr_bgzf_stats *out);
 
 #ifdef __cplusplus
 }

@@ -69,7 +69,13 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_writer_create", "lnr_writer_format", "lnr_writer_sam_header", "lnr_writer_destroy", "lnr_last_gaps", "lnr_gap_stream", "lnr_set_gap", "lnr_index_broadcast", "lnr_writer_set_preset", "lnr_writer_set_read_group",
            "lnr_writer_gpu_open", "lnr_writer_format_gpu", "lnr_writer_format_dev", "lnr_writer_gpu_times", "lnr_writer_error",
            "lnr_writer_set_genome", "lnr_writer_format_seq", "lnr_writer_format_seq_gpu", "lnr_writer_format_seq_dev",
+           "lnr_writer_set_bgzf", "lnr_writer_bgzf_bytes_gpu", "lnr_writer_bgzf_eof", "lnr_writer_bgzf_stats",
            "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats"]
+
+
+class LnrBgzfStats(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("text_bytes", C.c_uint64), ("compressed_bytes", C.c_uint64),
+                ("deflate_ms", C.c_double), ("pack_ms", C.c_double)]
 
 
 def load_library() -> C.CDLL:
@@ -130,6 +136,10 @@ def load_library() -> C.CDLL:
     lib.lnr_writer_format_seq.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.c_uint32, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_format_seq_gpu.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_format_seq_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev), C.c_void_p, C.c_void_p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_set_bgzf.argtypes = [C.c_void_p, C.c_int]
+    lib.lnr_writer_bgzf_bytes_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_bgzf_eof.argtypes = [C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_bgzf_stats.argtypes = [C.c_void_p, C.POINTER(LnrBgzfStats)]
     return lib
 
 
@@ -526,6 +536,29 @@ class Writer:
         ms = (C.c_double * 5)()
         self._check(self.lib.lnr_writer_gpu_times(self.h, ms))
         return dict(zip(("upload_ms", "measure_ms", "scan_ms", "emit_ms", "download_ms"), ms))
+
+    def set_bgzf(self, on: bool) -> None:
+        """on: format_gpu / format_dev / format_seq_gpu / format_seq_dev return BGZF members (compressed on the GPU, no EOF marker) that
+        inflate to the text they return with it off.  Needs gpu_open."""
+        self._check(self.lib.lnr_writer_set_bgzf(self.h, 1 if on else 0))
+
+    def bgzf_bytes_gpu(self, data: bytes, copy: bool = True):
+        """Any bytes (the SAM header) as BGZF members, compressed on the writer's GPU."""
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_bgzf_bytes_gpu(self.h, data, len(data), C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value) if copy else (out.value, size.value)
+
+    def bgzf_eof(self) -> bytes:
+        """The 28-byte empty member that ends a BGZF file."""
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_bgzf_eof(C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value)
+
+    def bgzf_stats(self) -> dict:
+        """The last GPU call: blocks, stored_blocks, text_bytes, compressed_bytes, deflate_ms and pack_ms (HIP events)."""
+        s = LnrBgzfStats()
+        self._check(self.lib.lnr_writer_bgzf_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in LnrBgzfStats._fields_}
 
     def sam_header(self, command_line: str) -> bytes:
         text, size = C.c_void_p(), C.c_uint64()

@@ -18,6 +18,9 @@
 //                  calculator runs lnr_filter_batch_dev on them and the text comes from lnr_cords_to_host + the host writer or, with --gpu-writer,
 //                  from lnr_writer_format_dev / _seq_dev on the same device buffers: no read base crosses PCIe.  One GPU, one batch at a time (the
 //                  device form of the filter has one lane); the same bytes as the default path.
+//   BGZF output    --bgzf (extension, needs --gpu-writer): the text is compressed on the GPU it was formatted on (lnr_writer_set_bgzf) and the
+//                  outputs are PREFIX.sam.gz / PREFIX.apf.gz: the SAM header through lnr_writer_bgzf_bytes_gpu, every block's members as
+//                  returned, the EOF marker at close.  bgzip -d, zcat and samtools read them.
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
 // Not built (exit 1 with a message, never a silently different result): BAM output (-ot 4 / 8), -ss 1 (use --sam-seq), -c 0, -f 1, -r 1, -p 0, -b 0
@@ -56,7 +59,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0;
     std::vector<int> devices;
 };
 
@@ -75,7 +78,8 @@ static void usage() {
             "    --gpu-writer               format .sam / .apf text on the first GPU in use instead of the writer's host threads {off}\n"
             "    --gpu-reader               parse the read files on the first GPU in use and keep the reads there: reader -> filter -> writer on device buffers {off}\n"
             "                               (one GPU; with --sam-seq it needs --gpu-writer: the read bases are not on the host)\n"
-            "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n");
+            "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n"
+            "    --bgzf                     compress the text on the GPU and write PREFIX.sam.gz / PREFIX.apf.gz (BGZF); needs --gpu-writer {off}\n");
 }
 
 // returns 0 ok, 1 error, 2 help shown
@@ -103,6 +107,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         if (name == "gpu-writer") { o.gpu_writer = 1; continue; }                                  // a switch: takes no value
         if (name == "sam-seq") { o.sam_seq = 1; continue; }
         if (name == "gpu-reader") { o.gpu_reader = 1; continue; }
+        if (name == "bgzf") { o.bgzf = 1; continue; }
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         const Opt *op = nullptr;
@@ -173,6 +178,7 @@ struct Shared {
 struct Outputs {
     FILE *fsam = nullptr, *fapf = nullptr;
     std::string cur_prefix; bool any_open = false; int cur_file = -1;
+    bool bgzf = false;                       // --bgzf: .gz names, `header` comes compressed, the EOF marker ends every file
     // makes the files of read file `file` current; header = the SAM header text.  false: the files cannot be written (err says which)
     bool turn_to(const Options &o, int file, const std::string &header, std::string &err) {
         if (file == cur_file) return true;
@@ -180,14 +186,21 @@ struct Outputs {
         std::string prefix = o.oPath.empty() ? output_prefix_of(o.r_paths[(size_t)file]) : o.oPath;
         if (any_open && !(o.oPath.empty() && prefix != cur_prefix)) return true;
         close();
-        fsam = (o.f_output_type & 2) ? fopen((prefix + ".sam").c_str(), "wb") : nullptr;
-        fapf = (o.f_output_type & 1) ? fopen((prefix + ".apf").c_str(), "wb") : nullptr;
+        bgzf = o.bgzf != 0;
+        fsam = (o.f_output_type & 2) ? fopen((prefix + (bgzf ? ".sam.gz" : ".sam")).c_str(), "wb") : nullptr;
+        fapf = (o.f_output_type & 1) ? fopen((prefix + (bgzf ? ".apf.gz" : ".apf")).c_str(), "wb") : nullptr;
         if (((o.f_output_type & 2) && !fsam) || ((o.f_output_type & 1) && !fapf)) { err = "can't write output files with prefix " + prefix; return false; }
         if (fsam) fwrite(header.data(), 1, header.size(), fsam);
         cur_prefix = prefix; any_open = true;
         return true;
     }
-    void close() { if (fsam) fclose(fsam); if (fapf) fclose(fapf); fsam = fapf = nullptr; }
+    void close() {
+        const char *eof = nullptr; uint64_t n = 0;
+        if (bgzf && (fsam || fapf)) lnr_writer_bgzf_eof(&eof, &n);
+        if (fsam) { if (n) fwrite(eof, 1, n, fsam); fclose(fsam); }
+        if (fapf) { if (n) fwrite(eof, 1, n, fapf); fclose(fapf); }
+        fsam = fapf = nullptr;
+    }
 };
 
 int main(int argc, char **argv) {
@@ -205,6 +218,7 @@ int main(int argc, char **argv) {
     else if (o.reform_ccs) nb = "-r 1"; else if (o.sensitivity != 1 && o.sensitivity != 2) nb = "-p other than 1 or 2"; else if (!o.bal_flag) nb = "-b 0 (the reference's -b 0 path writes a header-only SAM)";
     else if (o.index_t != 1 && o.index_t != 2) nb = "-i other than 1 or 2";
     if (nb) { fprintf(stderr, "\033[1;31mE[m02G]:\033[0m %s is not built in the MI355X filter path\n", nb); return 1; }
+    if (o.bgzf && !o.gpu_writer) { fprintf(stderr, "\033[1;31mE:\033[0m --bgzf compresses the text on the GPU that formats it: it needs --gpu-writer\n"); return 1; }
     if (o.thread < 1) o.thread = 1;
     if (o.gpus < 1) o.gpus = 1;
     if (o.block_reads < 1) o.block_reads = 1;
@@ -281,6 +295,23 @@ int main(int argc, char **argv) {
         for (auto *c : ctx) lnr_destroy(c);
         return 1;
     }
+    // --bgzf: the SAM header goes through the writer's device as well; false with a message when that fails
+    auto header_of = [&](std::string &header) {
+        const char *t; uint64_t z;
+        lnr_writer_sam_header(wr, "", &t, &z);
+        header.assign(t, z);
+        if (!o.bgzf) return true;
+        const std::string plain = header;
+        if (lnr_writer_bgzf_bytes_gpu(wr, plain.data(), plain.size(), &t, &z) != LNR_OK) return false;
+        header.assign(t, z);
+        return true;
+    };
+    if (o.bgzf && lnr_writer_set_bgzf(wr, 1) != LNR_OK) {
+        fprintf(stderr, "\033[1;31mE:\033[0m --bgzf: %s\n", lnr_writer_error(wr));
+        lnr_writer_destroy(wr);
+        for (auto *c : ctx) lnr_destroy(c);
+        return 1;
+    }
     if (o.gpu_reader) {                                                                          // before any output file is opened, too
         std::string why;
         if (!lnr_filter_batch_dev || !lnr_cords_to_host || !lnr_writer_format_dev || !lnr_writer_format_seq_dev || !lnr_reader_gpu_open || !lnr_reader_next_dev)
@@ -310,7 +341,12 @@ int main(int argc, char **argv) {
         std::mutex em; std::string err; std::atomic<int> failed{0};
         auto fail = [&](const std::string &e) { { std::lock_guard<std::mutex> l(em); if (!failed) { err = e; failed = 1; } } freeq.close(); readyq.close(); doneq.close(); };
         std::string sam_header;                                  // (taken here: the calculator thread is the writer's only user under --gpu-writer)
-        { const char *t; uint64_t z; lnr_writer_sam_header(wr, "", &t, &z); sam_header.assign(t, z); }
+        if (!header_of(sam_header)) {
+            fprintf(stderr, "\033[1;31mE:\033[0m --bgzf: %s\n", lnr_writer_error(wr));
+            lnr_writer_destroy(wr);
+            for (auto *c : ctx) lnr_destroy(c);
+            return 1;
+        }
         std::vector<DBlock> dblocks(3);
         for (auto &b : dblocks) freeq.push(&b);
         uint64_t cap = (uint64_t)o.block_reads * 12000 + (1u << 20);
@@ -523,8 +559,7 @@ int main(int argc, char **argv) {
         std::string sam_header;
         uint64_t want = 0;
         const char *text; uint64_t size;
-        lnr_writer_sam_header(wr, "", &text, &size);
-        sam_header.assign(text, size);
+        if (!header_of(sam_header)) sh.fail(std::string("--bgzf: ") + lnr_writer_error(wr));
         for (;;) {
             Block *b = nullptr;
             {

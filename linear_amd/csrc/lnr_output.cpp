@@ -379,6 +379,34 @@ lnr_status lnr_writer_format_seq_dev(lnr_writer *wr, const lnr_cords_dev *cords,
     return format_seq_on_gpu(wr, b, text, size);
 }
 
+// ---- BGZF output of the GPU side (the work: lnr_output_kernels.hip behind the weak hooks)
+lnr_status lnr_writer_set_bgzf(lnr_writer *wr, int on) {
+    if (!wr) return LNR_ERR_ARG;
+    if (!wr->gpu || !lnr_outgpu_set_bgzf) { snprintf(wr->err, sizeof wr->err, "lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
+    lnr_outgpu_set_bgzf(wr->gpu, on);
+    return LNR_OK;
+}
+lnr_status lnr_writer_bgzf_bytes_gpu(lnr_writer *wr, const char *bytes, uint64_t size, const char **data, uint64_t *out_size) {
+    if (!wr || (size && !bytes) || !data || !out_size) return LNR_ERR_ARG;
+    if (!wr->gpu || !lnr_outgpu_bgzf_bytes) { snprintf(wr->err, sizeof wr->err, "lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
+    wr->err[0] = 0;
+    return (lnr_status)lnr_outgpu_bgzf_bytes(wr->gpu, bytes, size, data, out_size, wr->err, sizeof wr->err);
+}
+lnr_status lnr_writer_bgzf_eof(const char **data, uint64_t *size) {
+    static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!data || !size) return LNR_ERR_ARG;
+    *data = (const char *)eof; *size = sizeof eof;
+    return LNR_OK;
+}
+lnr_status lnr_writer_bgzf_stats(const lnr_writer *wr, lnr_bgzf_stats *out) {
+    if (!wr || !out || !wr->gpu || !lnr_outgpu_bgzf_stats_get) return LNR_ERR_ARG;
+    lnr_outgpu_bgzf_stats s;
+    lnr_outgpu_bgzf_stats_get(wr->gpu, &s);
+    out->blocks = s.blocks; out->stored_blocks = s.stored_blocks; out->text_bytes = s.text_bytes; out->compressed_bytes = s.compressed_bytes;
+    out->deflate_ms = s.deflate_ms; out->pack_ms = s.pack_ms;
+    return LNR_OK;
+}
+
 // SAM header as `linear filter` writes it: @SQ per reference sequence, then @RG and @PG (no @HD)
 lnr_status lnr_writer_sam_header(lnr_writer *wr, const char *command_line, const char **text, uint64_t *size) {
     if (!wr || !text || !size) return LNR_ERR_ARG;

@@ -25,4 +25,10 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
 int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) __attribute__((weak));
 void lnr_outgpu_times(const lnr_outgpu *g, double *ms5) __attribute__((weak));   // last call: upload, measure, scan, emit, download
 void lnr_outgpu_close(lnr_outgpu *g) __attribute__((weak));
+// BGZF output (lnr_writer_set_bgzf): on != 0, lnr_outgpu_format compresses its text on the device (k_bgzf_deflate, one BGZF member per
+// 0xff00 text bytes) and hands out the members instead; lnr_outgpu_bgzf_bytes does the same to any host bytes.  Stats: the last call.
+struct lnr_outgpu_bgzf_stats { uint64_t blocks, stored_blocks, text_bytes, compressed_bytes; double deflate_ms, pack_ms; };
+void lnr_outgpu_set_bgzf(lnr_outgpu *g, int on) __attribute__((weak));
+int lnr_outgpu_bgzf_bytes(lnr_outgpu *g, const char *bytes, uint64_t size, const char **data, uint64_t *out_size, char *err, size_t err_cap) __attribute__((weak));
+void lnr_outgpu_bgzf_stats_get(const lnr_outgpu *g, lnr_outgpu_bgzf_stats *out) __attribute__((weak));
 }

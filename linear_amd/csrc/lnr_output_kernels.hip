@@ -20,12 +20,20 @@
 // by bisection over the table's SEQ positions, loads the source bytes (genome forward; read forward, or backward and complemented for
 // flag 16), maps them through ACGTN.  Single-byte stores: the first and last dword of a SEQ, which it shares with head and tail, and a
 // dword that straddles a refill of the table.  The measure kernel sums element counts and touches no base.
+//
+// BGZF output (lnr_writer_set_bgzf): the text stays in HBM and is compressed there, every 0xff00 bytes of it into one BGZF member by
+// lnr_deflate_hd.h -- the same text the CPU test pins against zlib.
+//   k_bgzf_deflate  one workgroup of 512 lanes per block (a grid of at most one workgroup per CU walks the blocks): the block's text and
+//                   the hash table in LDS, the member image built in the table's place, then copied to the block's 65536-byte slot
+//   k_out_scan      member sizes -> offsets
+//   k_bgzf_pack     the slots -> one contiguous run (destination-aligned dword stores), the only bytes that are downloaded
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <new>
 
+#include "lnr_deflate_hd.h"
 #include "lnr_output_hd.h"
 #include "lnr_output_hook.h"
 
@@ -247,6 +255,79 @@ __global__ __launch_bounds__(1024) void k_out_scan(u64 *a, u32 n) {
     for (u64 i = lo; i < hi; i++) { u64 v = a[i]; a[i] = run; run += v; }
 }
 
+// ---- BGZF
+constexpr u32 DEF_THREADS = 512;
+struct DevTeam {                               // the workgroup as lnr_deflate_hd.h's team
+    u32 tid, nt;
+    __device__ void sync() { __syncthreads(); }
+    __device__ void amax(u32 *p, u32 v) { atomicMax(p, v); }
+    __device__ void aadd(u32 *p, u32 v) { atomicAdd(p, v); }
+    __device__ void aor(u32 *p, u32 v) { atomicOr(p, v); }
+    __device__ void axor(u32 *p, u32 v) { atomicXor(p, v); }
+    // the greedy walk by wave 0: 64 positions in the lanes, the walker's position is wave-uniform and reads a lane's length with readlane
+    __device__ void parse(u32 *tok, u32 n) {
+        if (tid >= 64) return;
+        u32 p = 0;
+        u32 next = tid < n ? tok[tid] : 0;
+        for (u32 base = 0; base < n; base += 64) {
+            const u32 i = base + tid;
+            const u32 len = lnr_def::tok_len(next);
+            next = i + 64 < n ? tok[i + 64] : 0;            // (in flight while this tile is walked)
+            u64 vis = 0;
+            const u32 end = base + 64 < n ? base + 64 : n;
+            while (p < end) {
+                const u32 at = (u32)__builtin_amdgcn_readfirstlane((int)(p - base));
+                const u32 l = (u32)__builtin_amdgcn_readlane((int)len, (int)at);
+                vis |= 1ULL << at;
+                p += l ? l : 1;
+            }
+            if (i < n && !((vis >> tid) & 1ULL)) tok[i] = lnr_def::SKIP;
+        }
+    }
+};
+
+// text [k * 0xff00, ...) -> slot k (65536 bytes each), msize[k] = bytes of the member; msize[nblocks + 1] counts the stored members.
+// tok: 0xff00 words per workgroup of the grid.  text is 4-byte aligned.
+__global__ __launch_bounds__(DEF_THREADS) void k_bgzf_deflate(const uint8_t *text, u64 total, u32 nblocks, uint8_t *slots, u64 *msize, u32 *tok_all) {
+    __shared__ __attribute__((aligned(16))) uint8_t txt[lnr_def::BLOCK_TEXT];
+    __shared__ __attribute__((aligned(16))) u32 tab[lnr_def::HASH_SIZE];      // the hash table, then the member image (MEMBER_CAP bytes)
+    __shared__ lnr_def::Work W;
+    static_assert(sizeof(tab) == lnr_def::MEMBER_CAP, "the member image takes the table's place");
+    DevTeam T{threadIdx.x, blockDim.x};
+    u32 *tok = tok_all + (u64)blockIdx.x * lnr_def::BLOCK_TEXT;
+    for (u32 k = blockIdx.x; k < nblocks; k += gridDim.x) {
+        const u64 lo = (u64)k * lnr_def::BLOCK_TEXT;
+        const u32 n = total - lo < lnr_def::BLOCK_TEXT ? (u32)(total - lo) : lnr_def::BLOCK_TEXT;
+        const u32 *src = reinterpret_cast<const u32 *>(text + lo);           // (0xff00 is a multiple of 4)
+        for (u32 i = T.tid; i < n / 4; i += T.nt) reinterpret_cast<u32 *>(txt)[i] = src[i];
+        for (u32 i = (n & ~3u) + T.tid; i < n; i += T.nt) txt[i] = text[lo + i];
+        __syncthreads();
+        u32 stored = 0;
+        const u32 m = lnr_def::deflate_member(T, W, txt, n, tab, tok, reinterpret_cast<uint8_t *>(tab), &stored);
+        u32 *dst = reinterpret_cast<u32 *>(slots + (u64)k * lnr_def::MEMBER_CAP);
+        for (u32 i = T.tid; i < (m + 3) / 4; i += T.nt) dst[i] = tab[i];
+        if (T.tid == 0) { msize[k] = m; if (stored) atomicAdd((unsigned long long *)&msize[nblocks + 1], 1ULL); }
+        __syncthreads();
+    }
+}
+// slot k -> out + off[k], off[k + 1] - off[k] bytes: destination-aligned dwords put together from two aligned dwords of the slot
+__global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, const u64 *off, uint8_t *out) {
+    const u32 k = blockIdx.x, t = threadIdx.x;
+    const uint8_t *src = slots + (u64)k * lnr_def::MEMBER_CAP;
+    const u64 o = off[k];
+    const u32 m = (u32)(off[k + 1] - o);
+    uint8_t *dst = out + o;
+    u32 head = (4 - (u32)(o & 3)) & 3;
+    if (head > m) head = m;
+    if (t < head) dst[t] = src[t];
+    const u32 words = (m - head) / 4, r = 8 * (head & 3);
+    const u32 *sw = reinterpret_cast<const u32 *>(src);     // source byte head + 4 w = word w of sw shifted by r bits (head < 4)
+    u32 *dw = reinterpret_cast<u32 *>(dst + head);
+    for (u32 w = t; w < words; w += 256) dw[w] = r ? (sw[w] >> r) | (sw[w + 1] << (32 - r)) : sw[w];
+    const u32 done = head + 4 * words;
+    if (t < m - done) dst[done + t] = src[done + t];
+}
+
 double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Buf { void *p = nullptr; u64 cap = 0; };
@@ -257,7 +338,12 @@ struct lnr_outgpu {
     int device = 0;
     hipStream_t st = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t bev[4] = {nullptr, nullptr, nullptr, nullptr};       // BGZF: around k_bgzf_deflate, around k_bgzf_pack
     Buf gblob, goff, glen, ids, idoff, coff, cs, ce, len, sizes, text;
+    Buf slots, msize, tok, packed;              // BGZF: a slot per block, member sizes / offsets, tokens per workgroup, the contiguous run
+    int bgzf = 0; u32 cus = 1;
+    lnr_outgpu_bgzf_stats bz{};
+    u64 *h_bz = nullptr;                        // pinned: bytes of the run, stored members
     Buf genome, gstart, reads;                  // SEQ: the writer's own copy of the genome (lnr_outgpu_set_genome), the reads of a host-form call
     u32 nseq = 0;
     char *h_text = nullptr; u64 h_cap = 0;      // pinned
@@ -283,11 +369,63 @@ int dev_need(Buf &b, u64 bytes, char *err, size_t err_cap) {
     return 0;
 }
 void free_all(lnr_outgpu *g) {
-    for (Buf *b : {&g->gblob, &g->goff, &g->glen, &g->ids, &g->idoff, &g->coff, &g->cs, &g->ce, &g->len, &g->sizes, &g->text, &g->genome, &g->gstart, &g->reads}) if (b->p) (void)hipFree(b->p);
+    for (Buf *b : {&g->gblob, &g->goff, &g->glen, &g->ids, &g->idoff, &g->coff, &g->cs, &g->ce, &g->len, &g->sizes, &g->text, &g->genome, &g->gstart, &g->reads, &g->slots, &g->msize, &g->tok, &g->packed}) if (b->p) (void)hipFree(b->p);
     if (g->h_text) (void)hipHostFree(g->h_text);
+    if (g->h_bz) (void)hipHostFree(g->h_bz);
+    for (hipEvent_t e : g->bev) if (e) (void)hipEventDestroy(e);
     if (g->h_total) (void)hipHostFree(g->h_total);
     for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
+}
+
+int host_need(lnr_outgpu *g, u64 bytes, char *err, size_t err_cap) {      // the pinned buffer the caller reads
+    if (bytes + 8 <= g->h_cap) return 0;
+    if (g->h_text) { (void)hipHostFree(g->h_text); g->h_text = nullptr; g->h_cap = 0; }
+    u64 want = bytes + bytes / 4 + 4096;
+    OUT_CK(hipHostMalloc((void **)&g->h_text, want, hipHostMallocDefault), -4);
+    g->h_cap = want;
+    return 0;
+}
+
+// `total` bytes of text at d_text (device, 4-byte aligned) -> BGZF members in the pinned buffer.  Fills g->bz and g->ms[4].
+int bgzf_run(lnr_outgpu *g, const uint8_t *d_text, u64 total, const char **data, uint64_t *size, char *err, size_t err_cap) {
+    static const char empty[1] = "";
+    g->bz = lnr_outgpu_bgzf_stats{};
+    g->bz.text_bytes = total;
+    if (total == 0) { *data = empty; *size = 0; return 0; }
+    const u64 nb64 = (total + lnr_def::BLOCK_TEXT - 1) / lnr_def::BLOCK_TEXT;
+    if (nb64 > 0x7fffffffULL) { snprintf(err, err_cap, "text of %llu bytes is too long for one BGZF call", (unsigned long long)total); return -1; }
+    const u32 nb = (u32)nb64, grid = nb < g->cus ? nb : g->cus;
+    int s;
+    if ((s = dev_need(g->slots, (u64)nb * lnr_def::MEMBER_CAP, err, err_cap)) || (s = dev_need(g->msize, 8ULL * (nb + 2ULL), err, err_cap)) ||
+        (s = dev_need(g->tok, 4ULL * grid * lnr_def::BLOCK_TEXT, err, err_cap))) return s;
+    u64 *msize = (u64 *)g->msize.p;
+    OUT_CK(hipMemsetAsync(msize + nb, 0, 16, g->st), -3);
+    OUT_CK(hipEventRecord(g->bev[0], g->st), -3);
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(DEF_THREADS), 0, g->st, d_text, total, nb, (uint8_t *)g->slots.p, msize, (u32 *)g->tok.p);
+    OUT_CK(hipEventRecord(g->bev[1], g->st), -3);
+    hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, g->st, msize, nb);
+    OUT_CK(hipMemcpyAsync(g->h_bz, msize + nb, 16, hipMemcpyDeviceToHost, g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    OUT_CK(hipGetLastError(), -3);
+    const u64 ctotal = g->h_bz[0];
+    if (ctotal > (u64)nb * lnr_def::MEMBER_CAP) { snprintf(err, err_cap, "BGZF members of %llu bytes for %u blocks", (unsigned long long)ctotal, nb); return -3; }
+    if ((s = dev_need(g->packed, ctotal + 8, err, err_cap)) || (s = host_need(g, ctotal, err, err_cap))) return s;
+    OUT_CK(hipEventRecord(g->bev[2], g->st), -3);
+    hipLaunchKernelGGL(k_bgzf_pack, dim3(nb), dim3(256), 0, g->st, (const uint8_t *)g->slots.p, (const u64 *)msize, (uint8_t *)g->packed.p);
+    OUT_CK(hipEventRecord(g->bev[3], g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    OUT_CK(hipGetLastError(), -3);
+    const double t0 = wall_ms();
+    OUT_CK(hipMemcpyAsync(g->h_text, g->packed.p, ctotal, hipMemcpyDeviceToHost, g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    g->ms[4] = wall_ms() - t0;
+    float f = 0;
+    OUT_CK(hipEventElapsedTime(&f, g->bev[0], g->bev[1]), -3); g->bz.deflate_ms = f;
+    OUT_CK(hipEventElapsedTime(&f, g->bev[2], g->bev[3]), -3); g->bz.pack_ms = f;
+    g->bz.blocks = nb; g->bz.stored_blocks = g->h_bz[1]; g->bz.compressed_bytes = ctotal;
+    *data = g->h_text; *size = ctotal;
+    return 0;
 }
 
 }  // namespace
@@ -311,6 +449,11 @@ int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, con
     auto step = [&]() -> int {
         OUT_CK(hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking), -3);
         for (hipEvent_t &e : g->ev) OUT_CK(hipEventCreate(&e), -3);
+        for (hipEvent_t &e : g->bev) OUT_CK(hipEventCreate(&e), -3);
+        int cus = 0;
+        OUT_CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device), -3);
+        g->cus = cus > 0 ? (u32)cus : 1;
+        OUT_CK(hipHostMalloc((void **)&g->h_bz, 2 * sizeof(u64), hipHostMallocDefault), -4);
         OUT_CK(hipHostMalloc((void **)&g->h_total, sizeof(u64), hipHostMallocDefault), -4);
         if ((s = dev_need(g->gblob, gblob_bytes + 1, err, err_cap)) || (s = dev_need(g->goff, 8ULL * nseq + 8, err, err_cap)) || (s = dev_need(g->glen, 8ULL * nseq + 8, err, err_cap))) return s;
         if (nseq) {
@@ -352,6 +495,7 @@ int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64
 int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **text, uint64_t *size, char *err, size_t err_cap) {
     static const char empty[1] = "";
     for (double &m : g->ms) m = 0;
+    g->bz = lnr_outgpu_bgzf_stats{};
     const u32 n = b->n_reads;
     if (n == 0) { *text = empty; *size = 0; return 0; }
     DeviceGuard dg;
@@ -404,29 +548,45 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     OUT_CK(hipGetLastError(), -3);
     const u64 total = *g->h_total;
     if ((s = dev_need(g->text, total + 8, err, err_cap))) return s;
-    if (total + 8 > g->h_cap) {
-        if (g->h_text) { (void)hipHostFree(g->h_text); g->h_text = nullptr; g->h_cap = 0; }
-        u64 want = total + total / 4 + 4096;
-        OUT_CK(hipHostMalloc((void **)&g->h_text, want, hipHostMallocDefault), -4);
-        g->h_cap = want;
-    }
+    if (!g->bgzf && (s = host_need(g, total, err, err_cap))) return s;
     OUT_CK(hipEventRecord(g->ev[3], g->st), -3);
     if (seq) hipLaunchKernelGGL(k_out_emit_seq, dim3(n), dim3(64), 0, g->st, A, Q, (const u64 *)sizes, (char *)g->text.p);
     else hipLaunchKernelGGL(k_out_emit, dim3(n), dim3(64), 0, g->st, A, (const u64 *)sizes, (char *)g->text.p);
     OUT_CK(hipEventRecord(g->ev[4], g->st), -3);
     OUT_CK(hipStreamSynchronize(g->st), -3);
     OUT_CK(hipGetLastError(), -3);
-    t0 = wall_ms();
-    if (total) OUT_CK(hipMemcpyAsync(g->h_text, g->text.p, total, hipMemcpyDeviceToHost, g->st), -3);
-    OUT_CK(hipStreamSynchronize(g->st), -3);
-    g->ms[4] = wall_ms() - t0;
     float f = 0;
     OUT_CK(hipEventElapsedTime(&f, g->ev[0], g->ev[1]), -3); g->ms[1] = f;
     OUT_CK(hipEventElapsedTime(&f, g->ev[1], g->ev[2]), -3); g->ms[2] = f;
     OUT_CK(hipEventElapsedTime(&f, g->ev[3], g->ev[4]), -3); g->ms[3] = f;
+    if (g->bgzf) return bgzf_run(g, (const uint8_t *)g->text.p, total, text, size, err, err_cap);      // the text stays on the device
+    t0 = wall_ms();
+    if (total) OUT_CK(hipMemcpyAsync(g->h_text, g->text.p, total, hipMemcpyDeviceToHost, g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    g->ms[4] = wall_ms() - t0;
     *text = g->h_text; *size = total;
     return 0;
 }
+
+void lnr_outgpu_set_bgzf(lnr_outgpu *g, int on) { g->bgzf = on ? 1 : 0; }
+
+int lnr_outgpu_bgzf_bytes(lnr_outgpu *g, const char *bytes, uint64_t size, const char **data, uint64_t *out_size, char *err, size_t err_cap) {
+    for (double &m : g->ms) m = 0;
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    OUT_CK(hipSetDevice(g->device), -3);
+    int s;
+    if (size) {
+        if ((s = dev_need(g->text, size + 8, err, err_cap))) return s;
+        const double t0 = wall_ms();
+        OUT_CK(hipMemcpyAsync(g->text.p, bytes, size, hipMemcpyHostToDevice, g->st), -3);
+        OUT_CK(hipStreamSynchronize(g->st), -3);
+        g->ms[0] = wall_ms() - t0;
+    }
+    return bgzf_run(g, (const uint8_t *)g->text.p, size, data, out_size, err, err_cap);
+}
+
+void lnr_outgpu_bgzf_stats_get(const lnr_outgpu *g, lnr_outgpu_bgzf_stats *out) { *out = g->bz; }
 
 void lnr_outgpu_times(const lnr_outgpu *g, double *ms5) { for (int i = 0; i < 5; i++) ms5[i] = g->ms[i]; }
 
