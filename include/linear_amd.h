@@ -329,6 +329,35 @@ lnr_status lnr_writer_bgzf_eof(const char **data, uint64_t *size);
 typedef struct { uint64_t blocks, stored_blocks, text_bytes, compressed_bytes; double deflate_ms, pack_ms; } lnr_bgzf_stats;   /* last GPU call */
 lnr_status lnr_writer_bgzf_stats(const lnr_writer *w, lnr_bgzf_stats *out);
 
+/* BAM output (what the reference writes with -ot 4 / 8).  A record is the plain re-encoding of the SAM line the calls above print for the same
+ * cords, little endian: block_size, refID (index of RNAME among the writer's sequences, -1 for '*'), pos = POS - 1, l_read_name, mapq 255,
+ * bin = reg2bin(pos, pos + reference bases of the CIGAR), n_cigar_op, flag, l_seq, next_refID -1, next_pos -1, tlen 0, QNAME and a NUL, one
+ * word count << 4 | op per CIGAR element (MIDNSHP=X = 0..8), SEQ at two bases per byte (high nibble first, =ACMGRSVTWYHKDBN = 0..15; an
+ * odd tail gets a low nibble of 0), l_seq bytes 0xff, and where the line has SA:Z: the bytes 'S' 'A' 'Z', the tag's text and a NUL -- byte
+ * for byte the records of the reference's .bam (tests/golden/cli_bam_<case>.npz).  Fields narrower than their value take its low bits, as
+ * the reference's (SeqAn's) casts do: a QNAME of 255 or more characters and more than 65535 CIGAR elements give records no reader can
+ * walk; both are outside the tested ground.
+ * lnr_writer_bam_header (host only): "BAM\1", l_text, the text of lnr_writer_sam_header (pbsv != 0: the -ot 8 form, whose @RG line reads
+ * "@RG\t ID:" with a blank before ID), then the reference list: n_ref = the writer's nseq sequences, each l_name (with the NUL), the name,
+ * a NUL and l_ref.  THE ONE DELIBERATE DEVIATION FROM THE REFERENCE: it writes n_ref = 0 (an empty context, f_io.cpp:509-523) while its
+ * records carry refID >= 0, a file htslib refuses; with the list the same records open in samtools, pbsv and IGV.
+ * lnr_writer_format_bam (host threads; the in-library yardstick of the GPU forms): the records of a batch back to back.  ONE function
+ * for both forms: reads_concat == NULL -- no SEQ (l_seq 0) and read_len_or_off is read_len[n]; otherwise SEQ as lnr_writer_format_seq prints
+ * it, lnr_writer_set_genome is required (else LNR_ERR_ARG) and read_len_or_off is read_off[n + 1].  lnr_writer_format_bam_gpu takes the
+ * same arguments (host memory) and formats on the GPU (k_out_measure_bam / k_out_scan / k_out_emit_bam); lnr_writer_format_bam_dev takes
+ * what lnr_filter_batch_dev hands out, the batch's d_off and its device bases d_reads_concat or NULL.  With lnr_writer_set_bgzf off
+ * the two return the raw record bytes, with it on BGZF members of them, compressed where they lie.  A .bam file = the members of
+ * lnr_writer_bgzf_bytes_gpu(the header), of every batch, and lnr_writer_bgzf_eof.  No record: zero bytes.  Before lnr_writer_gpu_open:
+ * LNR_ERR_ARG; no device: LNR_ERR_NO_DEVICE (from lnr_writer_gpu_open).  Lifetime of the bytes, errors, current device,
+ * lnr_writer_gpu_times and lnr_writer_bgzf_stats as for the SAM calls. */
+lnr_status lnr_writer_bam_header(lnr_writer *w, const char *command_line, int pbsv, const char **data, uint64_t *size);
+lnr_status lnr_writer_format_bam(lnr_writer *w, const lnr_cords *cords, const uint8_t *reads_concat_or_null, const uint64_t *read_len_or_off,
+                                 const char *read_ids, const uint64_t *id_off, uint32_t threads, const char **data, uint64_t *size);
+lnr_status lnr_writer_format_bam_gpu(lnr_writer *w, const lnr_cords *cords, const uint8_t *reads_concat_or_null, const uint64_t *read_len_or_off,
+                                     const char *read_ids, const uint64_t *id_off, const char **data, uint64_t *size);
+lnr_status lnr_writer_format_bam_dev(lnr_writer *w, const lnr_cords_dev *cords, const uint8_t *d_reads_concat_or_null, const uint64_t *d_read_off,
+                                     const char *read_ids, const uint64_t *id_off, const char **data, uint64_t *size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,7 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_writer_gpu_open", "lnr_writer_format_gpu", "lnr_writer_format_dev", "lnr_writer_gpu_times", "lnr_writer_error",
            "lnr_writer_set_genome", "lnr_writer_format_seq", "lnr_writer_format_seq_gpu", "lnr_writer_format_seq_dev",
            "lnr_writer_set_bgzf", "lnr_writer_bgzf_bytes_gpu", "lnr_writer_bgzf_eof", "lnr_writer_bgzf_stats",
+           "lnr_writer_bam_header", "lnr_writer_format_bam", "lnr_writer_format_bam_gpu", "lnr_writer_format_bam_dev",
            "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats"]
 
 
@@ -140,6 +141,10 @@ def load_library() -> C.CDLL:
     lib.lnr_writer_bgzf_bytes_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_bgzf_eof.argtypes = [C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_bgzf_stats.argtypes = [C.c_void_p, C.POINTER(LnrBgzfStats)]
+    lib.lnr_writer_bam_header.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_bam.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.c_uint32, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_bam_gpu.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_bam_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev), C.c_void_p, C.c_void_p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
     return lib
 
 
@@ -559,6 +564,44 @@ class Writer:
         s = LnrBgzfStats()
         self._check(self.lib.lnr_writer_bgzf_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in LnrBgzfStats._fields_}
+
+    # ---- BAM: the records of the SAM lines in binary (the reference's -ot 4 / 8)
+    def bam_header(self, command_line: str, pbsv: bool = False) -> bytes:
+        """"BAM\\1", l_text, the text of sam_header (pbsv: the -ot 8 form of the @RG line), the reference list of the writer's sequences."""
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_bam_header(self.h, command_line.encode(), 1 if pbsv else 0, C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value)
+
+    def _bam_args(self, cord_off, cords_str, cords_end, read_len, reads, read_off):
+        """no SEQ: read_len[n], reads None; SEQ: reads + read_off[n + 1] (set_genome needed)"""
+        if reads is None:
+            c, _r, arr, keep = self._seq_args(cord_off, cords_str, cords_end, np.zeros(1, np.uint8), read_len)
+            return c, None, arr, keep
+        c, r, arr, keep = self._seq_args(cord_off, cords_str, cords_end, reads, read_off)
+        return c, _p(r, _u8p), arr, (keep, r)
+
+    def format_bam(self, cord_off, cords_str, cords_end, read_len, read_ids: list[str], reads=None, read_off=None, threads: int = 4) -> bytes:
+        """The BAM records of the batch on host threads.  reads / read_off given: with SEQ (as format_seq), read_len is ignored."""
+        c, rp, arr, _keep = self._bam_args(cord_off, cords_str, cords_end, read_len, reads, read_off)
+        blob, ido = self._ids(read_ids)
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_bam(self.h, C.byref(c), rp, _p(arr, _u64p), blob, _p(ido, _u64p), threads, C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value)
+
+    def format_bam_gpu(self, cord_off, cords_str, cords_end, read_len, read_ids: list[str], reads=None, read_off=None, copy: bool = True):
+        """The bytes of format_bam(), encoded on the GPU; with set_bgzf(True) BGZF members of them."""
+        c, rp, arr, _keep = self._bam_args(cord_off, cords_str, cords_end, read_len, reads, read_off)
+        blob, ido = self._ids(read_ids)
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_bam_gpu(self.h, C.byref(c), rp, _p(arr, _u64p), blob, _p(ido, _u64p), C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value) if copy else (out.value, size.value)
+
+    def format_bam_dev(self, cords_dev: "LnrCordsDev", d_off_ptr: int, read_ids: list[str], d_reads_ptr: int | None = None, copy: bool = True):
+        """Device form: the result of Filter.filter_batch_dev, the batch's device read offsets (n + 1) and, for SEQ, its device bases."""
+        blob, ido = self._ids(read_ids)
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_bam_dev(self.h, C.byref(cords_dev), d_reads_ptr, d_off_ptr, blob, _p(ido, _u64p), C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value) if copy else (out.value, size.value)
 
     def sam_header(self, command_line: str) -> bytes:
         text, size = C.c_void_p(), C.c_uint64()

@@ -21,9 +21,14 @@
 //   BGZF output    --bgzf (extension, needs --gpu-writer): the text is compressed on the GPU it was formatted on (lnr_writer_set_bgzf) and the
 //                  outputs are PREFIX.sam.gz / PREFIX.apf.gz: the SAM header through lnr_writer_bgzf_bytes_gpu, every block's members as
 //                  returned, the EOF marker at close.  bgzip -d, zcat and samtools read them.
+//   BAM output     -ot 4 (PREFIX.bam) / -ot 8 (PREFIX_pbsv.bam), in any combination with 1 and 2; needs --gpu-writer: the records are encoded
+//                  on the GPU (lnr_writer_format_bam_gpu / _dev) and compressed where they lie, whether --bgzf is given or not.  Each file: the
+//                  members of the header (lnr_writer_bam_header through lnr_writer_bgzf_bytes_gpu; -ot 8: the "@RG\t ID:" form), of every
+//                  block, and the EOF marker.  --sam-seq puts SEQ into the records as it does into the .sam.  The header lists the genome
+//                  (the reference writes n_ref 0: include/linear_amd.h).
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
-// Not built (exit 1 with a message, never a silently different result): BAM output (-ot 4 / 8), -ss 1 (use --sam-seq), -c 0, -f 1, -r 1, -p 0, -b 0
+// Not built (exit 1 with a message, never a silently different result): BAM output (-ot 4 / 8) without --gpu-writer, -ss 1 (use --sam-seq), -c 0, -f 1, -r 1, -p 0, -b 0
 // (the reference's -b 0 path writes a header-only SAM: SURVEY App. C.7).
 #include "../../include/linear_amd.h"
 
@@ -47,6 +52,7 @@ lnr_status lnr_filter_batch_dev(lnr_ctx *, const uint8_t *, const uint64_t *, ui
 lnr_status lnr_cords_to_host(lnr_ctx *, lnr_cords *) __attribute__((weak));
 lnr_status lnr_writer_format_dev(lnr_writer *, const lnr_cords_dev *, const uint64_t *, const char *, const uint64_t *, int, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_writer_format_seq_dev(lnr_writer *, const lnr_cords_dev *, const uint8_t *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
+lnr_status lnr_writer_format_bam_dev(lnr_writer *, const lnr_cords_dev *, const uint8_t *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_reader_gpu_open(lnr_reader *, int32_t, uint32_t) __attribute__((weak));
 lnr_status lnr_reader_next_dev(lnr_reader *, uint64_t, uint32_t, const uint8_t **, const uint64_t **, const uint64_t **, uint32_t *) __attribute__((weak));
 }
@@ -69,13 +75,13 @@ static void usage() {
     fprintf(stderr,
             "linear filter - options and arguments.\n\nSYNOPSIS\n    linear filter [OPTIONS] read.fa/fastq(.gz) genome.fa(.gz)\n    linear filter [OPTIONS] reads_1 reads_2 ... x genome_1 genome_2 ...\n\n"
             "Basic options\n    -o,  --output STR          prefix of the output (default: the read file's name up to its first '.')\n"
-            "    -ot, --output_type INT     1 .apf, 2 .sam {DEFAULT}, 3 both (4 / 8: BAM, not built here)\n    -t,  --thread INT          threads: the index layout of the reference's -t and the host threads of the writer {16}\n"
+            "    -ot, --output_type INT     1 .apf, 2 .sam {DEFAULT}, 4 .bam, 8 _pbsv.bam, or a sum of them (BAM needs --gpu-writer)\n    -t,  --thread INT          threads: the index layout of the reference's -t and the host threads of the writer {16}\n"
             "    -g,  --gap_len INT         minimal length of gaps to re-map; -g 0 off; bare -g or 1 = 50 {DEFAULT}\n    -rg, --read_group STR      @RG ID\n    -sn, --sample_name STR     @RG SM\n"
             "    -ss, --sequence_sam INT    0 {DEFAULT} (1 not built here: --sam-seq prints what the reference prints with -ss 1)\nMore options\n    -dup, --duplication INT    0 {DEFAULT} | 1\n    -b,  --bal_flag INT        1 {DEFAULT}\n"
             "    -p,  --preset INT          1 {DEFAULT} | 2   (0 not built here)\n    -i,  --index_type INT      1 {DEFAULT} | 2\n    -c,  --apx_c_flag INT      1 {DEFAULT}\n    -f,  --feature_type INT    2 {DEFAULT}\n"
             "    -r,  --reform_ccs_cigar_flag INT   0 {DEFAULT}\nMI355X front-end\n    --gpus INT                 GPUs to use {1}\n    --devices LIST             their HIP ordinals, e.g. 0,1,2,3\n"
             "    --block-reads INT          reads per block {65536}\n    --index-mode bcast|build   several GPUs: RCCL broadcast of the index {DEFAULT} or every GPU builds its own\n"
-            "    --gpu-writer               format .sam / .apf text on the first GPU in use instead of the writer's host threads {off}\n"
+            "    --gpu-writer               format .sam / .apf text and encode .bam records on the first GPU in use instead of the writer's host threads {off}\n"
             "    --gpu-reader               parse the read files on the first GPU in use and keep the reads there: reader -> filter -> writer on device buffers {off}\n"
             "                               (one GPU; with --sam-seq it needs --gpu-writer: the read bases are not on the host)\n"
             "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n"
@@ -174,13 +180,14 @@ struct Shared {
     void fail(const std::string &e) { std::lock_guard<std::mutex> l(m); if (!failed) { err = e; failed = 1; } cv.notify_all(); }
 };
 
+struct Headers { std::string sam, bam, pbsv; };      // what opens a .sam, a .bam and a _pbsv.bam (compressed where the file is)
 // the output files of the printer (Mapper::p_printResults mapper.cpp:478-509): a new pair when the prefix changes, or once with -o
 struct Outputs {
-    FILE *fsam = nullptr, *fapf = nullptr;
+    FILE *fsam = nullptr, *fapf = nullptr, *fbam = nullptr, *fpbsv = nullptr;
     std::string cur_prefix; bool any_open = false; int cur_file = -1;
-    bool bgzf = false;                       // --bgzf: .gz names, `header` comes compressed, the EOF marker ends every file
-    // makes the files of read file `file` current; header = the SAM header text.  false: the files cannot be written (err says which)
-    bool turn_to(const Options &o, int file, const std::string &header, std::string &err) {
+    bool bgzf = false;                       // --bgzf: .gz names, the SAM header comes compressed, the EOF marker ends every file
+    // makes the files of read file `file` current; h = the headers as they go into the files.  false: the files cannot be written (err says which)
+    bool turn_to(const Options &o, int file, const Headers &h, std::string &err) {
         if (file == cur_file) return true;
         cur_file = file;
         std::string prefix = o.oPath.empty() ? output_prefix_of(o.r_paths[(size_t)file]) : o.oPath;
@@ -189,8 +196,15 @@ struct Outputs {
         bgzf = o.bgzf != 0;
         fsam = (o.f_output_type & 2) ? fopen((prefix + (bgzf ? ".sam.gz" : ".sam")).c_str(), "wb") : nullptr;
         fapf = (o.f_output_type & 1) ? fopen((prefix + (bgzf ? ".apf.gz" : ".apf")).c_str(), "wb") : nullptr;
-        if (((o.f_output_type & 2) && !fsam) || ((o.f_output_type & 1) && !fapf)) { err = "can't write output files with prefix " + prefix; return false; }
-        if (fsam) fwrite(header.data(), 1, header.size(), fsam);
+        fbam = (o.f_output_type & 4) ? fopen((prefix + ".bam").c_str(), "wb") : nullptr;
+        fpbsv = (o.f_output_type & 8) ? fopen((prefix + "_pbsv.bam").c_str(), "wb") : nullptr;
+        if (((o.f_output_type & 2) && !fsam) || ((o.f_output_type & 1) && !fapf) || ((o.f_output_type & 4) && !fbam) || ((o.f_output_type & 8) && !fpbsv)) {
+            err = "can't write output files with prefix " + prefix;
+            return false;
+        }
+        if (fsam) fwrite(h.sam.data(), 1, h.sam.size(), fsam);
+        if (fbam) fwrite(h.bam.data(), 1, h.bam.size(), fbam);
+        if (fpbsv) fwrite(h.pbsv.data(), 1, h.pbsv.size(), fpbsv);
         cur_prefix = prefix; any_open = true;
         return true;
     }
@@ -199,7 +213,10 @@ struct Outputs {
         if (bgzf && (fsam || fapf)) lnr_writer_bgzf_eof(&eof, &n);
         if (fsam) { if (n) fwrite(eof, 1, n, fsam); fclose(fsam); }
         if (fapf) { if (n) fwrite(eof, 1, n, fapf); fclose(fapf); }
-        fsam = fapf = nullptr;
+        if (fbam || fpbsv) lnr_writer_bgzf_eof(&eof, &n);                                // a .bam is BGZF whatever --bgzf says
+        if (fbam) { fwrite(eof, 1, n, fbam); fclose(fbam); }
+        if (fpbsv) { fwrite(eof, 1, n, fpbsv); fclose(fpbsv); }
+        fsam = fapf = fbam = fpbsv = nullptr;
     }
 };
 
@@ -213,11 +230,15 @@ int main(int argc, char **argv) {
     for (const std::string &p : o.g_paths) if (access(p.c_str(), F_OK) == -1) { fprintf(stderr, "\033[1;31mE[06]:\033[0mCan't open file %s\n", p.c_str()); return 1; }
     // what the MI355X path does not build: say so instead of writing something else
     const char *nb = nullptr;
-    if (o.f_output_type & 12) nb = "-ot 4 / 8 (BAM output)"; else if (!(o.f_output_type & 3)) nb = "-ot without 1 (.apf) or 2 (.sam)";
+    if (!(o.f_output_type & 15)) nb = "-ot without 1 (.apf), 2 (.sam), 4 (.bam) or 8 (_pbsv.bam)";
     else if (o.sequence_sam) nb = "-ss 1 (read sequences in the SAM)"; else if (!o.apx_chain_flag) nb = "-c 0"; else if (o.feature_t != 2) nb = "-f other than 2";
     else if (o.reform_ccs) nb = "-r 1"; else if (o.sensitivity != 1 && o.sensitivity != 2) nb = "-p other than 1 or 2"; else if (!o.bal_flag) nb = "-b 0 (the reference's -b 0 path writes a header-only SAM)";
     else if (o.index_t != 1 && o.index_t != 2) nb = "-i other than 1 or 2";
     if (nb) { fprintf(stderr, "\033[1;31mE[m02G]:\033[0m %s is not built in the MI355X filter path\n", nb); return 1; }
+    if ((o.f_output_type & 12) && !o.gpu_writer) {
+        fprintf(stderr, "\033[1;31mE:\033[0m -ot 4 / 8 (BAM output) is encoded and compressed on the GPU: it needs --gpu-writer (BAM on the writer's host threads is not built)\n");
+        return 1;
+    }
     if (o.bgzf && !o.gpu_writer) { fprintf(stderr, "\033[1;31mE:\033[0m --bgzf compresses the text on the GPU that formats it: it needs --gpu-writer\n"); return 1; }
     if (o.thread < 1) o.thread = 1;
     if (o.gpus < 1) o.gpus = 1;
@@ -295,16 +316,32 @@ int main(int argc, char **argv) {
         for (auto *c : ctx) lnr_destroy(c);
         return 1;
     }
-    // --bgzf: the SAM header goes through the writer's device as well; false with a message when that fails
-    auto header_of = [&](std::string &header) {
+    // --bgzf: the SAM header goes through the writer's device as well, the BAM headers always; false with a message when that fails
+    const bool want_bam = (o.f_output_type & 12) != 0;
+    auto header_of = [&](Headers &h) {
         const char *t; uint64_t z;
         lnr_writer_sam_header(wr, "", &t, &z);
-        header.assign(t, z);
-        if (!o.bgzf) return true;
-        const std::string plain = header;
-        if (lnr_writer_bgzf_bytes_gpu(wr, plain.data(), plain.size(), &t, &z) != LNR_OK) return false;
-        header.assign(t, z);
+        h.sam.assign(t, z);
+        if (o.bgzf) {
+            const std::string plain = h.sam;
+            if (lnr_writer_bgzf_bytes_gpu(wr, plain.data(), plain.size(), &t, &z) != LNR_OK) return false;
+            h.sam.assign(t, z);
+        }
+        for (int pbsv = 0; pbsv < 2; pbsv++) {
+            if (!(o.f_output_type & (pbsv ? 8u : 4u))) continue;
+            lnr_writer_bam_header(wr, "", pbsv, &t, &z);
+            const std::string plain(t, z);
+            if (lnr_writer_bgzf_bytes_gpu(wr, plain.data(), plain.size(), &t, &z) != LNR_OK) return false;
+            (pbsv ? h.pbsv : h.bam).assign(t, z);
+        }
         return true;
+    };
+    // the BAM records of a block come compressed whatever --bgzf says: the switch is on for that call alone
+    auto bam_call = [&](auto &&call) {
+        lnr_status s = lnr_writer_set_bgzf(wr, 1);                // (a failure here must not let raw record bytes into the file)
+        if (s == LNR_OK) s = call();
+        const lnr_status back = lnr_writer_set_bgzf(wr, o.bgzf ? 1 : 0);
+        return s != LNR_OK ? s : back;
     };
     if (o.bgzf && lnr_writer_set_bgzf(wr, 1) != LNR_OK) {
         fprintf(stderr, "\033[1;31mE:\033[0m --bgzf: %s\n", lnr_writer_error(wr));
@@ -314,7 +351,7 @@ int main(int argc, char **argv) {
     }
     if (o.gpu_reader) {                                                                          // before any output file is opened, too
         std::string why;
-        if (!lnr_filter_batch_dev || !lnr_cords_to_host || !lnr_writer_format_dev || !lnr_writer_format_seq_dev || !lnr_reader_gpu_open || !lnr_reader_next_dev)
+        if (!lnr_filter_batch_dev || !lnr_cords_to_host || !lnr_writer_format_dev || !lnr_writer_format_seq_dev || !lnr_writer_format_bam_dev || !lnr_reader_gpu_open || !lnr_reader_next_dev)
             why = "no usable device: this library has no device form of the filter";
         else if (G != 1) why = "the device chain runs on one GPU (--gpus 1)";
         else if (o.sam_seq && !o.gpu_writer) why = "with --sam-seq the reads stay on the device: add --gpu-writer";
@@ -334,15 +371,15 @@ int main(int argc, char **argv) {
             const uint8_t *d_reads = nullptr; const uint64_t *d_off = nullptr;
             std::vector<uint64_t> off, len, id_off, coff, cs, ce;
             std::vector<char> ids;
-            std::string sam, apf;
+            std::string sam, apf, bam;
             uint32_t n = 0; int file = 0;
         };
         Queue<DBlock *> freeq, readyq, doneq;
         std::mutex em; std::string err; std::atomic<int> failed{0};
         auto fail = [&](const std::string &e) { { std::lock_guard<std::mutex> l(em); if (!failed) { err = e; failed = 1; } } freeq.close(); readyq.close(); doneq.close(); };
-        std::string sam_header;                                  // (taken here: the calculator thread is the writer's only user under --gpu-writer)
+        Headers sam_header;                                      // (taken here: the calculator thread is the writer's only user under --gpu-writer)
         if (!header_of(sam_header)) {
-            fprintf(stderr, "\033[1;31mE:\033[0m --bgzf: %s\n", lnr_writer_error(wr));
+            fprintf(stderr, "\033[1;31mE:\033[0m %s: %s\n", want_bam ? "BAM / BGZF header" : "--bgzf", lnr_writer_error(wr));
             lnr_writer_destroy(wr);
             for (auto *c : ctx) lnr_destroy(c);
             return 1;
@@ -395,7 +432,7 @@ int main(int argc, char **argv) {
                 if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
                 if (o.gpu_writer) {                                  // the text of the block, from the device buffers
                     const char *text; uint64_t size;
-                    b->sam.clear(); b->apf.clear();
+                    b->sam.clear(); b->apf.clear(); b->bam.clear();
                     if (o.f_output_type & 2) {
                         s = o.sam_seq ? lnr_writer_format_seq_dev(wr, &dev, b->d_reads, b->d_off, b->ids.data(), b->id_off.data(), &text, &size)
                                       : lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 1, &text, &size);
@@ -406,6 +443,11 @@ int main(int argc, char **argv) {
                         s = lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 2, &text, &size);
                         if (s != LNR_OK) { fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; }
                         b->apf.assign(text, size);
+                    }
+                    if (want_bam) {
+                        s = bam_call([&] { return lnr_writer_format_bam_dev(wr, &dev, o.sam_seq ? b->d_reads : nullptr, b->d_off, b->ids.data(), b->id_off.data(), &text, &size); });
+                        if (s != LNR_OK) { fail(std::string("writer (.bam): ") + lnr_writer_error(wr)); break; }
+                        b->bam.assign(text, size);
                     }
                 } else {
                     lnr_cords c{};
@@ -433,6 +475,8 @@ int main(int argc, char **argv) {
                 if (o.gpu_writer) {
                     if (fsam) ok = fwrite(b->sam.data(), 1, b->sam.size(), fsam) == b->sam.size();
                     if (ok && fapf) ok = fwrite(b->apf.data(), 1, b->apf.size(), fapf) == b->apf.size();
+                    if (ok && out.fbam) ok = fwrite(b->bam.data(), 1, b->bam.size(), out.fbam) == b->bam.size();
+                    if (ok && out.fpbsv) ok = fwrite(b->bam.data(), 1, b->bam.size(), out.fpbsv) == b->bam.size();
                     if (!ok) { fail("write error"); break; }
                 } else {
                     lnr_cords c{b->n, (uint64_t)b->cs.size(), b->coff.data(), b->cs.data(), b->ce.data()};
@@ -556,10 +600,10 @@ int main(int argc, char **argv) {
         Outputs out;
         FILE *&fsam = out.fsam, *&fapf = out.fapf;
         // `@PG ... CL:` stays empty: the reference's Options constructor fills cmd_line only `if (length(argv) < 1)` (base.cpp:64-72), i.e. never
-        std::string sam_header;
+        Headers sam_header;
         uint64_t want = 0;
         const char *text; uint64_t size;
-        if (!header_of(sam_header)) sh.fail(std::string("--bgzf: ") + lnr_writer_error(wr));
+        if (!header_of(sam_header)) sh.fail(std::string(want_bam ? "BAM / BGZF header: " : "--bgzf: ") + lnr_writer_error(wr));
         for (;;) {
             Block *b = nullptr;
             {
@@ -581,6 +625,12 @@ int main(int argc, char **argv) {
             };
             if (fsam) { if (format(1) != LNR_OK) { sh.fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fsam) != size) { sh.fail("write error (.sam)"); break; } }
             if (fapf) { if (format(2) != LNR_OK) { sh.fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fapf) != size) { sh.fail("write error (.apf)"); break; } }
+            if (out.fbam || out.fpbsv) {                                 // one encoding serves both files: they differ in their headers alone
+                lnr_status s = bam_call([&] { return o.sam_seq ? lnr_writer_format_bam_gpu(wr, &b->cords, b->bases, b->off.data(), b->ids.data(), b->id_off.data(), &text, &size)
+                                                               : lnr_writer_format_bam_gpu(wr, &b->cords, nullptr, b->len.data(), b->ids.data(), b->id_off.data(), &text, &size); });
+                if (s != LNR_OK) { sh.fail(std::string("writer (.bam): ") + lnr_writer_error(wr)); break; }
+                if ((out.fbam && fwrite(text, 1, size, out.fbam) != size) || (out.fpbsv && fwrite(text, 1, size, out.fpbsv) != size)) { sh.fail("write error (.bam)"); break; }
+            }
             us_writer += (uint64_t)((now() - tw0) * 1e6);
             total_reads += b->n;
             { std::lock_guard<std::mutex> l(sh.m); sh.written_upto[(size_t)b->worker]++; }

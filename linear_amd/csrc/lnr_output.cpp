@@ -10,9 +10,12 @@
 //   createSAZTagCigar & co.  src/align_util.cpp:452-744   SA:Z = the other records of the read as rname,pos,strand,xSyMz[ID]0S,mapq,nm;
 //   writeSam                 src/f_io.cpp:313-412    the text line; MAPQ is SeqAn's default 255, RNEXT '*', PNEXT 0, TLEN 0, SEQ / QUAL '*'
 //   print_cords_apf          src/f_io.cpp:100-207    '@' header per cord block + one '|' line per cord
+//   BAM (-ot 4 / 8)          src/f_io.cpp:509-523 + SeqAn write_bam.h:99-203   the records of the SAM lines in binary: here the shared
+//                                                     per-record logic of lnr_output_hd.h (bam_read) through a memory sink
 // Parity: byte-identical to the reference's own functions on the goldens (tests/test_output_cpu.py; APF blank lines follow the
 // reference's rule for a block = one call).
 #include "../../include/linear_amd.h"
+#include "lnr_output_hd.h"
 #include "lnr_output_hook.h"
 
 #include <cmath>
@@ -377,6 +380,77 @@ lnr_status lnr_writer_format_seq_dev(lnr_writer *wr, const lnr_cords_dev *cords,
     if (!wr || !cords || !read_ids || !id_off || !text || !size || (cords->n_reads && (!d_read_off || !d_reads_concat))) return LNR_ERR_ARG;
     lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, 1, 0, 0, 0, d_reads_concat};
     return format_seq_on_gpu(wr, b, text, size);
+}
+
+// ---- BAM: the header on the host; the records by the shared logic of lnr_output_hd.h, here through a memory sink on host threads (the
+// yardstick of the GPU forms below), there in k_out_measure_bam / k_out_emit_bam
+static void put_le32(std::string &o, uint32_t v) { for (int b = 0; b < 4; b++) o += (char)(v >> (8 * b)); }
+lnr_status lnr_writer_bam_header(lnr_writer *wr, const char *command_line, int pbsv, const char **data, uint64_t *size) {
+    if (!wr || !data || !size) return LNR_ERR_ARG;
+    const char *t; uint64_t z;
+    lnr_writer_sam_header(wr, command_line, &t, &z);
+    std::string text(t, z);
+    if (pbsv) {                                        // -ot 8: "@RG\t ID:" (mapper.cpp:308-312)
+        size_t p = text.find("@RG\tID:");
+        if (p != std::string::npos) text.insert(p + 4, " ");
+    }
+    std::string &o = wr->w.text;
+    o.assign("BAM\1", 4);
+    put_le32(o, (uint32_t)text.size());
+    o += text;
+    put_le32(o, (uint32_t)wr->w.gid.size());           // (the reference writes n_ref 0 here: see include/linear_amd.h)
+    for (size_t i = 0; i < wr->w.gid.size(); i++) {
+        put_le32(o, (uint32_t)wr->w.gid[i].size() + 1);
+        o += wr->w.gid[i]; o += '\0';
+        put_le32(o, (uint32_t)wr->w.glen[i]);
+    }
+    *data = o.data(); *size = o.size();
+    return LNR_OK;
+}
+namespace {
+struct StrSink { std::string &s; void put(char c) { s.push_back(c); } };
+}
+lnr_status lnr_writer_format_bam(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_len, const char *read_ids,
+                                 const uint64_t *id_off, uint32_t threads, const char **data, uint64_t *size) {
+    if (!wr || !cords || !read_len || !read_ids || !id_off || !data || !size || (reads_concat && !seq_ready(wr))) return LNR_ERR_ARG;
+    const Writer &w = wr->w;
+    const uint32_t n = cords->n_reads, nseq = (uint32_t)w.gid.size();
+    std::string blob; std::vector<u64> goff;
+    for (const std::string &g : w.gid) { goff.push_back(blob.size()); blob += g; blob += '\0'; }
+    const lnr_out::Params P{blob.data(), goff.data(), w.glen.data(), nseq, w.thd_large_X, w.thd_DI, w.thd_X};
+    if (threads < 1) threads = 1;
+    if (threads > n) threads = n ? n : 1;
+    std::vector<std::string> part(threads);
+    auto work = [&](uint32_t t) {
+        uint32_t lo = (uint32_t)((u64)n * t / threads), hi = (uint32_t)((u64)n * (t + 1) / threads);
+        StrSink o{part[t]};
+        for (uint32_t k = lo; k < hi; k++) {
+            const u64 a = cords->cord_off[k], nc = cords->cord_off[k + 1] - a;
+            const u64 L = reads_concat ? read_len[k + 1] - read_len[k] : read_len[k];
+            const lnr_out::SeqSrc q{nullptr, nullptr, w.glen.data(), nseq, reads_concat ? reads_concat + read_len[k] : nullptr, L, w.genome};      // the borrowed sequences, each where it lies
+            lnr_out::bam_read(o, P, reads_concat ? &q : nullptr, cords->cords_str + a, cords->cords_end + a, nc, L, read_ids + id_off[k]);
+        }
+    };
+    std::vector<std::thread> th;
+    for (uint32_t t = 1; t < threads; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &t : th) t.join();
+    wr->w.text.clear();
+    for (auto &p : part) wr->w.text += p;
+    *data = wr->w.text.data(); *size = wr->w.text.size();
+    return LNR_OK;
+}
+lnr_status lnr_writer_format_bam_gpu(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_len, const char *read_ids,
+                                     const uint64_t *id_off, const char **data, uint64_t *size) {
+    if (!wr || !cords || !read_len || !read_ids || !id_off || !data || !size) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{0, cords->n_reads, cords->n_cords, cords->cord_off, cords->cords_str, cords->cords_end, read_len, read_ids, id_off, 3, 0, 0, 0, reads_concat};
+    return reads_concat ? format_seq_on_gpu(wr, b, data, size) : format_on_gpu(wr, b, data, size);
+}
+lnr_status lnr_writer_format_bam_dev(lnr_writer *wr, const lnr_cords_dev *cords, const uint8_t *d_reads_concat, const uint64_t *d_read_off, const char *read_ids,
+                                     const uint64_t *id_off, const char **data, uint64_t *size) {
+    if (!wr || !cords || !read_ids || !id_off || !data || !size || (cords->n_reads && !d_read_off)) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, 3, 0, 0, 0, d_reads_concat};
+    return d_reads_concat ? format_seq_on_gpu(wr, b, data, size) : format_on_gpu(wr, b, data, size);
 }
 
 // ---- BGZF output of the GPU side (the work: lnr_output_kernels.hip behind the weak hooks)

@@ -1,4 +1,4 @@
-// lnr_output_hd.h -- the two per-read formatters of lnr_output.cpp (SAM records, APF text) as __host__ __device__ code over raw arrays.
+// lnr_output_hd.h -- the per-read formatters of lnr_output.cpp (SAM records, APF text, BAM records) as __host__ __device__ code over raw arrays.
 //
 // PRODUCT code: the kernels of lnr_output_kernels.hip call these functions on the device; tests/output_shim.cpp compiles the same text
 // with g++ so that every byte is pinned on a machine without a GPU (tests/test_output_hd_cpu.py).  The host writer lnr_writer_format keeps
@@ -198,31 +198,32 @@ template <class S> LNR_HD inline u64 sam_head(S &out, const Params &P, const u64
     put_str(out, "\t*\t0\t0\t");
     return t.seq;
 }
+// the entries of SA:Z: every other record of the read, in record order
+template <class S> LNR_HD inline void sa_entries(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 L, u64 it) {
+    u64 a = 1;
+    for (u64 jr = 0; a < n; jr++) {
+        SazOps z;
+        u64 b = record_ops(z, P, cs, ce, n, a, L);
+        if (jr != it) {
+            // NM cache (createSAZTagCigarOneChimeric align_util.cpp:642-678): a record's NM is summed the first time any line lists it --
+            // line 0 lists all others first, line 1 lists record 0 first; every later listing prints 0
+            bool first_visit = it == 0 || (it == 1 && jr == 0);
+            put_str(out, gname(P, (u64)(int)cid(cs[a]))); out.put(',');
+            put_i(out, (i64)cx(cs[a]) + 1); out.put(',');
+            out.put(cstrand(cs[a]) ? '-' : '+'); out.put(',');
+            put_u(out, z.s0); out.put('S');
+            put_u(out, (unsigned)z.cm); out.put('M');
+            put_u(out, (unsigned)iabs(z.ci)); out.put(z.ci < 0 ? 'I' : 'D');
+            put_str(out, "0S,255,");
+            put_i(out, first_visit ? (int)z.nm : 0); out.put(';');
+        }
+        a = b + 1;
+    }
+}
 // tail: the tab after SEQ, QUAL, SA:Z, end of line
 template <class S> LNR_HD inline void sam_tail(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 L, u64 it, u64 n_rec) {
     put_str(out, "\t*");
-    if (n_rec > 1) {                                   // SA:Z: every other record of the read, in record order
-        put_str(out, "\tSA:Z:");
-        u64 a = 1;
-        for (u64 jr = 0; a < n; jr++) {
-            SazOps z;
-            u64 b = record_ops(z, P, cs, ce, n, a, L);
-            if (jr != it) {
-                // NM cache (createSAZTagCigarOneChimeric align_util.cpp:642-678): a record's NM is summed the first time any line lists it --
-                // line 0 lists all others first, line 1 lists record 0 first; every later listing prints 0
-                bool first_visit = it == 0 || (it == 1 && jr == 0);
-                put_str(out, gname(P, (u64)(int)cid(cs[a]))); out.put(',');
-                put_i(out, (i64)cx(cs[a]) + 1); out.put(',');
-                out.put(cstrand(cs[a]) ? '-' : '+'); out.put(',');
-                put_u(out, z.s0); out.put('S');
-                put_u(out, (unsigned)z.cm); out.put('M');
-                put_u(out, (unsigned)iabs(z.ci)); out.put(z.ci < 0 ? 'I' : 'D');
-                put_str(out, "0S,255,");
-                put_i(out, first_visit ? (int)z.nm : 0); out.put(';');
-            }
-            a = b + 1;
-        }
-    }
+    if (n_rec > 1) { put_str(out, "\tSA:Z:"); sa_entries(out, P, cs, ce, n, L, it); }
     out.put('\n');
 }
 template <class S> LNR_HD inline void sam_item(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname, u64 it, u64 n_rec) {
@@ -243,12 +244,13 @@ struct SeqSrc {                 // plain data: where the bases of one read's rec
     u32 nseq;
     const uint8_t *read;        // the read, forward
     u64 L;
+    const uint8_t *const *gseq = nullptr;      // host writer: nseq separately held sequences instead of genome + gstart
 };
 struct RecSrc { const uint8_t *g; u64 gl; const uint8_t *read; u64 L; bool rev; };     // the two sources of ONE record: its genome sequence, the read and its strand
 LNR_HD inline RecSrc rec_src(const SeqSrc &q, const u64 *cs, u64 lo) {
     const u64 g = (u64)(int)cid(cs[lo]);
     const bool ok = g < q.nseq;
-    return RecSrc{ok ? q.genome + q.gstart[g] : nullptr, ok ? q.glen[g] : 0, q.read, q.L, cstrand(cs[lo]) != 0};
+    return RecSrc{ok ? (q.gseq ? q.gseq[g] : q.genome + q.gstart[g]) : nullptr, ok ? q.glen[g] : 0, q.read, q.L, cstrand(cs[lo]) != 0};
 }
 enum { SEG_READ = 0, SEG_GENOME = 1, SEG_X = 2 };
 LNR_HD inline u32 seq_read_ord(const RecSrc &r, u64 y) {                           // base y of the read, or of its reverse complement
@@ -261,14 +263,14 @@ LNR_HD inline u32 seq_genome_ord(const RecSrc &r, u64 x) {
     u32 b = r.g[x];
     return b > 4 ? 4u : b;
 }
+LNR_HD inline u32 seq_ord(const RecSrc &r, u32 kind, u64 x, u64 y) {               // 0..4 = ACGTN
+    if (kind == SEG_GENOME) return seq_genome_ord(r, x);
+    u32 o = seq_read_ord(r, y);
+    if (kind == SEG_X && o == seq_genome_ord(r, x)) o = 4;
+    return o;
+}
 LNR_HD inline char seq_char(const RecSrc &r, u32 kind, u64 x, u64 y) {
-    u32 o;
-    if (kind == SEG_GENOME) o = seq_genome_ord(r, x);
-    else {
-        o = seq_read_ord(r, y);
-        if (kind == SEG_X && o == seq_genome_ord(r, x)) o = 4;
-    }
-    return (char)((0x4e54474341ULL >> (8 * o)) & 0xff);                            // "ACGTN"
+    return (char)((0x4e54474341ULL >> (8 * seq_ord(r, kind, x, y))) & 0xff);       // "ACGTN"
 }
 // The SEQ as a stream of SEGMENTS off the walk that prints the CIGAR: F::seg(number, kind, position in SEQ, genome x, read y, bases)
 template <class F> struct SegOps {
@@ -297,6 +299,87 @@ template <class S> LNR_HD inline void sam_item_seq(S &out, const Params &P, cons
     sam_tail(out, P, cs, ce, n, q.L, it, n_rec);
 }
 
+// ---- BAM records (-ot 4 / 8: the reference hands its records to SeqAn's writer, write_bam.h:99-203).  A record is the plain re-encoding of
+// its SAM line, little endian: block_size, refID (index of RNAME, -1 for '*'), pos = POS - 1, l_read_name, mapq 255, bin, n_cigar_op, flag,
+// l_seq, next_refID -1, next_pos -1, tlen 0, QNAME '\0', one word count << 4 | op per CIGAR element (MIDNSHP=X = 0..8), SEQ at two bases
+// per byte (high nibble first, =ACMGRSVTWYHKDBN = 0..15), l_seq bytes 0xff, and where the line has one the tag SA:Z.  Without SEQ l_seq is 0.
+// Fields narrower than their value take its low bits, as SeqAn's casts do: a QNAME of 255 or more characters (l_read_name is one byte) and
+// more than 65535 CIGAR elements (n_cigar_op is two) give records no reader can walk; both are outside the tested ground.
+// bam_head: block_size, core, QNAME, CIGAR words.  bam_tail: the tag.  Between them: packed SEQ and the 0xff run.
+struct BamCount {                                 // one walk before the first byte: CIGAR elements, reference bases, SEQ bases
+    u32 k = 0; u64 reflen = 0, seq = 0;
+    LNR_HD void op(char o, u32 c, u32) { k++; if (o != 'D') seq += c; if (o == '=' || o == 'X' || o == 'D') reflen += c; }
+};
+LNR_HD inline u32 bam_op(char o) { return o == 'S' ? 4u : o == 'I' ? 1u : o == 'D' ? 2u : o == '=' ? 7u : o == 'X' ? 8u : 0u; }
+template <class S> struct BamOps {                // the CIGAR words
+    S &out;
+    LNR_HD explicit BamOps(S &o) : out(o) {}
+    LNR_HD void op(char o, u32 c, u32) { const u32 w = (c << 4) | bam_op(o); for (int b = 0; b < 4; b++) out.put((char)(w >> (8 * b))); }
+};
+template <class S> LNR_HD inline void put_le(S &s, u64 v, int bytes) { for (int b = 0; b < bytes; b++) s.put((char)(v >> (8 * b))); }
+LNR_HD inline u32 reg2bin(u32 beg, u32 end) {     // the bin of [beg, end) in the usual BAM scheme
+    --end;
+    if (beg >> 14 == end >> 14) return 4681 + (beg >> 14);
+    if (beg >> 17 == end >> 17) return 585 + (beg >> 17);
+    if (beg >> 20 == end >> 20) return 73 + (beg >> 20);
+    if (beg >> 23 == end >> 23) return 9 + (beg >> 23);
+    if (beg >> 26 == end >> 26) return 1 + (beg >> 26);
+    return 0;
+}
+LNR_HD inline u64 str_len(const char *z) { u64 n = 0; while (z[n]) n++; return n; }
+// bytes of bam_head for a QNAME of qlen characters and k CIGAR elements
+LNR_HD inline u64 bam_head_size(u64 qlen, u32 k) { return 36 + qlen + 1 + 4ULL * k; }
+LNR_HD inline u64 bam_packed(u64 l_seq) { return (l_seq + 1) >> 1; }
+// c: the record's counts; l_seq: the SEQ bases the record will carry (c.seq or 0); tag: bytes of bam_tail
+template <class S> LNR_HD inline void bam_head(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname, const BamCount &c, u64 l_seq, u64 tag) {
+    const u64 qlen = str_len(qname), g = (u64)(int)cid(cs[lo]);
+    const u32 pos = (u32)cx(cs[lo]);
+    put_le(out, bam_head_size(qlen, c.k) - 4 + bam_packed(l_seq) + l_seq + tag, 4);
+    put_le(out, g < P.nseq ? g : ~0ULL, 4);
+    put_le(out, pos, 4);
+    out.put((char)(qlen + 1)); out.put((char)255);
+    put_le(out, reg2bin(pos, pos + (u32)c.reflen), 2);
+    put_le(out, c.k, 2);
+    put_le(out, rec_flag(cs, lo), 2);
+    put_le(out, l_seq, 4);
+    put_le(out, ~0ULL, 8);                        // next_refID, next_pos
+    put_le(out, 0, 4);                            // tlen
+    put_str(out, qname); out.put('\0');
+    BamOps<S> w(out);
+    record_ops(w, P, cs, ce, n, lo, L);
+}
+template <class S> LNR_HD inline void bam_tail(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 L, u64 it, u64 n_rec) {
+    if (n_rec > 1) { put_str(out, "SAZ"); sa_entries(out, P, cs, ce, n, L, it); out.put('\0'); }
+}
+LNR_HD inline u32 seq_nib(const RecSrc &r, u32 kind, u64 x, u64 y) { return (0xf8421u >> (4 * seq_ord(r, kind, x, y))) & 15u; }     // A 1, C 2, G 4, T 8, N 15
+template <class S> struct SeqPack {               // the serial form: two bases per byte through the sink
+    S &out; RecSrc r; u32 half = 0; bool odd = false;
+    LNR_HD void seg(u32, u32 kind, u64, u64 x, u64 y, u32 c) {
+        for (u32 i = 0; i < c; i++) {
+            const u32 nb = seq_nib(r, kind, x + i, y + i);
+            if (odd) out.put((char)(half | nb)); else half = nb << 4;
+            odd = !odd;
+        }
+    }
+    LNR_HD void finish() { if (odd) out.put((char)half); }
+};
+// q == nullptr: no SEQ (l_seq 0)
+template <class S> LNR_HD inline void bam_item(S &out, const Params &P, const SeqSrc *q, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname, u64 it, u64 n_rec) {
+    BamCount c;
+    record_ops(c, P, cs, ce, n, lo, L);
+    const u64 l_seq = q ? c.seq : 0;
+    CountSink t;
+    bam_tail(t, P, cs, ce, n, L, it, n_rec);
+    bam_head(out, P, cs, ce, n, lo, L, qname, c, l_seq, t.n);
+    if (l_seq) {
+        SeqPack<S> sp{out, rec_src(*q, cs, lo)};
+        record_segs(sp, P, cs, ce, n, lo, L);
+        sp.finish();
+        for (u64 i = 0; i < l_seq; i++) out.put((char)0xff);
+    }
+    bam_tail(out, P, cs, ce, n, L, it, n_rec);
+}
+
 // ---- one read, item after item (what the host shim runs; the kernels deal the items of a read to the lanes of a wave instead)
 template <class S> LNR_HD inline void apf_read(S &out, const Params &P, const u64 *c, u64 n, u64 L, const char *rid, bool blank_before) {
     for (u64 j = 1; j < n; j++) apf_item(out, P, c, n, j, L, rid, blank_before);
@@ -314,6 +397,13 @@ template <class S> LNR_HD inline void sam_read_seq(S &out, const Params &P, cons
     u64 it = 0;
     for (u64 j = 1; j < n; j++)
         if (rec_first(cs, ce, j, P.thd_large_X)) sam_item_seq(out, P, q, cs, ce, n, j, qname, it++, n_rec);
+}
+template <class S> LNR_HD inline void bam_read(S &out, const Params &P, const SeqSrc *q, const u64 *cs, const u64 *ce, u64 n, u64 L, const char *qname) {
+    u64 n_rec = 0;
+    for (u64 j = 1; j < n; j++) n_rec += rec_first(cs, ce, j, P.thd_large_X);
+    u64 it = 0;
+    for (u64 j = 1; j < n; j++)
+        if (rec_first(cs, ce, j, P.thd_large_X)) bam_item(out, P, q, cs, ce, n, j, L, qname, it++, n_rec);
 }
 
 }  // namespace lnr_out

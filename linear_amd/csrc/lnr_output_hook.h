@@ -13,10 +13,10 @@ struct lnr_outgpu_batch {
     const uint64_t *cord_off, *cords_str, *cords_end;
     const uint64_t *read_len;        // dev_form 0: n lengths (host); dev_form 1: n + 1 read offsets (device), length k = off[k + 1] - off[k]
     const char *read_ids; const uint64_t *id_off;      // host, id_off[k] = start of id k; the blob ends with the '\0' of the last id
-    int what;                        // 1 SAM, 2 APF
+    int what;                        // 1 SAM, 2 APF, 3 BAM records
     uint64_t thd_large_X; int64_t thd_DI, thd_X;
     const uint8_t *reads;            // SAM with SEQ: the reads' bases back to back (host or device as dev_form says), and read_len then holds n + 1
-                                     // read offsets in both forms; NULL: SEQ prints as '*'
+                                     // read offsets in both forms; NULL: SEQ prints as '*' (BAM: l_seq 0)
 };
 int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, const uint64_t *goff, const uint64_t *glen, uint32_t nseq,
                     lnr_outgpu **out, char *err, size_t err_cap) __attribute__((weak));

@@ -21,6 +21,9 @@
 // flag 16), maps them through ACGTN.  Single-byte stores: the first and last dword of a SEQ, which it shares with head and tail, and a
 // dword that straddles a refill of the table.  The measure kernel sums element counts and touches no base.
 //
+// BAM records (lnr_writer_format_bam_gpu / _dev: k_out_measure_bam, k_out_emit_bam): the same three steps with the binary record of
+// lnr_output_hd.h in the text's place, without SEQ and with it; see the comment above format_read_bam.
+//
 // BGZF output (lnr_writer_set_bgzf): the text stays in HBM and is compressed there, every 0xff00 bytes of it into one BGZF member by
 // lnr_deflate_hd.h -- the same text the CPU test pins against zlib.
 //   k_bgzf_deflate  one workgroup of 512 lanes per block (a grid of at most one workgroup per CU walks the blocks): the block's text and
@@ -220,6 +223,160 @@ template <bool EMIT> __device__ u64 format_read_seq(const ReadArgs &A, const Seq
         rec_carry += (u64)__popcll(bal);
     }
     return pos;
+}
+
+// ---- BAM records (lnr_writer_format_bam_gpu / _dev: k_out_measure_bam, k_out_emit_bam).  A record is head (block_size, core, QNAME, CIGAR
+// words), packed SEQ, the 0xff run, tag (lnr_output_hd.h).  Head and tag go lane = record through the LDS window as the text forms do, but a
+// BAM core is full of zero bytes, so nothing marks a window byte as "not formatted": the wave copies explicit byte RANGES out of the window --
+// the whole tile without SEQ (head and tag of consecutive records touch), per record its head range and its tag range with SEQ.  Packed SEQ
+// is written by the whole wave off the segment table as k_out_emit_seq writes its letters: a lane's dword is 8 bases, found by bisection,
+// and may straddle segments; a table round that ends on an odd base hands the high nibble on (`carry`) and leaves the byte to the next
+// round; the last byte of an odd SEQ gets a low nibble of 0.  The 0xff run is a wave-wide fill.  Same LDS as k_out_emit_seq (window + table).
+// the wave copies staged positions [a, b) that fall into the window at wlo (4-byte aligned) from lds to dst: dwords, single bytes at the edges
+__device__ __forceinline__ void copy_range(const char *lds, u64 wlo, char *dst, u64 a, u64 b) {
+    const int lane = threadIdx.x & 63;
+    const u64 lo = a > wlo ? a : wlo, hi = b < wlo + OUT_WIN ? b : wlo + OUT_WIN;
+    if (lo >= hi) return;
+    for (u64 p = (lo & ~3ULL) + 4ULL * lane; p < hi; p += 256) {
+        const u32 d = (u32)(p - wlo) >> 2;
+        if (p >= lo && p + 4 <= hi) *reinterpret_cast<u32 *>(dst + p) = reinterpret_cast<const u32 *>(lds)[d];
+        else for (u32 b4 = 0; b4 < 4; b4++) if (p + b4 >= lo && p + b4 < hi) dst[p + b4] = lds[4 * d + b4];
+    }
+}
+// the wave fills staged positions [a, b) with 0xff
+__device__ __forceinline__ void fill_ff(char *dst, u64 a, u64 b) {
+    const int lane = threadIdx.x & 63;
+    for (u64 p = (a & ~3ULL) + 4ULL * lane; p < b; p += 256) {
+        if (p >= a && p + 4 <= b) *reinterpret_cast<u32 *>(dst + p) = 0xffffffffu;
+        else for (u32 b4 = 0; b4 < 4; b4++) if (p + b4 >= a && p + b4 < b) dst[p + b4] = (char)0xff;
+    }
+}
+// the wave writes the packed bytes of SEQ bases [tab.pos[0], tab.pos[cnt]) of one record; staged position of packed byte j = q0 + j.
+// A first base at an odd position shares its byte with `carry`, the nibble of the base before it; a last base at an even position is
+// left to the next round unless this round is the record's last (then its byte's low nibble is 0).
+__device__ __forceinline__ void seq_pack_copy(const SegTable *tab, u32 cnt, const RecSrc &r, char *dst, u64 q0, u32 carry, bool last_round) {
+    const int lane = threadIdx.x & 63;
+    const u64 b0 = tab->pos[0], b1 = tab->pos[cnt];
+    const u64 e0 = q0 + (b0 >> 1), e1 = q0 + (last_round ? (b1 + 1) >> 1 : b1 >> 1);
+    for (u64 p = (e0 & ~3ULL) + 4ULL * lane; p < e1; p += 256) {
+        u64 first = 2 * ((p > e0 ? p : e0) - q0);
+        if (first < b0) first = b0;
+        u32 s = 0, hi = cnt;                   // the last segment that starts at or before `first`
+        while (hi - s > 1) { const u32 mid = (s + hi) >> 1; if (tab->pos[mid] <= first) s = mid; else hi = mid; }
+        u64 s_lo = tab->pos[s], s_hi = tab->pos[s + 1];
+        u32 word = 0;
+        for (u32 b = 0; b < 4; b++) {
+            const u64 pb = p + b;
+            if (pb < e0 || pb >= e1) continue;
+            u32 byte = 0;
+            for (u32 h = 0; h < 2; h++) {
+                const u64 sp = 2 * (pb - q0) + h;
+                u32 nb;
+                if (sp < b0) nb = carry;
+                else if (sp >= b1) nb = 0;
+                else {
+                    while (sp >= s_hi) { s++; s_lo = s_hi; s_hi = tab->pos[s + 1]; }
+                    const u64 o = sp - s_lo;
+                    nb = seq_nib(r, tab->kind[s], tab->x[s] + o, tab->y[s] + o);
+                }
+                byte |= h ? nb : nb << 4;
+            }
+            word |= byte << (8 * b);
+        }
+        if (p >= e0 && p + 4 <= e1) *reinterpret_cast<u32 *>(dst + p) = word;
+        else for (u32 b = 0; b < 4; b++) if (p + b >= e0 && p + b < e1) dst[p + b] = (char)(word >> (8 * b));
+    }
+}
+
+// one wave = read k, as format_read.  seq: records carry SEQ (Q holds the genome and the reads, A.len read offsets)
+template <bool EMIT> __device__ __forceinline__ u64 format_read_bam(const ReadArgs &A, const SeqArgs &Q, bool seq, u32 k, char *text, u64 toff, char *lds, SegTable *tab) {
+    const int lane = threadIdx.x & 63;
+    const u64 a = A.coff[k], nc = A.coff[k + 1] - a;
+    const u64 *cs = A.cs + a, *ce = A.ce + a;
+    const u64 L = A.len_is_off ? A.len[k + 1] - A.len[k] : A.len[k];
+    const SeqSrc q{Q.genome, Q.gstart, A.P.glen, A.P.nseq, seq ? Q.reads + A.len[k] : nullptr, L};
+    const char *id = A.ids + A.idoff[k];
+    const u64 qlen = str_len(id);
+    u64 n_rec = 0;
+    for (u64 base = 1; base < nc; base += 64) {
+        u64 j = base + lane;
+        n_rec += (u64)__popcll(__ballot(j < nc && rec_first(cs, ce, j, A.P.thd_large_X)));
+    }
+    const u32 mis = (u32)(toff & 3);
+    char *dst = text + (toff - mis);
+    u64 pos = 0, rec_carry = 0;
+    for (u64 base = 1; base < nc; base += 64) {
+        const u64 j = base + lane;
+        const bool item = j < nc && rec_first(cs, ce, j, A.P.thd_large_X);
+        const u64 bal = __ballot(item);
+        const u64 it = rec_carry + (u64)__popcll(bal & ((1ULL << lane) - 1ULL));
+        BamCount c;
+        u64 hsz = 0, bases = 0, tsz = 0;       // head, SEQ bases (packed + the 0xff run between head and tag), tag
+        if (item) {
+            record_ops(c, A.P, cs, ce, nc, j, L);
+            hsz = bam_head_size(qlen, c.k);
+            bases = seq ? c.seq : 0;
+            CountSink t; bam_tail(t, A.P, cs, ce, nc, L, it, n_rec); tsz = t.n;
+        }
+        const u64 sz = hsz + bam_packed(bases) + bases + tsz;
+        const u64 incl = wave_incl_scan_u64(sz);
+        const u64 tile_total = __shfl(incl, 63, 64);
+        if constexpr (EMIT) {
+            const u64 s0 = mis + pos, s1 = s0 + tile_total, mine = s0 + incl - sz, tpos = mine + sz - tsz;
+            for (u64 wlo = s0 & ~3ULL; wlo < s1; wlo += OUT_WIN) {
+                const bool hin = item && mine < wlo + OUT_WIN && mine + hsz > wlo, tin = item && tsz && tpos < wlo + OUT_WIN && tpos + tsz > wlo;
+                const u64 in = __ballot(hin || tin);
+                if (!in) continue;                                 // a window inside one SEQ
+                if (hin) { LdsSink s{lds, mine - wlo}; bam_head(s, A.P, cs, ce, nc, j, L, id, c, bases, tsz); }
+                if (tin) { LdsSink s{lds, tpos - wlo}; bam_tail(s, A.P, cs, ce, nc, L, it, n_rec); }
+                __syncthreads();
+                if (!seq) copy_range(lds, wlo, dst, s0, s1);       // head and tag of consecutive records touch: the tile is one range
+                else
+                    for (u64 todo = in; todo; todo &= todo - 1) {
+                        const int own = __ffsll((unsigned long long)todo) - 1;
+                        const u64 h0 = __shfl(mine, own, 64), h1 = h0 + __shfl(hsz, own, 64), t0 = __shfl(tpos, own, 64), t1 = t0 + __shfl(tsz, own, 64);
+                        copy_range(lds, wlo, dst, h0, h1);
+                        copy_range(lds, wlo, dst, t0, t1);
+                    }
+                __syncthreads();
+            }
+            for (u64 todo = __ballot(item && bases > 0); todo; todo &= todo - 1) {        // the records of the tile, one after the other
+                const int own = __ffsll((unsigned long long)todo) - 1;
+                const u64 lo = base + (u64)own;                    // its first cord: wave-uniform
+                const u64 q0 = __shfl(mine + hsz, own, 64), nb = __shfl(bases, own, 64);
+                const RecSrc r = rec_src(q, cs, lo);
+                fill_ff(dst, q0 + bam_packed(nb), q0 + bam_packed(nb) + nb);
+                u32 done = 0, total, carry = 0;
+                do {
+                    u32 seen = 0;
+                    if (lane == own) { SegFill f{tab, done}; SegOps<SegFill> so(f, cx(cs[lo])); record_ops(so, A.P, cs, ce, nc, lo, L); seen = so.k; }
+                    __syncthreads();
+                    total = (u32)__builtin_amdgcn_readfirstlane((int)__shfl(seen, own, 64));
+                    const u32 cnt = total - done < SEG_CAP ? total - done : SEG_CAP;
+                    if (cnt) {
+                        seq_pack_copy(tab, cnt, r, dst, q0, carry, done + cnt == total);
+                        const u64 last = tab->pos[cnt] - 1 - tab->pos[cnt - 1];        // the round's last base: the next round's carry
+                        carry = seq_nib(r, tab->kind[cnt - 1], tab->x[cnt - 1] + last, tab->y[cnt - 1] + last);
+                    }
+                    done += cnt;
+                    __syncthreads();
+                } while (done < total);
+            }
+        }
+        pos += tile_total;
+        rec_carry += (u64)__popcll(bal);
+    }
+    return pos;
+}
+
+__global__ __launch_bounds__(64) void k_out_measure_bam(ReadArgs A, SeqArgs Q, int seq, u64 *sizes) {
+    u64 s = format_read_bam<false>(A, Q, seq != 0, blockIdx.x, nullptr, 0, nullptr, nullptr);
+    if (threadIdx.x == 0) sizes[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(64) void k_out_emit_bam(ReadArgs A, SeqArgs Q, int seq, const u64 *toff, char *text) {
+    __shared__ __attribute__((aligned(16))) char lds[OUT_WIN];
+    __shared__ SegTable tab;
+    format_read_bam<true>(A, Q, seq != 0, blockIdx.x, text, toff[blockIdx.x], lds, &tab);
 }
 
 __global__ __launch_bounds__(64) void k_out_measure_seq(ReadArgs A, SeqArgs Q, u64 *sizes) {
@@ -506,7 +663,7 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     A.P.gblob = (const char *)g->gblob.p; A.P.goff = (const u64 *)g->goff.p; A.P.glen = (const u64 *)g->glen.p; A.P.nseq = g->nseq;
     A.P.thd_large_X = b->thd_large_X; A.P.thd_DI = b->thd_DI; A.P.thd_X = b->thd_X;
     A.what = b->what;
-    const bool seq = b->reads != nullptr;      // SAM with SEQ: b->read_len holds n + 1 offsets in both forms
+    const bool seq = b->reads != nullptr;      // SAM / BAM with SEQ: b->read_len holds n + 1 offsets in both forms
     SeqArgs Q{(const uint8_t *)g->genome.p, (const u64 *)g->gstart.p, b->reads};
     // read ids: once per call, '\0'-separated blob + offsets
     double t0 = wall_ms();
@@ -538,7 +695,9 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     g->ms[0] = wall_ms() - t0;
     u64 *sizes = (u64 *)g->sizes.p;
     OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
-    if (seq) hipLaunchKernelGGL(k_out_measure_seq, dim3(n), dim3(64), 0, g->st, A, Q, sizes);
+    const bool bam = b->what == 3;
+    if (bam) hipLaunchKernelGGL(k_out_measure_bam, dim3(n), dim3(64), 0, g->st, A, Q, seq ? 1 : 0, sizes);
+    else if (seq) hipLaunchKernelGGL(k_out_measure_seq, dim3(n), dim3(64), 0, g->st, A, Q, sizes);
     else hipLaunchKernelGGL(k_out_measure, dim3(n), dim3(64), 0, g->st, A, sizes);
     OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
     hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, g->st, sizes, n);
@@ -550,7 +709,8 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     if ((s = dev_need(g->text, total + 8, err, err_cap))) return s;
     if (!g->bgzf && (s = host_need(g, total, err, err_cap))) return s;
     OUT_CK(hipEventRecord(g->ev[3], g->st), -3);
-    if (seq) hipLaunchKernelGGL(k_out_emit_seq, dim3(n), dim3(64), 0, g->st, A, Q, (const u64 *)sizes, (char *)g->text.p);
+    if (bam) hipLaunchKernelGGL(k_out_emit_bam, dim3(n), dim3(64), 0, g->st, A, Q, seq ? 1 : 0, (const u64 *)sizes, (char *)g->text.p);
+    else if (seq) hipLaunchKernelGGL(k_out_emit_seq, dim3(n), dim3(64), 0, g->st, A, Q, (const u64 *)sizes, (char *)g->text.p);
     else hipLaunchKernelGGL(k_out_emit, dim3(n), dim3(64), 0, g->st, A, (const u64 *)sizes, (char *)g->text.p);
     OUT_CK(hipEventRecord(g->ev[4], g->st), -3);
     OUT_CK(hipStreamSynchronize(g->st), -3);
