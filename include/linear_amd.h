@@ -213,7 +213,7 @@ lnr_status lnr_gap_stream(lnr_ctx *ctx, int set, int *state);
 lnr_status lnr_set_gap(lnr_ctx *ctx, uint32_t gap_len, uint32_t dup);
 
 /* Input side (host code; replaces, for this path, the fetcher's SeqAn readRecords of src/parallel_io.cpp:433-485): FASTA or
- * FASTQ records, plain or gzip, decoded into the layout lnr_filter_batch / lnr_filter_submit take.  Characters convert as SeqAn's
+ * FASTQ records, plain or gzip, or BAM records (an extension, see below), decoded into the layout lnr_filter_batch / lnr_filter_submit take.  Characters convert as SeqAn's
  * char -> Dna5 table does (A/a 0, C/c 1, G/g 2, T/t/U/u 3, anything else N = 4).  lnr_reader_next fills dst (e.g. a block from
  * lnr_host_alloc) with up to max_reads records and at most dst_cap bases, writes off[0 .. *n_out]; *n_out == 0 at end of file.
  * A record that no longer fits is delivered first by the next call.  lnr_reader_ids: header lines of the last block (without the
@@ -264,6 +264,35 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
                                const uint64_t **off /* n+1, host */, uint32_t *n_out);
 lnr_status lnr_reader_gpu_times(const lnr_reader *r, double *ms5);
 uint32_t lnr_reader_gpu_tile(void);
+/* BAM input (an extension: the reference reads FASTA / FASTQ).  A read file whose first four inflated bytes are "BAM\1" is read as BAM, aligned
+ * or unaligned, whatever its name; lnr_reader_next reads it through gzread, lnr_reader_next_dev in both ways it reads BGZF text (device inflate,
+ * or gzread into the pinned staging buffer under LNR_READER_BGZF=0) and delivers the blocks lnr_reader_next delivers.  A record is a read as
+ * `samtools fastq` prints it: records with flag 0x100 or 0x800 (secondary, supplementary) are skipped; a record with flag 0x10 is delivered
+ * reverse-complemented; the id is read_name without its NUL; the 4-bit codes A C G T become 0 1 2 3 and every other code N = 4; l_seq == 0 is a
+ * read of length 0.  Qualities, CIGAR and aux tags are not carried anywhere.  A header-only BAM gives *n_out == 0.  A record that fails the
+ * conditions every real record meets (l_read_name >= 1, l_seq >= 0, its parts fit block_size, block_size below 2^29, -1 <= refID, next_refID <
+ * n_ref, pos, next_pos >= -1, the name ends in NUL), or that the file ends inside, makes the call return LNR_ERR_ARG and deliver no block;
+ * lnr_reader_error names the record's ordinal in the file (from 0, skipped records counted) and its offset in the uncompressed stream, the same
+ * from both entry points; the reader can only be closed after that.  On the device the record starts of a window are found tile by tile
+ * (lnr_reader_gpu_bam_tile bytes each, 0 without the device half): every tile guesses its first start and walks on from it, one pass verifies
+ * the guesses in order and walks a tile again where its guess was not the true position.  lnr_reader_gpu_bam_stats: counts of the
+ * last lnr_reader_next_dev and of all calls so far.  lnr_reader_gpu_times keeps its five slots: find -> measure, stitch + take -> scan, emit -> emit. */
+typedef struct {
+    uint64_t records;                /* records delivered in blocks */
+    uint64_t skipped;                /* secondary / supplementary records passed over */
+    uint64_t reverse;                /* delivered records that were reverse-complemented (flag 0x10) */
+    uint64_t tiles;                  /* tiles k_bam_find looked at */
+    uint64_t repaired_tiles;         /* tiles whose guess did not stand: walked again from the true position, or lying inside a record */
+    double find_ms, stitch_ms, emit_ms;      /* k_bam_find; k_bam_stitch + k_bam_meta; k_bam_emit (HIP events) */
+} lnr_bam_counts;
+typedef struct { lnr_bam_counts last, total; } lnr_bam_stats;
+lnr_status lnr_reader_gpu_bam_stats(const lnr_reader *r, lnr_bam_stats *out);
+/* The format of the file: 3 BAM, else what the reads so far have shown: 1 FASTA, 2 FASTQ, 0 not decided yet, -1 neither.  Not a pure
+ * query: where nothing was read yet it reads the first buffer of the inflate stream (the bytes stay in front of the next read) and, on
+ * "BAM\1", sets the reader's format.  A plain file that is not gzip (mapped at open) is never a BAM: there it does not look and returns 0
+ * until a read has decided.  The front-end uses it to refuse a BAM genome. */
+int lnr_reader_format(lnr_reader *r);
+uint32_t lnr_reader_gpu_bam_tile(void);
 
 /* Output side (host threads, and a GPU twin below; replaces, for this path, the calculator's tail cords2BamLink + fillBamRecords, src/mapper.cpp:463-470,
  * src/f_io.cpp:758-1011, src/align_util.cpp:301-343,452-744, and the printer's writeSam / print_cords_apf, src/f_io.cpp:100-207,

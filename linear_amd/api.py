@@ -56,6 +56,14 @@ class LnrInflateStats(C.Structure):
     _fields_ = [("last", LnrInflateCounts), ("total", LnrInflateCounts)]
 
 
+class LnrBamCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "skipped", "reverse", "tiles", "repaired_tiles")] + [(k, C.c_double) for k in ("find_ms", "stitch_ms", "emit_ms")]
+
+
+class LnrBamStats(C.Structure):
+    _fields_ = [("last", LnrBamCounts), ("total", LnrBamCounts)]
+
+
 class LnrError(RuntimeError):
     def __init__(self, status: int, msg: str, detail: str = ""):
         super().__init__(f"linear_amd: {msg} (status {status}){': ' + detail if detail else ''}")
@@ -71,7 +79,8 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_writer_set_genome", "lnr_writer_format_seq", "lnr_writer_format_seq_gpu", "lnr_writer_format_seq_dev",
            "lnr_writer_set_bgzf", "lnr_writer_bgzf_bytes_gpu", "lnr_writer_bgzf_eof", "lnr_writer_bgzf_stats",
            "lnr_writer_bam_header", "lnr_writer_format_bam", "lnr_writer_format_bam_gpu", "lnr_writer_format_bam_dev",
-           "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats"]
+           "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats",
+           "lnr_reader_gpu_bam_stats", "lnr_reader_gpu_bam_tile", "lnr_reader_format"]
 
 
 class LnrBgzfStats(C.Structure):
@@ -121,6 +130,10 @@ def load_library() -> C.CDLL:
     lib.lnr_reader_gpu_inflate_stats.argtypes = [C.c_void_p, C.POINTER(LnrInflateStats)]
     lib.lnr_reader_gpu_tile.restype = C.c_uint32
     lib.lnr_reader_gpu_tile.argtypes = []
+    lib.lnr_reader_gpu_bam_stats.argtypes = [C.c_void_p, C.POINTER(LnrBamStats)]
+    lib.lnr_reader_gpu_bam_tile.restype = C.c_uint32
+    lib.lnr_reader_gpu_bam_tile.argtypes = []
+    lib.lnr_reader_format.argtypes = [C.c_void_p]
     lib.lnr_writer_create.argtypes = [C.POINTER(C.c_char_p), _u64p, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.lnr_writer_format.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u64p, C.c_char_p, _u64p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_sam_header.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), _u64p]
@@ -344,7 +357,7 @@ class Filter:
 
 
 class Reader:
-    """FASTA / FASTQ (plain or gzip) -> blocks in the ABI's layout (host code; no GPU needed)."""
+    """FASTA / FASTQ (plain or gzip) or BAM (found by content) -> blocks in the ABI's layout (host code; no GPU needed)."""
 
     def __init__(self, path: str):
         self.lib = load_library()
@@ -402,6 +415,23 @@ class Reader:
     @staticmethod
     def gpu_tile() -> int:
         return int(load_library().lnr_reader_gpu_tile())
+
+    def format(self) -> int:
+        """3 BAM (looked up in the file's first bytes), else what the reads so far have shown: 1 FASTA, 2 FASTQ, 0 undecided."""
+        return int(self.lib.lnr_reader_format(self.h))
+
+    def gpu_bam_stats(self) -> dict:
+        """BAM input: {"last": counts of the last next_dev, "total": of all calls}; each {records, skipped, reverse, tiles, repaired_tiles,
+        find_ms, stitch_ms, emit_ms} -- records delivered, secondary / supplementary records passed over, reverse-complemented ones, tiles
+        k_bam_find guessed in, tiles whose guess did not stand, and the kernels' milliseconds (HIP events)."""
+        st = LnrBamStats()
+        self._ck(self.lib.lnr_reader_gpu_bam_stats(self.h, C.byref(st)))
+        return {w: {k: getattr(getattr(st, w), k) for k, _ in LnrBamCounts._fields_} for w in ("last", "total")}
+
+    @staticmethod
+    def gpu_bam_tile() -> int:
+        """Bytes of records per tile of k_bam_find (0 when the library has no device half)."""
+        return int(load_library().lnr_reader_gpu_bam_tile())
 
     def close(self):
         if getattr(self, "h", None):

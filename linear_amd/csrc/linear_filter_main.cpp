@@ -6,7 +6,7 @@
 //   output naming  Mapper::p_printResults src/mapper.cpp:478-509 -- without -o one output per read file, named by the file's name up to its first '.';
 //                  with -o one output for all read files
 //   pipeline       process3 / p_ThreadProcess src/linear.cpp:68-91, src/parallel_io.cpp:372-608 -- ONE fetcher, calculators, ONE printer, output in
-//                  input order -- here: a reader thread (FASTA / FASTQ(.gz) -> pinned blocks), one calculator thread + one lnr_ctx PER GPU (blocks dealt in
+//                  input order -- here: a reader thread (FASTA / FASTQ(.gz) / BAM -> pinned blocks), one calculator thread + one lnr_ctx PER GPU (blocks dealt in
 //                  order, three blocks in flight per GPU: upload, kernels and download of consecutive blocks overlap), a writer thread that restores
 //                  the file order and formats on -t host threads.
 //   several GPUs   --gpus N (extension): the index is built once on the first GPU and moved to the others with RCCL (lnr_index_broadcast, north_star;
@@ -28,6 +28,12 @@
 //                  (the reference writes n_ref 0: include/linear_amd.h).
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
+//   BAM input      (extension) a read file may be a BAM, aligned or unaligned: found by its content (the first four inflated bytes are "BAM\1"), never
+//                  by its name, with the default host reader and under --gpu-reader (record starts found on the GPU: DESIGN 6h).  Its reads are
+//                  what `samtools fastq` prints: secondary / supplementary records (flag 0x100 / 0x800) are skipped, reverse-strand records
+//                  (0x10) reverse-complemented, the id is read_name; qualities and tags are dropped.  A record that is not valid BAM, or that
+//                  the file ends inside, ends the run with the record's ordinal and offset in the uncompressed stream.  Output naming is
+//                  unchanged.  A genome file that is a BAM is refused.
 // Not built (exit 1 with a message, never a silently different result): BAM output (-ot 4 / 8) without --gpu-writer, -ss 1 (use --sam-seq), -c 0, -f 1, -r 1, -p 0, -b 0
 // (the reference's -b 0 path writes a header-only SAM: SURVEY App. C.7).
 #include "../../include/linear_amd.h"
@@ -55,6 +61,7 @@ lnr_status lnr_writer_format_seq_dev(lnr_writer *, const lnr_cords_dev *, const 
 lnr_status lnr_writer_format_bam_dev(lnr_writer *, const lnr_cords_dev *, const uint8_t *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_reader_gpu_open(lnr_reader *, int32_t, uint32_t) __attribute__((weak));
 lnr_status lnr_reader_next_dev(lnr_reader *, uint64_t, uint32_t, const uint8_t **, const uint64_t **, const uint64_t **, uint32_t *) __attribute__((weak));
+int lnr_reader_format(lnr_reader *) __attribute__((weak));
 }
 
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -73,7 +80,9 @@ static bool is_number(const std::string &s) { if (s.empty()) return false; for (
 
 static void usage() {
     fprintf(stderr,
-            "linear filter - options and arguments.\n\nSYNOPSIS\n    linear filter [OPTIONS] read.fa/fastq(.gz) genome.fa(.gz)\n    linear filter [OPTIONS] reads_1 reads_2 ... x genome_1 genome_2 ...\n\n"
+            "linear filter - options and arguments.\n\nSYNOPSIS\n    linear filter [OPTIONS] read.fa/fastq(.gz)|reads.bam genome.fa(.gz)\n    linear filter [OPTIONS] reads_1 reads_2 ... x genome_1 genome_2 ...\n\n"
+            "    a read file may be a BAM (aligned or unaligned; found by content): secondary / supplementary records are skipped, reverse-strand records\n"
+            "    reverse-complemented, as `samtools fastq` prints them; the genome is FASTA / FASTQ only\n\n"
             "Basic options\n    -o,  --output STR          prefix of the output (default: the read file's name up to its first '.')\n"
             "    -ot, --output_type INT     1 .apf, 2 .sam {DEFAULT}, 4 .bam, 8 _pbsv.bam, or a sum of them (BAM needs --gpu-writer)\n    -t,  --thread INT          threads: the index layout of the reference's -t and the host threads of the writer {16}\n"
             "    -g,  --gap_len INT         minimal length of gaps to re-map; -g 0 off; bare -g or 1 = 50 {DEFAULT}\n    -rg, --read_group STR      @RG ID\n    -sn, --sample_name STR     @RG SM\n"
@@ -255,6 +264,7 @@ int main(int argc, char **argv) {
         for (const std::string &gpath : o.g_paths) {
             lnr_reader *gr = nullptr;
             if (lnr_reader_open(gpath.c_str(), &gr) != LNR_OK) { fprintf(stderr, "\033[1;31mE[06]:\033[0mCan't open file %s\n", gpath.c_str()); return 1; }
+            if (lnr_reader_format && lnr_reader_format(gr) == 3) { fprintf(stderr, "\033[1;31mE:\033[0m genome %s is a BAM file: a genome is read from FASTA / FASTQ only\n", gpath.c_str()); return 1; }
             for (;;) {
                 uint32_t n = 0;
                 if (lnr_reader_next(gr, buf.data(), buf.size(), off.data(), 1, &n) != LNR_OK) { fprintf(stderr, "E: genome %s: %s\n", gpath.c_str(), lnr_reader_error(gr)); return 1; }

@@ -13,6 +13,7 @@
 #include "../../include/linear_amd.h"
 #include "lnr_reader_hook.h"
 #include "lnr_inflate_hd.h"
+#include "lnr_bam_hd.h"
 
 // Plain (not gzip) files take a PARALLEL path (f4's reason to exist: feed a GPU that filters 2 M reads/s): the file is mapped, one pass of
 // memchr finds the record boundaries of the next block (a FASTA record ends before the next '>' at a line start; a FASTQ record is taken as four
@@ -43,7 +44,7 @@ struct lnr_reader {
     std::vector<unsigned char> buf;
     size_t pos = 0, end = 0;
     bool eof = false;
-    int format = 0;              // 0 unknown, 1 FASTA, 2 FASTQ
+    int format = 0;              // 0 unknown, 1 FASTA, 2 FASTQ, 3 BAM (by content: the first four inflated bytes)
     std::string err;
     std::vector<char> ids;       // ids of the last block, '\0' separated
     std::vector<uint8_t> spill;  // a record that did not fit the last block any more (a gzip stream cannot be rewound): first record of the next
@@ -69,6 +70,13 @@ struct lnr_reader {
     std::vector<BBlk> chain;
     lnr_inflate_counts ist_last{}, ist_total{};
     uint64_t gz_bytes = 0;                                            // text bytes that came out of gzread
+    // BAM: the header has been passed; a record was refused (the reader can only be closed); the header's n_ref; records passed so far
+    // (skipped ones included) and the offset of the next one in the uncompressed stream -- what an error message names
+    bool bam_hdr = false, bam_failed = false;
+    int32_t bam_nref = 0;
+    uint64_t bam_ord = 0, bam_off = 0;
+    std::vector<unsigned char> bam_tmp;
+    lnr_bam_counts bam_last{}, bam_total{};
 
     bool fill() {
         if (eof) return false;
@@ -81,6 +89,16 @@ struct lnr_reader {
         return true;
     }
     int peek() { return fill() ? buf[pos] : -1; }
+    // the next n bytes of the stream -> dst (dropped when dst is null); returns how many there were
+    uint64_t bytes(unsigned char *dst, uint64_t n) {
+        uint64_t got = 0;
+        while (got < n && fill()) {
+            const uint64_t k = end - pos < n - got ? end - pos : n - got;
+            if (dst) memcpy(dst + got, buf.data() + pos, k);
+            pos += k; got += k;
+        }
+        return got;
+    }
     int get() { return fill() ? buf[pos++] : -1; }
     // appends the rest of the current line (without CR / LF) to s (or drops it when s is null); returns false at end of file with nothing read
     bool line(std::vector<char> *s) {
@@ -124,6 +142,75 @@ static bool bgzf_to_stream(lnr_reader *r) {
         skip -= (uint64_t)got; r->gz_bytes += (uint64_t)got;
     }
     return true;
+}
+
+// ---- BAM (format 3; every decision from lnr_bam_hd.h).  The records come through the gzread stream one after the other.
+static lnr_status bam_fail(lnr_reader *r, uint64_t ord, uint64_t off, const char *why) {
+    char m[200];
+    snprintf(m, sizeof m, "BAM record %llu at offset %llu of the uncompressed stream: %s", (unsigned long long)ord, (unsigned long long)off, why);
+    r->err = m; r->bam_failed = true;
+    return LNR_ERR_ARG;
+}
+static const char *const BAM_INVALID = "not a valid record", *const BAM_CUT = "the file ends inside it";
+// the header, from the stream
+static lnr_status bam_header(lnr_reader *r) {
+    std::vector<unsigned char> hb;
+    for (;;) {
+        const lnr_bam::Header h = lnr_bam::header_span(hb.data(), hb.size());
+        if (h.status < 0) { r->err = "not a BAM header"; r->bam_failed = true; return LNR_ERR_ARG; }
+        if (h.status == 0) { r->bam_hdr = true; r->bam_nref = h.n_ref; r->bam_off = h.first; return LNR_OK; }
+        const size_t have = hb.size();
+        hb.resize(h.need);
+        if (r->bytes(hb.data() + have, h.need - have) < h.need - have) { r->err = "the file ends inside the BAM header"; r->bam_failed = true; return LNR_ERR_ARG; }
+    }
+}
+static lnr_status bam_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64_t *off, uint32_t max_reads, uint32_t *n_out, uint32_t n, uint64_t used) {
+    using namespace lnr_bam;
+    if (r->bam_failed) return LNR_ERR_ARG;
+    if (!r->bam_hdr) if (lnr_status s = bam_header(r)) return s;
+    while (n < max_reads) {
+        unsigned char h[HEAD + 256];
+        const uint64_t at = r->bam_off;
+        const uint64_t got = r->bytes(h, HEAD);
+        if (!got) break;
+        if (got < HEAD) return bam_fail(r, r->bam_ord, at, BAM_CUT);
+        const Fields f = rec_fields(h);
+        if (!rec_valid(f, r->bam_nref, h, HEAD)) return bam_fail(r, r->bam_ord, at, BAM_INVALID);
+        if (r->bytes(h + HEAD, f.l_read_name) < f.l_read_name) return bam_fail(r, r->bam_ord, at, BAM_CUT);
+        if (!rec_valid(f, r->bam_nref, h, HEAD + f.l_read_name)) return bam_fail(r, r->bam_ord, at, BAM_INVALID);
+        const uint64_t cig = 4ULL * f.n_cigar_op, packed = ((uint64_t)f.l_seq + 1) / 2, l = (uint64_t)f.l_seq;
+        uint64_t rest = (uint64_t)f.block_size - 32 - f.l_read_name - cig;
+        if (r->bytes(nullptr, cig) < cig) return bam_fail(r, r->bam_ord, at, BAM_CUT);
+        const bool want = delivered(f.flag);
+        if (want) {
+            if (r->bam_tmp.size() < packed) r->bam_tmp.resize(packed);
+            if (r->bytes(r->bam_tmp.data(), packed) < packed) return bam_fail(r, r->bam_ord, at, BAM_CUT);
+            rest -= packed;
+        }
+        if (r->bytes(nullptr, rest) < rest) return bam_fail(r, r->bam_ord, at, BAM_CUT);
+        r->bam_ord++; r->bam_off += 4 + (uint64_t)f.block_size;
+        if (!want) continue;
+        const uint32_t len1 = (uint32_t)l;
+        const Take t = take(&len1, 1, dst_cap - used, max_reads - n, n == 0);
+        const bool rev = reversed(f.flag);
+        r->records++; r->bases += l;
+        if (!t.n) {                                                // keep it for the next block
+            r->spill.resize(l);
+            for (uint64_t j = 0; j < l; j++) r->spill[j] = base_at(r->bam_tmp.data(), l, j, rev);
+            r->spill_id.assign((const char *)h + HEAD, (const char *)h + HEAD + f.l_read_name);
+            r->have_spill = true;
+            if (t.too_big) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
+            break;
+        }
+        for (uint64_t j = 0; j < l; j++) dst[used + j] = base_at(r->bam_tmp.data(), l, j, rev);
+        used += l;
+        r->ids.insert(r->ids.end(), (const char *)h + HEAD, (const char *)h + HEAD + f.l_read_name);
+        n++;
+        off[n] = used;
+        r->id_off.push_back(r->ids.size());
+    }
+    *n_out = n;
+    return LNR_OK;
 }
 
 extern "C" {
@@ -175,6 +262,13 @@ void lnr_reader_close(lnr_reader *r) {
 }
 
 const char *lnr_reader_error(const lnr_reader *r) { return r ? r->err.c_str() : "null reader"; }
+
+// 3 when the file is a BAM (looked up in the stream's first bytes where nothing was read yet), else the format decided so far
+int lnr_reader_format(lnr_reader *r) {
+    if (!r) return 0;
+    if (r->format == 0 && !r->use_map && r->fill() && lnr_bam::is_magic(r->buf.data() + r->pos, r->end - r->pos)) r->format = 3;
+    return r->format;
+}
 
 // Next block of records: at most max_reads records and never more than dst_cap bases (a record that does not fit any more is left
 // for the next call; one that could never fit is LNR_ERR_LIMIT).  off[0] = 0 .. off[*n_out] written.  *n_out == 0 at end of file.
@@ -300,6 +394,8 @@ static lnr_status next_from(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint6
             r->pos = r->end = 0; r->eof = false;
         } else { *n_out = n; return LNR_OK; }
     }
+    if (r->format == 0 && r->fill() && lnr_bam::is_magic(r->buf.data() + r->pos, r->end - r->pos)) r->format = 3;
+    if (r->format == 3) return bam_next(r, dst, dst_cap, off, max_reads, n_out, n, used);
     while (n < max_reads) {
         int c;
         while ((c = r->peek()) == '\n' || c == '\r' || c == ' ' || c == '\t') r->pos++;     // blank lines between records
@@ -392,6 +488,13 @@ lnr_status lnr_reader_gpu_open(lnr_reader *r, int32_t device, uint32_t slots) {
 }
 
 uint32_t lnr_reader_gpu_tile(void) { return lnr_rdgpu_tile ? lnr_rdgpu_tile() : 0; }
+uint32_t lnr_reader_gpu_bam_tile(void) { return lnr_rdgpu_bam_tile ? lnr_rdgpu_bam_tile() : 0; }
+
+lnr_status lnr_reader_gpu_bam_stats(const lnr_reader *r, lnr_bam_stats *out) {
+    if (!r || !out || !r->gpu) return LNR_ERR_ARG;
+    out->last = r->bam_last; out->total = r->bam_total;
+    return LNR_OK;
+}
 
 lnr_status lnr_reader_gpu_times(const lnr_reader *r, double *ms5) {
     if (!r || !ms5 || !r->gpu) return LNR_ERR_ARG;
@@ -421,6 +524,8 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
     lnr_rdgpu_times_reset(r->gpu);
     r->ids.clear(); r->id_off.assign(1, 0);
     r->ist_last = lnr_inflate_counts{};
+    r->bam_last = lnr_bam_counts{};
+    if (r->bam_failed) return LNR_ERR_ARG;
     const uint64_t gz0 = r->gz_bytes;
     struct StatsAtExit {                                          // the counts of this call join the totals however it ends
         lnr_reader *r; uint64_t gz0;
@@ -431,6 +536,9 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
             l.gzread_bytes = r->gz_bytes - gz0; l.inflate_ms = ms2[0]; l.gather_ms = ms2[1];
             t.blocks += l.blocks; t.compressed_bytes += l.compressed_bytes; t.text_bytes += l.text_bytes; t.gzread_bytes += l.gzread_bytes;
             t.inflate_ms += l.inflate_ms; t.gather_ms += l.gather_ms;
+            lnr_bam_counts &bl = r->bam_last, &bt = r->bam_total;
+            bt.records += bl.records; bt.skipped += bl.skipped; bt.reverse += bl.reverse; bt.tiles += bl.tiles; bt.repaired_tiles += bl.repaired_tiles;
+            bt.find_ms += bl.find_ms; bt.stitch_ms += bl.stitch_ms; bt.emit_ms += bl.emit_ms;
         }
     } stats_at_exit{r, gz0};
     uint64_t wcap = 256ULL << 20, grow = 1, used = 0;
@@ -439,6 +547,21 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
     uint32_t n = 0;
     bool full = false;
     auto is_ws = [](unsigned char c) { return c == '\n' || c == '\r' || c == ' ' || c == '\t'; };
+    // BAM: what a window's parse leaves behind it -- the error the host reader would meet here, the position in the stream, the counts, the names
+    auto bam_done = [&](const lnr_rdgpu_result &res, const lnr_rdgpu_bam_result &bb) -> lnr_status {
+        if (bb.bad) return bam_fail(r, r->bam_ord + bb.bad_ord, r->bam_off + bb.bad_off, bb.bad == 1 ? BAM_INVALID : BAM_CUT);
+        r->bam_ord += bb.passed; r->bam_off += res.consumed;
+        lnr_bam_counts &c = r->bam_last;
+        c.records += res.n; c.skipped += bb.skipped; c.reverse += bb.reverse; c.tiles += bb.tiles; c.repaired_tiles += bb.repaired;
+        c.find_ms += bb.find_ms; c.stitch_ms += bb.stitch_ms; c.emit_ms += bb.emit_ms;
+        for (uint64_t k = 0; k < res.n; k++) {
+            r->ids.insert(r->ids.end(), bb.ids + bb.id_off[k], bb.ids + bb.id_off[k] + bb.id_len[k]);
+            r->ids.push_back('\0');
+            r->id_off.push_back(r->ids.size());
+        }
+        return LNR_OK;
+    };
+    auto bam_header_fail = [&](const char *why) { r->err = why; r->bam_failed = true; return LNR_ERR_ARG; };
     while (!r->gpu_serial && !r->have_spill && n < max_reads) {
         const uint64_t freeb = dst_cap - used, allowed = max_reads - n;
         // the window: what the free bases can take as text, but no more than the records still allowed will probably need -- by the bytes
@@ -487,14 +610,58 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
             w.fmt = r->format; w.eof = r->bend; w.slot = slot; w.threads = r->threads;
             w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
             lnr_rdgpu_result res{};
-            lnr_rdgpu_bgzf_result br{};
-            if (int s = lnr_rdgpu_parse_bgzf(r->gpu, &job, &w, &res, &br, r->gerr, sizeof r->gerr)) { r->bfailed = true; return gfail(s); }
-            if (br.bad_status) {                                  // a call that meets a bad block delivers no block
-                snprintf(r->gerr, sizeof r->gerr, "BGZF block at file offset %llu: %s", (unsigned long long)r->chain[chain0 + br.bad_blk].off, lnr_inf::status_text(br.bad_status));
+            // a call that meets a bad block delivers no block
+            auto bad_block = [&](uint32_t blk, uint32_t status) {
+                snprintf(r->gerr, sizeof r->gerr, "BGZF block at file offset %llu: %s", (unsigned long long)r->chain[chain0 + blk].off, lnr_inf::status_text(status));
                 r->bfailed = true;
                 return gfail(LNR_ERR_ARG);
+            };
+            // what the window used up (`lead` bytes in front of the parsed text, `consumed` of it) leaves the chain; the rest stays on the
+            // device for the next window, `keep_from` = where it starts in the device text
+            auto advance = [&](uint64_t lead, uint64_t consumed, uint64_t keep_from) {
+                const uint64_t adv = lead + consumed;
+                r->bkeep_from = keep_from;
+                r->bcarry = tl - adv;
+                r->bskip += adv;
+                size_t gone = 0;
+                while (gone < r->chain.size() && r->bskip >= r->chain[gone].isize) r->bskip -= r->chain[gone++].isize;
+                r->chain.erase(r->chain.begin(), r->chain.begin() + (long)gone);
+            };
+            // a window without a whole record is doubled
+            auto grow_window = [&]() -> bool {
+                if (tl + 65536 > (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return false; }
+                grow *= 2;
+                return true;
+            };
+            if (r->format == 3) {                                 // BAM records, not text: the same inflate, then find / stitch / take / emit
+                lnr_rdgpu_bam_result bb{};
+                const lnr_rdgpu_bam_in in{r->bam_hdr ? 1 : 0, r->bam_nref};
+                if (int s = lnr_rdgpu_parse_bam(r->gpu, &job, &w, &in, &res, &bb, r->gerr, sizeof r->gerr)) { r->bfailed = true; return gfail(s); }
+                if (bb.bad_status) return bad_block(bb.bad_blk, bb.bad_status);
+                r->ist_last.blocks += tab.size(); r->ist_last.compressed_bytes += job.comp_len; r->ist_last.text_bytes += fresh;
+                if (bb.hdr_state == 2) return bam_header_fail("not a BAM header");
+                if (bb.hdr_state == 1 && r->bend) return bam_header_fail("the file ends inside the BAM header");
+                if (bb.hdr_state == 0 && !r->bam_hdr) { r->bam_hdr = true; r->bam_nref = bb.n_ref; r->bam_off = bb.lead; }
+                if (lnr_status s = bam_done(res, bb)) return s;
+                n += (uint32_t)res.n; used += res.bases;
+                r->records += res.n; r->bases += res.bases;
+                r->g_recs += bb.passed; r->g_text += res.consumed;
+                advance(bb.lead, res.consumed, res.consumed);     // (the header was moved out of the device text)
+                if (r->bstop) { if (!bgzf_to_stream(r)) return LNR_ERR_ARG; }     // a member that is not BGZF: gzread goes on, inside the header too
+                if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
+                if (res.full) { full = true; break; }
+                if (r->bend && r->bcarry == 0) break;
+                if (res.n == 0 && res.consumed == 0 && r->bgzf && !grow_window()) return LNR_ERR_LIMIT;
+                continue;
             }
+            lnr_rdgpu_bgzf_result br{};
+            if (int s = lnr_rdgpu_parse_bgzf(r->gpu, &job, &w, &res, &br, r->gerr, sizeof r->gerr)) { r->bfailed = true; return gfail(s); }
+            if (br.bad_status) return bad_block(br.bad_blk, br.bad_status);
             r->ist_last.blocks += tab.size(); r->ist_last.compressed_bytes += job.comp_len; r->ist_last.text_bytes += fresh;
+            if (r->format == 0 && w.fmt == 3) {                   // "BAM\1": the text stays on the device whole, the next pass reads it as records
+                r->format = 3; r->bkeep_from = 0; r->bcarry = tl;
+                continue;
+            }
             if (r->format == 0 && br.first >= 0) r->format = w.fmt;
             bool handover = br.first >= 0 && !br.parsed;          // not a record start: the serial parser reports it
             if (br.parsed) {
@@ -508,14 +675,7 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
                 r->g_recs += res.n; r->g_text += res.consumed;
                 handover = res.handover != 0;
             }
-            // what the window used up leaves the chain; the rest stays on the device for the next window
-            const uint64_t adv = br.lead + (br.parsed ? res.consumed : 0);
-            r->bkeep_from = br.parsed ? res.consumed : br.lead;
-            r->bcarry = tl - adv;
-            r->bskip += adv;
-            size_t gone = 0;
-            while (gone < r->chain.size() && r->bskip >= r->chain[gone].isize) r->bskip -= r->chain[gone++].isize;
-            r->chain.erase(r->chain.begin(), r->chain.begin() + (long)gone);
+            advance(br.lead, br.parsed ? res.consumed : 0, br.parsed ? res.consumed : br.lead);
             if (handover || r->bstop) {                           // the stream goes on at the first byte the device has not used up
                 if (!bgzf_to_stream(r)) return LNR_ERR_ARG;
                 if (handover) { r->gpu_serial = true; break; }
@@ -523,10 +683,7 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
             if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
             if (res.full) { full = true; break; }
             if (r->bend && r->bcarry == 0) break;
-            if (br.parsed && res.n == 0 && r->bgzf) {
-                if (tl + 65536 > (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
-                grow *= 2;
-            }
+            if (br.parsed && res.n == 0 && r->bgzf && !grow_window()) return LNR_ERR_LIMIT;
             continue;
         }
         if (r->use_map) {
@@ -551,6 +708,45 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
                 len += (uint64_t)got; r->gz_bytes += (uint64_t)got;
             }
             eof = r->gz_done;
+            if (r->format == 0 && lnr_bam::is_magic(S, len)) r->format = 3;
+            if (r->format == 3) {                                 // BAM through gzread: the header is passed here, the records go up as they are
+                auto put_back = [&](const uint8_t *p, uint64_t left) {
+                    if (r->buf.size() < left) r->buf.resize(left);
+                    memcpy(r->buf.data(), p, left);
+                    r->pos = 0; r->end = left;
+                };
+                if (!r->bam_hdr) {
+                    const lnr_bam::Header h = lnr_bam::header_span(S, len);
+                    if (h.status < 0) return bam_header_fail("not a BAM header");
+                    if (h.status == 1) {
+                        if (eof) return bam_header_fail("the file ends inside the BAM header");
+                        if (len >= (1ULL << 30)) { r->err = "the BAM header is longer than the reader's window"; return LNR_ERR_LIMIT; }
+                        put_back(S, len); grow *= 2;
+                        continue;
+                    }
+                    r->bam_hdr = true; r->bam_nref = h.n_ref; r->bam_off = h.first; lead = h.first;
+                }
+                if (len == lead) { if (eof) break; continue; }
+                w.fmt = 3; w.eof = eof; w.text = S + lead; w.len = len - lead; w.pinned = 1; w.slot = slot; w.threads = r->threads;
+                w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
+                const lnr_rdgpu_bam_in in{1, r->bam_nref};
+                lnr_rdgpu_result res{};
+                lnr_rdgpu_bam_result bb{};
+                if (int s = lnr_rdgpu_parse_bam(r->gpu, nullptr, &w, &in, &res, &bb, r->gerr, sizeof r->gerr)) return gfail(s);
+                if (lnr_status s = bam_done(res, bb)) return s;
+                n += (uint32_t)res.n; used += res.bases;
+                r->records += res.n; r->bases += res.bases;
+                r->g_recs += bb.passed; r->g_text += res.consumed;
+                put_back(S + lead + res.consumed, w.len - res.consumed);
+                if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
+                if (res.full) { full = true; break; }
+                if (eof && res.consumed == w.len) break;
+                if (res.n == 0 && res.consumed == 0) {
+                    if (len >= (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
+                    grow *= 2;
+                }
+                continue;
+            }
             while (lead < len && is_ws(S[lead])) lead++;
             text = S + lead; len -= lead;
             w.pinned = 1;

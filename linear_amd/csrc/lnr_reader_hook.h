@@ -8,7 +8,7 @@
 extern "C" {
 struct lnr_rdgpu;
 struct lnr_rdgpu_window {
-    int fmt;                         // 1 FASTA, 2 FASTQ
+    int fmt;                         // 1 FASTA, 2 FASTQ, 3 BAM (lnr_rdgpu_parse_bam)
     int eof;                         // the window ends at the end of the file
     int pinned;                      // text lies in a staging buffer of lnr_rdgpu_stage: copied up as it is
     const uint8_t *text; uint64_t len;               // host text; byte 0 starts a record
@@ -40,6 +40,25 @@ struct lnr_rdgpu_bgzf_result {
 // not used, w->len is set here; w->fmt == 0: decided by the first byte.
 int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
                          char *err, size_t err_cap) __attribute__((weak));
+// ---- BAM input: the window's bytes are BAM records behind `lead` header bytes.  job != null: BGZF blocks are inflated first, as in
+// lnr_rdgpu_parse_bgzf (which sets w->fmt = 3 and parses nothing when an undecided file starts with "BAM\1"); job == null: w->text / w->len
+// is the staged stream and byte 0 starts a record.  Then find / stitch / meta on the device, the take on the host from the per-record
+// metadata (lnr_bam::take), emit and the gather of the names.
+struct lnr_rdgpu_bam_in { int hdr_done; int32_t n_ref; };
+struct lnr_rdgpu_bam_result {
+    uint32_t bad_blk, bad_status;                    // as in lnr_rdgpu_bgzf_result
+    uint32_t hdr_state;                              // 0 passed; 1 the window is too short for the header (nothing was parsed); 2 not a BAM header
+    int32_t n_ref; uint64_t lead;                    // set when the header was passed by this call: its n_ref and its bytes
+    uint32_t bad;                                    // the record the host reader would read next: 1 fails rec_valid, 2 the file ends inside it
+    uint64_t bad_ord, bad_off;                       // ... records of the window in front of it, its window offset (behind lead)
+    uint64_t passed;                                 // records in front of `consumed`, skipped ones included
+    uint64_t skipped, reverse, tiles, repaired;      // among the passed; of the window
+    double find_ms, stitch_ms, emit_ms;
+    const char *ids; const uint64_t *id_off; const uint32_t *id_len;   // names of the taken records (pinned, valid until the next parse)
+};
+int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, const lnr_rdgpu_bam_in *in, lnr_rdgpu_result *r,
+                        lnr_rdgpu_bam_result *br, char *err, size_t err_cap) __attribute__((weak));
+uint32_t lnr_rdgpu_bam_tile(void) __attribute__((weak));
 void lnr_rdgpu_inflate_times(const lnr_rdgpu *g, double *ms2) __attribute__((weak));   // last block: inflate kernel, header gather (HIP events)
 int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, size_t err_cap) __attribute__((weak));
 // makes block `slot` hold dst_cap bases and max_reads + 1 offsets; hands out its device arrays and the host copy of the offsets

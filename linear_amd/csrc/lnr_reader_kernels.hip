@@ -1,5 +1,6 @@
 // lnr_reader_kernels.hip -- the GPU side of the reader (lnr_reader_next_dev): FASTA / FASTQ text -> Dna5 ordinals back to back + read
-// offsets in HBM.  gfx950, wave64.  Every decision comes from lnr_reader_hd.h, the same text the CPU test pins.
+// offsets in HBM.  gfx950, wave64.  Every decision comes from lnr_reader_hd.h, the same text the CPU test pins.  BAM records (further
+// down: k_bam_find and its siblings) come from the same device text; their decisions are lnr_bam_hd.h's.
 //
 // Three steps per window of text, on the reader's own stream:
 //   k_rd_measure   one workgroup = one wave per tile of RD_TILE bytes: the tile goes to LDS by 16-byte loads, the wave walks it in groups
@@ -27,6 +28,7 @@
 #define LNR_INFLATE_UNIFORM(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))      // the decoder's state is the same in every lane
 #endif
 #include "lnr_inflate_hd.h"
+#include "lnr_bam_hd.h"
 
 namespace {
 
@@ -234,6 +236,149 @@ __global__ __launch_bounds__(64) void k_rd_gather(const u8 *text, u64 len, const
     if (lane == 0) lens[k] = (u32)(he - hb);
 }
 
+// ---- BAM input: the window's bytes are length-prefixed records, so record starts form a serial chain.  Every decision comes
+// from lnr_bam_hd.h.  Separate launches on the reader's stream, no kernel waits for another workgroup:
+//   k_bam_find     one wave per tile of BAM_TILE bytes GUESSES the tile's first record start -- 64 offsets at a time, lane = offset, the bytes
+//                  staged through LDS by 16-byte loads, the first lane that passes rec_plausible wins -- and walks the chain from there to
+//                  the tile's end, storing the starts in the tile's slice of a list
+//   k_bam_stitch   one wave carries the TRUE position through the tiles in order (summaries loaded 64 at a time, stepped through by
+//                  shuffles; serial in the number of tiles, and a repair walk is run by all lanes alike, as in k_bam_find): a tile whose guess is the true position is accepted whole, any other is walked again from the true position
+//                  and its slice rewritten; then the prefix sum of the tiles' counts numbers the records
+//   k_bam_meta     per record 16 bytes (offset, l_seq, flag, name length, CIGAR length) in record order: all the host sees of the records;
+//                  the take (lnr_bam::take) runs there
+//   k_bam_emit     the packed SEQ of every taken record -> ordinals at off[k], 16 bases per lane and store, a reverse-strand record
+//                  mirrored and complemented; qualities, CIGAR and aux bytes are never read
+//   k_bam_names    the names of the taken records, byte for byte (k_rd_gather drops trailing '\r': not here)
+#ifndef LNR_BAM_TILE
+#define LNR_BAM_TILE 131072                    // a multiple of BAM_STAGE; variant builds for the tile-size comparison set it (tools/measure/reader_bam_ab.py)
+#endif
+constexpr u32 BAM_TILE = LNR_BAM_TILE;                // bytes of records per wave of k_bam_find (32 KiB, 64 KiB and 128 KiB compared in profiles/r12)
+constexpr u32 BAM_SLICE = BAM_TILE / lnr_bam::MIN_REC + 2;
+constexpr u32 BAM_STAGE = 1024;                // offsets tested per LDS fill; a candidate's 36 bytes reach at most 35 bytes past them
+constexpr u32 BAM_CHUNK = 4096;                // bases of one record per wave of k_bam_emit
+u64 bam_text_cap(u64 tlen) { return ((tlen + BAM_TILE - 1) / BAM_TILE) * BAM_TILE + BAM_STAGE; }      // every LDS fill stays inside the buffer
+
+struct BamStitch { u64 consumed, nrec, bad_off; u32 flag, repaired; };
+
+__global__ __launch_bounds__(64) void k_bam_find(const u8 *text, u64 len, int n_ref, u32 *list, lnr_bam::Tile *tiles) {
+    __shared__ __attribute__((aligned(16))) u8 lds[BAM_STAGE + 64];
+    const u32 lane = threadIdx.x, tile = blockIdx.x;
+    const u64 t0 = (u64)tile * BAM_TILE, tend = t0 + BAM_TILE < len ? t0 + BAM_TILE : len;
+    u32 first = lnr_bam::NONE;
+    for (u64 c = t0; c < tend && first == lnr_bam::NONE; c += BAM_STAGE) {
+        __syncthreads();
+        const uint4 *src = reinterpret_cast<const uint4 *>(text + c);             // c is a multiple of 16; the buffer holds bam_text_cap bytes
+        for (u32 i = lane; i < (BAM_STAGE + 64) / 16; i += 64) reinterpret_cast<uint4 *>(lds)[i] = src[i];
+        __syncthreads();
+        for (u32 g = 0; g < BAM_STAGE && c + g < tend; g += 64) {
+            const u64 p = c + g + lane;
+            bool ok = p < tend && p + lnr_bam::HEAD <= len;
+            if (ok) ok = lnr_bam::rec_plausible(lnr_bam::rec_fields(lds + g + lane), n_ref, text + p, len - p);      // (the name's NUL from global memory)
+            const u64 m = __ballot(ok);
+            if (m) { first = (u32)(c + g - t0) + ctz(m); break; }
+        }
+    }
+    // the walk is serial and wave-uniform: all 64 lanes run it with the same values (the loads are one request per step, lane 0 stores);
+    // nothing is gained over one lane, nothing lost either -- a cooperative walk would have to know the chain it is looking for
+    const lnr_bam::Tile T = lnr_bam::speculate(text, len, n_ref, t0, tend, first, list + (u64)tile * BAM_SLICE, BAM_SLICE, lane == 0);
+    if (lane == 0) tiles[tile] = T;
+}
+
+__global__ __launch_bounds__(64) void k_bam_stitch(const u8 *text, u64 len, int n_ref, u32 nt, u32 *list, const lnr_bam::Tile *tiles, u32 *cnt, u64 *prefix, BamStitch *out) {
+    const u32 lane = threadIdx.x;
+    u64 p = 0, nrec = 0;
+    u32 flag = lnr_bam::CH_OK, repaired = 0, next = 0, base = lnr_bam::NONE;
+    lnr_bam::Tile mine; mine.exit = 0; mine.first = lnr_bam::NONE; mine.count = 0; mine.flag = 0; mine.pad = 0;
+    while (p < len && flag == lnr_bam::CH_OK) {
+        const u32 t = (u32)(p / BAM_TILE);                                        // the tile that holds the true position (t < nt, t >= next)
+        for (u32 i = next + lane; i < t; i += 64) cnt[i] = 0;                     // tiles that lie inside a record: no start, whatever they guessed
+        repaired += t - next;
+        if (base == lnr_bam::NONE || t >= base + 64) { base = t & ~63u; if (base + lane < nt) mine = tiles[base + lane]; }
+        lnr_bam::Tile T;
+        const int srcl = (int)(t - base);
+        T.exit = (u64)(u32)__shfl((int)(u32)mine.exit, srcl, 64) | ((u64)(u32)__shfl((int)(u32)(mine.exit >> 32), srcl, 64) << 32);
+        T.first = (u32)__shfl((int)mine.first, srcl, 64); T.count = (u32)__shfl((int)mine.count, srcl, 64); T.flag = (u32)__shfl((int)mine.flag, srcl, 64); T.pad = 0;
+        const u64 t0 = (u64)t * BAM_TILE, tend = t0 + BAM_TILE < len ? t0 + BAM_TILE : len;
+        u32 count = 0;
+        flag = lnr_bam::stitch_tile(text, len, n_ref, p, t0, tend, T, list + (u64)t * BAM_SLICE, BAM_SLICE, count, repaired, lane == 0);
+        if (count > BAM_SLICE) count = BAM_SLICE;                                 // (cannot happen: a valid record is MIN_REC bytes or more)
+        if (lane == 0) cnt[t] = count;
+        nrec += count;
+        next = t + 1;
+        if (flag == lnr_bam::CH_OK && p < tend) break;                             // (cannot happen: a walk that is not stopped leaves its tile)
+    }
+    for (u32 i = next + lane; i < nt; i += 64) cnt[i] = 0;                        // tiles behind the stop hold no record of this window
+    __syncthreads();
+    u64 run = 0;
+    for (u32 b = 0; b < nt; b += 64) {                                            // record numbering: exclusive prefix sum of the counts
+        const u32 v = b + lane < nt ? cnt[b + lane] : 0;
+        u32 inc = v;
+        for (int d = 1; d < 64; d <<= 1) { const u32 o = (u32)__shfl_up((int)inc, d, 64); if ((int)lane >= d) inc += o; }
+        if (b + lane < nt) prefix[b + lane] = run + inc - v;
+        run += (u32)__shfl((int)inc, 63, 64);
+    }
+    if (lane == 0) {
+        prefix[nt] = run;
+        BamStitch o; o.consumed = p; o.nrec = nrec; o.bad_off = p; o.flag = flag; o.repaired = repaired;
+        *out = o;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_bam_meta(const u8 *text, u64 len, const u32 *list, const u32 *cnt, const u64 *prefix, u64 nrec, lnr_bam::Meta *meta) {
+    const u32 tile = blockIdx.x, c = cnt[tile];
+    const u64 k0 = prefix[tile];
+    for (u32 j = threadIdx.x; j < c && j < BAM_SLICE; j += 64) {
+        const u32 p = list[(u64)tile * BAM_SLICE + j];
+        if (k0 + j < nrec && (u64)p + lnr_bam::HEAD <= len) meta[k0 + j] = lnr_bam::meta_of(p, lnr_bam::rec_fields(text + p));
+    }
+}
+
+// one taken record: its packed SEQ in the window, its bases, where they go in the block, reverse strand; chunk = BAM_CHUNK bases of one record
+struct BamJob { u64 dst; u32 seq, l_seq, rev, pad; };
+struct BamChunk { u32 rec, start; };
+
+__global__ __launch_bounds__(64) void k_bam_emit(const u8 *text, u64 len, const BamJob *jobs, const BamChunk *chunks, u32 nchunk, u8 *out, u64 out_cap) {
+    if (blockIdx.x >= nchunk) return;
+    const BamChunk C = chunks[blockIdx.x];
+    const BamJob J = jobs[C.rec];
+    const u64 l = J.l_seq;
+    if ((u64)J.seq + (l + 1) / 2 > len || J.dst + l > out_cap) return;             // (checked on the host too)
+    const u8 *seq = text + J.seq;
+    // lnr_bam::base_at with the packed byte kept between the two bases it holds: a lane's run loads every byte once
+    u64 held = ~0ULL; u8 cur = 0;
+    const bool rev = J.rev != 0;
+    auto base = [&](u64 j) -> u8 {
+        const u64 s = rev ? l - 1 - j : j;
+        if ((s >> 1) != held) { held = s >> 1; cur = seq[held]; }
+        const u8 o = lnr_bam::nib2ord((s & 1) ? (cur & 15u) : (u32)(cur >> 4));
+        return rev ? lnr_bam::ord_complement(o) : o;
+    };
+    // the wave's share of the record, in block coordinates; lanes take the 16-byte aligned segments that meet it
+    const u64 a = J.dst + C.start, e = J.dst + (C.start + BAM_CHUNK < l ? C.start + BAM_CHUNK : l);
+    for (u64 s0 = (a & ~15ULL) + 16ULL * threadIdx.x; s0 < e; s0 += 16ULL * 64) {
+        if (s0 >= a && s0 + 16 <= e) {
+            uint32_t wds[4];
+            for (u32 q = 0; q < 4; q++) {
+                u32 v = 0;
+                for (u32 i = 0; i < 4; i++) v |= (u32)base(s0 + 4 * q + i - J.dst) << (8 * i);
+                wds[q] = v;
+            }
+            *reinterpret_cast<uint4 *>(out + s0) = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+        } else {
+            for (u64 x = s0 < a ? a : s0; x < e && x < s0 + 16; x++) out[x] = base(x - J.dst);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_bam_names(const u8 *text, u64 len, const u64 *span, const u64 *dst_off, u64 n, u8 *dst, u64 dst_cap, u32 *lens) {
+    const u64 k = blockIdx.x;
+    if (k >= n) return;
+    const u64 hb = span[2 * k], he = span[2 * k + 1], o = dst_off[k];
+    if (hb > he || he > len || o > dst_cap || he - hb > dst_cap - o) { if (threadIdx.x == 0) lens[k] = ~0u; return; }
+    for (u64 i = threadIdx.x; i < he - hb; i += 64) dst[o + i] = text[hb + i];
+    if (threadIdx.x == 0) lens[k] = (u32)(he - hb);
+}
+
 double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Buf { void *p = nullptr; u64 cap = 0; };
@@ -255,6 +400,11 @@ struct lnr_rdgpu {
     // BGZF: compressed bytes, block table, status per block, a buffer for moves that overlap, the gathered headers
     Buf comp, btab, bstat, move, idoff, idbytes, idlen;
     Pin h_btab, h_bstat, h_head, h_idoff, h_idbytes, h_idlen;
+    // BAM: the list of record starts (a slice per tile), the tiles' speculation, their counts and prefix sums, the stitch's result, the
+    // per-record metadata, the emit's jobs and chunks
+    Buf blist, btiles, bcnt, bprefix, bstitch, bmeta, bjobs, bchunks;
+    Pin h_bstitch, h_bmeta, h_bjobs, h_bchunks;
+    hipEvent_t ev_b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_i[4] = {nullptr, nullptr, nullptr, nullptr};
     double ms_inf[2] = {0, 0};
 };
@@ -296,8 +446,11 @@ void par_copy(void *dst, const void *src, u64 n, u32 threads) {
     for (auto &x : th) x.join();
 }
 void free_all(lnr_rdgpu *g) {
-    for (Buf *b : {&g->text, &g->sums, &g->carry, &g->hdr, &g->res, &g->comp, &g->btab, &g->bstat, &g->move, &g->idoff, &g->idbytes, &g->idlen}) if (b->p) (void)hipFree(b->p);
-    for (Pin *b : {&g->up[0], &g->up[1], &g->stage, &g->h_res, &g->h_hdr, &g->h_btab, &g->h_bstat, &g->h_head, &g->h_idoff, &g->h_idbytes, &g->h_idlen}) if (b->p) (void)hipHostFree(b->p);
+    for (Buf *b : {&g->text, &g->sums, &g->carry, &g->hdr, &g->res, &g->comp, &g->btab, &g->bstat, &g->move, &g->idoff, &g->idbytes, &g->idlen,
+                   &g->blist, &g->btiles, &g->bcnt, &g->bprefix, &g->bstitch, &g->bmeta, &g->bjobs, &g->bchunks}) if (b->p) (void)hipFree(b->p);
+    for (Pin *b : {&g->up[0], &g->up[1], &g->stage, &g->h_res, &g->h_hdr, &g->h_btab, &g->h_bstat, &g->h_head, &g->h_idoff, &g->h_idbytes, &g->h_idlen,
+                   &g->h_bstitch, &g->h_bmeta, &g->h_bjobs, &g->h_bchunks}) if (b->p) (void)hipHostFree(b->p);
+    for (hipEvent_t e : g->ev_b) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->ev_i) if (e) (void)hipEventDestroy(e);
     for (Block &b : g->blk) { if (b.reads.p) (void)hipFree(b.reads.p); if (b.off.p) (void)hipFree(b.off.p); if (b.h_off.p) (void)hipHostFree(b.h_off.p); }
     for (hipEvent_t e : g->ev_up) if (e) (void)hipEventDestroy(e);
@@ -351,6 +504,7 @@ int scan_emit(lnr_rdgpu *g, const lnr_rdgpu_window *w, u32 nt, u64 nchunk, u64 m
 extern "C" {
 
 uint32_t lnr_rdgpu_tile(void) { return RD_TILE; }
+uint32_t lnr_rdgpu_bam_tile(void) { return BAM_TILE; }
 
 int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, size_t err_cap) {
     int count = 0;
@@ -370,6 +524,7 @@ int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, s
         for (hipEvent_t &e : g->ev_up) RD_CK(hipEventCreate(&e), -3);
         for (hipEvent_t &e : g->ev) RD_CK(hipEventCreate(&e), -3);
         for (hipEvent_t &e : g->ev_i) RD_CK(hipEventCreate(&e), -3);
+        for (hipEvent_t &e : g->ev_b) RD_CK(hipEventCreate(&e), -3);
         if (!pin_need(g->h_res, sizeof(Result))) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
         return dev_need(g->res, sizeof(Result), err, err_cap);
     };
@@ -467,20 +622,16 @@ static int move_text(lnr_rdgpu *g, u8 *text, u64 to, u64 from, u64 n, char *err,
     return 0;
 }
 
-int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
-                         char *err, size_t err_cap) {
-    *br = lnr_rdgpu_bgzf_result{};
-    br->first = -1;
-    *r = lnr_rdgpu_result{};
-    u64 tlen = job->carry + job->new_text;
+// the inflate step of a BGZF window: the carried text to the front, the blocks inflated behind it, the first bytes of the text (up to 64 KiB)
+// and the blocks' status words on the host.  bad_status != 0: block bad_blk did not inflate.  The caller has set the device.
+static int inflate_window(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, const lnr_rdgpu_window *w, uint32_t *bad_blk, uint32_t *bad_status, u64 *hl_out,
+                          char *err, size_t err_cap) {
+    const u64 tlen = job->carry + job->new_text;
     if (!tlen || tlen > (1ULL << 30) || w->slot >= g->slots || job->comp_len > (1ULL << 31)) { snprintf(err, err_cap, "internal: window of %llu bytes", (unsigned long long)tlen); return -8; }
     if (job->keep_from + job->carry > g->text.cap) { snprintf(err, err_cap, "internal: carried text outside the buffer"); return -8; }
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
     int s;
     // ---- the text buffer: whole tiles; the carried text moves to its front (into a new buffer where this one is too small)
-    const u64 need = ((tlen + RD_TILE - 1) / RD_TILE) * RD_TILE + 16;
+    const u64 need = w->fmt == 3 ? bam_text_cap(tlen) : ((tlen + RD_TILE - 1) / RD_TILE) * RD_TILE + 16;
     if (need > g->text.cap) {
         Buf nb;
         if ((s = dev_need(nb, need, err, err_cap))) return s;
@@ -521,8 +672,26 @@ int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_wind
     if (nblk) {
         RD_CK(hipEventElapsedTime(&f, g->ev_i[0], g->ev_i[1]), -3); g->ms_inf[0] += f;
         const u32 *stt = (const u32 *)g->h_bstat.p;
-        for (u32 k = 0; k < nblk; k++) if (stt[k]) { br->bad_blk = k; br->bad_status = stt[k]; return 0; }
+        for (u32 k = 0; k < nblk; k++) if (stt[k]) { *bad_blk = k; *bad_status = stt[k]; return 0; }
     }
+    *hl_out = hl;
+    return 0;
+}
+
+int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
+                         char *err, size_t err_cap) {
+    *br = lnr_rdgpu_bgzf_result{};
+    br->first = -1;
+    *r = lnr_rdgpu_result{};
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    RD_CK(hipSetDevice(g->device), -3);
+    int s;
+    u64 tlen = job->carry + job->new_text, hl = 0;
+    float f = 0;
+    if ((s = inflate_window(g, job, w, &br->bad_blk, &br->bad_status, &hl, err, err_cap)) || br->bad_status) return s;
+    u8 *d_text = (u8 *)g->text.p;
+    if (w->fmt == 0 && lnr_bam::is_magic((const u8 *)g->h_head.p, hl)) { w->fmt = 3; br->first = 'B'; return 0; }     // BAM: lnr_rdgpu_parse_bam reads this text
     // ---- a window starts at a record start: white space in front of it (the start of the file) is skipped
     const u8 *head = (const u8 *)g->h_head.p;
     u64 lead = 0;
@@ -576,6 +745,164 @@ int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_wind
         RD_CK(hipEventElapsedTime(&f, g->ev_i[2], g->ev_i[3]), -3); g->ms_inf[1] += f;
         for (u64 k = 0; k < n; k++)
             if (br->id_len[k] > r->hdr[2 * k + 1] - r->hdr[2 * k]) { snprintf(err, err_cap, "internal: gathered header of record %llu", (unsigned long long)k); return -8; }
+    }
+    return 0;
+}
+
+int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, const lnr_rdgpu_bam_in *in, lnr_rdgpu_result *r,
+                        lnr_rdgpu_bam_result *br, char *err, size_t err_cap) {
+    using namespace lnr_bam;
+    *br = lnr_rdgpu_bam_result{};
+    *r = lnr_rdgpu_result{};
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    RD_CK(hipSetDevice(g->device), -3);
+    int s;
+    u64 tlen;
+    int n_ref = in->n_ref;
+    w->fmt = 3;
+    if (job) {
+        // ---- inflate behind the carried text, then pass the header where it still stands in front
+        tlen = job->carry + job->new_text;
+        u64 hl = 0;
+        if ((s = inflate_window(g, job, w, &br->bad_blk, &br->bad_status, &hl, err, err_cap)) || br->bad_status) return s;
+        if (!in->hdr_done) {
+            Header h = header_span((const u8 *)g->h_head.p, hl);
+            while (h.status == 1 && h.need <= tlen) {                          // a header longer than the head: the head is downloaded again, larger
+                hl = h.need + 65536 < tlen ? h.need + 65536 : tlen;
+                if (!pin_need(g->h_head, hl)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+                RD_CK(hipMemcpyAsync(g->h_head.p, g->text.p, hl, hipMemcpyDeviceToHost, g->st), -3);
+                RD_CK(hipStreamSynchronize(g->st), -3);
+                h = header_span((const u8 *)g->h_head.p, hl);
+            }
+            if (h.status) { br->hdr_state = h.status < 0 ? 2 : 1; return 0; }
+            br->lead = h.first; br->n_ref = n_ref = h.n_ref;
+            if (h.first) {
+                if ((s = move_text(g, (u8 *)g->text.p, 0, h.first, tlen - h.first, err, err_cap))) return s;
+                tlen -= h.first;
+            }
+        }
+    } else {
+        tlen = w->len;
+        if (!tlen || tlen > (1ULL << 30) || w->slot >= g->slots) { snprintf(err, err_cap, "internal: window of %llu bytes", (unsigned long long)tlen); return -8; }
+        if ((s = dev_need(g->text, bam_text_cap(tlen), err, err_cap))) return s;
+        const double t0 = wall_ms();
+        RD_CK(hipMemcpyAsync(g->text.p, w->text, tlen, hipMemcpyHostToDevice, g->st), -3);
+        RD_CK(hipStreamSynchronize(g->st), -3);
+        g->ms[0] += wall_ms() - t0;
+    }
+    w->len = tlen;
+    if (!tlen) return 0;
+    if (g->text.cap < bam_text_cap(tlen)) { snprintf(err, err_cap, "internal: text buffer of %llu bytes", (unsigned long long)g->text.cap); return -8; }
+    Block &b = g->blk[w->slot];
+    if (w->base_base + w->free + 16 > b.reads.cap || 8 * (w->rec_base + w->allowed + 1) > b.off.cap) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
+    const u8 *d_text = (const u8 *)g->text.p;
+    const u32 nt = (u32)((tlen + BAM_TILE - 1) / BAM_TILE);
+    // ---- find, stitch: the record starts of the window
+    if ((s = dev_need(g->blist, 4ULL * nt * BAM_SLICE, err, err_cap)) || (s = dev_need(g->btiles, (u64)nt * sizeof(Tile), err, err_cap)) ||
+        (s = dev_need(g->bcnt, 4ULL * nt, err, err_cap)) || (s = dev_need(g->bprefix, 8ULL * (nt + 1), err, err_cap)) || (s = dev_need(g->bstitch, sizeof(BamStitch), err, err_cap))) return s;
+    if (!pin_need(g->h_bstitch, sizeof(BamStitch))) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    RD_CK(hipEventRecord(g->ev_b[0], g->st), -3);
+    hipLaunchKernelGGL(k_bam_find, dim3(nt), dim3(64), 0, g->st, d_text, tlen, n_ref, (u32 *)g->blist.p, (Tile *)g->btiles.p);
+    RD_CK(hipEventRecord(g->ev_b[1], g->st), -3);
+    hipLaunchKernelGGL(k_bam_stitch, dim3(1), dim3(64), 0, g->st, d_text, tlen, n_ref, nt, (u32 *)g->blist.p, (const Tile *)g->btiles.p, (u32 *)g->bcnt.p, (u64 *)g->bprefix.p,
+                       (BamStitch *)g->bstitch.p);
+    RD_CK(hipMemcpyAsync(g->h_bstitch.p, g->bstitch.p, sizeof(BamStitch), hipMemcpyDeviceToHost, g->st), -3);
+    RD_CK(hipStreamSynchronize(g->st), -3);
+    RD_CK(hipGetLastError(), -3);
+    const BamStitch S = *(const BamStitch *)g->h_bstitch.p;
+    const u64 nrec = S.nrec;
+    if (S.consumed > tlen || nrec > tlen / MIN_REC + 1 || S.flag > CH_CUT) { snprintf(err, err_cap, "internal: the stitch found %llu records", (unsigned long long)nrec); return -8; }
+    // ---- per-record metadata to the host (never a base)
+    const Meta *M = nullptr;
+    if (nrec) {
+        if ((s = dev_need(g->bmeta, nrec * sizeof(Meta), err, err_cap))) return s;
+        if (!pin_need(g->h_bmeta, nrec * sizeof(Meta))) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+        RD_CK(hipMemsetAsync(g->bmeta.p, 0xff, nrec * sizeof(Meta), g->st), -3);
+        hipLaunchKernelGGL(k_bam_meta, dim3(nt), dim3(64), 0, g->st, d_text, tlen, (const u32 *)g->blist.p, (const u32 *)g->bcnt.p, (const u64 *)g->bprefix.p, nrec, (Meta *)g->bmeta.p);
+    }
+    RD_CK(hipEventRecord(g->ev_b[2], g->st), -3);
+    double t0 = wall_ms();
+    if (nrec) {
+        RD_CK(hipMemcpyAsync(g->h_bmeta.p, g->bmeta.p, nrec * sizeof(Meta), hipMemcpyDeviceToHost, g->st), -3);
+        RD_CK(hipStreamSynchronize(g->st), -3);
+        RD_CK(hipGetLastError(), -3);
+        M = (const Meta *)g->h_bmeta.p;
+    }
+    // ---- the take, on the host: the delivered records' lengths in order against the limits
+    std::vector<u32> lens; std::vector<u64> which;
+    for (u64 k = 0; k < nrec; k++) {
+        const u32 flag = M[k].flag_name & 0xffffu, lname = M[k].flag_name >> 16;
+        const u64 end = (u64)M[k].off + HEAD + lname + 4ULL * M[k].n_cigar + ((u64)M[k].l_seq + 1) / 2;
+        if (lname < 1 || end > S.consumed || (k && M[k].off <= M[k - 1].off)) { snprintf(err, err_cap, "internal: metadata of record %llu", (unsigned long long)k); return -8; }
+        if (delivered(flag)) { lens.push_back(M[k].l_seq); which.push_back(k); }
+    }
+    const lnr_bam::Take T = lnr_bam::take(lens.data(), lens.size(), w->free, w->allowed, w->rec_base == 0);
+    // the host reader meets a refused record (or the end of the file inside one) when it has taken every delivered record in front of it
+    // and may read on: then this call is the one that fails
+    const bool at_end = !T.full && T.n < w->allowed;
+    if (at_end && (S.flag == CH_BAD || (S.flag == CH_CUT && w->eof))) { br->bad = S.flag == CH_BAD ? 1 : 2; br->bad_ord = nrec; br->bad_off = S.bad_off; return 0; }
+    // what is used up: everything in front of the first delivered record that was not taken
+    const u64 stop = T.n < which.size() ? which[T.n] : nrec;
+    r->n = T.n; r->bases = T.bases; r->full = T.full; r->too_big = T.too_big; r->handover = 0;
+    r->consumed = stop < nrec ? M[stop].off : S.consumed;
+    br->passed = stop; br->skipped = stop - T.n; br->tiles = nt; br->repaired = S.repaired;
+    // ---- emit: jobs and chunks up, ordinals and offsets into the block
+    u64 *h_off = (u64 *)b.h_off.p;
+    const u64 n = T.n;
+    if (!pin_need(g->h_bjobs, (n + 1) * sizeof(BamJob)) || !pin_need(g->h_idoff, 8 * n + 8) || !pin_need(g->h_idlen, 4 * n + 4) || !pin_need(g->h_hdr, 16 * n + 16)) {
+        snprintf(err, err_cap, "pinned host allocation failed"); return -4;
+    }
+    BamJob *J = (BamJob *)g->h_bjobs.p;
+    u64 *span = (u64 *)g->h_hdr.p, *ido = (u64 *)g->h_idoff.p, id_total = 0, at = w->base_base, nchunk = 0;
+    for (u64 i = 0; i < n; i++) {
+        const Meta &m = M[which[i]];
+        const u32 flag = m.flag_name & 0xffffu, lname = m.flag_name >> 16;
+        J[i].dst = at; J[i].seq = m.off + HEAD + lname + 4 * m.n_cigar; J[i].l_seq = m.l_seq; J[i].rev = reversed(flag) ? 1u : 0u; J[i].pad = 0;
+        br->reverse += J[i].rev;
+        h_off[w->rec_base + i] = at;
+        at += m.l_seq;
+        nchunk += ((u64)m.l_seq + BAM_CHUNK - 1) / BAM_CHUNK;
+        span[2 * i] = (u64)m.off + HEAD; span[2 * i + 1] = (u64)m.off + HEAD + lname - 1;
+        ido[i] = id_total; id_total += lname - 1;
+    }
+    h_off[w->rec_base + n] = at;
+    if (at != w->base_base + T.bases || nchunk > 0xffffffffULL) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
+    if (!pin_need(g->h_bchunks, (nchunk + 1) * sizeof(BamChunk)) || !pin_need(g->h_idbytes, id_total + 1)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    BamChunk *C = (BamChunk *)g->h_bchunks.p;
+    for (u64 i = 0, c = 0; i < n; i++) for (u32 st = 0; st < J[i].l_seq; st += BAM_CHUNK) { C[c].rec = (u32)i; C[c].start = st; c++; }
+    br->ids = (const char *)g->h_idbytes.p; br->id_off = ido; br->id_len = (const uint32_t *)g->h_idlen.p;
+    g->ms[4] += wall_ms() - t0;
+    RD_CK(hipMemcpyAsync((u64 *)b.off.p + w->rec_base, h_off + w->rec_base, 8 * (n + 1), hipMemcpyHostToDevice, g->st), -3);
+    RD_CK(hipEventRecord(g->ev_b[3], g->st), -3);
+    if (n) {
+        if ((s = dev_need(g->bjobs, n * sizeof(BamJob), err, err_cap)) || (s = dev_need(g->bchunks, (nchunk + 1) * sizeof(BamChunk), err, err_cap)) ||
+            (s = dev_need(g->hdr, 16 * n, err, err_cap)) || (s = dev_need(g->idoff, 8 * n, err, err_cap)) || (s = dev_need(g->idlen, 4 * n, err, err_cap)) ||
+            (s = dev_need(g->idbytes, id_total + 1, err, err_cap))) return s;
+        RD_CK(hipMemcpyAsync(g->bjobs.p, J, n * sizeof(BamJob), hipMemcpyHostToDevice, g->st), -3);
+        if (nchunk) RD_CK(hipMemcpyAsync(g->bchunks.p, C, nchunk * sizeof(BamChunk), hipMemcpyHostToDevice, g->st), -3);
+        RD_CK(hipMemcpyAsync(g->hdr.p, span, 16 * n, hipMemcpyHostToDevice, g->st), -3);
+        RD_CK(hipMemcpyAsync(g->idoff.p, ido, 8 * n, hipMemcpyHostToDevice, g->st), -3);
+        RD_CK(hipEventRecord(g->ev_b[3], g->st), -3);
+        if (nchunk) hipLaunchKernelGGL(k_bam_emit, dim3((u32)nchunk), dim3(64), 0, g->st, d_text, tlen, (const BamJob *)g->bjobs.p, (const BamChunk *)g->bchunks.p, (u32)nchunk,
+                                       (u8 *)b.reads.p, (u64)(w->base_base + w->free));
+        RD_CK(hipEventRecord(g->ev_b[4], g->st), -3);
+        RD_CK(hipEventRecord(g->ev_i[2], g->st), -3);
+        hipLaunchKernelGGL(k_bam_names, dim3((u32)n), dim3(64), 0, g->st, d_text, tlen, (const u64 *)g->hdr.p, (const u64 *)g->idoff.p, n, (u8 *)g->idbytes.p, id_total, (u32 *)g->idlen.p);
+        RD_CK(hipEventRecord(g->ev_i[3], g->st), -3);
+        RD_CK(hipMemcpyAsync(g->h_idlen.p, g->idlen.p, 4 * n, hipMemcpyDeviceToHost, g->st), -3);
+        if (id_total) RD_CK(hipMemcpyAsync(g->h_idbytes.p, g->idbytes.p, id_total, hipMemcpyDeviceToHost, g->st), -3);
+    } else RD_CK(hipEventRecord(g->ev_b[4], g->st), -3);
+    RD_CK(hipStreamSynchronize(g->st), -3);
+    RD_CK(hipGetLastError(), -3);
+    float f = 0;
+    RD_CK(hipEventElapsedTime(&f, g->ev_b[0], g->ev_b[1]), -3); br->find_ms = f; g->ms[1] += f;
+    RD_CK(hipEventElapsedTime(&f, g->ev_b[1], g->ev_b[2]), -3); br->stitch_ms = f; g->ms[2] += f;
+    RD_CK(hipEventElapsedTime(&f, g->ev_b[3], g->ev_b[4]), -3); br->emit_ms = f; g->ms[3] += f;
+    if (n) {
+        RD_CK(hipEventElapsedTime(&f, g->ev_i[2], g->ev_i[3]), -3); g->ms_inf[1] += f;
+        for (u64 i = 0; i < n; i++)
+            if (br->id_len[i] != span[2 * i + 1] - span[2 * i]) { snprintf(err, err_cap, "internal: gathered name of record %llu", (unsigned long long)i); return -8; }
     }
     return 0;
 }
