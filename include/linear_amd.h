@@ -387,6 +387,50 @@ lnr_status lnr_writer_format_bam_gpu(lnr_writer *w, const lnr_cords *cords, cons
 lnr_status lnr_writer_format_bam_dev(lnr_writer *w, const lnr_cords_dev *cords, const uint8_t *d_reads_concat_or_null, const uint64_t *d_read_off,
                                      const char *read_ids, const uint64_t *id_off, const char **data, uint64_t *size);
 
+/* Coordinate-sorted BAM with a BAI index (an extension: the reference tells its users to run `samtools sort` / `samtools index`).
+ * A sort mode of the GPU writer.  Between lnr_writer_sort_begin and lnr_writer_sort_finish, lnr_writer_format_bam_gpu / _dev keep the
+ * batch's raw records on the device (copied into segments the GPU side owns: at least 256 MiB each -- less where max_device_bytes leaves
+ * less --, a batch contiguous in one) and return *size = 0; lnr_writer_bam_header puts "@HD\tVN:1.6\tSO:coordinate\n" in front of its text;
+ * every other call is unchanged.  max_device_bytes bounds the record bytes kept (0: no bound of its own); a batch that would pass it, or a
+ * segment that cannot be allocated, makes the BAM call return LNR_ERR_NOMEM (lnr_writer_error names the bytes held and asked for) and
+ * leaves the batches added before intact.  ALL records stay in HBM until lnr_writer_sort_end: about 0.8 KB per read without SEQ, 15.8 KB
+ * per 10 kb read with it; spilling to the host is not built.
+ * THE ORDER: (uint32)refID (so -1 sorts last), (uint32)pos, the reverse-strand bit (flag & 0x10, forward first), then the record's byte
+ * offset in the stream of records as they were added (batches in call order, records as the BAM calls emit them).  The order is total: the
+ * output is a function of the input alone.  Whether samtools breaks (refID, pos) ties by strand has not been verified here.
+ * lnr_writer_sort_finish sorts on the device (k_sort_index per batch, rocPRIM's stable radix sort, a scan of the sorted sizes).  The sorted
+ * stream S is then handed out by lnr_writer_sort_next in pieces of piece_members (0: 4096) BGZF members: k_sort_gather writes S[a, b) of
+ * the piece, k_bgzf_deflate / k_bgzf_pack compress it; member k holds S[k * 0xff00, ...) whatever piece_members is, so the file's bytes do
+ * not depend on it.  *size == 0: no piece is left.  A file = the members of the header, the pieces, lnr_writer_bgzf_eof.
+ * lnr_writer_sort_bai (valid once lnr_writer_sort_next has returned size 0): the .bai of that file, first_offset = file bytes in front of
+ * the first record member (the header's members).  Layout: "BAI\1", n_ref = nseq, per reference n_bin, per bin (ascending) bin, n_chunk,
+ * chunks (beg, end), n_intv, ioffset[]; n_no_coor.  Virtual offset of stream offset s: (first_offset + member_off[s / 0xff00]) << 16 |
+ * s % 0xff00.  Bin = reg2bin(pos, end), end = pos + max(1, reference bases of the CIGAR); a bin's chunks in file order, a record whose
+ * predecessor in the file has the same refID and bin extends that chunk, no other merging; pseudo-bin 37450 last (first start .. last end;
+ * records without / with flag 4); ioffset[w] = smallest start of the records over 16 KiB window w, an empty window takes the next higher
+ * one's value; a reference without records has n_bin 0 and n_intv 0; refID < 0 counts in n_no_coor.  A record with refID >= 0 and pos < 0
+ * or end > 2^29 cannot be indexed: LNR_ERR_UNSUPPORTED naming the record (the sorted BAM stays valid).  Byte equality with `samtools index`
+ * is not claimed (htslib merges chunks further).  Bytes returned live until the writer's next call.
+ * Errors: before lnr_writer_gpu_open, and calls out of order (begin twice, next before finish, bai before the last piece): LNR_ERR_ARG with
+ * the reason in lnr_writer_error.  lnr_writer_sort_end frees the segments and leaves the mode; lnr_writer_destroy does so too.
+ * lnr_writer_sort_host / lnr_writer_bai_host: the same order and the same index on the host, no device needed (the in-library yardsticks). */
+typedef struct {
+    uint64_t records, record_bytes;  /* kept records and their bytes (the length of S) */
+    uint64_t device_bytes;           /* device memory the sort holds: segments and per-record arrays */
+    uint64_t members;                /* BGZF members of S */
+    double index_ms, sort_ms;        /* k_sort_index summed over the batches; the sort with its gathers and scan (HIP events) */
+    double gather_ms, deflate_ms, pack_ms, download_ms;   /* summed over the pieces handed out so far */
+} lnr_sort_info;
+lnr_status lnr_writer_sort_begin(lnr_writer *w, uint64_t max_device_bytes);
+lnr_status lnr_writer_sort_finish(lnr_writer *w, uint32_t piece_members, lnr_sort_info *info /* optional; piece times still 0 */);
+lnr_status lnr_writer_sort_next(lnr_writer *w, const char **data, uint64_t *size);
+lnr_status lnr_writer_sort_bai(lnr_writer *w, uint64_t first_offset, const char **data, uint64_t *size);
+lnr_status lnr_writer_sort_info_get(const lnr_writer *w, lnr_sort_info *info);      /* any time between finish and end: the sums so far */
+lnr_status lnr_writer_sort_end(lnr_writer *w);
+lnr_status lnr_writer_sort_host(lnr_writer *w, const char *records, uint64_t size, const char **sorted);
+lnr_status lnr_writer_bai_host(lnr_writer *w, const char *sorted_records, uint64_t size, uint64_t first_offset, const uint64_t *member_off /* n_members + 1 */,
+                               uint64_t n_members, const char **data, uint64_t *bai_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,12 +80,19 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_writer_set_bgzf", "lnr_writer_bgzf_bytes_gpu", "lnr_writer_bgzf_eof", "lnr_writer_bgzf_stats",
            "lnr_writer_bam_header", "lnr_writer_format_bam", "lnr_writer_format_bam_gpu", "lnr_writer_format_bam_dev",
            "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats",
-           "lnr_reader_gpu_bam_stats", "lnr_reader_gpu_bam_tile", "lnr_reader_format"]
+           "lnr_reader_gpu_bam_stats", "lnr_reader_gpu_bam_tile", "lnr_reader_format",
+           "lnr_writer_sort_begin", "lnr_writer_sort_finish", "lnr_writer_sort_next", "lnr_writer_sort_bai", "lnr_writer_sort_info_get", "lnr_writer_sort_end",
+           "lnr_writer_sort_host", "lnr_writer_bai_host"]
 
 
 class LnrBgzfStats(C.Structure):
     _fields_ = [("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("text_bytes", C.c_uint64), ("compressed_bytes", C.c_uint64),
                 ("deflate_ms", C.c_double), ("pack_ms", C.c_double)]
+
+
+class LnrSortInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "record_bytes", "device_bytes", "members")] + \
+               [(k, C.c_double) for k in ("index_ms", "sort_ms", "gather_ms", "deflate_ms", "pack_ms", "download_ms")]
 
 
 def load_library() -> C.CDLL:
@@ -158,6 +165,14 @@ def load_library() -> C.CDLL:
     lib.lnr_writer_format_bam.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.c_uint32, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_format_bam_gpu.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_format_bam_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev), C.c_void_p, C.c_void_p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_sort_begin.argtypes = [C.c_void_p, C.c_uint64]
+    lib.lnr_writer_sort_finish.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LnrSortInfo)]
+    lib.lnr_writer_sort_next.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_sort_bai.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_sort_info_get.argtypes = [C.c_void_p, C.POINTER(LnrSortInfo)]
+    lib.lnr_writer_sort_end.argtypes = [C.c_void_p]
+    lib.lnr_writer_sort_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.lnr_writer_bai_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, _u64p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
     return lib
 
 
@@ -632,6 +647,53 @@ class Writer:
         out, size = C.c_void_p(), C.c_uint64()
         self._check(self.lib.lnr_writer_format_bam_dev(self.h, C.byref(cords_dev), d_reads_ptr, d_off_ptr, blob, _p(ido, _u64p), C.byref(out), C.byref(size)))
         return C.string_at(out, size.value) if copy else (out.value, size.value)
+
+    # ---- coordinate-sorted BAM with a BAI index: a sort mode of the GPU writer (include/linear_amd.h)
+    def sort_begin(self, max_device_bytes: int = 0) -> None:
+        """From here on format_bam_gpu / format_bam_dev keep their records on the device and return b""; bam_header carries @HD SO:coordinate."""
+        self._check(self.lib.lnr_writer_sort_begin(self.h, max_device_bytes))
+
+    def sort_finish(self, piece_members: int = 0) -> dict:
+        """Sorts the kept records on the device; the pieces then come from sort_pieces().  Returns sort_info()."""
+        info = LnrSortInfo()
+        self._check(self.lib.lnr_writer_sort_finish(self.h, piece_members, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in LnrSortInfo._fields_}
+
+    def sort_pieces(self):
+        """Iterator over the BGZF members of the sorted stream, a piece of at most piece_members members at a time."""
+        while True:
+            out, size = C.c_void_p(), C.c_uint64()
+            self._check(self.lib.lnr_writer_sort_next(self.h, C.byref(out), C.byref(size)))
+            if size.value == 0:
+                return
+            yield C.string_at(out, size.value)
+
+    def sort_bai(self, first_offset: int) -> bytes:
+        """The .bai of header members (first_offset bytes) + pieces + EOF; valid once sort_pieces() is exhausted."""
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_sort_bai(self.h, first_offset, C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value)
+
+    def sort_info(self) -> dict:
+        info = LnrSortInfo()
+        self._check(self.lib.lnr_writer_sort_info_get(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in LnrSortInfo._fields_}
+
+    def sort_end(self) -> None:
+        self._check(self.lib.lnr_writer_sort_end(self.h))
+
+    def sort_host(self, records: bytes) -> bytes:
+        """The record stream in the coordinate order, on the host (no device needed)."""
+        out = C.c_void_p()
+        self._check(self.lib.lnr_writer_sort_host(self.h, records, len(records), C.byref(out)))
+        return C.string_at(out, len(records))
+
+    def bai_host(self, sorted_records: bytes, first_offset: int, member_off) -> bytes:
+        """The .bai of a sorted record stream whose members (0xff00 bytes of it each) lie at first_offset + member_off[k]; member_off has one more entry than members."""
+        mo = np.ascontiguousarray(member_off, dtype=np.uint64)
+        out, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_bai_host(self.h, sorted_records, len(sorted_records), first_offset, _p(mo, _u64p), mo.size - 1, C.byref(out), C.byref(size)))
+        return C.string_at(out, size.value)
 
     def sam_header(self, command_line: str) -> bytes:
         text, size = C.c_void_p(), C.c_uint64()

@@ -26,6 +26,11 @@
 //                  members of the header (lnr_writer_bam_header through lnr_writer_bgzf_bytes_gpu; -ot 8: the "@RG\t ID:" form), of every
 //                  block, and the EOF marker.  --sam-seq puts SEQ into the records as it does into the .sam.  The header lists the genome
 //                  (the reference writes n_ref 0: include/linear_amd.h).
+//   sorted BAM     --sort (extension, needs -ot with 4 or 8 and --gpu-writer): the records of an output file stay on the GPU (lnr_writer_sort_begin
+//                  before the file's first block), and when the file ends they are sorted by coordinate there: the header's members (with
+//                  @HD SO:coordinate), the pieces of lnr_writer_sort_next as they come, the EOF marker, then PREFIX.bam.bai / PREFIX_pbsv.bam.bai
+//                  from lnr_writer_sort_bai(bytes of that file's header).  The .sam / .apf next to it stay in read order.  All records of
+//                  a file are held in HBM until it ends.
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
 //   BAM input      (extension) a read file may be a BAM, aligned or unaligned: found by its content (the first four inflated bytes are "BAM\1"), never
@@ -62,6 +67,12 @@ lnr_status lnr_writer_format_bam_dev(lnr_writer *, const lnr_cords_dev *, const 
 lnr_status lnr_reader_gpu_open(lnr_reader *, int32_t, uint32_t) __attribute__((weak));
 lnr_status lnr_reader_next_dev(lnr_reader *, uint64_t, uint32_t, const uint8_t **, const uint64_t **, const uint64_t **, uint32_t *) __attribute__((weak));
 int lnr_reader_format(lnr_reader *) __attribute__((weak));
+// entry points only --sort uses
+lnr_status lnr_writer_sort_begin(lnr_writer *, uint64_t) __attribute__((weak));
+lnr_status lnr_writer_sort_finish(lnr_writer *, uint32_t, lnr_sort_info *) __attribute__((weak));
+lnr_status lnr_writer_sort_next(lnr_writer *, const char **, uint64_t *) __attribute__((weak));
+lnr_status lnr_writer_sort_bai(lnr_writer *, uint64_t, const char **, uint64_t *) __attribute__((weak));
+lnr_status lnr_writer_sort_end(lnr_writer *) __attribute__((weak));
 }
 
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -72,7 +83,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0;
     std::vector<int> devices;
 };
 
@@ -94,7 +105,10 @@ static void usage() {
             "    --gpu-reader               parse the read files on the first GPU in use and keep the reads there: reader -> filter -> writer on device buffers {off}\n"
             "                               (one GPU; with --sam-seq it needs --gpu-writer: the read bases are not on the host)\n"
             "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n"
-            "    --bgzf                     compress the text on the GPU and write PREFIX.sam.gz / PREFIX.apf.gz (BGZF); needs --gpu-writer {off}\n");
+            "    --bgzf                     compress the text on the GPU and write PREFIX.sam.gz / PREFIX.apf.gz (BGZF); needs --gpu-writer {off}\n"
+            "    --sort                     sort the .bam / _pbsv.bam by coordinate on the GPU and write PREFIX.bam.bai next to it; needs -ot with 4 or 8 and\n"
+            "                               --gpu-writer; every record of a file stays in GPU memory until the file ends (about 0.8 KB per read, with\n"
+            "                               --sam-seq 16 KB per 10 kb read: some 10^7 such reads do not fit) {off}\n");
 }
 
 // returns 0 ok, 1 error, 2 help shown
@@ -123,6 +137,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         if (name == "sam-seq") { o.sam_seq = 1; continue; }
         if (name == "gpu-reader") { o.gpu_reader = 1; continue; }
         if (name == "bgzf") { o.bgzf = 1; continue; }
+        if (name == "sort") { o.sort = 1; continue; }
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         const Opt *op = nullptr;
@@ -195,6 +210,9 @@ struct Outputs {
     FILE *fsam = nullptr, *fapf = nullptr, *fbam = nullptr, *fpbsv = nullptr;
     std::string cur_prefix; bool any_open = false; int cur_file = -1;
     bool bgzf = false;                       // --bgzf: .gz names, the SAM header comes compressed, the EOF marker ends every file
+    lnr_writer *sort_wr = nullptr;           // --sort: the writer that holds the records of the files in work; close() sorts and writes them
+    uint64_t head_bam = 0, head_pbsv = 0;    // bytes of the headers' members: where the record members start
+    std::string sort_err;                    // why close() could not finish the sorted files
     // makes the files of read file `file` current; h = the headers as they go into the files.  false: the files cannot be written (err says which)
     bool turn_to(const Options &o, int file, const Headers &h, std::string &err) {
         if (file == cur_file) return true;
@@ -202,6 +220,7 @@ struct Outputs {
         std::string prefix = o.oPath.empty() ? output_prefix_of(o.r_paths[(size_t)file]) : o.oPath;
         if (any_open && !(o.oPath.empty() && prefix != cur_prefix)) return true;
         close();
+        if (!sort_err.empty()) { err = sort_err; return false; }
         bgzf = o.bgzf != 0;
         fsam = (o.f_output_type & 2) ? fopen((prefix + (bgzf ? ".sam.gz" : ".sam")).c_str(), "wb") : nullptr;
         fapf = (o.f_output_type & 1) ? fopen((prefix + (bgzf ? ".apf.gz" : ".apf")).c_str(), "wb") : nullptr;
@@ -215,9 +234,41 @@ struct Outputs {
         if (fbam) fwrite(h.bam.data(), 1, h.bam.size(), fbam);
         if (fpbsv) fwrite(h.pbsv.data(), 1, h.pbsv.size(), fpbsv);
         cur_prefix = prefix; any_open = true;
+        head_bam = h.bam.size(); head_pbsv = h.pbsv.size();
         return true;
     }
+    // --sort: the kept records of the files in work, sorted: their members into both files; after the EOF markers the indexes; a new round begins
+    bool sorted_records() {
+        const char *d; uint64_t z;
+        if (lnr_writer_sort_finish(sort_wr, 0, nullptr) != LNR_OK) return false;
+        for (;;) {
+            if (lnr_writer_sort_next(sort_wr, &d, &z) != LNR_OK) return false;
+            if (!z) return true;
+            if ((fbam && fwrite(d, 1, z, fbam) != z) || (fpbsv && fwrite(d, 1, z, fpbsv) != z)) { sort_err = "write error (.bam)"; return false; }
+        }
+    }
+    bool sorted_index(const std::string &path, uint64_t head) {
+        const char *d; uint64_t z;
+        if (lnr_writer_sort_bai(sort_wr, head, &d, &z) != LNR_OK) return false;
+        FILE *f = fopen(path.c_str(), "wb");
+        const bool ok = f && fwrite(d, 1, z, f) == z;
+        if (f) fclose(f);
+        if (!ok) sort_err = "can't write " + path;
+        return ok;
+    }
     void close() {
+        const bool sorting = sort_wr && (fbam || fpbsv);
+        const bool had_bam = fbam != nullptr, had_pbsv = fpbsv != nullptr;
+        bool sorted = sorting && sorted_records();
+        close_files();
+        if (sorted) sorted = (!had_bam || sorted_index(cur_prefix + ".bam.bai", head_bam)) && (!had_pbsv || sorted_index(cur_prefix + "_pbsv.bam.bai", head_pbsv));
+        if (sorting) {
+            if (!sorted && sort_err.empty()) sort_err = std::string("--sort: ") + lnr_writer_error(sort_wr);
+            lnr_writer_sort_end(sort_wr);
+            if (lnr_writer_sort_begin(sort_wr, 0) != LNR_OK && sort_err.empty()) sort_err = std::string("--sort: ") + lnr_writer_error(sort_wr);      // the next file's round
+        }
+    }
+    void close_files() {
         const char *eof = nullptr; uint64_t n = 0;
         if (bgzf && (fsam || fapf)) lnr_writer_bgzf_eof(&eof, &n);
         if (fsam) { if (n) fwrite(eof, 1, n, fsam); fclose(fsam); }
@@ -244,6 +295,12 @@ int main(int argc, char **argv) {
     else if (o.reform_ccs) nb = "-r 1"; else if (o.sensitivity != 1 && o.sensitivity != 2) nb = "-p other than 1 or 2"; else if (!o.bal_flag) nb = "-b 0 (the reference's -b 0 path writes a header-only SAM)";
     else if (o.index_t != 1 && o.index_t != 2) nb = "-i other than 1 or 2";
     if (nb) { fprintf(stderr, "\033[1;31mE[m02G]:\033[0m %s is not built in the MI355X filter path\n", nb); return 1; }
+    if (o.sort && !o.gpu_writer) { fprintf(stderr, "\033[1;31mE:\033[0m --sort sorts the BAM records on the GPU that encodes them: it needs --gpu-writer\n"); return 1; }
+    if (o.sort && !(o.f_output_type & 12)) { fprintf(stderr, "\033[1;31mE:\033[0m --sort sorts BAM output: it needs -ot with 4 (.bam) or 8 (_pbsv.bam)\n"); return 1; }
+    if (o.sort && (!lnr_writer_sort_begin || !lnr_writer_sort_finish || !lnr_writer_sort_next || !lnr_writer_sort_bai || !lnr_writer_sort_end)) {
+        fprintf(stderr, "\033[1;31mE:\033[0m --sort: this library has no sort mode of the writer\n");
+        return 1;
+    }
     if ((o.f_output_type & 12) && !o.gpu_writer) {
         fprintf(stderr, "\033[1;31mE:\033[0m -ot 4 / 8 (BAM output) is encoded and compressed on the GPU: it needs --gpu-writer (BAM on the writer's host threads is not built)\n");
         return 1;
@@ -359,6 +416,13 @@ int main(int argc, char **argv) {
         for (auto *c : ctx) lnr_destroy(c);
         return 1;
     }
+    // --sort: the mode is on before the headers are made (they carry @HD SO:coordinate); Outputs::close ends a file's round and begins the next
+    if (o.sort && lnr_writer_sort_begin(wr, 0) != LNR_OK) {
+        fprintf(stderr, "\033[1;31mE:\033[0m --sort: %s\n", lnr_writer_error(wr));
+        lnr_writer_destroy(wr);
+        for (auto *c : ctx) lnr_destroy(c);
+        return 1;
+    }
     if (o.gpu_reader) {                                                                          // before any output file is opened, too
         std::string why;
         if (!lnr_filter_batch_dev || !lnr_cords_to_host || !lnr_writer_format_dev || !lnr_writer_format_seq_dev || !lnr_writer_format_bam_dev || !lnr_reader_gpu_open || !lnr_reader_next_dev)
@@ -396,6 +460,11 @@ int main(int argc, char **argv) {
         }
         std::vector<DBlock> dblocks(3);
         for (auto &b : dblocks) freeq.push(&b);
+        // --sort with one output per read file: the writer thread ends a file's sort round (lnr_writer_sort_finish .. _begin on `wr`) while this
+        // thread would add the next file's records to it.  A fence block (n == 0) goes through the queue in front of the first block of a new
+        // output; the calculator waits until the writer thread has turned to the new files.
+        DBlock fence; std::mutex fm; std::condition_variable fcv; uint64_t fences_passed = 0, fences_sent = 0;
+        std::string calc_prefix; bool calc_has_prefix = false;
         uint64_t cap = (uint64_t)o.block_reads * 12000 + (1u << 20);
         if (cap > ((uint64_t)3 << 30)) cap = (uint64_t)3 << 30;
         lnr_reader *cur = nullptr;                               // the reader of the file in work: its device blocks live until the file's last block is written
@@ -440,6 +509,18 @@ int main(int argc, char **argv) {
                 lnr_cords_dev dev{};
                 lnr_status s = lnr_filter_batch_dev(ctx[0], b->d_reads, b->d_off, b->n, &dev);
                 if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
+                if (o.sort && o.oPath.empty()) {
+                    const std::string prefix = output_prefix_of(o.r_paths[(size_t)b->file]);
+                    if (calc_has_prefix && prefix != calc_prefix) {
+                        fence.n = 0; fence.file = b->file;
+                        fences_sent++;
+                        doneq.push(&fence);
+                        std::unique_lock<std::mutex> l(fm);
+                        while (fences_passed != fences_sent && !failed) fcv.wait_for(l, std::chrono::milliseconds(50));      // (a failure elsewhere does not signal here)
+                        if (failed) break;
+                    }
+                    calc_prefix = prefix; calc_has_prefix = true;
+                }
                 if (o.gpu_writer) {                                  // the text of the block, from the device buffers
                     const char *text; uint64_t size;
                     b->sam.clear(); b->apf.clear(); b->bam.clear();
@@ -477,9 +558,11 @@ int main(int argc, char **argv) {
             FILE *&fsam = out.fsam, *&fapf = out.fapf;
             const char *text; uint64_t size;
             DBlock *b = nullptr;
+            if (o.sort) out.sort_wr = wr;
             while (doneq.pop(b) && !failed) {
                 std::string oe;
-                if (!out.turn_to(o, b->file, sam_header, oe)) { fail(oe); break; }
+                if (!out.turn_to(o, b->file, sam_header, oe)) { fail(oe); fcv.notify_all(); break; }
+                if (!b->n) { { std::lock_guard<std::mutex> l(fm); fences_passed++; } fcv.notify_all(); continue; }      // a fence: the files are turned
                 double tw0 = now();
                 bool ok = true;
                 if (o.gpu_writer) {
@@ -497,7 +580,10 @@ int main(int argc, char **argv) {
                 total_reads += b->n;
                 freeq.push(b);
             }
+            if (failed) out.sort_wr = nullptr;                       // (the calculator may still be at the writer: nothing is sorted after a failure)
             out.close();
+            if (!out.sort_err.empty()) fail(out.sort_err);
+            fcv.notify_all();
         });
         calc.join();
         writer.join();
@@ -613,6 +699,7 @@ int main(int argc, char **argv) {
         Headers sam_header;
         uint64_t want = 0;
         const char *text; uint64_t size;
+        if (o.sort) out.sort_wr = wr;
         if (!header_of(sam_header)) sh.fail(std::string(want_bam ? "BAM / BGZF header: " : "--bgzf: ") + lnr_writer_error(wr));
         for (;;) {
             Block *b = nullptr;
@@ -648,7 +735,9 @@ int main(int argc, char **argv) {
             sh.free_blocks.push(b);
             want++;
         }
+        if (sh.failed) out.sort_wr = nullptr;
         out.close();
+        if (!out.sort_err.empty()) sh.fail(out.sort_err);
     });
     for (auto &t : workers) t.join();
     { std::lock_guard<std::mutex> l(sh.m); sh.workers_done = true; }

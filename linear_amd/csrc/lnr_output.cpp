@@ -18,10 +18,12 @@
 #include "lnr_output_hd.h"
 #include "lnr_output_hook.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <new>
 #include <string>
 #include <thread>
@@ -247,7 +249,12 @@ void apf_read(const Writer &w, const u64 *c, u64 n, u64 L, const char *rid, bool
 
 }  // namespace
 
-struct lnr_writer { Writer w; lnr_outgpu *gpu = nullptr; bool genome_on_gpu = false; char err[256] = ""; };
+struct lnr_writer {
+    Writer w; lnr_outgpu *gpu = nullptr; bool genome_on_gpu = false; char err[256] = "";
+    int sort_state = 0;                        // lnr_writer_sort_*: 0 off, 1 collecting, 2 sorted: pieces go out, 3 every piece handed out
+    std::vector<u64> sort_moff;                // offsets of the members handed out so far in the run of record members (+ the end of the last)
+    std::string sorted, bai;                   // what lnr_writer_sort_host / _sort_bai / _bai_host return
+};
 
 extern "C" {
 
@@ -282,6 +289,7 @@ lnr_status lnr_writer_gpu_open(lnr_writer *wr, int32_t device) {
 
 static lnr_status format_on_gpu(lnr_writer *wr, lnr_outgpu_batch &b, const char **text, uint64_t *size) {
     if (!wr->gpu) { snprintf(wr->err, sizeof wr->err, "lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
+    if (b.what == 3 && wr->sort_state >= 2) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_finish has been called: no BAM call before lnr_writer_sort_end"); return LNR_ERR_ARG; }
     b.thd_large_X = wr->w.thd_large_X; b.thd_DI = wr->w.thd_DI; b.thd_X = wr->w.thd_X;
     wr->err[0] = 0;
     return (lnr_status)lnr_outgpu_format(wr->gpu, &b, text, size, wr->err, sizeof wr->err);
@@ -390,6 +398,7 @@ lnr_status lnr_writer_bam_header(lnr_writer *wr, const char *command_line, int p
     const char *t; uint64_t z;
     lnr_writer_sam_header(wr, command_line, &t, &z);
     std::string text(t, z);
+    if (wr->sort_state) text.insert(0, "@HD\tVN:1.6\tSO:coordinate\n");      // sort mode: the file will be coordinate-sorted
     if (pbsv) {                                        // -ot 8: "@RG\t ID:" (mapper.cpp:308-312)
         size_t p = text.find("@RG\tID:");
         if (p != std::string::npos) text.insert(p + 4, " ");
@@ -451,6 +460,174 @@ lnr_status lnr_writer_format_bam_dev(lnr_writer *wr, const lnr_cords_dev *cords,
     if (!wr || !cords || !read_ids || !id_off || !data || !size || (cords->n_reads && !d_read_off)) return LNR_ERR_ARG;
     lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, 3, 0, 0, 0, d_reads_concat};
     return d_reads_concat ? format_seq_on_gpu(wr, b, data, size) : format_on_gpu(wr, b, data, size);
+}
+
+// ---- coordinate sort + BAI (the order and the index format: include/linear_amd.h).  The host forms walk a record stream; the GPU forms
+// (lnr_output_kernels.hip behind the weak hooks) leave the same per-record arrays, so ONE function writes the index for both.
+namespace {
+constexpr u64 MEMBER_TEXT = 0xff00;            // bytes of the sorted stream per BGZF member
+struct SRec { u64 key; uint32_t flag; i64 end; u64 off, size; };
+bool walk_stream(const char *raw, u64 size, std::vector<SRec> &out, char *err, size_t err_cap) {
+    const uint8_t *r = (const uint8_t *)raw;
+    for (u64 p = 0; p < size;) {
+        const u64 bs = p + 36 <= size ? lnr_out::le32_at(r + p) : 0;
+        if (bs < 32 || p + 4 + bs > size) { snprintf(err, err_cap, "record %zu at byte %llu of the stream: block_size does not fit the %llu bytes given", out.size(), (unsigned long long)p, (unsigned long long)size); return false; }
+        const lnr_out::BamKey k = lnr_out::bam_key(r + p, size - p);
+        out.push_back({lnr_out::bam_sort_key(k), k.flag, k.end, p, 4 + bs});
+        p += 4 + bs;
+    }
+    return true;
+}
+// n records in file order: key, flag, end; off[n + 1] their offsets in the stream
+lnr_status bai_core(uint32_t n_ref, size_t n, const u64 *key, const uint32_t *flag, const i64 *end, const u64 *off, u64 first_offset, const u64 *moff, u64 n_members,
+                    std::string &o, char *err, size_t err_cap) {
+    struct RefIx { std::map<uint32_t, std::vector<std::pair<u64, u64> > > bins; std::vector<u64> lin; u64 first = 0, last = 0, mapped = 0, unmapped = 0; bool any = false; };
+    if ((off[n] + MEMBER_TEXT - 1) / MEMBER_TEXT != n_members) { snprintf(err, err_cap, "%llu bytes of records do not make %llu members", (unsigned long long)off[n], (unsigned long long)n_members); return LNR_ERR_ARG; }
+    auto voff = [&](u64 s) { return (first_offset + moff[s / MEMBER_TEXT]) << 16 | s % MEMBER_TEXT; };
+    std::vector<RefIx> R(n_ref);
+    u64 no_coor = 0;
+    bool have_prev = false; int32_t prev_ref = 0; uint32_t prev_bin = 0;
+    for (size_t i = 0; i < n; i++) {
+        const int32_t ref = (int32_t)(key[i] >> 32), pos = (int32_t)(uint32_t)key[i];
+        if (ref < 0) { no_coor++; have_prev = false; continue; }
+        if ((uint32_t)ref >= n_ref) { snprintf(err, err_cap, "record %zu of the sorted stream has refID %d, the writer has %u sequences", i, (int)ref, n_ref); return LNR_ERR_ARG; }
+        if (pos < 0 || end[i] > ((i64)1 << 29)) {
+            snprintf(err, err_cap, "record %zu of the sorted stream (refID %d, pos %d, end %lld) lies outside what a BAI can index (0 .. 2^29)", i, (int)ref, (int)pos, (long long)end[i]);
+            return LNR_ERR_UNSUPPORTED;
+        }
+        const u64 vs = voff(off[i]), ve = voff(off[i + 1]);
+        const uint32_t bin = lnr_out::reg2bin((uint32_t)pos, (uint32_t)end[i]);
+        RefIx &x = R[(size_t)ref];
+        std::vector<std::pair<u64, u64> > &ch = x.bins[bin];
+        if (have_prev && prev_ref == ref && prev_bin == bin) ch.back().second = ve; else ch.push_back({vs, ve});
+        have_prev = true; prev_ref = ref; prev_bin = bin;
+        if (!x.any) { x.any = true; x.first = vs; }
+        x.last = ve;
+        (flag[i] & 4 ? x.unmapped : x.mapped)++;
+        const size_t w0 = (size_t)(pos >> 14), w1 = (size_t)((end[i] - 1) >> 14);
+        if (x.lin.size() <= w1) x.lin.resize(w1 + 1, ~0ULL);
+        for (size_t w = w0; w <= w1; w++) if (vs < x.lin[w]) x.lin[w] = vs;
+    }
+    auto put64 = [&](u64 v) { for (int b = 0; b < 8; b++) o += (char)(v >> (8 * b)); };
+    auto put32 = [&](uint32_t v) { for (int b = 0; b < 4; b++) o += (char)(v >> (8 * b)); };
+    o.assign("BAI\1", 4);
+    put32(n_ref);
+    for (RefIx &x : R) {
+        put32(x.any ? (uint32_t)x.bins.size() + 1 : 0);
+        for (auto &b : x.bins) {
+            put32(b.first); put32((uint32_t)b.second.size());
+            for (auto &c : b.second) { put64(c.first); put64(c.second); }
+        }
+        if (x.any) { put32(37450); put32(2); put64(x.first); put64(x.last); put64(x.mapped); put64(x.unmapped); }
+        for (size_t w = x.lin.size(); w-- > 1;) if (x.lin[w - 1] == ~0ULL) x.lin[w - 1] = x.lin[w];       // (the highest window has a record)
+        put32((uint32_t)x.lin.size());
+        for (u64 v : x.lin) put64(v);
+    }
+    put64(no_coor);
+    return LNR_OK;
+}
+bool sort_ready(lnr_writer *wr) {
+    if (wr->gpu && lnr_outgpu_sort_begin) return true;
+    snprintf(wr->err, sizeof wr->err, "lnr_writer_gpu_open has not been called on this writer");
+    return false;
+}
+}  // namespace
+
+lnr_status lnr_writer_sort_host(lnr_writer *wr, const char *records, uint64_t size, const char **sorted) {
+    if (!wr || (size && !records) || !sorted) return LNR_ERR_ARG;
+    std::vector<SRec> recs;
+    wr->err[0] = 0;
+    if (!walk_stream(records, size, recs, wr->err, sizeof wr->err)) return LNR_ERR_ARG;
+    std::sort(recs.begin(), recs.end(), [](const SRec &a, const SRec &b) {
+        if (a.key != b.key) return a.key < b.key;
+        if ((a.flag ^ b.flag) & 16) return !(a.flag & 16);
+        return a.off < b.off;
+    });
+    std::string o;
+    o.reserve(size);
+    for (const SRec &r : recs) o.append(records + r.off, r.size);
+    wr->sorted.swap(o);                            // (records may be an earlier result of this call)
+    *sorted = wr->sorted.data();
+    return LNR_OK;
+}
+lnr_status lnr_writer_bai_host(lnr_writer *wr, const char *sorted_records, uint64_t size, uint64_t first_offset, const uint64_t *member_off, uint64_t n_members,
+                               const char **data, uint64_t *bai_size) {
+    if (!wr || (size && !sorted_records) || !member_off || !data || !bai_size) return LNR_ERR_ARG;
+    std::vector<SRec> recs;
+    wr->err[0] = 0;
+    if (!walk_stream(sorted_records, size, recs, wr->err, sizeof wr->err)) return LNR_ERR_ARG;
+    const size_t n = recs.size();
+    std::vector<u64> key(n), off(n + 1); std::vector<uint32_t> flag(n); std::vector<i64> end(n);
+    for (size_t i = 0; i < n; i++) { key[i] = recs[i].key; flag[i] = recs[i].flag; end[i] = recs[i].end; off[i] = recs[i].off; }
+    off[n] = size;
+    const lnr_status s = bai_core((uint32_t)wr->w.gid.size(), n, key.data(), flag.data(), end.data(), off.data(), first_offset, member_off, n_members, wr->bai, wr->err, sizeof wr->err);
+    if (s != LNR_OK) return s;
+    *data = wr->bai.data(); *bai_size = wr->bai.size();
+    return LNR_OK;
+}
+
+static void sort_info_of(const lnr_writer *wr, lnr_sort_info *info) {
+    lnr_outgpu_sort_info i;
+    lnr_outgpu_sort_info_get(wr->gpu, &i);
+    info->records = i.records; info->record_bytes = i.record_bytes; info->device_bytes = i.device_bytes; info->members = i.members;
+    info->index_ms = i.index_ms; info->sort_ms = i.sort_ms; info->gather_ms = i.gather_ms; info->deflate_ms = i.deflate_ms; info->pack_ms = i.pack_ms; info->download_ms = i.download_ms;
+}
+lnr_status lnr_writer_sort_begin(lnr_writer *wr, uint64_t max_device_bytes) {
+    if (!wr || !sort_ready(wr)) return LNR_ERR_ARG;
+    if (wr->sort_state) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_begin: the sort mode is on already (lnr_writer_sort_end leaves it)"); return LNR_ERR_ARG; }
+    wr->err[0] = 0;
+    const lnr_status s = (lnr_status)lnr_outgpu_sort_begin(wr->gpu, max_device_bytes, wr->err, sizeof wr->err);
+    if (s == LNR_OK) { wr->sort_state = 1; wr->sort_moff.assign(1, 0); }
+    return s;
+}
+lnr_status lnr_writer_sort_finish(lnr_writer *wr, uint32_t piece_members, lnr_sort_info *info) {
+    if (!wr || !sort_ready(wr)) return LNR_ERR_ARG;
+    if (wr->sort_state != 1) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_finish: %s", wr->sort_state ? "called already" : "lnr_writer_sort_begin has not been called"); return LNR_ERR_ARG; }
+    wr->err[0] = 0;
+    const lnr_status s = (lnr_status)lnr_outgpu_sort_finish(wr->gpu, piece_members, wr->err, sizeof wr->err);
+    if (s != LNR_OK) return s;
+    wr->sort_state = 2;
+    if (info) sort_info_of(wr, info);
+    return LNR_OK;
+}
+lnr_status lnr_writer_sort_next(lnr_writer *wr, const char **data, uint64_t *size) {
+    if (!wr || !data || !size || !sort_ready(wr)) return LNR_ERR_ARG;
+    if (wr->sort_state < 2) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_next: lnr_writer_sort_finish has not been called"); return LNR_ERR_ARG; }
+    const uint64_t *moff = nullptr; uint32_t nb = 0;
+    wr->err[0] = 0;
+    const lnr_status s = (lnr_status)lnr_outgpu_sort_next(wr->gpu, data, size, &moff, &nb, wr->err, sizeof wr->err);
+    if (s != LNR_OK) return s;
+    if (!nb) { wr->sort_state = 3; return LNR_OK; }
+    const u64 base = wr->sort_moff.back();
+    for (uint32_t k = 1; k <= nb; k++) wr->sort_moff.push_back(base + moff[k]);
+    return LNR_OK;
+}
+lnr_status lnr_writer_sort_bai(lnr_writer *wr, uint64_t first_offset, const char **data, uint64_t *size) {
+    if (!wr || !data || !size || !sort_ready(wr)) return LNR_ERR_ARG;
+    if (wr->sort_state != 3) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_bai: valid once lnr_writer_sort_next has returned size 0"); return LNR_ERR_ARG; }
+    lnr_sort_info info;
+    sort_info_of(wr, &info);
+    const size_t n = (size_t)info.records;
+    std::vector<u64> key(n + 1), off(n + 1); std::vector<uint32_t> flag(n + 1); std::vector<i64> end(n + 1);
+    wr->err[0] = 0;
+    lnr_status s = (lnr_status)lnr_outgpu_sort_fetch(wr->gpu, key.data(), flag.data(), end.data(), off.data(), wr->err, sizeof wr->err);
+    if (s != LNR_OK) return s;
+    s = bai_core((uint32_t)wr->w.gid.size(), n, key.data(), flag.data(), end.data(), off.data(), first_offset, wr->sort_moff.data(), wr->sort_moff.size() - 1, wr->bai, wr->err, sizeof wr->err);
+    if (s != LNR_OK) return s;
+    *data = wr->bai.data(); *size = wr->bai.size();
+    return LNR_OK;
+}
+lnr_status lnr_writer_sort_info_get(const lnr_writer *wr, lnr_sort_info *info) {
+    if (!wr || !info || !wr->gpu || !lnr_outgpu_sort_info_get || wr->sort_state < 2) return LNR_ERR_ARG;
+    sort_info_of(wr, info);
+    return LNR_OK;
+}
+lnr_status lnr_writer_sort_end(lnr_writer *wr) {
+    if (!wr || !sort_ready(wr)) return LNR_ERR_ARG;
+    lnr_outgpu_sort_end(wr->gpu);
+    wr->sort_state = 0;
+    wr->sort_moff.clear();
+    return LNR_OK;
 }
 
 // ---- BGZF output of the GPU side (the work: lnr_output_kernels.hip behind the weak hooks)

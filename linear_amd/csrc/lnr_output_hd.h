@@ -406,4 +406,30 @@ template <class S> LNR_HD inline void bam_read(S &out, const Params &P, const Se
         if (rec_first(cs, ce, j, P.thd_large_X)) bam_item(out, P, q, cs, ce, n, j, L, qname, it++, n_rec);
 }
 
+// ---- the coordinate sort of a record stream (lnr_writer_sort_*): what decides a record's place, read from the raw record at ANY byte
+// alignment (byte loads only).  end = pos + max(1, reference bases of the CIGAR: the counts of M D N = X), the end the index bins by.
+// `avail`: bytes that may be read from rec (at least 36); CIGAR words past 4 + block_size or past avail are not looked at.
+struct BamKey { int32_t ref, pos; u32 flag, block_size; i64 end; };
+LNR_HD inline u32 le32_at(const uint8_t *p) { return (u32)p[0] | (u32)p[1] << 8 | (u32)p[2] << 16 | (u32)p[3] << 24; }
+LNR_HD inline BamKey bam_key(const uint8_t *rec, u64 avail) {
+    BamKey k;
+    k.block_size = le32_at(rec);
+    k.ref = (int32_t)le32_at(rec + 4);
+    k.pos = (int32_t)le32_at(rec + 8);
+    k.flag = (u32)rec[18] | (u32)rec[19] << 8;
+    const u64 lim = 4ULL + k.block_size < avail ? 4ULL + k.block_size : avail;
+    u64 p = 36ULL + rec[12];                      // l_read_name holds the low 8 bits of a longer name's length: the name ends at its NUL
+    while (p - 1 < lim && rec[12] && rec[p - 1] != 0) p += 256;
+    u32 n = (u32)rec[16] | (u32)rec[17] << 8;
+    u64 ref_bases = 0;
+    for (; n && p + 4 <= lim; n--, p += 4) {
+        const u32 w = le32_at(rec + p), op = w & 15u;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_bases += w >> 4;
+    }
+    k.end = (i64)k.pos + (i64)(ref_bases ? ref_bases : 1);
+    return k;
+}
+// the sort key of the order's first two fields: (uint32)refID, then (uint32)pos -- refID -1 sorts last
+LNR_HD inline u64 bam_sort_key(const BamKey &k) { return (u64)(u32)k.ref << 32 | (u64)(u32)k.pos; }
+
 }  // namespace lnr_out

@@ -31,4 +31,15 @@ struct lnr_outgpu_bgzf_stats { uint64_t blocks, stored_blocks, text_bytes, compr
 void lnr_outgpu_set_bgzf(lnr_outgpu *g, int on) __attribute__((weak));
 int lnr_outgpu_bgzf_bytes(lnr_outgpu *g, const char *bytes, uint64_t size, const char **data, uint64_t *out_size, char *err, size_t err_cap) __attribute__((weak));
 void lnr_outgpu_bgzf_stats_get(const lnr_outgpu *g, lnr_outgpu_bgzf_stats *out) __attribute__((weak));
+// Sort mode (lnr_writer_sort_*): between _begin and _finish, lnr_outgpu_format with what == 3 keeps the batch's records in device segments
+// and returns size 0.  _finish sorts; _next hands out the BGZF members of the next piece of the sorted stream with their offsets inside the
+// piece (moff[0 .. nb], host memory valid until the next call; nb == 0 and size 0: done); _fetch downloads the sorted per-record arrays
+// (records each: key = (u32)refID << 32 | (u32)pos, flag, reference end; off: records + 1 offsets in the sorted stream) for the index.
+struct lnr_outgpu_sort_info { uint64_t records, record_bytes, device_bytes, members; double index_ms, sort_ms, gather_ms, deflate_ms, pack_ms, download_ms; };
+int lnr_outgpu_sort_begin(lnr_outgpu *g, uint64_t max_bytes, char *err, size_t err_cap) __attribute__((weak));
+int lnr_outgpu_sort_finish(lnr_outgpu *g, uint32_t piece_members, char *err, size_t err_cap) __attribute__((weak));
+int lnr_outgpu_sort_next(lnr_outgpu *g, const char **data, uint64_t *size, const uint64_t **moff, uint32_t *nb, char *err, size_t err_cap) __attribute__((weak));
+int lnr_outgpu_sort_fetch(lnr_outgpu *g, uint64_t *key, uint32_t *flag, int64_t *end, uint64_t *off, char *err, size_t err_cap) __attribute__((weak));
+void lnr_outgpu_sort_info_get(const lnr_outgpu *g, lnr_outgpu_sort_info *out) __attribute__((weak));
+void lnr_outgpu_sort_end(lnr_outgpu *g) __attribute__((weak));
 }

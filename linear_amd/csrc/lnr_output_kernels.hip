@@ -30,11 +30,26 @@
 //                   the hash table in LDS, the member image built in the table's place, then copied to the block's 65536-byte slot
 //   k_out_scan      member sizes -> offsets
 //   k_bgzf_pack     the slots -> one contiguous run (destination-aligned dword stores), the only bytes that are downloaded
+//
+// Coordinate sort (lnr_writer_sort_*): the BAM records of every batch stay in HBM (device segments), the order is computed on keys alone
+// and the records move once, straight into the buffer the deflate kernel reads.
+//   k_sort_index    per batch, one lane per read: walks the read's records by block_size (byte loads: records start anywhere) and appends
+//                   key = (u32)refID << 32 | (u32)pos, flag, stream offset, device address, size and reference end per record.  The append is
+//                   atomic; the stream offset is part of the order, so the result does not depend on the append order.
+//   the sort        rocPRIM's stable radix sort twice: by (reverse bit, stream offset), then by key; k_sort_apply gathers the per-record
+//                   arrays into that order and a scan of the sorted sizes places every record in the sorted stream S
+//   k_sort_gather   per piece: one workgroup per 0xff00 bytes of S (= one BGZF member); bisection finds the first record that reaches into
+//                   the tile, waves copy record after record (destination-aligned dwords put together from two aligned source dwords,
+//                   single bytes at both ends; a piece of 8 KiB or more is copied by the whole workgroup).  No atomics.
+//   per piece       k_bgzf_deflate / k_out_scan / k_bgzf_pack as for any text
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>   // AMD's native primitives library: the stable radix sort and the scan of the coordinate sort
+#include <rocprim/device/device_scan.hpp>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "lnr_deflate_hd.h"
 #include "lnr_output_hd.h"
@@ -485,9 +500,99 @@ __global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, const u
     if (t < m - done) dst[done + t] = src[done + t];
 }
 
+// ---- coordinate sort
+struct SortArrays { u64 *key; u32 *flag; u64 *soff; u64 *addr; u32 *size; i64 *end; };     // per record, in arrival order
+// recs: the batch's records as they lie in their segment; roff[n + 1]: the reads' offsets in them (what k_out_scan left).  COUNT: only
+// *counter += records; else record number base + (*counter)++ is filled in.  A block_size that does not fit its read ends the read's walk
+// in both passes alike (the encoder writes none).
+template <bool COUNT> __global__ __launch_bounds__(256) void k_sort_index(const uint8_t *recs, const u64 *roff, u32 n, u64 stream_base, SortArrays A, u64 base, unsigned long long *counter) {
+    const u32 k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    u64 p = roff[k];
+    const u64 e = roff[k + 1];
+    u32 cnt = 0;
+    while (p + 36 <= e) {
+        const u64 sz = 4ULL + le32_at(recs + p);
+        if (sz < 36 || p + sz > e) break;
+        if (COUNT) cnt++;
+        else {
+            const BamKey key = bam_key(recs + p, sz);
+            const u64 i = base + atomicAdd(counter, 1ULL);
+            A.key[i] = bam_sort_key(key); A.flag[i] = key.flag; A.soff[i] = stream_base + p;
+            A.addr[i] = (u64)(recs + p); A.size[i] = (u32)sz; A.end[i] = key.end;
+        }
+        p += sz;
+    }
+    if (COUNT && cnt) atomicAdd(counter, (unsigned long long)cnt);
+}
+// first pass of the sort: (reverse bit, stream offset) as one key, the record's number as the value
+__global__ __launch_bounds__(256) void k_sort_prep(const u32 *flag, const u64 *soff, u64 n, u64 *k1, u32 *v1) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { k1[i] = ((u64)((flag[i] >> 4) & 1u) << 63) | soff[i]; v1[i] = (u32)i; }
+}
+__global__ __launch_bounds__(256) void k_sort_take(const u64 *key, const u32 *perm, u64 n, u64 *out) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = key[perm[i]];
+}
+// the per-record arrays in sorted order; size64[n] = 0, so that the scan over n + 1 elements leaves the total in off[n]
+__global__ __launch_bounds__(256) void k_sort_apply(SortArrays A, const u32 *perm, u64 n, u64 *s_addr, u64 *s_size, u32 *s_flag, i64 *s_end) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { const u32 r = perm[i]; s_addr[i] = A.addr[r]; s_size[i] = A.size[r]; s_flag[i] = A.flag[r]; s_end[i] = A.end[r]; }
+    else if (i == n) s_size[i] = 0;
+}
+// len bytes src -> dst by lanes t of nt (nt >= 3): single bytes up to dst's first dword boundary and after its last whole dword, between them
+// destination-aligned dwords put together from two aligned source dwords.  Reads at most 3 bytes before src (never below its dword) and 3
+// bytes past src + len: the segments' slack.
+__device__ __forceinline__ void copy_bytes(uint8_t *dst, const uint8_t *src, u32 len, u32 t, u32 nt) {
+    u32 head = (4 - (u32)((uintptr_t)dst & 3)) & 3;
+    if (head > len) head = len;
+    if (t < head) dst[t] = src[t];
+    const u32 words = (len - head) / 4;
+    const uint8_t *s = src + head;
+    const u32 sh = (u32)((uintptr_t)s & 3), r = 8 * sh;
+    const u32 *sw = reinterpret_cast<const u32 *>(s - sh);
+    u32 *dw = reinterpret_cast<u32 *>(dst + head);
+    for (u32 w = t; w < words; w += nt) dw[w] = r ? (sw[w] >> r) | (sw[w + 1] << (32 - r)) : sw[w];
+    const u32 done = head + 4 * words;
+    if (t < len - done) dst[done + t] = src[done + t];
+}
+constexpr u32 GATHER_BIG = 8192;               // a piece of a record this long is copied by the whole workgroup, a shorter one by one wave
+// S[a, b) -> out (4-byte aligned), one workgroup per BLOCK_TEXT bytes; s_off[n + 1]: the records' offsets in S, s_addr[n] where they lie
+__global__ __launch_bounds__(256) void k_sort_gather(const u64 *s_off, const u64 *s_addr, u64 n, u64 a, u64 b, uint8_t *out) {
+    const u64 t0 = a + (u64)blockIdx.x * lnr_def::BLOCK_TEXT;
+    const u64 t1 = t0 + lnr_def::BLOCK_TEXT < b ? t0 + lnr_def::BLOCK_TEXT : b;
+    u64 lo = 0, hi = n;                          // the last record that starts at or before t0 (s_off[0] = 0)
+    while (hi - lo > 1) { const u64 mid = lo + (hi - lo) / 2; if (s_off[mid] <= t0) lo = mid; else hi = mid; }
+    uint8_t *dst = out + (t0 - a);
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int big = 0; big < 2; big++)
+        for (u64 r = big ? lo : lo + wave; r < n; r += big ? 1 : 4) {
+            const u64 o = s_off[r];
+            if (o >= t1) break;
+            const u64 e = s_off[r + 1], c0 = o > t0 ? o : t0, c1 = e < t1 ? e : t1;
+            if (c1 <= c0) continue;
+            const u32 len = (u32)(c1 - c0);
+            if ((len >= GATHER_BIG) != (big != 0)) continue;
+            copy_bytes(dst + (c0 - t0), reinterpret_cast<const uint8_t *>(s_addr[r]) + (c0 - o), len, big ? threadIdx.x : lane, big ? 256u : 64u);
+        }
+}
+
 double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Buf { void *p = nullptr; u64 cap = 0; };
+
+struct SortSeg { char *p; u64 cap, used; };       // cap: bytes for records; the allocation has 8 more (copy_bytes reads past a record's end)
+struct SortState {
+    int on = 0;                                 // 0 off, 1 collecting, 2 sorted: pieces go out
+    u64 max_bytes = 0, stream = 0, nrec = 0, rec_cap = 0;
+    std::vector<SortSeg> segs;
+    Buf key, flag, soff, addr, size, end;       // per record in arrival order, rec_cap entries
+    Buf k1, k2, v1, v2, tmp, s_addr, s_size, s_off, s_flag, s_end, counter;      // the sort's scratch and the arrays in sorted order (keys: k2)
+    u32 piece_members = 0; u64 members = 0, cursor = 0;
+    std::vector<u64> moff;                      // member offsets of the last piece
+    lnr_outgpu_sort_info info{};
+};
+constexpr u64 SORT_SEG_MIN = 256ULL << 20;
 
 }  // namespace
 
@@ -505,7 +610,9 @@ struct lnr_outgpu {
     u32 nseq = 0;
     char *h_text = nullptr; u64 h_cap = 0;      // pinned
     u64 *h_total = nullptr;                     // pinned
+    u64 *h_sort = nullptr;                      // pinned: the sort's counts and totals
     double ms[5] = {0, 0, 0, 0, 0};
+    SortState sort;
 };
 
 namespace {
@@ -525,12 +632,21 @@ int dev_need(Buf &b, u64 bytes, char *err, size_t err_cap) {
     b.cap = want;
     return 0;
 }
+void sort_free(lnr_outgpu *g) {
+    SortState &S = g->sort;
+    for (SortSeg &sg : S.segs) (void)hipFree(sg.p);
+    for (Buf *b : {&S.key, &S.flag, &S.soff, &S.addr, &S.size, &S.end, &S.k1, &S.k2, &S.v1, &S.v2, &S.tmp, &S.s_addr, &S.s_size, &S.s_off, &S.s_flag, &S.s_end, &S.counter})
+        if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    S = SortState();
+}
 void free_all(lnr_outgpu *g) {
+    sort_free(g);
     for (Buf *b : {&g->gblob, &g->goff, &g->glen, &g->ids, &g->idoff, &g->coff, &g->cs, &g->ce, &g->len, &g->sizes, &g->text, &g->genome, &g->gstart, &g->reads, &g->slots, &g->msize, &g->tok, &g->packed}) if (b->p) (void)hipFree(b->p);
     if (g->h_text) (void)hipHostFree(g->h_text);
     if (g->h_bz) (void)hipHostFree(g->h_bz);
     for (hipEvent_t e : g->bev) if (e) (void)hipEventDestroy(e);
     if (g->h_total) (void)hipHostFree(g->h_total);
+    if (g->h_sort) (void)hipHostFree(g->h_sort);
     for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
     if (g->st) (void)hipStreamDestroy(g->st);
 }
@@ -582,6 +698,78 @@ int bgzf_run(lnr_outgpu *g, const uint8_t *d_text, u64 total, const char **data,
     OUT_CK(hipEventElapsedTime(&f, g->bev[2], g->bev[3]), -3); g->bz.pack_ms = f;
     g->bz.blocks = nb; g->bz.stored_blocks = g->h_bz[1]; g->bz.compressed_bytes = ctotal;
     *data = g->h_text; *size = ctotal;
+    return 0;
+}
+
+// sort mode: the batch's `total` record bytes at g->text (roff: the reads' offsets, n + 1) into a segment, their keys into the arrays.
+// Nothing of the state changes unless everything succeeded.
+int sort_add(lnr_outgpu *g, u64 total, const u64 *roff, u32 n, char *err, size_t err_cap) {
+    SortState &S = g->sort;
+    if (total == 0) return 0;
+    if (S.max_bytes && S.stream + total > S.max_bytes) {
+        snprintf(err, err_cap, "sort: %llu record bytes held on the device, %llu more asked for, max_device_bytes is %llu", (unsigned long long)S.stream, (unsigned long long)total, (unsigned long long)S.max_bytes);
+        return -4;
+    }
+    SortSeg *sg = S.segs.empty() ? nullptr : &S.segs.back();
+    u64 at = sg ? (sg->used + 15) & ~15ULL : 0;
+    if (!sg || at + total > sg->cap) {
+        u64 want = SORT_SEG_MIN;
+        if (S.max_bytes && S.max_bytes - S.stream < want) want = S.max_bytes - S.stream;
+        if (want < total) want = total;
+        void *p = nullptr;
+        if (hipMalloc(&p, want + 8) != hipSuccess) {
+            (void)hipGetLastError();
+            snprintf(err, err_cap, "sort: %llu record bytes held on the device, a segment of %llu bytes for %llu more could not be allocated", (unsigned long long)S.stream, (unsigned long long)want, (unsigned long long)total);
+            return -4;
+        }
+        S.segs.push_back({(char *)p, want, 0});
+        sg = &S.segs.back(); at = 0;
+    }
+    uint8_t *recs = (uint8_t *)sg->p + at;
+    int s;
+    if (!g->h_sort) OUT_CK(hipHostMalloc((void **)&g->h_sort, 2 * sizeof(u64), hipHostMallocDefault), -4);
+    if ((s = dev_need(S.counter, 16, err, err_cap))) return s;
+    unsigned long long *counter = (unsigned long long *)S.counter.p;
+    OUT_CK(hipMemcpyAsync(recs, g->text.p, total, hipMemcpyDeviceToDevice, g->st), -3);
+    OUT_CK(hipMemsetAsync(counter, 0, 16, g->st), -3);
+    SortArrays A{};
+    const u32 grid = (n + 255) / 256;
+    OUT_CK(hipEventRecord(g->bev[0], g->st), -3);
+    hipLaunchKernelGGL(k_sort_index<true>, dim3(grid), dim3(256), 0, g->st, (const uint8_t *)recs, roff, n, S.stream, A, S.nrec, counter);
+    OUT_CK(hipEventRecord(g->bev[1], g->st), -3);
+    OUT_CK(hipMemcpyAsync(g->h_sort, counter, 8, hipMemcpyDeviceToHost, g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    OUT_CK(hipGetLastError(), -3);
+    const u64 more = g->h_sort[0];
+    if (S.nrec + more > 0xffffffffULL) { snprintf(err, err_cap, "sort: more than 2^32 - 1 records"); return -6; }
+    if (S.nrec + more > S.rec_cap) {              // grow: new arrays, the old entries copied over
+        const u64 cap = (S.nrec + more) + (S.nrec + more) / 2 + 1024;
+        struct { Buf *b; u64 w; } arr[6] = {{&S.key, 8}, {&S.flag, 4}, {&S.soff, 8}, {&S.addr, 8}, {&S.size, 4}, {&S.end, 8}};
+        for (auto &x : arr) {
+            void *p = nullptr;
+            if (hipMalloc(&p, cap * x.w) != hipSuccess) {
+                (void)hipGetLastError();
+                snprintf(err, err_cap, "sort: %llu record bytes held on the device, the arrays for %llu records could not be allocated", (unsigned long long)S.stream, (unsigned long long)cap);
+                return -4;
+            }
+            if (S.nrec && hipMemcpy(p, x.b->p, S.nrec * x.w, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(p); snprintf(err, err_cap, "sort: copying the record arrays failed"); return -3; }
+            if (x.b->p) (void)hipFree(x.b->p);
+            x.b->p = p; x.b->cap = cap * x.w;
+        }
+        S.rec_cap = cap;
+    }
+    A = SortArrays{(u64 *)S.key.p, (u32 *)S.flag.p, (u64 *)S.soff.p, (u64 *)S.addr.p, (u32 *)S.size.p, (i64 *)S.end.p};
+    OUT_CK(hipMemsetAsync(counter, 0, 16, g->st), -3);
+    OUT_CK(hipEventRecord(g->bev[2], g->st), -3);
+    hipLaunchKernelGGL(k_sort_index<false>, dim3(grid), dim3(256), 0, g->st, (const uint8_t *)recs, roff, n, S.stream, A, S.nrec, counter);
+    OUT_CK(hipEventRecord(g->bev[3], g->st), -3);
+    OUT_CK(hipStreamSynchronize(g->st), -3);
+    OUT_CK(hipGetLastError(), -3);
+    float f0 = 0, f1 = 0;
+    OUT_CK(hipEventElapsedTime(&f0, g->bev[0], g->bev[1]), -3);
+    OUT_CK(hipEventElapsedTime(&f1, g->bev[2], g->bev[3]), -3);
+    S.info.index_ms += f0 + f1;
+    sg->used = at + total; S.stream += total; S.nrec += more;
     return 0;
 }
 
@@ -719,6 +907,7 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     OUT_CK(hipEventElapsedTime(&f, g->ev[0], g->ev[1]), -3); g->ms[1] = f;
     OUT_CK(hipEventElapsedTime(&f, g->ev[1], g->ev[2]), -3); g->ms[2] = f;
     OUT_CK(hipEventElapsedTime(&f, g->ev[3], g->ev[4]), -3); g->ms[3] = f;
+    if (bam && g->sort.on == 1) { *text = empty; *size = 0; return sort_add(g, total, sizes, n, err, err_cap); }      // sort mode: the records stay
     if (g->bgzf) return bgzf_run(g, (const uint8_t *)g->text.p, total, text, size, err, err_cap);      // the text stays on the device
     t0 = wall_ms();
     if (total) OUT_CK(hipMemcpyAsync(g->h_text, g->text.p, total, hipMemcpyDeviceToHost, g->st), -3);
@@ -747,6 +936,119 @@ int lnr_outgpu_bgzf_bytes(lnr_outgpu *g, const char *bytes, uint64_t size, const
 }
 
 void lnr_outgpu_bgzf_stats_get(const lnr_outgpu *g, lnr_outgpu_bgzf_stats *out) { *out = g->bz; }
+
+// ---- sort mode
+int lnr_outgpu_sort_begin(lnr_outgpu *g, uint64_t max_bytes, char *err, size_t err_cap) {
+    if (g->sort.on) { snprintf(err, err_cap, "the sort mode is on already"); return -1; }
+    g->sort.on = 1; g->sort.max_bytes = max_bytes;
+    return 0;
+}
+
+int lnr_outgpu_sort_finish(lnr_outgpu *g, uint32_t piece_members, char *err, size_t err_cap) {
+    SortState &S = g->sort;
+    if (S.on != 1) { snprintf(err, err_cap, "the sort mode is not collecting"); return -1; }
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    OUT_CK(hipSetDevice(g->device), -3);
+    const u64 n = S.nrec;
+    int s;
+    if (n) {
+        size_t t1 = 0, t2 = 0, t3 = 0;
+        OUT_CK(rocprim::radix_sort_pairs(nullptr, t1, (u64 *)nullptr, (u64 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (size_t)n, 0u, 64u, g->st), -3);
+        OUT_CK(rocprim::exclusive_scan(nullptr, t3, (u64 *)nullptr, (u64 *)nullptr, (u64)0, (size_t)(n + 1), rocprim::plus<u64>(), g->st), -3);
+        t2 = t1 > t3 ? t1 : t3;
+        if ((s = dev_need(S.k1, 8 * n, err, err_cap)) || (s = dev_need(S.k2, 8 * n, err, err_cap)) || (s = dev_need(S.v1, 4 * n, err, err_cap)) || (s = dev_need(S.v2, 4 * n, err, err_cap)) ||
+            (s = dev_need(S.tmp, t2 + 16, err, err_cap)) || (s = dev_need(S.s_addr, 8 * n, err, err_cap)) || (s = dev_need(S.s_size, 8 * (n + 1), err, err_cap)) ||
+            (s = dev_need(S.s_off, 8 * (n + 1), err, err_cap)) || (s = dev_need(S.s_flag, 4 * n, err, err_cap)) || (s = dev_need(S.s_end, 8 * n, err, err_cap))) return s;
+        const SortArrays A{(u64 *)S.key.p, (u32 *)S.flag.p, (u64 *)S.soff.p, (u64 *)S.addr.p, (u32 *)S.size.p, (i64 *)S.end.p};
+        u64 *k1 = (u64 *)S.k1.p, *k2 = (u64 *)S.k2.p;
+        u32 *v1 = (u32 *)S.v1.p, *v2 = (u32 *)S.v2.p;
+        const u32 grid = (u32)((n + 256) / 256);          // (n + 1 lanes: k_sort_apply writes the scan's last input)
+        OUT_CK(hipEventRecord(g->bev[0], g->st), -3);
+        hipLaunchKernelGGL(k_sort_prep, dim3(grid), dim3(256), 0, g->st, (const u32 *)A.flag, (const u64 *)A.soff, n, k1, v1);
+        size_t tb = t2;
+        OUT_CK(rocprim::radix_sort_pairs(S.tmp.p, tb, k1, k2, v1, v2, (size_t)n, 0u, 64u, g->st), -3);          // by (reverse bit, stream offset)
+        hipLaunchKernelGGL(k_sort_take, dim3(grid), dim3(256), 0, g->st, (const u64 *)A.key, (const u32 *)v2, n, k1);
+        tb = t2;
+        OUT_CK(rocprim::radix_sort_pairs(S.tmp.p, tb, k1, k2, v2, v1, (size_t)n, 0u, 64u, g->st), -3);          // stably by key: k2 sorted keys, v1 the order
+        hipLaunchKernelGGL(k_sort_apply, dim3(grid), dim3(256), 0, g->st, A, (const u32 *)v1, n, (u64 *)S.s_addr.p, (u64 *)S.s_size.p, (u32 *)S.s_flag.p, (i64 *)S.s_end.p);
+        tb = t2;
+        OUT_CK(rocprim::exclusive_scan(S.tmp.p, tb, (u64 *)S.s_size.p, (u64 *)S.s_off.p, (u64)0, (size_t)(n + 1), rocprim::plus<u64>(), g->st), -3);
+        OUT_CK(hipEventRecord(g->bev[1], g->st), -3);
+        OUT_CK(hipMemcpyAsync(g->h_sort, (u64 *)S.s_off.p + n, 8, hipMemcpyDeviceToHost, g->st), -3);
+        OUT_CK(hipStreamSynchronize(g->st), -3);
+        OUT_CK(hipGetLastError(), -3);
+        float f = 0;
+        OUT_CK(hipEventElapsedTime(&f, g->bev[0], g->bev[1]), -3);
+        S.info.sort_ms = f;
+        if (g->h_sort[0] != S.stream) { snprintf(err, err_cap, "sort: the sorted records have %llu bytes, %llu were kept", (unsigned long long)g->h_sort[0], (unsigned long long)S.stream); return -8; }
+    }
+    S.members = (S.stream + lnr_def::BLOCK_TEXT - 1) / lnr_def::BLOCK_TEXT;
+    S.cursor = 0;
+    S.piece_members = piece_members ? (piece_members < 65536u ? piece_members : 65536u) : 4096u;
+    S.info.records = n; S.info.record_bytes = S.stream; S.info.members = S.members;
+    u64 held = 0;
+    for (const SortSeg &sg : S.segs) held += sg.cap + 8;
+    for (const Buf *b : {&S.key, &S.flag, &S.soff, &S.addr, &S.size, &S.end, &S.k1, &S.k2, &S.v1, &S.v2, &S.tmp, &S.s_addr, &S.s_size, &S.s_off, &S.s_flag, &S.s_end, &S.counter}) held += b->cap;
+    S.info.device_bytes = held;
+    S.on = 2;
+    return 0;
+}
+
+int lnr_outgpu_sort_next(lnr_outgpu *g, const char **data, uint64_t *size, const uint64_t **moff, uint32_t *nb, char *err, size_t err_cap) {
+    static const char empty[1] = "";
+    SortState &S = g->sort;
+    if (S.on != 2) { snprintf(err, err_cap, "the records have not been sorted"); return -1; }
+    *data = empty; *size = 0; *moff = nullptr; *nb = 0;
+    if (S.cursor >= S.members) return 0;
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    OUT_CK(hipSetDevice(g->device), -3);
+    const u64 left = S.members - S.cursor;
+    const u32 cnt = left < S.piece_members ? (u32)left : S.piece_members;
+    const u64 a = S.cursor * lnr_def::BLOCK_TEXT, b = a + (u64)cnt * lnr_def::BLOCK_TEXT < S.stream ? a + (u64)cnt * lnr_def::BLOCK_TEXT : S.stream;
+    int s;
+    if ((s = dev_need(g->text, b - a + 8, err, err_cap))) return s;
+    OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
+    hipLaunchKernelGGL(k_sort_gather, dim3(cnt), dim3(256), 0, g->st, (const u64 *)S.s_off.p, (const u64 *)S.s_addr.p, S.nrec, a, b, (uint8_t *)g->text.p);
+    OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
+    if ((s = bgzf_run(g, (const uint8_t *)g->text.p, b - a, data, size, err, err_cap))) return s;
+    if (g->bz.blocks != cnt) { snprintf(err, err_cap, "sort: a piece of %u members came back as %llu", cnt, (unsigned long long)g->bz.blocks); return -8; }
+    S.moff.resize((size_t)cnt + 1);
+    OUT_CK(hipMemcpy(S.moff.data(), g->msize.p, 8ULL * (cnt + 1ULL), hipMemcpyDeviceToHost), -3);      // msize after its scan: the members' offsets
+    float f = 0;
+    OUT_CK(hipEventElapsedTime(&f, g->ev[0], g->ev[1]), -3);
+    S.info.gather_ms += f; S.info.deflate_ms += g->bz.deflate_ms; S.info.pack_ms += g->bz.pack_ms; S.info.download_ms += g->ms[4];
+    S.cursor += cnt;
+    *moff = S.moff.data(); *nb = cnt;
+    return 0;
+}
+
+int lnr_outgpu_sort_fetch(lnr_outgpu *g, uint64_t *key, uint32_t *flag, int64_t *end, uint64_t *off, char *err, size_t err_cap) {
+    SortState &S = g->sort;
+    if (S.on != 2) { snprintf(err, err_cap, "the records have not been sorted"); return -1; }
+    const u64 n = S.nrec;
+    off[0] = 0;
+    if (!n) return 0;
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    OUT_CK(hipSetDevice(g->device), -3);
+    OUT_CK(hipMemcpy(key, S.k2.p, 8 * n, hipMemcpyDeviceToHost), -3);
+    OUT_CK(hipMemcpy(flag, S.s_flag.p, 4 * n, hipMemcpyDeviceToHost), -3);
+    OUT_CK(hipMemcpy(end, S.s_end.p, 8 * n, hipMemcpyDeviceToHost), -3);
+    OUT_CK(hipMemcpy(off, S.s_off.p, 8 * (n + 1), hipMemcpyDeviceToHost), -3);
+    return 0;
+}
+
+void lnr_outgpu_sort_info_get(const lnr_outgpu *g, lnr_outgpu_sort_info *out) { *out = g->sort.info; }
+
+void lnr_outgpu_sort_end(lnr_outgpu *g) {
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    (void)hipSetDevice(g->device);
+    (void)hipStreamSynchronize(g->st);
+    sort_free(g);
+}
 
 void lnr_outgpu_times(const lnr_outgpu *g, double *ms5) { for (int i = 0; i < 5; i++) ms5[i] = g->ms[i]; }
 
