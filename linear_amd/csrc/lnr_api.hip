@@ -88,7 +88,7 @@ lnr_status submit_reads(lnr_ctx *ctx, Lane *L, int slot, const u8 *reads, const 
 std::unique_ptr<Lane> lane_create(lnr_ctx *ctx, int id) {
     std::unique_ptr<Lane> L(new (std::nothrow) Lane());
     if (!L) return nullptr;
-    L->opts = &ctx->opts; L->tun = &ctx->tun; L->ix = &ctx->ix; L->id = id;
+    L->opts = &ctx->opts; L->tun = &ctx->tun; L->ix = &ctx->ix; L->top = ctx; L->id = id;
     if (!L->init(id == 1 ? ctx->tun.lane1_prio : 0)) return nullptr;
     return L;
 }

@@ -55,11 +55,13 @@ lnr_status seed_jobs(Lane *L, JobSet &S, const HostJobs &hj, hipStream_t st, u32
     S.cap.assign(nj, 0); S.look.assign(nj, 0); S.nanc.assign(nj, 0); S.anc_off.assign(nj, 0);
     if (nj == 0) return f1_reads ? launch_f1(L, f1_reads) : LNR_OK;
     lnr_status s;
-    if ((s = upload_on(L->err, S.j_read, hj.read, st)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, S.j_str, hj.str, st)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, S.j_end, hj.end, st)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, S.j_mode, hj.mode, st)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, S.grp_beg, hj.grp_beg, st)) != LNR_OK) return s;
+    CopyBatch up;     // the five job arrays: one launch
+    if ((s = upload_to(L->err, S.j_read, hj.read, up, st)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, S.j_str, hj.str, up, st)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, S.j_end, hj.end, up, st)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, S.j_mode, hj.mode, up, st)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, S.grp_beg, hj.grp_beg, up, st)) != LNR_OK) return s;
+    LCK(up.flush(st));
     LENSURE(S.j_cap, (size_t)nj * 4);
     LENSURE(S.j_look, (size_t)nj * 4);
     LENSURE(S.j_nanc, (size_t)nj * 4);
@@ -102,6 +104,7 @@ lnr_status seed_jobs(Lane *L, JobSet &S, const HostJobs &hj, hipStream_t st, u32
         LCK(rb.add(S.nanc.data(), S.j_nanc.p, (size_t)nj * 4, st));
         LCK(rb.add(S.anc_off.data(), S.j_anc_off.p, (size_t)nj * 8, st));
         LCK(rb.add(&ovf, S.seed_ctl.as<char>() + 16, 4, st));
+        LCK(rb.flush(st));
         LCK(hipStreamSynchronize(st));
         rb.finish();
         if (!ovf) {                                   // only the successful launch is the stage's time
@@ -139,13 +142,39 @@ lnr_status export_anchors(Lane *L, JobSet &S, u32 nj, std::vector<u64> &a_off, s
     return LNR_OK;
 }
 
+// A lane's place in the order of the job launches (lnr_handover.h) for one filter_dev call: enter() in front of the round-0 launch, leave()
+// once the round-1 launch is enqueued or known to be empty -- and on every other way out, by the destructor.  Bypassed with one lane
+// (LNR_LANES=1, -g > 0, lane 1 switched off) and by LNR_HANDOVER_GATE=0.  LNR_DEBUG_TIMES=1 prints a host stamp (ms) at every phase change.
+struct HandoverScope : NoCopy {
+    Lane *L; lnr_ctx *c; bool on, held = false;
+    explicit HandoverScope(Lane *l) : L(l), c(l->top) { on = c && c->tun.handover_gate && two_lanes(c) && !c->lane1_off; }
+    void stamp(const char *what) const {
+        if (held && getenv("LNR_DEBUG_TIMES")) fprintf(stderr, "[lnr] handover lane %d %s %.3f\n", L->id, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count());
+    }
+    bool enter() {      // true: the lane had to wait for the other lane's hand-over to end
+        if (!on || held) return false;
+        lnr_ctx *cc = c;
+        bool waited = lnr_ho::handover_enter(c->ho, c->mu, c->cv, L->id, [cc] { return cc->quit; });
+        held = true;
+        stamp(waited ? "gate-passed-after-wait" : "gate-passed");
+        return waited;
+    }
+    void leave() {
+        if (!held) return;
+        stamp("handover-end");      // (before the other lane can pass)
+        held = false;
+        (void)lnr_ho::handover_leave(c->ho, c->mu, c->cv, L->id);
+    }
+    ~HandoverScope() { leave(); }
+};
+
 // Per-read job kernels for all groups of the seeded job set S (hj = its host list).  Heaviest group first (anchors that
 // passed the Y filter are the work proxy), so the long tail of repeat-rich reads starts at once.  The multi-wave kernels
 // are launched first: a multi-wave workgroup only finds a CU with enough free wave slots while the single-wave kernel has
 // not flooded the chip (it refills every slot a finished wave frees -- a late heavy launch was measured to start only
 // when the bulk kernel drained, 47 ms late).  The bulk kernel follows on s_bulk.  On return everything is enqueued and
 // the main stream waits for the side streams; nothing is synchronised unless the scratch budget forces several slices.
-lnr_status launch_jobs(Lane *L, JobSet &S, const HostJobs &hj) {
+lnr_status launch_jobs(Lane *L, JobSet &S, const HostJobs &hj, HandoverScope *gate = nullptr) {
     const Index &ix = *L->ix; const Tuning &tun = *L->tun;
     u32 ngrp = (u32)hj.grp_beg.size() - 1;
     if (ngrp == 0) return LNR_OK;
@@ -181,7 +210,8 @@ lnr_status launch_jobs(Lane *L, JobSet &S, const HostJobs &hj) {
     Lx.h_order = order;
     laps.lap("order");
     lnr_status s;
-    if ((s = upload_on(L->err, Lx.grp_order, Lx.h_order, sm)) != LNR_OK) return s;
+    CopyBatch up;     // the order travels with the first slice's scratch offsets
+    if ((s = upload_to(L->err, Lx.grp_order, Lx.h_order, up, sm)) != LNR_OK) return s;
     laps.lap("upload-order");
     LENSURE(Lx.j_scr_off, (size_t)nj * 8);
     std::vector<u64> &scr_off = Lx.h_scr_off;
@@ -206,7 +236,8 @@ lnr_status launch_jobs(Lane *L, JobSet &S, const HostJobs &hj) {
             void *h = Lx.j_scr_off.host_stage((size_t)nj * 8);
             if (!h) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
             memcpy(h, scr_off.data(), (size_t)nj * 8);
-            LCK(words_in(Lx.j_scr_off.p, h, (size_t)nj * 8, sm));
+            LCK(up.add(Lx.j_scr_off.p, h, (u64)nj * 2, sm));
+            LCK(up.flush(sm));
         }
         laps.lap("upload-scr");
         JobArgs A;
@@ -246,6 +277,11 @@ lnr_status launch_jobs(Lane *L, JobSet &S, const HostJobs &hj) {
         // streams: kernels on one stream run back to back.  The 16-wave kernel stays on the main stream (no event wait, it reaches
         // the GPU first); the 4/2-wave kernel takes the spare stream when the 16-wave class is present, else the main stream; the
         // single-wave kernel goes to the bulk stream when a multi-wave class is present, else the main stream.
+        // The gate of the two lanes' order (HandoverScope), for round 0: in front of the first kernel and behind the host work and the small
+        // uploads above, which need no order.  A lane that had to wait launches right behind the other lane's round-1 kernels: its bulk
+        // kernel then gets the head start below even without a multi-wave class of its own.
+        bool head_start = gate && g0 == 0 && gate->enter();
+        if (gate && g0 == 0) laps.lap("gate");
         hipStream_t smid = gh > g0 ? L->s_spare : sm;
         bool fork_m = gm > gh && gh > g0, fork_b = g1 > gm && gm > g0;
         if (fork_m || fork_b) LCK(hipEventRecord(L->ev_fork, sm));    // before any launch: nobody waits for another kernel
@@ -269,10 +305,9 @@ lnr_status launch_jobs(Lane *L, JobSet &S, const HostJobs &hj) {
         }
         if (g1 > gm) {
             hipStream_t bulk = fork_b ? sb : sm;
-            if (fork_b) {
-                LCK(hipStreamWaitEvent(sb, L->ev_fork, 0));
-                hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, sb, tun.bulk_delay_ticks); LKCHECK();
-            }
+            if (fork_b) LCK(hipStreamWaitEvent(sb, L->ev_fork, 0));
+            // (head_start: the other lane's round-1 launch has only just been enqueued, and its wide workgroups take their CUs first)
+            if (fork_b || head_start) { hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, bulk, tun.bulk_delay_ticks); LKCHECK(); }
             JobArgs K = A;
             K.grp_lo = gm; K.grp_hi = g1;
             hipLaunchKernelGGL(k_job, dim3(g1 - gm), dim3(64), lds, bulk, K); LKCHECK();
@@ -298,6 +333,7 @@ lnr_status prepare_batch(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, Ba
         Readback rb;
         if (!rb.begin(L->h_rb[0], ((size_t)n + 1) * 8)) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
         LCK(rb.add(B.off.data(), d_off, ((size_t)n + 1) * 8, L->stream));
+        LCK(rb.flush(L->stream));
         LCK(hipStreamSynchronize(L->stream));
         rb.finish();
     }
@@ -318,16 +354,18 @@ lnr_status prepare_batch(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, Ba
         B.gaps_off[i] = go; go += B.gaps_cap[i];
     }
     lnr_status s;
-    if ((s = upload_on(L->err, L->rlen, B.len, L->stream)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, L->pk_off, B.pk_off, L->stream)) != LNR_OK) return s;
+    CopyBatch up;     // the eight per-read tables: one launch
+    if ((s = upload_to(L->err, L->rlen, B.len, up, L->stream)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, L->pk_off, B.pk_off, up, L->stream)) != LNR_OK) return s;
     LENSURE(L->pk, std::max<u64>(po * 8, 16));
     LENSURE(L->nm, std::max<u64>(po * 4, 16));
-    if ((s = upload_on(L->err, L->nf, B.nf, L->stream)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, L->f1_off, B.f1_off, L->stream)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, L->cords_cap, B.cords_cap, L->stream)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, L->cords_off, B.cords_off, L->stream)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, L->gaps_cap, B.gaps_cap, L->stream)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, L->gaps_off, B.gaps_off, L->stream)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, L->nf, B.nf, up, L->stream)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, L->f1_off, B.f1_off, up, L->stream)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, L->cords_cap, B.cords_cap, up, L->stream)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, L->cords_off, B.cords_off, up, L->stream)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, L->gaps_cap, B.gaps_cap, up, L->stream)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, L->gaps_off, B.gaps_off, up, L->stream)) != LNR_OK) return s;
+    LCK(up.flush(L->stream));
     LENSURE(L->rks, (size_t)n * 4);
     LENSURE(L->f1, std::max<u64>(fo * sizeof(F96), 16));
     LENSURE(L->cords, std::max<u64>(co * 8, 16));
@@ -352,19 +390,20 @@ lnr_status prepare_batch(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, Ba
     return LNR_OK;
 }
 
-// Scratch layout + launch arguments of a tail kernel over the reads in `list` (null = all reads), on stream st.
-// Returns with the stream idle (it reads the current cord counts back to size the scratch).
-lnr_status tail_prepare(Lane *L, const BatchHost &B, TailBuf &tb, const std::vector<u32> *list, hipStream_t st, TailArgs &T) {
+// The reads' current cord counts on their way to the host, on stream st: they size a tail's scratch (tail_prepare).  The caller issues this
+// in front of a sync it needs anyway -- the end of round 0, the end of the re-map round -- so the counts cost no round trip of their own.
+lnr_status counts_out(Lane *L, u32 n, Readback &rb, std::vector<u32> &ncords, hipStream_t st) {
+    ncords.resize(n);
+    if (!rb.begin(L->h_rb[1], (size_t)n * 4)) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+    LCK(rb.add(ncords.data(), L->ncords.p, (size_t)n * 4, st));
+    LCK(rb.flush(st));
+    return LNR_OK;
+}
+
+// Scratch layout + launch arguments of a tail kernel over the reads in `list` (null = all reads), on stream st; ncords: the cord counts
+// the kernel will meet (counts of reads outside `list` are not used).  Returns with the tables' upload enqueued.
+lnr_status tail_prepare(Lane *L, const BatchHost &B, TailBuf &tb, const std::vector<u32> *list, hipStream_t st, TailArgs &T, const u32 *ncords) {
     u32 n = B.n;
-    std::vector<u32> ncords(n);
-    {
-        Readback rb;
-        PinBuf &pb = L->h_rb[st == L->s_tail ? 2 : 1];
-        if (!rb.begin(pb, (size_t)n * 4)) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
-        LCK(rb.add(ncords.data(), L->ncords.p, (size_t)n * 4, st));
-        LCK(hipStreamSynchronize(st));   // (on s_tail: counts of the reads the re-map round is still working on are not used)
-        rb.finish();
-    }
     tb.h_off.assign(n, 0); tb.h_cap.assign(n, 0);
     u64 o = 0;
     u32 cnt = list ? (u32)list->size() : n;
@@ -373,15 +412,17 @@ lnr_status tail_prepare(Lane *L, const BatchHost &B, TailBuf &tb, const std::vec
         tb.h_cap[i] = ncords[i] + 4; tb.h_off[i] = o; o += align_up(tail_scratch_bytes(tb.h_cap[i]), 256);
     }
     lnr_status s;
-    if ((s = upload_on(L->err, tb.off, tb.h_off, st)) != LNR_OK) return s;
-    if ((s = upload_on(L->err, tb.cap, tb.h_cap, st)) != LNR_OK) return s;
+    CopyBatch up;     // off / cap / list: one launch
+    if ((s = upload_to(L->err, tb.off, tb.h_off, up, st)) != LNR_OK) return s;
+    if ((s = upload_to(L->err, tb.cap, tb.h_cap, up, st)) != LNR_OK) return s;
     LENSURE(tb.scr, std::max<u64>(o, 16));
     T.read_len = L->rlen.as<u32>(); T.n = cnt; T.list = nullptr;
     if (list) {
         tb.h_list = *list;
-        if ((s = upload_on(L->err, tb.list, tb.h_list, st)) != LNR_OK) return s;
+        if ((s = upload_to(L->err, tb.list, tb.h_list, up, st)) != LNR_OK) return s;
         T.list = tb.list.as<u32>();
     }
+    LCK(up.flush(st));
     T.cords = L->cords.as<u64>(); T.cords_off = L->cords_off.as<u64>(); T.cords_cap = L->cords_cap.as<u32>(); T.ncords = L->ncords.as<u32>();
     T.read_err = L->read_err.as<i32>();
     T.scratch = tb.scr.as<char>(); T.scr_off = tb.off.as<u64>(); T.scr_cap = tb.cap.as<u32>();
@@ -398,34 +439,46 @@ void finish_stats(Lane *L, const BatchHost &B) {
     L->stats.seed_bytes = rb + L->stats.lookups * 8 + L->stats.bucket_entries * 8 + L->stats.anchors * 8;
 }
 
-// Tail A + re-map round of every read (round 0 has completed on the main stream): clean / gather / gaps decide the remap
-// loop (pmpfinder.cpp:2744-2749); every gap of a poorly covered read is then re-seeded with step 7 / score0
-// (pmpfinder.cpp:2749-2767) into job set 1 (j1).  Returns with the launches enqueued.
-lnr_status remap_round(Lane *L, const BatchHost &B, HostJobs &j1) {
+// Tail A + re-map round of every read (round 0 has completed on the main stream; nc0: the cord counts it left): clean / gather / gaps
+// decide the remap loop (pmpfinder.cpp:2744-2749); every gap of a poorly covered read is then re-seeded with step 7 / score0
+// (pmpfinder.cpp:2749-2767) into job set 1 (j1).  Returns with the launches enqueued and nc_a = the cord counts after tail A.
+lnr_status remap_round(Lane *L, const BatchHost &B, HostJobs &j1, const std::vector<u32> &nc0, std::vector<u32> &nc_a) {
     hipStream_t st = L->stream;
     JobSet &S = L->js[1];
     u32 n = B.n;
     TailArgs T;
     lnr_status s;
-    if ((s = tail_prepare(L, B, L->tb_remap, nullptr, st, T)) != LNR_OK) return s;
+    if ((s = tail_prepare(L, B, L->tb_remap, nullptr, st, T, nc0.data())) != LNR_OK) return s;
     Laps laps;
     laps.lap("tail_prepare");
     LCK(hipMemsetAsync(L->gcursor.p, 0, 4, st));
     hipLaunchKernelGGL(k_tail_a, dim3((T.n + 63) / 64), dim3(64), 0, st, T); LKCHECK();
-    if (!L->h_flags.ensure((size_t)n * 12 + 16)) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
-    u32 *remap = L->h_flags.as<u32>(), *ngaps = remap + n, *gpos = ngaps + n, *gtot_p = gpos + n;
-    LCK(copy_words(remap, L->remap.p, n, st));
-    LCK(copy_words(ngaps, L->ngaps.p, n, st));
-    LCK(copy_words(gpos, L->gpos.p, n, st));
-    LCK(copy_words(gtot_p, L->gcursor.p, 1, st));
+    // One round trip for everything tail A decided: the flags, the cord counts (final for the reads that skip the re-map round: they size
+    // the early tail B) and the dense gap list up to a sticky capacity.  A second trip only when tail A wrote more gaps than that.
+    if (!L->h_flags.ensure((size_t)n * 16 + 16)) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+    u32 *remap = L->h_flags.as<u32>(), *ngaps = remap + n, *gpos = ngaps + n, *nca = gpos + n, *gtot_p = nca + n;
+    u64 spec = std::min<u64>(L->tun->gaps_spec ? L->tun->gaps_spec : L->gaps_spec_cap, L->gdense.cap / sizeof(UP));
+    if (!L->h_gaps.ensure(std::max<u64>(spec, 1) * sizeof(UP))) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+    CopyBatch cb;
+    LCK(cb.add(remap, L->remap.p, n, st));
+    LCK(cb.add(ngaps, L->ngaps.p, n, st));
+    LCK(cb.add(gpos, L->gpos.p, n, st));
+    LCK(cb.add(nca, L->ncords.p, n, st));
+    LCK(cb.add(gtot_p, L->gcursor.p, 1, st));
+    LCK(cb.add(L->h_gaps.p, L->gdense.p, spec * sizeof(UP) / 4, st));
+    LCK(cb.flush(st));
     LCK(hipStreamSynchronize(st));
     laps.lap("tail_a+flags");
+    nc_a.assign(nca, nca + n);
     u64 gtot = *gtot_p;
     if (gtot == 0) return LNR_OK;
-    if (!L->h_gaps.ensure(gtot * sizeof(UP))) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+    if (gtot > spec) {
+        if (!L->h_gaps.ensure(gtot * sizeof(UP))) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }   // (may move: all of the list again)
+        LCK(copy_words(L->h_gaps.p, L->gdense.p, gtot * sizeof(UP) / 4, st));
+        LCK(hipStreamSynchronize(st));
+        L->gaps_spec_cap = gtot + gtot / 2;
+    }
     UP *gaps = L->h_gaps.as<UP>();
-    LCK(copy_words(gaps, L->gdense.p, gtot * sizeof(UP) / 4, st));
-    LCK(hipStreamSynchronize(st));
     for (u32 i = 0; i < n; i++) {
         if (!(remap[i] && ngaps[i])) continue;
         L->stats.remap_reads++;
@@ -450,6 +503,8 @@ lnr_status filter_dev(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, lnr_c
     if (!ix.has_index) { L->err = "no index: call lnr_index_build or lnr_index_adopt first"; return LNR_ERR_NO_INDEX; }
     reset_stats(L);
     AllocCount count_(&L->allocs);
+    HandoverScope gate(L);     // (its own in the re-run after an overflow: the outer call's hand-over ended with its round-1 launch)
+    if (attempt == 0) t_copy_launches = 0;
     L->last_n = n; L->last_ncords = 0;
     if (out) { out->n_reads = n; out->n_cords = 0; out->d_cord_off = nullptr; out->d_cords_str = nullptr; out->d_cords_end = nullptr; }
     LENSURE(L->r_off, ((size_t)n + 1) * 8);
@@ -480,11 +535,19 @@ lnr_status filter_dev(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, lnr_c
     LCK(hipStreamWaitEvent(L->s_spare, L->ev_start, 0));
     LCK(hipStreamWaitEvent(L->s_bulk, L->ev_start, 0));
     laps.lap("events");
-    if ((s = launch_jobs(L, L->js[0], j0)) != LNR_OK) return s;
+    if ((s = launch_jobs(L, L->js[0], j0, &gate)) != LNR_OK) return s;
+    gate.stamp("round0-enqueued");
     laps.lap("launch0");
-    LCK(hipStreamSynchronize(L->stream));
+    std::vector<u32> nc0, nc_a, nc1;
+    {   // the cord counts of round 0 (they size tail A's scratch) come back with the sync that ends round 0
+        Readback rb;
+        if ((s = counts_out(L, n, rb, nc0, L->stream)) != LNR_OK) return s;
+        LCK(hipStreamSynchronize(L->stream));
+        rb.finish();
+    }
     HostJobs j1;
-    if ((s = remap_round(L, B, j1)) != LNR_OK) return s;
+    if ((s = remap_round(L, B, j1, nc0, nc_a)) != LNR_OK) return s;
+    gate.leave();
     laps.lap("tailA+seed1+launch1");
     // Tail B (block chaining on both strands, flags, cords_end; pmpfinder.cpp:2764-2801) of the reads that do not go through
     // the re-map round is final after tail A: it runs on its own stream while the re-map jobs (a few long reads) are busy.
@@ -495,16 +558,21 @@ lnr_status filter_dev(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, lnr_c
         for (u32 q = 0; q < j1.size(); q++) in_r1[j1.read[q]] = 1;
         for (u32 i = 0; i < n; i++) (in_r1[i] ? late_list : early_list).push_back(i);
         TailArgs TE;
-        if ((s = tail_prepare(L, B, L->tb_early, &early_list, L->s_tail, TE)) != LNR_OK) return s;
+        if ((s = tail_prepare(L, B, L->tb_early, &early_list, L->s_tail, TE, nc_a.data())) != LNR_OK) return s;
         if (TE.n) { hipLaunchKernelGGL(k_tail_b, dim3((TE.n + 63) / 64), dim3(64), 0, L->s_tail, TE); LKCHECK(); }   // (every read may be in the re-map round)
         LCK(hipEventRecord(L->ev_prep, L->s_tail));
     }
     L->t_job.stop(L->stream);
-    LCK(hipStreamSynchronize(L->stream));
+    {   // the final cord counts of the late tail's reads come back with the sync that ends the re-map round
+        Readback rb;
+        if ((s = counts_out(L, n, rb, nc1, L->stream)) != LNR_OK) return s;
+        LCK(hipStreamSynchronize(L->stream));
+        rb.finish();
+    }
     L->stats.job_ms += L->t_job.ms();
     laps.lap("wait-r1");
     TailArgs T;
-    if ((s = tail_prepare(L, B, L->tb_late, early ? &late_list : nullptr, L->stream, T)) != LNR_OK) return s;
+    if ((s = tail_prepare(L, B, L->tb_late, early ? &late_list : nullptr, L->stream, T, nc1.data())) != LNR_OK) return s;
     L->t_tail.start(L->stream);
     if (T.n) { hipLaunchKernelGGL(k_tail_b, dim3((T.n + 63) / 64), dim3(64), 0, L->stream, T); LKCHECK(); }
     L->t_tail.stop(L->stream);
@@ -525,6 +593,7 @@ lnr_status filter_dev(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, lnr_c
         LCK(rb.add(rerr.data(), L->read_err.p, (size_t)n * 4, L->stream));
         if (L->opts->gap_len) LCK(rb.add(&gap_second, L->gap_next.as<u32>() + 16, 4, L->stream));
         if (L->opts->gap_len) LCK(rb.add(&gap_last, L->gap_next.as<u32>() + 24 + 8, 4, L->stream));   // (k_gap_team's count of the reads it did)
+        LCK(rb.flush(L->stream));
         LCK(hipStreamSynchronize(L->stream));
         rb.finish();
     }
@@ -558,14 +627,14 @@ lnr_status filter_dev(Lane *L, const u8 *d_reads, const u64 *d_off, u32 n, lnr_c
         void *h = L->r_off.host_stage(((size_t)n + 1) * 8);
         if (!h) { L->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
         memcpy(h, L->h_cord_off.data(), ((size_t)n + 1) * 8);
-        LCK(words_in(L->r_off.p, h, ((size_t)n + 1) * 8, L->stream));
+        LCK(copy_words(L->r_off.p, h, ((u64)n + 1) * 2, L->stream));
     }
     hipLaunchKernelGGL(k_gather_out, dim3(n), dim3(64), 0, L->stream, L->out_str.as<u64>(), L->out_end.as<u64>(), L->cords_off.as<u64>(), L->nout.as<u32>(),
                        L->r_off.as<u64>(), n, L->r_str.as<u64>(), L->r_end.as<u64>()); LKCHECK();
     L->t_total.stop(L->stream);
     LCK(hipStreamSynchronize(L->stream));
     laps.lap("tailB+gather");
-    if (laps.on) { char b[64]; snprintf(b, sizeof b, " | lane %d allocations so far %u", L->id, L->allocs.load()); laps.out += b; }
+    if (laps.on) { char b[96]; snprintf(b, sizeof b, " | lane %d allocations so far %u, copy launches of this batch %u", L->id, L->allocs.load(), t_copy_launches); laps.out += b; }
     laps.done();
     L->stats.prep_ms = L->t_prep.ms();
     L->stats.total_ms = L->t_total.ms();

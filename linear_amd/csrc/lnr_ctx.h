@@ -4,6 +4,9 @@
 //   Lane    everything one filter_dev / seed_dev call works on, plus the lane's queue (guarded by lnr_ctx::mu)
 //   lnr_ctx what only the caller's thread and the scheduler touch, and the two lanes
 #pragma once
+#include "lnr_handover.h"
+
+struct lnr_ctx;
 
 namespace {
 
@@ -39,12 +42,16 @@ struct Tuning {
     u32 nlanes = 2;                     // LNR_LANES=1|2
     int lane1_prio = 1;                 // stream priority of lane 1's kernel streams: 1 = low (diagnostic: LNR_LANE1_PRIO=-1|0|1; see lane_create)
     bool lane1_nomem = false;           // diagnostic (LNR_LANE1_NOMEM=1): lane 1's first batch fails as if the device were full, to exercise that fallback
+    bool handover_gate = true;          // the order of the two lanes' job launches (lnr_handover.h); LNR_HANDOVER_GATE=0 switches it off, for profiling only
+    u64 gaps_spec = 0;                  // diagnostic (LNR_GAPS_SPEC=<entries>): fixes how many gap entries travel with the tail-A flags (0: the lane's sticky capacity)
 };
 
 Tuning tuning_from_env(int device) {
     Tuning t;
     if (const char *e = getenv("LNR_LANES")) { long v = atol(e); if (v == 1 || v == 2) t.nlanes = (u32)v; }
     if (const char *e = getenv("LNR_LANE1_NOMEM")) t.lane1_nomem = atoi(e) != 0;
+    if (const char *e = getenv("LNR_HANDOVER_GATE")) t.handover_gate = atoi(e) != 0;
+    if (const char *e = getenv("LNR_GAPS_SPEC")) { long long v = atoll(e); if (v >= 1) t.gaps_spec = (u64)v; }
     if (const char *e = getenv("LNR_LANE1_PRIO")) { long v = atol(e); if (v >= -1 && v <= 1) t.lane1_prio = (int)v; }
     if (const char *e = getenv("LNR_CAP_SHRINK")) { long v = atol(e); if (v >= 1 && v <= 4096) t.cap_shrink = (u32)v; }
     if (const char *e = getenv("LNR_GAP_TEAMS")) { long v = atol(e); if (v >= 1 && v <= 4096) t.gap_teams = (u32)v; }
@@ -96,6 +103,7 @@ struct Lane {
     const lnr_opts *opts = nullptr;     // the context's (lnr_set_gap changes them with nothing in flight)
     const Tuning *tun = nullptr;
     const Index *ix = nullptr;
+    struct ::lnr_ctx *top = nullptr;    // the context: its mutex, condition variable and hand-over state (filter_dev's gate)
     int id = 0;
     ErrText err;                         // of the lane's last batch; copied into the context's when the batch is handed out
     // Kernel streams: `stream` carries seeds, tails and the 16-wave job kernel; s_spare the 4/2-wave job kernel when the 16-wave kernel is
@@ -115,10 +123,11 @@ struct Lane {
     DevBuf cords, out_str, out_end, cords_off, cords_cap, ncords, nout, read_err;
     DevBuf gaps, gaps_off, gaps_cap, ngaps, remap, gdense, gcursor, gpos;
     PinBuf h_gaps, h_flags;             // pinned staging of the tail-A results
+    u64 gaps_spec_cap = 0;              // gap entries copied in the same round trip as the flags: sticky, grown by half when a batch wrote more
     JobSet js[2];
     Launch ln;
     TailBuf tb_remap, tb_early, tb_late;
-    PinBuf h_rb[3];                     // pinned landing zones of the small readbacks: [0] batch offsets, [1] tails on the main stream, [2] on s_tail
+    PinBuf h_rb[2];                     // pinned landing zones of the small readbacks: [0] batch offsets and the final counts, [1] the cord counts that size the tails
     DevBuf prof, tl; u32 tl_round = 0, tl_n[4] = {0, 0, 0, 0}; u32 tl_nh[4] = {0, 0, 0, 0};   // LNR_PROF builds
     // ---- the gap re-mapper (-g > 0): arenas of its workers, per-read retry flags, the work counters
     DevBuf gap_arena, gap_flag, gap_next, gap_prof, gap_first, gap_list, gap_rank, gap_weight;
@@ -187,6 +196,7 @@ struct lnr_ctx {
     std::condition_variable cv;
     bool quit = false;
     std::atomic<bool> lane1_off{false}; // lane 1 could not be set up or ran out of memory: everything is computed on lane 0 from now on
+    lnr_ho::Handover ho;                // which lane is in its hand-over (mu; lnr_handover.h)
     bool lane1_nomem_test = false;      // Tuning::lane1_nomem, until lane 1's first batch has consumed it
     std::unique_ptr<Lane> lane[2];      // (last: the lanes go first, while the copy streams are still there)
 

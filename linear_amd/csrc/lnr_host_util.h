@@ -92,35 +92,58 @@ struct Timer : NoCopy {
     double ms() { float f = 0; if (hipEventSynchronize(b) != hipSuccess) return 0; (void)hipEventElapsedTime(&f, a, b); return f; }
 };
 
-// nw 32-bit words from src to dst, either of them pinned host memory, as a kernel's loads and stores on stream st
+// Copy launches of the thread's current batch (LNR_DEBUG_TIMES prints the count: filter_dev resets it)
+thread_local unsigned t_copy_launches = 0;
+
+// Up to COPY_SEGS copies of 32-bit words, either side of each pinned host memory, as one single-wave kernel's loads and stores on
+// stream st (k_words_out).  add() collects, flush() launches; a ninth add launches the eight before it.
+struct CopyBatch {
+    lnr::CopySegs S{};
+    u32 wgs = 0;
+    hipError_t add(void *dst, const void *src, u64 nw, hipStream_t st) {
+        if (!nw) return hipSuccess;
+        if (S.n == COPY_SEGS) { hipError_t e = flush(st); if (e != hipSuccess) return e; }
+        wgs += (u32)std::min<u64>((nw + 63) / 64, 2048);      // (a wave per 64 words, at most 2048 per copy: they loop)
+        S.s[S.n] = {(const u32 *)src, (u32 *)dst, nw};
+        S.wg_end[S.n++] = wgs;
+        return hipSuccess;
+    }
+    hipError_t flush(hipStream_t st) {
+        if (!S.n) return hipSuccess;
+        hipLaunchKernelGGL(lnr::k_words_out, dim3(wgs), dim3(64), 0, st, S);
+        t_copy_launches++;
+        S.n = 0; wgs = 0;
+        return hipGetLastError();
+    }
+};
+// one copy, one launch
 static inline hipError_t copy_words(void *dst, const void *src, u64 nw, hipStream_t st) {
-    if (!nw) return hipSuccess;
-    hipLaunchKernelGGL(lnr::k_words_out, dim3((u32)std::min<u64>((nw + 255) / 256, 1024)), dim3(256), 0, st, (const u32 *)src, (u32 *)dst, nw);
-    return hipGetLastError();
+    CopyBatch cb;
+    (void)cb.add(dst, src, nw, st);
+    return cb.flush(st);
 }
 
 // Device-to-host readbacks of the batch pipeline (counts, flags: a few MB per batch) land in pinned memory and are copied out
 // after the stream sync.  They are written there by a kernel's stores, not by a DMA copy: while the copy stream uploads the next
 // batch (lnr_filter_submit, 1 GB, 18 ms) a DMA readback on the compute stream was measured to queue behind that upload -- the
 // seed stage took 24 ms instead of 6.7 -- and a copy into pageable memory is staged by the runtime on top of that.
+// The adds of one round trip go through one launch: flush(st) before the stream sync, finish() after it.
 struct Readback {
     struct Item { void *dst; size_t off, bytes; };
     PinBuf *pin = nullptr;
     std::vector<Item> items;
     size_t used = 0;
+    CopyBatch cb;
     bool begin(PinBuf &p, size_t total) { pin = &p; items.clear(); used = 0; return p.ensure(total + 64 * 8); }
     hipError_t add(void *dst, const void *dsrc, size_t bytes, hipStream_t st) {   // bytes: a multiple of 4, dsrc 4-byte aligned
         size_t o = (used + 15) & ~(size_t)15;
         used = o + bytes;
         items.push_back({dst, o, bytes});
-        return copy_words((char *)pin->p + o, dsrc, bytes / 4, st);
+        return cb.add((char *)pin->p + o, dsrc, bytes / 4, st);
     }
+    hipError_t flush(hipStream_t st) { return cb.flush(st); }
     void finish() { for (auto &i : items) if (i.bytes) memcpy(i.dst, (char *)pin->p + i.off, i.bytes); }
 };
-
-// pinned host -> device for the small per-batch tables, as a kernel's loads (same reason as Readback: a DMA copy on the compute
-// stream queues behind the copy stream's upload of the next batch)
-static inline hipError_t words_in(void *d_dst, const void *h_pinned, size_t bytes, hipStream_t st) { return copy_words(d_dst, h_pinned, (bytes + 3) / 4, st); }
 
 static const u64 SEQ_PAD = 64;
 static inline u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
@@ -151,16 +174,26 @@ struct ErrText {
 #define LKCHECK() LCK(hipGetLastError())
 #define HIPCK_CTX(c, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { (c)->err = std::string(#call) + ": " + hipGetErrorString(e__); return LNR_ERR_HIP; } } while (0)
 
-// v into b through b's pinned staging, as a kernel's loads on stream st
+// v into b through b's pinned staging, as a kernel's loads (same reason as Readback: a DMA copy on the compute stream queues behind the
+// copy stream's upload of the next batch): collected in cb, on the stream the caller flushes cb on
 template <class T>
-lnr_status upload_on(ErrText &err, DevBuf &b, const std::vector<T> &v, hipStream_t st) {
+lnr_status upload_to(ErrText &err, DevBuf &b, const std::vector<T> &v, CopyBatch &cb, hipStream_t st) {
     ENSURE_TO(err, b, std::max<size_t>(v.size() * sizeof(T), 16));
     if (!v.empty()) {
         void *h = b.host_stage(v.size() * sizeof(T));
         if (!h) { err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
         memcpy(h, v.data(), v.size() * sizeof(T));
-        HIPCK_TO(err, words_in(b.p, h, v.size() * sizeof(T), st));
+        HIPCK_TO(err, cb.add(b.p, h, (v.size() * sizeof(T) + 3) / 4, st));
     }
+    return LNR_OK;
+}
+// (one array, one launch)
+template <class T>
+lnr_status upload_on(ErrText &err, DevBuf &b, const std::vector<T> &v, hipStream_t st) {
+    CopyBatch cb;
+    lnr_status s = upload_to(err, b, v, cb, st);
+    if (s != LNR_OK) return s;
+    HIPCK_TO(err, cb.flush(st));
     return LNR_OK;
 }
 

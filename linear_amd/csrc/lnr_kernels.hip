@@ -22,9 +22,19 @@ namespace lnr {
 #include "lnr_wave.h"
 namespace lnr {
 
-// small device -> pinned-host readbacks as a kernel's stores (see Readback in lnr_api.hip)
-__global__ void __launch_bounds__(256) k_words_out(const u32 *src, u32 *dst, u64 n) {
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) dst[i] = src[i];
+// Small copies between device and pinned host memory as a kernel's loads and stores (see Readback in lnr_host_util.h).  Single-wave
+// workgroups: a wider workgroup needs all its wave slots free on one CU at once, which does not happen while another lane's single-wave
+// bulk kernel refills every slot that frees -- a 256-thread read-back of a few KB was measured to wait 16-25 ms for that kernel to drain.
+// Up to COPY_SEGS copies go through one launch: the workgroups are dealt over the segments by the prefix wg_end of their shares.
+#define COPY_SEGS 8
+struct CopySeg { const u32 *src; u32 *dst; u64 words; };
+struct CopySegs { CopySeg s[COPY_SEGS]; u32 wg_end[COPY_SEGS]; u32 n; };
+__global__ void __launch_bounds__(64) k_words_out(CopySegs S) {
+    u32 b = blockIdx.x, k = 0;
+    while (k + 1 < S.n && b >= S.wg_end[k]) k++;
+    u32 w0 = k ? S.wg_end[k - 1] : 0, nwg = S.wg_end[k] - w0;
+    const u32 *src = S.s[k].src; u32 *dst = S.s[k].dst; u64 n = S.s[k].words;
+    for (u64 i = (u64)(b - w0) * 64 + threadIdx.x; i < n; i += (u64)nwg * 64) dst[i] = src[i];
 }
 
 #if defined(K_JOB_WAVES) && K_JOB_WAVES > 4
