@@ -27,6 +27,24 @@ typedef uint8_t u8;
 
 struct UP { u64 first, second; };   // UPair
 
+// Typed pointers.  A plain `T *` in device code is a generic pointer: every access through it is a flat_ instruction, which counts in both
+// wait counters (the compiler can then only wait for zero: an LDS result waits for every outstanding memory load and the reverse) and takes
+// a 64-bit vector address.  `LNR_GLOBAL T *` / `LNR_LDS T *` say where the array lives: global_ / ds_ instructions, separate counters, a
+// scalar base.  Host pass and host compilers: nothing, so the host twins of the stage code are the same source.
+// Rule of provenance: a typed pointer is made (as_global / as_lds, or a cast from an integer) only where the memory is of that kind by
+// construction -- a kernel argument, the dynamic LDS, a __shared__ object, the global level of the job arena -- never because an array
+// usually is there.  A cast of a pointer into the other space reads or writes a wrong address.  Arrays that live in either (the arena's
+// fast level falls through to the global one) stay generic.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LNR_GLOBAL __attribute__((address_space(1)))
+#define LNR_LDS __attribute__((address_space(3)))
+#else
+#define LNR_GLOBAL
+#define LNR_LDS
+#endif
+template <class T> LNR_HD inline LNR_GLOBAL T *as_global(T *p) { return (LNR_GLOBAL T *)p; }
+template <class T> LNR_HD inline LNR_LDS T *as_lds(T *p) { return (LNR_LDS T *)p; }
+
 // ------------------------------------------------------------------ cords ----
 static const u64 ANCHOR_ZERO = 1ULL << 20;
 static const u64 F_END = 1ULL << 60, F_STRAND = 1ULL << 61, F_RECD = 1ULL << 62, F_MAIN = 1ULL << 63;
@@ -86,10 +104,11 @@ LNR_HD inline u32 lnr_uni32(u32 v) {
 }
 LNR_HD inline u64 lnr_uni64(u64 v) { return ((u64)lnr_uni32((u32)(v >> 32)) << 32) | (u64)lnr_uni32((u32)v); }
 // bounded vector view over caller-provided storage; overflow is recorded, never written past cap
-template <class T>
+// (P: the storage's pointer type where it is known to be global memory, see LNR_GLOBAL; operator[] / back() are for the generic form)
+template <class T, class P = T *>
 struct Vec {
-    T *p; u32 n, cap; int *ovf;
-    LNR_HD void init(T *p_, u32 cap_, int *ovf_) { p = p_; n = 0; cap = cap_; ovf = ovf_; }
+    P p; u32 n, cap; int *ovf;
+    LNR_HD void init(P p_, u32 cap_, int *ovf_) { p = p_; n = 0; cap = cap_; ovf = ovf_; }
     LNR_HD void push(const T &v) { if (n < cap) p[n++] = v; else *ovf = 1; }
     // SIMT-uniform form for code that all lanes of a wave execute together: every lane tracks n, lane 0 stores
     LNR_HD void push_u(const T &v) {
@@ -113,6 +132,19 @@ struct Arena {
         }
         T *r = (T *)(a->base + a->off);
         a->off += bytes;
+        return r;
+    }
+};
+// One level only (the tails: a read's global scratch).  No chain to walk, so in a kernel the base stays a value the compiler can follow
+// back to the kernel argument it was made from: the arrays carved from it are then addressed as global memory without being typed.
+struct Arena1 {
+    char *base; u64 off, cap; int ovf;
+    LNR_HD void init(void *b, u64 c) { base = (char *)b; off = 0; cap = c; ovf = 0; }
+    template <class T> LNR_HD T *get(u64 n) {
+        u64 bytes = (n * sizeof(T) + 15) & ~15ULL;
+        if (off + bytes > cap) { ovf = 1; return (T *)base; }
+        T *r = (T *)(base + off);
+        off += bytes;
         return r;
     }
 };
@@ -323,7 +355,12 @@ LNR_HD inline u64 genome_feature_count(u64 len) { return len < 48 ? 0 : ((len - 
 
 // ---------------------------------------------------------------- features ----
 struct F96 { i32 v0, v1, v2, pad; };   // int96 + pad: one 16-byte load per entry
-struct FeatView { const F96 *p; u32 n; };
+// (the job kernels' views carry typed pointers -- the feature tables are kernel arguments, global memory by construction; the gap
+// re-mapper keeps the generic form)
+template <class FP> struct FeatViewT { FP p; u32 n; };
+typedef FeatViewT<const F96 *> FeatView;
+typedef FeatViewT<LNR_GLOBAL const F96 *> GFeatView;
+template <class FP> LNR_HD inline F96 f96_load(FP p) { F96 r; r.v0 = p->v0; r.v1 = p->v1; r.v2 = p->v2; r.pad = p->pad; return r; }
 
 // 2-mer -> (word, bit) table of pmpfinder.cpp:543-548 folded into arithmetic: pairs (a,b) with
 // a,b<4 and not TT map to bit 6*((4a+b)%5) of word (4a+b)/5; anything else adds nothing.
@@ -365,16 +402,19 @@ LNR_HD inline i64 script_dist(i32 s1, i32 s2) {   // pmpfinder.cpp:497-506
     i32 a0 = ((d >> 24) & 63) - 31, a1 = ((d >> 18) & 63) - 31, a2 = ((d >> 12) & 63) - 31, a3 = ((d >> 6) & 63) - 31, a4 = (d & 63) - 31;
     return (i64)((a0 < 0 ? -a0 : a0) + (a1 < 0 ? -a1 : a1) + (a2 < 0 ? -a2 : a2) + (a3 < 0 ? -a3 : a3) + (a4 < 0 ? -a4 : a4));
 }
-LNR_HD inline i64 window_dist(const F96 *a, const F96 *b) {   // _windowDist2_48 pmpfinder.cpp:523-533
-    F96 a0 = a[0], a3 = a[3], b0 = b[0], b3 = b[3];
+template <class PA, class PB>
+LNR_HD inline i64 window_dist(PA a, PB b) {   // _windowDist2_48 pmpfinder.cpp:523-533
+    F96 a0 = f96_load(a), a3 = f96_load(a + 3), b0 = f96_load(b), b3 = f96_load(b + 3);
     return script_dist(a0.v0, b0.v0) + script_dist(a0.v1, b0.v1) + script_dist(a0.v2, b0.v2) +
            script_dist(a3.v0, b3.v0) + script_dist(a3.v1, b3.v1) + script_dist(a3.v2, b3.v2);
 }
-LNR_HD inline u32 wdist_checked(FeatView f1, FeatView f2, u64 x1, u64 x2) {   // _windowDist pmpfinder.cpp:680-695
+template <class FV>
+LNR_HD inline u32 wdist_checked(FV f1, FV f2, u64 x1, u64 x2) {   // _windowDist pmpfinder.cpp:680-695
     if (x1 + 4 < f1.n && x2 + 4 < f2.n) return (u32)window_dist(f1.p + x1, f2.p + x2);
     return 1000;
 }
-LNR_HD inline u32 wdist_raw(FeatView f1, FeatView f2, u64 x1, u64 x2) {   // __windowDist pmpfinder.cpp:655-663; out of range pinned to abort score
+template <class FV>
+LNR_HD inline u32 wdist_raw(FV f1, FV f2, u64 x1, u64 x2) {   // __windowDist pmpfinder.cpp:655-663; out of range pinned to abort score
     if (x1 + 3 < f1.n && x2 + 3 < f2.n) return (u32)window_dist(f1.p + x1, f2.p + x2);
     return 1000;
 }
@@ -1025,18 +1065,19 @@ static __device__ __attribute__((unused)) int lnr_pd_dummy;
 #define PD_T0() do {} while (0)
 #define PD_T(k) do {} while (0)
 #endif
-LNR_HD inline bool extend_window(FeatView f1, FeatView f2, Vec<u64> &cords, u64 &tail, u64 cordy_str, u64 cordy_end, unsigned long long *lnr_pd_cnt = nullptr) {
+template <class FV, class CV>
+LNR_HD inline bool extend_window(FV f1, FV f2, CV &cords, u64 &tail, u64 cordy_str, u64 cordy_end, unsigned long long *lnr_pd_cnt = nullptr) {
     const int lane = (int)(threadIdx.x & 63);
     (void)lnr_pd_cnt;
     PD_T0();
     // What every lane holds identically goes to scalar registers: the kernel runs at its VGPR cap, and a uniform pointer kept in (spilled)
     // vector registers cost a scratch reload and a wait for ALL outstanding memory traffic before every store of a cord -- a memory round
     // trip per cord pushed.  Scalar registers spill to VGPR lanes, which is a v_readlane.
-    u64 *const cp = (u64 *)lnr_uni64((u64)cords.p);
+    const auto cp = (decltype(cords.p))lnr_uni64((u64)cords.p);   // (keeps the pointer's kind: global_store with a scalar base for the job kernels' cord list)
     const u32 ccap = lnr_uni32(cords.cap);
     u32 cn = lnr_uni32(cords.n);
-    f1.p = (const F96 *)lnr_uni64((u64)f1.p); f1.n = lnr_uni32(f1.n);
-    f2.p = (const F96 *)lnr_uni64((u64)f2.p); f2.n = lnr_uni32(f2.n);
+    f1.p = (decltype(f1.p))lnr_uni64((u64)f1.p); f1.n = lnr_uni32(f1.n);
+    f2.p = (decltype(f2.p))lnr_uni64((u64)f2.p); f2.n = lnr_uni32(f2.n);
     const u32 p_str = cn - 1;
     tail = lnr_uni64(tail); cordy_str = lnr_uni64(cordy_str); cordy_end = lnr_uni64(cordy_end);
     // this lane's window inside the two frontiers
@@ -1090,7 +1131,7 @@ LNR_HD inline bool extend_window(FeatView f1, FeatView f2, Vec<u64> &cords, u64 
         PD_CNT(5, 1);
         lnr_wave_sync();
         if (lnr_is_leader())
-            for (u32 k = p_str; k < (p_str + p_end) / 2; k++) rs_swap(cp[k], cp[cn - k + p_str - 1]);
+            for (u32 k = p_str; k < (p_str + p_end) / 2; k++) { const u32 k2 = cn - k + p_str - 1; const u64 t = cp[k]; cp[k] = cp[k2]; cp[k2] = t; }
         lnr_wave_sync();
         tail = lnr_uni64(cp[cn - 1]);
     }
@@ -1129,7 +1170,8 @@ LNR_HD inline bool extend_window(FeatView f1, FeatView f2, Vec<u64> &cords, u64 
 }
 #else
 // host form: the serial walk
-LNR_HD inline bool extend_window(FeatView f1, FeatView f2, Vec<u64> &cords, u64 &tail, u64 cordy_str, u64 cordy_end) {
+template <class FV, class CV>
+LNR_HD inline bool extend_window(FV f1, FV f2, CV &cords, u64 &tail, u64 cordy_str, u64 cordy_end) {
     u32 p_str = cords.n - 1;
     u64 nc;
     while ((nc = previous_window(f1, f2, tail)) && cord_y(nc) >= cordy_str) {
@@ -1148,16 +1190,20 @@ LNR_HD inline bool extend_window(FeatView f1, FeatView f2, Vec<u64> &cords, u64 
     return true;
 }
 #endif
-struct GenomeFeat { const F96 *base; const u64 *off; u32 nseq; };   // f2 of all sequences, off[nseq+1] in entries
-LNR_HD inline FeatView f2_view(GenomeFeat g, u64 id) {
-    FeatView v;
+template <class FP, class OP> struct GenomeFeatT { FP base; OP off; u32 nseq; };   // f2 of all sequences, off[nseq+1] in entries
+typedef GenomeFeatT<const F96 *, const u64 *> GenomeFeat;
+typedef GenomeFeatT<LNR_GLOBAL const F96 *, LNR_GLOBAL const u64 *> GGenomeFeat;   // (typed form of the job kernels, see FeatViewT)
+template <class FP, class OP>
+LNR_HD inline FeatViewT<FP> f2_view(GenomeFeatT<FP, OP> g, u64 id) {
+    FeatViewT<FP> v;
     if (id >= g.nseq) { v.p = g.base; v.n = 0; return v; }
     v.p = g.base + g.off[id]; v.n = (u32)(g.off[id + 1] - g.off[id]);
     return v;
 }
 // _filterHits pmpfinder.cpp:1417-1445 in two steps: the window distances (elementwise, one hit per lane in the
 // kernel), then the order-dependent compaction with block-end propagation.
-LNR_HD inline void filter_hits_flags(const u64 *hits, u32 nhits, const FeatView f1[2], GenomeFeat g, i32 *keep, u32 first, u32 step) {
+template <class FV, class GF>
+LNR_HD inline void filter_hits_flags(const u64 *hits, u32 nhits, const FV f1[2], GF g, i32 *keep, u32 first, u32 step) {
     for (u32 it = 1 + first; it < nhits; it += step) {
         u32 dist = wdist_checked(f1[cord_strand(hits[it])], f2_view(g, cord_id(hits[it])), cord_y(hits[it]) >> 4, cord_x(hits[it]) >> 4);
         keep[it] = dist < 50 ? 1 : 0;
@@ -1173,21 +1219,22 @@ LNR_HD inline u32 filter_hits_apply(u64 *hits, u32 nhits, const i32 *keep) {
     return nhits - mv;
 }
 // SIMT-uniform (all lanes execute it together on the device; hits are read-only, cords are written by the leader).
-LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2], GenomeFeat g, Vec<u64> &cords_, u64 read_str, u64 read_end, u64 L) {   // pmpfinder.cpp:1309-1410
+template <class FV, class GF, class CV>
+LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FV f1_[2], GF g, CV &cords_, u64 read_str, u64 read_end, u64 L) {   // pmpfinder.cpp:1309-1410
     i64 hitBegin = 1, hitEnd = (i64)nhits;
     if (hitBegin >= hitEnd - 1) return;
     // (wave form: the uniform state in scalar registers, see extend_window; the count goes back to the caller's vector on every way out)
-    Vec<u64> cords = cords_;
-    struct NBack { Vec<u64> &dst; Vec<u64> &src; LNR_HD ~NBack() { dst.n = src.n; } } nback_{cords_, cords};
-    FeatView f1[2] = {f1_[0], f1_[1]};
-    cords.p = (u64 *)lnr_uni64((u64)cords.p); cords.n = lnr_uni32(cords.n); cords.cap = lnr_uni32(cords.cap); cords.ovf = (int *)lnr_uni64((u64)cords.ovf);
-    for (int k = 0; k < 2; k++) { f1[k].p = (const F96 *)lnr_uni64((u64)f1[k].p); f1[k].n = lnr_uni32(f1[k].n); }
-    g.base = (const F96 *)lnr_uni64((u64)g.base); g.off = (const u64 *)lnr_uni64((u64)g.off); g.nseq = lnr_uni32(g.nseq);
+    CV cords = cords_;
+    struct NBack { CV &dst; CV &src; LNR_HD ~NBack() { dst.n = src.n; } } nback_{cords_, cords};
+    FV f1[2] = {f1_[0], f1_[1]};
+    cords.p = (decltype(cords.p))lnr_uni64((u64)cords.p); cords.n = lnr_uni32(cords.n); cords.cap = lnr_uni32(cords.cap); cords.ovf = (int *)lnr_uni64((u64)cords.ovf);
+    for (int k = 0; k < 2; k++) { f1[k].p = (decltype(f1[k].p))lnr_uni64((u64)f1[k].p); f1[k].n = lnr_uni32(f1[k].n); }
+    g.base = (decltype(g.base))lnr_uni64((u64)g.base); g.off = (decltype(g.off))lnr_uni64((u64)g.off); g.nseq = lnr_uni32(g.nseq);
     read_str = lnr_uni64(read_str); read_end = lnr_uni64(read_end); L = lnr_uni64(L);
     hitEnd = (i64)lnr_uni32(nhits);
     u64 tail;
     if (cords.n == 0) { cords.push_u(F_END); tail = F_END; }   // initCords
-    else tail = lnr_uni64(cords[cords.n - 1]);
+    else tail = lnr_uni64(cords.p[cords.n - 1]);
     u64 ready_str, ready_end, cordy_str = 0, cordy_end = 0;
     bool f_sp_l, f_sp_r = false, f_block_end = false, f_append;
     i64 itt_next = hitBegin + 1, itt_first = hitBegin;
@@ -1214,7 +1261,7 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2],
 #else
     auto HIT = [&](i64 i) -> u64 { return hits[i]; };
 #endif
-    u64 view_id = ~0ULL; FeatView view_f2; view_f2.p = g.base; view_f2.n = 0;
+    u64 view_id = ~0ULL; FV view_f2; view_f2.p = g.base; view_f2.n = 0;
     for (i64 itt = hitBegin; itt < hitEnd; itt = itt_next++) {
         const u64 hi = HIT(itt), hpv = HIT(itt - 1);
         bool first_i = is_end(hpv);
@@ -1258,7 +1305,7 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FeatView f1_[2],
         if (0)
 #endif
         if (f_append && !extend_window(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end)) return;
-        if (f_block_end) { tail |= F_END; if (lnr_is_leader()) cords[cords.n - 1] = tail; }
+        if (f_block_end) { tail |= F_END; if (lnr_is_leader()) cords.p[cords.n - 1] = tail; }
         itt_next = f_block_end ? itt_first : itt_next;
         f_sp_r = false; f_block_end = false;
     }
@@ -1399,8 +1446,8 @@ LNR_HD inline u32 filter_blocks_cords(const BlockSink &ch, const u64 *hits, u64 
 struct JobCtx {
     u64 L, read_str, read_end;
     int mode;
-    FeatView f1[2];
-    GenomeFeat g;
+    GFeatView f1[2];   // typed: kernel arguments in the job kernels (host: the plain views)
+    GGenomeFeat g;
     u16 *bins; u32 nbins;
     u64 *pair_evals;
     unsigned long long *prof;   // diagnostic build only
@@ -1515,12 +1562,13 @@ LNR_HD inline int job_phase3a(u64 *a, u32 m, JobScratch &S, const JobCtx &c, Job
 // clean, gather (sets block ends), gaps.  Returns the number of remap gaps written (0 = no remap).
 LNR_HD inline u32 drop_len_of(u64 L) { i64 d = (i64)((double)L * 0.05 / 96); return (u32)(d < 2 ? d : 2); }
 
-LNR_HD inline int tail_a(u64 *cords, u32 &ncords, u64 L, Arena &ar, UP *gaps_out, u32 gaps_cap, u32 &ngaps, u32 &remap, LeaderScratch &ls) {
+template <class AR>
+LNR_HD inline int tail_a(u64 *cords, u32 &ncords, u64 L, AR &ar, UP *gaps_out, u32 gaps_cap, u32 &ngaps, u32 &remap, LeaderScratch &ls) {
     int ovf = 0;
     ncords = clean_blocks(cords, ncords, drop_len_of(L));
     u32 cap = ncords + 2;
-    Vec<UP> str_ends; str_ends.init(ar.get<UP>(cap), cap, &ovf);
-    Vec<UP> sep; sep.init(ar.get<UP>(cap), cap, &ovf);
+    Vec<UP> str_ends; str_ends.init(ar.template get<UP>(cap), cap, &ovf);
+    Vec<UP> sep; sep.init(ar.template get<UP>(cap), cap, &ovf);
     if (ar.ovf) return 1;
     gather_blocks(cords, ncords, &str_ends, sep, 1, ncords, L, 1000, 96, 1);
     Vec<UP> gaps; gaps.init(gaps_out, gaps_cap, &ovf);
@@ -1531,25 +1579,26 @@ LNR_HD inline int tail_a(u64 *cords, u32 &ncords, u64 L, Arena &ar, UP *gaps_out
 }
 // Tail B = rest of apxMap (pmpfinder.cpp:2764-2801): re-gather, chain cord blocks on both strands, clean, flags.
 // out_str/out_end receive the final cords; returns count through nout.
-LNR_HD inline int tail_b(u64 *cords, u32 ncords, u64 L, Arena &ar, u64 *out_str, u64 *out_end, u32 out_cap, u32 &nout, LeaderScratch &ls) {
+template <class AR>
+LNR_HD inline int tail_b(u64 *cords, u32 ncords, u64 L, AR &ar, u64 *out_str, u64 *out_end, u32 out_cap, u32 &nout, LeaderScratch &ls) {
     int ovf = 0;
     u32 cap = ncords + 2;
-    Vec<UP> sep; sep.init(ar.get<UP>(cap), cap, &ovf);
+    Vec<UP> sep; sep.init(ar.template get<UP>(cap), cap, &ovf);
     gather_blocks(cords, ncords, nullptr, sep, 1, ncords, L, 1000, 96, 1);
     // chainBlocksCords cluster_util.cpp:1068-1102
     u32 nb = sep.n;
-    UP *sep1 = ar.get<UP>(cap), *sep2 = ar.get<UP>(cap);
-    i32 *score1 = ar.get<i32>(cap), *score2 = ar.get<i32>(cap);
+    UP *sep1 = ar.template get<UP>(cap), *sep2 = ar.template get<UP>(cap);
+    i32 *score1 = ar.template get<i32>(cap), *score2 = ar.template get<i32>(cap);
     for (u32 i = 0; i < nb; i++) { sep1[i] = sep[i]; sep2[i] = sep[i]; }
     BlockSink c1, c2;
-    c1.el = ar.get<UP>(cap + 1); c1.off = ar.get<i32>(cap + 2); c1.nchains = 0; c1.nel = 0; c1.cap = cap; c1.ovf = &ovf; c1.first_len = 0; c1.off[0] = 0;
-    c2.el = ar.get<UP>(cap + 1); c2.off = ar.get<i32>(cap + 2); c2.nchains = 0; c2.nel = 0; c2.cap = cap; c2.ovf = &ovf; c2.first_len = 0; c2.off[0] = 0;
+    c1.el = ar.template get<UP>(cap + 1); c1.off = ar.template get<i32>(cap + 2); c1.nchains = 0; c1.nel = 0; c1.cap = cap; c1.ovf = &ovf; c1.first_len = 0; c1.off[0] = 0;
+    c2.el = ar.template get<UP>(cap + 1); c2.off = ar.template get<i32>(cap + 2); c2.nchains = 0; c2.nel = 0; c2.cap = cap; c2.ovf = &ovf; c2.first_len = 0; c2.off[0] = 0;
     BlockScratch s;
-    s.ptr = ar.get<u32>(cap); s.sep_tmp = ar.get<UP>(cap); s.score_tmp = ar.get<i32>(cap);
-    s.rec.score = ar.get<i32>(cap); s.rec.score2 = ar.get<i32>(cap); s.rec.len = ar.get<i32>(cap); s.rec.p2 = ar.get<i32>(cap); s.rec.root = ar.get<i32>(cap); s.rec.leaf = ar.get<i32>(cap);
-    s.chain = ar.get<i32>(cap); s.chain_sc = ar.get<i32>(cap); s.cnt = ar.get<i32>(cap); s.ls = &ls;
-    UP *sep_tmp2 = ar.get<UP>(cap);
-    u64 *tmp_cords = ar.get<u64>(cap + 2);
+    s.ptr = ar.template get<u32>(cap); s.sep_tmp = ar.template get<UP>(cap); s.score_tmp = ar.template get<i32>(cap);
+    s.rec.score = ar.template get<i32>(cap); s.rec.score2 = ar.template get<i32>(cap); s.rec.len = ar.template get<i32>(cap); s.rec.p2 = ar.template get<i32>(cap); s.rec.root = ar.template get<i32>(cap); s.rec.leaf = ar.template get<i32>(cap);
+    s.chain = ar.template get<i32>(cap); s.chain_sc = ar.template get<i32>(cap); s.cnt = ar.template get<i32>(cap); s.ls = &ls;
+    UP *sep_tmp2 = ar.template get<UP>(cap);
+    u64 *tmp_cords = ar.template get<u64>(cap + 2);
     if (ar.ovf) return 1;
     chain_blocks_single_strand(cords, sep1, nb, score1, c1, 0, L, s);
     // chains of strand 0 reference s.sep_tmp through copies in c1.el, so the scratch can be reused

@@ -1131,7 +1131,8 @@ struct JobArgs {
 // (bit 63, unused by the anchor format cords.cpp:319-322) and the compaction strips the mark.
 #define BIN_SAT 100u   /* counts saturate here: only "more than 10" is asked.  At most 64 adds are in flight beyond it (one
                           wave instruction; its undo is issued before the next add), so a byte never carries into its neighbour */
-__device__ u32 binning_exact_wave(u64 *a, u32 n, u32 *binw, u32 hist_bytes, u32 nbins) {
+// (a: global memory -- the job's anchors or the radix buffer; binw: the dynamic LDS)
+__device__ u32 binning_exact_wave(LNR_GLOBAL u64 *a, u32 n, LNR_LDS u32 *binw, u32 hist_bytes, u32 nbins) {
     int lane = lane_id();
     const u64 MARK = 1ULL << 63;
     u32 per = hist_bytes & ~3u;                         // bins per pass
@@ -1150,8 +1151,8 @@ __device__ u32 binning_exact_wave(u64 *a, u32 n, u32 *binw, u32 hist_bytes, u32 
                 u32 b = (u32)(cord_x(v[u]) / 30000) - b_lo;
                 if (i < n && b < b_n) {
                     u32 sh = 8 * (b & 3), inc = 1u << sh;
-                    u32 old = atomicAdd(&binw[b >> 2], inc);
-                    if (((old >> sh) & 0xffu) >= BIN_SAT) atomicSub(&binw[b >> 2], inc);
+                    u32 old = lds_add(&binw[b >> 2], inc);
+                    if (((old >> sh) & 0xffu) >= BIN_SAT) lds_add(&binw[b >> 2], 0u - inc);
                 }
                 WLDS();                         // this chunk's undo is issued before the next chunk's add
             }
@@ -1215,7 +1216,7 @@ __device__ u32 binning_exact_wave(u64 *a, u32 n, u32 *binw, u32 hist_bytes, u32 
 // (Measured on the GRCh38 stand-in: no change of the kernel's time against the plain two-pass histogram -- the stage costs 1.3 ms of
 // 31 when the kernel has the chip to itself; what made it look like 7 ms was the 4-wave kernel holding 14 of 16 wave slots per CU.)
 #define BIN_HASH 4096u
-__device__ JOB_INLINE u32 binning_wave(u64 *a, u32 n, u64 *tmp, u32 *binw, u32 hist_bytes, u32 nbins) {
+__device__ JOB_INLINE u32 binning_wave(LNR_GLOBAL u64 *a, u32 n, LNR_GLOBAL u64 *tmp, LNR_LDS u32 *binw, u32 hist_bytes, u32 nbins) {
     int lane = lane_id();
     if (n <= 256 || hist_bytes < BIN_HASH || !tmp) {           // short lists: the exact histogram directly (in place)
         u32 k = binning_exact_wave(a, n, binw, hist_bytes, nbins);
@@ -1233,8 +1234,8 @@ __device__ JOB_INLINE u32 binning_wave(u64 *a, u32 n, u64 *tmp, u32 *binw, u32 h
             u32 b = (u32)(cord_x(v[u]) / 30000);
             if (i < n && b < nbins) {
                 u32 hb = b & (BIN_HASH - 1), sh = 8 * (hb & 3), inc = 1u << sh;
-                u32 old = atomicAdd(&binw[hb >> 2], inc);
-                if (((old >> sh) & 0xffu) >= BIN_SAT) atomicSub(&binw[hb >> 2], inc);
+                u32 old = lds_add(&binw[hb >> 2], inc);
+                if (((old >> sh) & 0xffu) >= BIN_SAT) lds_add(&binw[hb >> 2], 0u - inc);
             }
             WLDS();
         }
@@ -1275,9 +1276,9 @@ __device__ JOB_INLINE u32 binning_wave(u64 *a, u32 n, u64 *tmp, u32 *binw, u32 h
 
 // wave-level LSD radix sort, ascending u64 (the reference's ska_sort, base.cpp:570; result unique).
 // Returns with the sorted keys in `a`.  hist = 256 LDS words.
-__device__ void radix_sort_wave(u64 *a, u64 *alt, u32 n, u32 *hist) {
+__device__ void radix_sort_wave(LNR_GLOBAL u64 *a, LNR_GLOBAL u64 *alt, u32 n, LNR_LDS u32 *hist) {
     int lane = lane_id();
-    u64 *src = a, *dst = alt;
+    LNR_GLOBAL u64 *src = a, *dst = alt;
     for (int pass = 0; pass < 8; pass++) {
         int shift = pass * 8;
         for (int b = lane; b < 256; b += 64) hist[b] = 0;
@@ -1287,7 +1288,7 @@ __device__ void radix_sort_wave(u64 *a, u64 *alt, u32 n, u32 *hist) {
 #pragma unroll
             for (int u = 0; u < 4; u++) { u32 i = i0 + 64 * u + lane; k[u] = i < n ? src[i] : 0; }
 #pragma unroll
-            for (int u = 0; u < 4; u++) if (i0 + 64 * u + lane < n) atomicAdd(&hist[(k[u] >> shift) & 255], 1u);
+            for (int u = 0; u < 4; u++) if (i0 + 64 * u + lane < n) lds_add(&hist[(k[u] >> shift) & 255], 1u);
         }
         WSYNC();
         // exclusive prefix over the 256 bins: 4 bins per lane
@@ -1329,7 +1330,7 @@ __device__ void radix_sort_wave(u64 *a, u64 *alt, u32 n, u32 *hist) {
             }
         }
         WSYNC();                                     // the pass's stores are visible before the next pass reads them
-        u64 *t = src; src = dst; dst = t;
+        LNR_GLOBAL u64 *t = src; src = dst; dst = t;
     }
     if (src != a) { for (u32 i = lane; i < n; i += 64) a[i] = src[i]; }
     WSYNC();
@@ -1339,16 +1340,17 @@ __device__ void radix_sort_wave(u64 *a, u64 *alt, u32 n, u32 *hist) {
 // the keys; per pass the per-wave digit counts are turned into per-wave cursors (bin b of wave w starts behind all smaller
 // bins and behind bin b of the waves before it), so equal digits keep their order -- the result is the one of the wave form.
 // rh = NW x 256 LDS words, tot = 256, flag = 1.  Every wave of the workgroup calls this; it ends with a workgroup barrier.
+typedef u32 RadixHist[256];
 template <int NW>
-__device__ void radix_sort_block(u64 *a, u64 *alt, u32 n, u32 (*rh)[256], u32 *tot, u32 *flag) {
+__device__ void radix_sort_block(LNR_GLOBAL u64 *a, LNR_GLOBAL u64 *alt, u32 n, LNR_LDS RadixHist *rh, LNR_LDS u32 *tot, LNR_LDS u32 *flag) {
     int lane = lane_id();
     int wave = (int)(threadIdx.x >> 6);
     u32 tid = threadIdx.x;
     u32 per = (((n + NW - 1) / NW) + 63u) & ~63u;            // slice length, whole chunks of 64
     u32 lo = (u32)wave * per; lo = lo < n ? lo : n;
     u32 hi = lo + per < n ? lo + per : n;
-    u32 *hist = rh[wave];
-    u64 *src = a, *dst = alt;
+    LNR_LDS u32 *hist = rh[wave];
+    LNR_GLOBAL u64 *src = a, *dst = alt;
     if (tid == 0) *flag = 0;
     for (int pass = 0; pass < 8; pass++) {
         int shift = pass * 8;
@@ -1359,7 +1361,7 @@ __device__ void radix_sort_block(u64 *a, u64 *alt, u32 n, u32 (*rh)[256], u32 *t
 #pragma unroll
             for (int u = 0; u < 4; u++) { u32 i = i0 + 64 * u + lane; k[u] = i < hi ? src[i] : 0; }
 #pragma unroll
-            for (int u = 0; u < 4; u++) if (i0 + 64 * u + lane < hi) atomicAdd(&hist[(k[u] >> shift) & 255], 1u);
+            for (int u = 0; u < 4; u++) if (i0 + 64 * u + lane < hi) lds_add(&hist[(k[u] >> shift) & 255], 1u);
         }
         __syncthreads();
         for (u32 b = tid; b < 256; b += NW * 64) {            // (a two-wave workgroup has 128 threads for the 256 bins)
@@ -1413,7 +1415,7 @@ __device__ void radix_sort_block(u64 *a, u64 *alt, u32 n, u32 (*rh)[256], u32 *t
             }
         }
         __syncthreads();                                      // the pass's stores are visible to the waves that read them next
-        u64 *t = src; src = dst; dst = t;
+        LNR_GLOBAL u64 *t = src; src = dst; dst = t;
     }
     if (src != a) { for (u32 i = tid; i < n; i += NW * 64) a[i] = src[i]; }
     __syncthreads();
@@ -2483,7 +2485,7 @@ __device__ void best_chains_block(const u32 *xs, const u32 *ys, u32 m, Rec r, in
 //             waves join for the radix sort (radix_sort_block), the x-descending sort (introsort_xdesc_block) and the chaining
 //             DP (best_chains_block) and otherwise wait at the workgroup barriers that frame those three phases.
 struct DpShare { const u32 *xs, *ys; Rec rec; i32 *jlo; u32 m; int score_type; int abort; };
-struct RadixShare { u64 *a, *alt; u32 n; };
+struct RadixShare { LNR_GLOBAL u64 *a, *alt; u32 n; };
 #ifndef RADIX_BLOCK_MIN
 #define RADIX_BLOCK_MIN 2048   // shortest array the workgroup forms are used for (tools/stress_parity.py runs a build with 64)
 #endif
@@ -2491,8 +2493,10 @@ struct SortShare { u64 *a; u32 *L, *R; u64 *tasks, *stg; u32 stg_cap, n; };
 #ifndef SORT_BLOCK_MIN
 #define SORT_BLOCK_MIN 2048
 #endif
+// (inlined into its four kernels: JobArgs stays in the kernel arguments -- scalar loads, pointers known to be global memory -- instead of
+// reaching the job code as a stack copy behind a call)
 template <int NW>
-__device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
+__device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS u32 *dyn_lds) {
     __shared__ u32 s_m;
     __shared__ int s_ovf, s_flag[4];
     __shared__ u64 *s_H;
@@ -2501,7 +2505,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
     // the 256 digit counters of the wave radix sort live in the four 64-entry tree tables (used by the traceback only): every
     // static LDS byte of the single-wave kernel is one byte less for its arena at 16 workgroups per CU
     static_assert(sizeof(s_ls.l_root) + sizeof(s_ls.l_score) + sizeof(s_ls.l_len) + sizeof(s_ls.l_leaf) == 256 * sizeof(u32), "tree tables = 256 words");
-    u32 *hist = (u32 *)s_ls.l_root;
+    LNR_LDS u32 *hist = as_lds((u32 *)s_ls.l_root);
     __shared__ DpTile<NW> s_tile;    // tiled chaining DP: leaf flags (+ the per-wave candidates of a multi-wave workgroup)
     __shared__ DpShare s_dp;         // NW > 1: what the helper waves need for the DP
     __shared__ RadixShare s_rs;      // NW > 1: ... and for the radix sort
@@ -2519,8 +2523,8 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
     u64 L = A.read_len[r];
     if (threadIdx.x == 0) s_ovf = 0;
     if (NW == 1) WSYNC(); else __syncthreads();
-    Vec<u64> cords;
-    cords.init(A.cords + A.cords_off[r], A.cords_cap[r], &s_ovf);
+    Vec<u64, LNR_GLOBAL u64 *> cords;
+    cords.init(as_global(A.cords) + A.cords_off[r], A.cords_cap[r], &s_ovf);
     cords.n = A.ncords[r];
     unsigned long long tk_ = 0;
 #ifdef LNR_PROF
@@ -2545,22 +2549,22 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
 #ifdef LNR_PROF
         for (int q = 0; q < 16; q++) lnr_job_ph[q] = 0;
 #endif
-        u64 *ag = nullptr, *s_alt = nullptr;
+        LNR_GLOBAL u64 *ag = nullptr, *s_alt = nullptr;   // the job's anchors and the radix buffer (global level of the arena)
         u32 n = 0, cap = 0;
         u32 *so_L = nullptr, *so_R = nullptr; u64 *so_tasks = nullptr, *so_stg = nullptr; u32 so_stg_cap = 0;   // scratch of the x-descending sort
         if (lead) {
-            ag = A.anchors + A.anc_off[j];
+            ag = as_global(A.anchors) + A.anc_off[j];
             n = A.n_anchors[j];
             cap = n + 2;   // scratch is sized by the anchors that passed the Y filter (known before the launch), not by the bucket entries
             LNR_TICK(prof, 0, tk_);
             // two-level arena: dynamic LDS first (re-used once binning is done), the job's global scratch behind it
             slow.init(A.scratch + A.scr_off[j], job_scratch_bytes(cap));
-            u64 *alt = slow.get<u64>(cap);            // radix ping-pong buffer; before that, the survivors of the binning pre-filter
+            LNR_GLOBAL u64 *alt = as_global(slow.get<u64>(cap));   // radix ping-pong buffer; before that, the survivors of the binning pre-filter
             if (NW == 1 && A.stop_after == 1) break;   // (diagnostic: start-up only)
             n = binning_wave(ag, n, alt, dyn_lds, A.lds_bytes, A.nbins);   // uses the dynamic LDS as its histogram
             LNR_TICK(prof, 1, tk_);
             if (NW == 1 && A.stop_after == 2) break;
-            ar.init((void *)dyn_lds, A.arena_lds); ar.next = &slow;
+            ar.init((void *)(u32 *)dyn_lds, A.arena_lds); ar.next = &slow;
             a = ag;
             if (n > 1) {
                 s_alt = alt;
@@ -2576,8 +2580,8 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             __syncthreads();
             RadixShare rs = s_rs;
             if (rs.n) {                                // ends with a workgroup barrier (call / inline: see chain_blocks_prepare_wave)
-                if (NW >= 4) { [[clang::noinline]] radix_sort_block<NW>(rs.a, rs.alt, rs.n, s_rhist, s_rtot, &s_rflag); }
-                else radix_sort_block<NW>(rs.a, rs.alt, rs.n, s_rhist, s_rtot, &s_rflag);
+                if (NW >= 4) { [[clang::noinline]] radix_sort_block<NW>(rs.a, rs.alt, rs.n, as_lds(s_rhist), as_lds(s_rtot), as_lds(&s_rflag)); }
+                else radix_sort_block<NW>(rs.a, rs.alt, rs.n, as_lds(s_rhist), as_lds(s_rtot), as_lds(&s_rflag));
             }
             else if (lead && n > 1) radix_sort_wave(ag, s_alt, n, hist);
         }
@@ -2594,13 +2598,13 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             if (NW == 1 && A.stop_after == 13) break;   // after the list filter
             if (m > 1) {
                 // scratch of the sort: position lists in the (dead) radix buffer, task list behind it
-                so_L = (u32 *)s_alt; so_R = so_L + (m + 2);
+                so_L = (u32 *)(u64 *)s_alt; so_R = so_L + (m + 2);
                 so_tasks = slow.get<u64>((u64)m + 2);
                 // free LDS behind the arena's current mark can stage the final small sorts when `a` itself is in global memory
                 {
-                    bool a_in_lds = (char *)a >= (char *)dyn_lds && (char *)a < (char *)dyn_lds + A.arena_lds;
+                    bool a_in_lds = (char *)a >= (char *)(u32 *)dyn_lds && (char *)a < (char *)(u32 *)dyn_lds + A.arena_lds;
                     u64 used = (ar.off + 15) & ~15ULL;
-                    if (!a_in_lds && A.arena_lds > used + 4096) { so_stg = (u64 *)((char *)dyn_lds + used); so_stg_cap = (u32)((A.arena_lds - used) / 8); }
+                    if (!a_in_lds && A.arena_lds > used + 4096) { so_stg = (u64 *)((char *)(u32 *)dyn_lds + used); so_stg_cap = (u32)((A.arena_lds - used) / 8); }
                 }
                 if (NW == 1) introsort_xdesc_wave(a, m, so_L, so_R, so_tasks, &s_ls, so_stg, so_stg_cap);
             }
@@ -2663,9 +2667,9 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             c.traceback_done = 1;
             c.L = L; c.read_str = A.J.str[j]; c.read_end = A.J.end[j]; c.mode = mode;
             u32 nf = A.nf[r];
-            c.f1[0].p = A.f1 + A.f1_off[r]; c.f1[0].n = nf;
-            c.f1[1].p = A.f1 + A.f1_off[r] + nf; c.f1[1].n = nf;
-            c.g = A.g; c.bins = nullptr; c.nbins = 0; c.pair_evals = nullptr; c.prof = prof;
+            c.f1[0].p = as_global(A.f1) + A.f1_off[r]; c.f1[0].n = nf;
+            c.f1[1].p = as_global(A.f1) + A.f1_off[r] + nf; c.f1[1].n = nf;
+            c.g.base = as_global(A.g.base); c.g.off = as_global(A.g.off); c.g.nseq = A.g.nseq; c.bins = nullptr; c.nbins = 0; c.pair_evals = nullptr; c.prof = prof;
             // hit blocks: gather (leader) -> prefilter (lanes over blocks) -> scores -> block DP (lanes over predecessors)
             // -> traceback + rewrite (leader)
             if (lane == 0) s_nhits = S.hits.n;
@@ -2681,7 +2685,7 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
             u32 nb = 0;
             bool in_lds = false;
             if (A.arena_lds) {
-                Arena pl; pl.init((void *)dyn_lds, A.arena_lds);
+                Arena pl; pl.init((void *)(u32 *)dyn_lds, A.arena_lds);
                 const u32 nh = S.hits.n;
                 u64 *lh = pl.get<u64>((u64)nh + 2), *lH = pl.get<u64>((u64)nh + 2);
                 i32 *lcnt = pl.get<i32>((u64)nh + 2);
@@ -2804,23 +2808,23 @@ __device__ void job_group_run(const JobArgs &A, u32 grp, u32 *dyn_lds) {
 __global__ void __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(K_JOB_WAVES, K_JOB_WAVES))) k_job(JobArgs A) {
     extern __shared__ u32 dyn_lds[];
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<1>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
+    job_group_run<1>(A, A.grp_order[A.grp_lo + blockIdx.x], as_lds(dyn_lds));
 }
 __global__ void __launch_bounds__(1024) k_job_heavy(JobArgs A) {
     extern __shared__ u32 dyn_lds[];
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<16>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
+    job_group_run<16>(A, A.grp_order[A.grp_lo + blockIdx.x], as_lds(dyn_lds));
 }
 __global__ void __launch_bounds__(256, 4) k_job_mid(JobArgs A) {
     extern __shared__ u32 dyn_lds[];
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<4>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
+    job_group_run<4>(A, A.grp_order[A.grp_lo + blockIdx.x], as_lds(dyn_lds));
 }
 // the same class on two waves (LNR_MID_WAVES=2): half the wave slots per read for a longer time
 __global__ void __launch_bounds__(128, 4) k_job_mid2(JobArgs A) {
     extern __shared__ u32 dyn_lds[];
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
-    job_group_run<2>(A, A.grp_order[A.grp_lo + blockIdx.x], dyn_lds);
+    job_group_run<2>(A, A.grp_order[A.grp_lo + blockIdx.x], as_lds(dyn_lds));
 }
 
 // Placed on the bulk stream ahead of k_job when multi-wave kernels were launched beside it: a 4- or 16-wave workgroup
@@ -2848,7 +2852,7 @@ __global__ void __launch_bounds__(64) k_tail_a(TailArgs T) {
     T.ngaps[r] = 0; T.remap[r] = 0;
     u64 L = T.read_len[r];
     if (L <= 200 || T.read_err[r]) return;
-    Arena ar; ar.init(T.scratch + T.scr_off[r], tail_scratch_bytes(T.scr_cap[r]));
+    Arena1 ar; ar.init(T.scratch + T.scr_off[r], tail_scratch_bytes(T.scr_cap[r]));
     u32 nc = T.ncords[r], ng = 0, rm = 0;
     LeaderScratch ls;
     int rc = tail_a(T.cords + T.cords_off[r], nc, L, ar, T.gaps + T.gaps_off[r], T.gaps_cap[r], ng, rm, ls);
@@ -2868,7 +2872,7 @@ __global__ void __launch_bounds__(64) k_tail_b(TailArgs T) {
     T.nout[r] = 0;
     u64 L = T.read_len[r];
     if (L <= 200 || T.read_err[r]) return;
-    Arena ar; ar.init(T.scratch + T.scr_off[r], tail_scratch_bytes(T.scr_cap[r]));
+    Arena1 ar; ar.init(T.scratch + T.scr_off[r], tail_scratch_bytes(T.scr_cap[r]));
     u32 no = 0;
     LeaderScratch ls;
     int rc = tail_b(T.cords + T.cords_off[r], T.ncords[r], L, ar, T.out_str + T.cords_off[r], T.out_end + T.cords_off[r], T.cords_cap[r], no, ls);

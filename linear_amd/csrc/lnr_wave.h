@@ -23,6 +23,8 @@ __device__ __forceinline__ void WLDS() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// counter in LDS: ds_add (the address is typed, see LNR_LDS in lnr_hd.h); what atomicAdd / atomicSub do through a generic pointer
+__device__ __forceinline__ u32 lds_add(LNR_LDS u32 *p, u32 v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u64 lanemask_lt() { return (1ULL << lane_id()) - 1ULL; }
 // Cross-lane reductions and scans on the DPP path of the VALU (row operations inside 16 lanes, row broadcasts across the
 // four rows of a wave64): a dozen VALU instructions instead of six dependent ds_bpermute round trips through the LDS
