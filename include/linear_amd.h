@@ -389,12 +389,21 @@ lnr_status lnr_writer_format_bam_dev(lnr_writer *w, const lnr_cords_dev *cords, 
 
 /* Coordinate-sorted BAM with a BAI index (an extension: the reference tells its users to run `samtools sort` / `samtools index`).
  * A sort mode of the GPU writer.  Between lnr_writer_sort_begin and lnr_writer_sort_finish, lnr_writer_format_bam_gpu / _dev keep the
- * batch's raw records on the device (copied into segments the GPU side owns: at least 256 MiB each -- less where max_device_bytes leaves
+ * batch's raw records (copied by k_sort_keep into segments the GPU side owns: at least 256 MiB each -- less where max_device_bytes leaves
  * less --, a batch contiguous in one) and return *size = 0; lnr_writer_bam_header puts "@HD\tVN:1.6\tSO:coordinate\n" in front of its text;
- * every other call is unchanged.  max_device_bytes bounds the record bytes kept (0: no bound of its own); a batch that would pass it, or a
- * segment that cannot be allocated, makes the BAM call return LNR_ERR_NOMEM (lnr_writer_error names the bytes held and asked for) and
- * leaves the batches added before intact.  ALL records stay in HBM until lnr_writer_sort_end: about 0.8 KB per read without SEQ, 15.8 KB
- * per 10 kb read with it; spilling to the host is not built.
+ * every other call is unchanged.
+ * THE HOLD IS COMPACT: this writer has no qualities, every record with SEQ carries l_seq bytes of 0xff, and those are not held; the gather
+ * writes them again, so the sorted stream and every size reported about it are those of the full records.  Held per read: about 0.8 KB
+ * without SEQ, 5.8 KB of the 15.8 KB record of a 10 kb read with it.  max_device_bytes bounds the bytes HELD on the device (0: no bound of
+ * its own; without SEQ held and record bytes are the same number).
+ * THE TIERS: a batch goes to the device if it fits under max_device_bytes and its segment can be allocated.  Otherwise, once
+ * lnr_writer_sort_spill(max_host_bytes) has been called in this round (while collecting; 0 switches it off again), it goes to the host tier
+ * if held_host_bytes + batch <= max_host_bytes and its segment can be allocated: pinned host memory the GPU reads in place (hipHostMalloc;
+ * segments of 64 MiB, less where max_host_bytes leaves less, never less than the batch; no managed memory, no XNACK), written by one
+ * device-to-host copy per batch and read by k_sort_gather over the bus when the pieces are made.  Otherwise the BAM call returns
+ * LNR_ERR_NOMEM (lnr_writer_error names the bytes held -- on both tiers where the host tier is on -- and asked for) and leaves the batches
+ * added before intact.  A batch is whole in one segment of one tier.  Everything is held until lnr_writer_sort_end, which also ends the
+ * spill setting: it belongs to the round.  lnr_writer_sort_hold_info_get (any time between begin and end): what is held where.
  * THE ORDER: (uint32)refID (so -1 sorts last), (uint32)pos, the reverse-strand bit (flag & 0x10, forward first), then the record's byte
  * offset in the stream of records as they were added (batches in call order, records as the BAM calls emit them).  The order is total: the
  * output is a function of the input alone.  Whether samtools breaks (refID, pos) ties by strand has not been verified here.
@@ -411,7 +420,7 @@ lnr_status lnr_writer_format_bam_dev(lnr_writer *w, const lnr_cords_dev *cords, 
  * one's value; a reference without records has n_bin 0 and n_intv 0; refID < 0 counts in n_no_coor.  A record with refID >= 0 and pos < 0
  * or end > 2^29 cannot be indexed: LNR_ERR_UNSUPPORTED naming the record (the sorted BAM stays valid).  Byte equality with `samtools index`
  * is not claimed (htslib merges chunks further).  Bytes returned live until the writer's next call.
- * Errors: before lnr_writer_gpu_open, and calls out of order (begin twice, next before finish, bai before the last piece): LNR_ERR_ARG with
+ * Errors: before lnr_writer_gpu_open, and calls out of order (begin twice, spill before begin or after finish, next before finish, bai before the last piece): LNR_ERR_ARG with
  * the reason in lnr_writer_error.  lnr_writer_sort_end frees the segments and leaves the mode; lnr_writer_destroy does so too.
  * lnr_writer_sort_host / lnr_writer_bai_host: the same order and the same index on the host, no device needed (the in-library yardsticks). */
 typedef struct {
@@ -421,7 +430,15 @@ typedef struct {
     double index_ms, sort_ms;        /* k_sort_index summed over the batches; the sort with its gathers and scan (HIP events) */
     double gather_ms, deflate_ms, pack_ms, download_ms;   /* summed over the pieces handed out so far */
 } lnr_sort_info;
+typedef struct {
+    uint64_t stream_bytes;                 /* length of S so far */
+    uint64_t held_device_bytes, held_host_bytes;   /* record bytes held per tier (compact) */
+    uint64_t device_batches, host_batches; /* batches that went to each tier */
+    double keep_ms, spill_ms;              /* k_sort_keep summed; device->host copies summed */
+} lnr_sort_hold_info;
 lnr_status lnr_writer_sort_begin(lnr_writer *w, uint64_t max_device_bytes);
+lnr_status lnr_writer_sort_spill(lnr_writer *w, uint64_t max_host_bytes);   /* while collecting; 0 switches it off again */
+lnr_status lnr_writer_sort_hold_info_get(const lnr_writer *w, lnr_sort_hold_info *out);  /* any time between begin and end */
 lnr_status lnr_writer_sort_finish(lnr_writer *w, uint32_t piece_members, lnr_sort_info *info /* optional; piece times still 0 */);
 lnr_status lnr_writer_sort_next(lnr_writer *w, const char **data, uint64_t *size);
 lnr_status lnr_writer_sort_bai(lnr_writer *w, uint64_t first_offset, const char **data, uint64_t *size);

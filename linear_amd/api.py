@@ -82,7 +82,7 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats",
            "lnr_reader_gpu_bam_stats", "lnr_reader_gpu_bam_tile", "lnr_reader_format",
            "lnr_writer_sort_begin", "lnr_writer_sort_finish", "lnr_writer_sort_next", "lnr_writer_sort_bai", "lnr_writer_sort_info_get", "lnr_writer_sort_end",
-           "lnr_writer_sort_host", "lnr_writer_bai_host"]
+           "lnr_writer_sort_host", "lnr_writer_bai_host", "lnr_writer_sort_spill", "lnr_writer_sort_hold_info_get"]
 
 
 class LnrBgzfStats(C.Structure):
@@ -93,6 +93,11 @@ class LnrBgzfStats(C.Structure):
 class LnrSortInfo(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("records", "record_bytes", "device_bytes", "members")] + \
                [(k, C.c_double) for k in ("index_ms", "sort_ms", "gather_ms", "deflate_ms", "pack_ms", "download_ms")]
+
+
+class LnrSortHoldInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("stream_bytes", "held_device_bytes", "held_host_bytes", "device_batches", "host_batches")] + \
+               [(k, C.c_double) for k in ("keep_ms", "spill_ms")]
 
 
 def load_library() -> C.CDLL:
@@ -166,6 +171,8 @@ def load_library() -> C.CDLL:
     lib.lnr_writer_format_bam_gpu.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u8p, _u64p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_format_bam_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev), C.c_void_p, C.c_void_p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_sort_begin.argtypes = [C.c_void_p, C.c_uint64]
+    lib.lnr_writer_sort_spill.argtypes = [C.c_void_p, C.c_uint64]
+    lib.lnr_writer_sort_hold_info_get.argtypes = [C.c_void_p, C.POINTER(LnrSortHoldInfo)]
     lib.lnr_writer_sort_finish.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LnrSortInfo)]
     lib.lnr_writer_sort_next.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _u64p]
     lib.lnr_writer_sort_bai.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
@@ -652,6 +659,16 @@ class Writer:
     def sort_begin(self, max_device_bytes: int = 0) -> None:
         """From here on format_bam_gpu / format_bam_dev keep their records on the device and return b""; bam_header carries @HD SO:coordinate."""
         self._check(self.lib.lnr_writer_sort_begin(self.h, max_device_bytes))
+
+    def sort_spill(self, max_host_bytes: int) -> None:
+        """While collecting: batches that do not fit on the device go to pinned host memory, max_host_bytes of it at most (0: off again)."""
+        self._check(self.lib.lnr_writer_sort_spill(self.h, max_host_bytes))
+
+    def sort_hold_info(self) -> dict:
+        """What the round holds so far and where (lnr_sort_hold_info); any time between sort_begin and sort_end."""
+        info = LnrSortHoldInfo()
+        self._check(self.lib.lnr_writer_sort_hold_info_get(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in LnrSortHoldInfo._fields_}
 
     def sort_finish(self, piece_members: int = 0) -> dict:
         """Sorts the kept records on the device; the pieces then come from sort_pieces().  Returns sort_info()."""

@@ -30,7 +30,9 @@
 //                  before the file's first block), and when the file ends they are sorted by coordinate there: the header's members (with
 //                  @HD SO:coordinate), the pieces of lnr_writer_sort_next as they come, the EOF marker, then PREFIX.bam.bai / PREFIX_pbsv.bam.bai
 //                  from lnr_writer_sort_bai(bytes of that file's header).  The .sam / .apf next to it stay in read order.  All records of
-//                  a file are held in HBM until it ends.
+//                  a file are held until it ends, without their 0xff quality runs: in HBM, --sort-device-mem SIZE of it at most
+//                  (lnr_writer_sort_begin's max_device_bytes), and with --sort-host-mem SIZE what does not fit there in pinned host memory
+//                  (lnr_writer_sort_spill right after every begin).
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
 //   BAM input      (extension) a read file may be a BAM, aligned or unaligned: found by its content (the first four inflated bytes are "BAM\1"), never
@@ -73,6 +75,7 @@ lnr_status lnr_writer_sort_finish(lnr_writer *, uint32_t, lnr_sort_info *) __att
 lnr_status lnr_writer_sort_next(lnr_writer *, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_writer_sort_bai(lnr_writer *, uint64_t, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_writer_sort_end(lnr_writer *) __attribute__((weak));
+lnr_status lnr_writer_sort_spill(lnr_writer *, uint64_t) __attribute__((weak));        // (--sort-host-mem alone)
 }
 
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -84,10 +87,33 @@ struct Options {
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
     unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0;
+    uint64_t sort_device_mem = 0, sort_host_mem = 0;      // --sort-device-mem / --sort-host-mem in bytes
+    bool has_sort_device_mem = false, has_sort_host_mem = false;
     std::vector<int> devices;
 };
 
 static bool is_number(const std::string &s) { if (s.empty()) return false; for (char c : s) if (c < '0' || c > '9') return false; return true; }
+
+// SIZE: digits with an optional K, M or G (powers of 1024)
+static bool parse_size(const std::string &s, uint64_t &out) {
+    size_t n = s.size();
+    unsigned shift = 0;
+    if (n && (s[n - 1] == 'K' || s[n - 1] == 'M' || s[n - 1] == 'G')) { shift = s[n - 1] == 'K' ? 10 : s[n - 1] == 'M' ? 20 : 30; n--; }
+    if (n == 0 || n > 18 || !is_number(s.substr(0, n))) return false;
+    const uint64_t v = strtoull(s.substr(0, n).c_str(), nullptr, 10);
+    if (v > (~0ULL >> shift)) return false;
+    out = v << shift;
+    return true;
+}
+// --sort: a round of the writer's sort mode begins, with the limits of --sort-device-mem / --sort-host-mem
+static bool sort_round_begin(lnr_writer *wr, uint64_t device_mem, bool spill, uint64_t host_mem) {
+    if (lnr_writer_sort_begin(wr, device_mem) != LNR_OK) return false;
+    return !spill || lnr_writer_sort_spill(wr, host_mem) == LNR_OK;
+}
+// what a failed BAM call of a sorted run adds to its message
+static std::string sort_hint(const Options &o, lnr_status s) {
+    return o.sort && s == LNR_ERR_NOMEM ? " (--sort holds every record of a file: --sort-device-mem SIZE bounds the GPU memory, --sort-host-mem SIZE lets the rest go to pinned host memory)" : "";
+}
 
 static void usage() {
     fprintf(stderr,
@@ -108,7 +134,9 @@ static void usage() {
             "    --bgzf                     compress the text on the GPU and write PREFIX.sam.gz / PREFIX.apf.gz (BGZF); needs --gpu-writer {off}\n"
             "    --sort                     sort the .bam / _pbsv.bam by coordinate on the GPU and write PREFIX.bam.bai next to it; needs -ot with 4 or 8 and\n"
             "                               --gpu-writer; every record of a file stays in GPU memory until the file ends (about 0.8 KB per read, with\n"
-            "                               --sam-seq 16 KB per 10 kb read: some 10^7 such reads do not fit) {off}\n");
+            "                               --sam-seq 6 KB per 10 kb read; what does not fit goes to host memory with --sort-host-mem) {off}\n"
+            "    --sort-device-mem SIZE     --sort: GPU memory the held records may take, digits with an optional K, M or G {no bound of its own}\n"
+            "    --sort-host-mem SIZE       --sort: records that do not fit into GPU memory are held in pinned host memory, SIZE of it at most {off}\n");
 }
 
 // returns 0 ok, 1 error, 2 help shown
@@ -140,6 +168,13 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         if (name == "sort") { o.sort = 1; continue; }
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
+        if (name == "sort-device-mem" || name == "sort-host-mem") {
+            if (!has_val) { if (i + 1 >= a.size()) { fprintf(stderr, "linear filter: option requires an argument -- %s\n", name.c_str()); return 1; } val = a[++i]; }
+            uint64_t v = 0;
+            if (!parse_size(val, v)) { fprintf(stderr, "linear filter: --%s SIZE: '%s' is not digits with an optional K, M or G\n", name.c_str(), val.c_str()); return 1; }
+            if (name == "sort-device-mem") { o.sort_device_mem = v; o.has_sort_device_mem = true; } else { o.sort_host_mem = v; o.has_sort_host_mem = true; }
+            continue;
+        }
         const Opt *op = nullptr;
         for (const Opt &t : table) if (name == t.sh || name == t.lg) op = &t;
         if (!op) { fprintf(stderr, "linear filter: illegal option -- %s\n", name.c_str()); return 1; }
@@ -211,6 +246,7 @@ struct Outputs {
     std::string cur_prefix; bool any_open = false; int cur_file = -1;
     bool bgzf = false;                       // --bgzf: .gz names, the SAM header comes compressed, the EOF marker ends every file
     lnr_writer *sort_wr = nullptr;           // --sort: the writer that holds the records of the files in work; close() sorts and writes them
+    uint64_t sort_device_mem = 0, sort_host_mem = 0; bool sort_spill = false;      // the limits every round of it begins with
     uint64_t head_bam = 0, head_pbsv = 0;    // bytes of the headers' members: where the record members start
     std::string sort_err;                    // why close() could not finish the sorted files
     // makes the files of read file `file` current; h = the headers as they go into the files.  false: the files cannot be written (err says which)
@@ -265,7 +301,7 @@ struct Outputs {
         if (sorting) {
             if (!sorted && sort_err.empty()) sort_err = std::string("--sort: ") + lnr_writer_error(sort_wr);
             lnr_writer_sort_end(sort_wr);
-            if (lnr_writer_sort_begin(sort_wr, 0) != LNR_OK && sort_err.empty()) sort_err = std::string("--sort: ") + lnr_writer_error(sort_wr);      // the next file's round
+            if (!sort_round_begin(sort_wr, sort_device_mem, sort_spill, sort_host_mem) && sort_err.empty()) sort_err = std::string("--sort: ") + lnr_writer_error(sort_wr);      // the next file's round
         }
     }
     void close_files() {
@@ -295,12 +331,17 @@ int main(int argc, char **argv) {
     else if (o.reform_ccs) nb = "-r 1"; else if (o.sensitivity != 1 && o.sensitivity != 2) nb = "-p other than 1 or 2"; else if (!o.bal_flag) nb = "-b 0 (the reference's -b 0 path writes a header-only SAM)";
     else if (o.index_t != 1 && o.index_t != 2) nb = "-i other than 1 or 2";
     if (nb) { fprintf(stderr, "\033[1;31mE[m02G]:\033[0m %s is not built in the MI355X filter path\n", nb); return 1; }
+    if (!o.sort && (o.has_sort_device_mem || o.has_sort_host_mem)) {
+        fprintf(stderr, "\033[1;31mE:\033[0m %s bounds what --sort holds: it needs --sort\n", o.has_sort_device_mem ? "--sort-device-mem" : "--sort-host-mem");
+        return 1;
+    }
     if (o.sort && !o.gpu_writer) { fprintf(stderr, "\033[1;31mE:\033[0m --sort sorts the BAM records on the GPU that encodes them: it needs --gpu-writer\n"); return 1; }
     if (o.sort && !(o.f_output_type & 12)) { fprintf(stderr, "\033[1;31mE:\033[0m --sort sorts BAM output: it needs -ot with 4 (.bam) or 8 (_pbsv.bam)\n"); return 1; }
     if (o.sort && (!lnr_writer_sort_begin || !lnr_writer_sort_finish || !lnr_writer_sort_next || !lnr_writer_sort_bai || !lnr_writer_sort_end)) {
         fprintf(stderr, "\033[1;31mE:\033[0m --sort: this library has no sort mode of the writer\n");
         return 1;
     }
+    if (o.has_sort_host_mem && !lnr_writer_sort_spill) { fprintf(stderr, "\033[1;31mE:\033[0m --sort-host-mem: this library has no host tier in the sort mode of the writer\n"); return 1; }
     if ((o.f_output_type & 12) && !o.gpu_writer) {
         fprintf(stderr, "\033[1;31mE:\033[0m -ot 4 / 8 (BAM output) is encoded and compressed on the GPU: it needs --gpu-writer (BAM on the writer's host threads is not built)\n");
         return 1;
@@ -417,7 +458,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     // --sort: the mode is on before the headers are made (they carry @HD SO:coordinate); Outputs::close ends a file's round and begins the next
-    if (o.sort && lnr_writer_sort_begin(wr, 0) != LNR_OK) {
+    if (o.sort && !sort_round_begin(wr, o.sort_device_mem, o.has_sort_host_mem, o.sort_host_mem)) {
         fprintf(stderr, "\033[1;31mE:\033[0m --sort: %s\n", lnr_writer_error(wr));
         lnr_writer_destroy(wr);
         for (auto *c : ctx) lnr_destroy(c);
@@ -537,7 +578,7 @@ int main(int argc, char **argv) {
                     }
                     if (want_bam) {
                         s = bam_call([&] { return lnr_writer_format_bam_dev(wr, &dev, o.sam_seq ? b->d_reads : nullptr, b->d_off, b->ids.data(), b->id_off.data(), &text, &size); });
-                        if (s != LNR_OK) { fail(std::string("writer (.bam): ") + lnr_writer_error(wr)); break; }
+                        if (s != LNR_OK) { fail(std::string("writer (.bam): ") + lnr_writer_error(wr) + sort_hint(o, s)); break; }
                         b->bam.assign(text, size);
                     }
                 } else {
@@ -558,7 +599,7 @@ int main(int argc, char **argv) {
             FILE *&fsam = out.fsam, *&fapf = out.fapf;
             const char *text; uint64_t size;
             DBlock *b = nullptr;
-            if (o.sort) out.sort_wr = wr;
+            if (o.sort) { out.sort_wr = wr; out.sort_device_mem = o.sort_device_mem; out.sort_host_mem = o.sort_host_mem; out.sort_spill = o.has_sort_host_mem; }
             while (doneq.pop(b) && !failed) {
                 std::string oe;
                 if (!out.turn_to(o, b->file, sam_header, oe)) { fail(oe); fcv.notify_all(); break; }
@@ -699,7 +740,7 @@ int main(int argc, char **argv) {
         Headers sam_header;
         uint64_t want = 0;
         const char *text; uint64_t size;
-        if (o.sort) out.sort_wr = wr;
+        if (o.sort) { out.sort_wr = wr; out.sort_device_mem = o.sort_device_mem; out.sort_host_mem = o.sort_host_mem; out.sort_spill = o.has_sort_host_mem; }
         if (!header_of(sam_header)) sh.fail(std::string(want_bam ? "BAM / BGZF header: " : "--bgzf: ") + lnr_writer_error(wr));
         for (;;) {
             Block *b = nullptr;
@@ -725,7 +766,7 @@ int main(int argc, char **argv) {
             if (out.fbam || out.fpbsv) {                                 // one encoding serves both files: they differ in their headers alone
                 lnr_status s = bam_call([&] { return o.sam_seq ? lnr_writer_format_bam_gpu(wr, &b->cords, b->bases, b->off.data(), b->ids.data(), b->id_off.data(), &text, &size)
                                                                : lnr_writer_format_bam_gpu(wr, &b->cords, nullptr, b->len.data(), b->ids.data(), b->id_off.data(), &text, &size); });
-                if (s != LNR_OK) { sh.fail(std::string("writer (.bam): ") + lnr_writer_error(wr)); break; }
+                if (s != LNR_OK) { sh.fail(std::string("writer (.bam): ") + lnr_writer_error(wr) + sort_hint(o, s)); break; }
                 if ((out.fbam && fwrite(text, 1, size, out.fbam) != size) || (out.fpbsv && fwrite(text, 1, size, out.fpbsv) != size)) { sh.fail("write error (.bam)"); break; }
             }
             us_writer += (uint64_t)((now() - tw0) * 1e6);

@@ -580,6 +580,21 @@ lnr_status lnr_writer_sort_begin(lnr_writer *wr, uint64_t max_device_bytes) {
     if (s == LNR_OK) { wr->sort_state = 1; wr->sort_moff.assign(1, 0); }
     return s;
 }
+lnr_status lnr_writer_sort_spill(lnr_writer *wr, uint64_t max_host_bytes) {
+    if (!wr) return LNR_ERR_ARG;
+    if (!wr->gpu || !lnr_outgpu_sort_spill) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_spill: lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
+    if (wr->sort_state != 1) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_spill: valid between lnr_writer_sort_begin and lnr_writer_sort_finish"); return LNR_ERR_ARG; }
+    wr->err[0] = 0;
+    return (lnr_status)lnr_outgpu_sort_spill(wr->gpu, max_host_bytes, wr->err, sizeof wr->err);
+}
+lnr_status lnr_writer_sort_hold_info_get(const lnr_writer *wr, lnr_sort_hold_info *out) {
+    if (!wr || !out || !wr->gpu || !lnr_outgpu_sort_hold_info_get || wr->sort_state < 1) return LNR_ERR_ARG;
+    lnr_outgpu_hold_info i;
+    lnr_outgpu_sort_hold_info_get(wr->gpu, &i);
+    out->stream_bytes = i.stream_bytes; out->held_device_bytes = i.held_device_bytes; out->held_host_bytes = i.held_host_bytes;
+    out->device_batches = i.device_batches; out->host_batches = i.host_batches; out->keep_ms = i.keep_ms; out->spill_ms = i.spill_ms;
+    return LNR_OK;
+}
 lnr_status lnr_writer_sort_finish(lnr_writer *wr, uint32_t piece_members, lnr_sort_info *info) {
     if (!wr || !sort_ready(wr)) return LNR_ERR_ARG;
     if (wr->sort_state != 1) { snprintf(wr->err, sizeof wr->err, "lnr_writer_sort_finish: %s", wr->sort_state ? "called already" : "lnr_writer_sort_begin has not been called"); return LNR_ERR_ARG; }

@@ -431,5 +431,17 @@ LNR_HD inline BamKey bam_key(const uint8_t *rec, u64 avail) {
 }
 // the sort key of the order's first two fields: (uint32)refID, then (uint32)pos -- refID -1 sorts last
 LNR_HD inline u64 bam_sort_key(const BamKey &k) { return (u64)(u32)k.ref << 32 | (u64)(u32)k.pos; }
+// The quality span of a raw record of `size` = 4 + block_size bytes (at least 36): the l_seq bytes at qoff = 36 + l_read_name + 4 n_cigar_op +
+// (l_seq + 1) / 2, which this writer fills with 0xff (bam_item) -- what the sort mode does not hold and its gather puts back.  The name ends
+// where bam_key finds its end.  A span that does not fit in the record (or l_seq 0): {0, 0}, the record is kept whole.
+struct BamQual { u32 qoff, l_seq; };
+LNR_HD inline BamQual bam_qual_span(const uint8_t *rec, u64 size) {
+    const u64 l_seq = le32_at(rec + 20);
+    u64 p = 36ULL + rec[12];
+    while (p - 1 < size && rec[12] && rec[p - 1] != 0) p += 256;
+    p += 4ULL * ((u32)rec[16] | (u32)rec[17] << 8) + ((l_seq + 1) >> 1);
+    if (l_seq == 0 || p + l_seq > size || size > 0xffffffffULL) return BamQual{0, 0};
+    return BamQual{(u32)p, (u32)l_seq};
+}
 
 }  // namespace lnr_out

@@ -36,6 +36,11 @@ void lnr_outgpu_bgzf_stats_get(const lnr_outgpu *g, lnr_outgpu_bgzf_stats *out) 
 // piece (moff[0 .. nb], host memory valid until the next call; nb == 0 and size 0: done); _fetch downloads the sorted per-record arrays
 // (records each: key = (u32)refID << 32 | (u32)pos, flag, reference end; off: records + 1 offsets in the sorted stream) for the index.
 struct lnr_outgpu_sort_info { uint64_t records, record_bytes, device_bytes, members; double index_ms, sort_ms, gather_ms, deflate_ms, pack_ms, download_ms; };
+// The hold (lnr_sort_hold_info): records are held without their quality spans; _sort_spill (while collecting; 0 switches it off) lets
+// batches that do not fit on the device go to pinned host segments, max_host_bytes of them at most.
+struct lnr_outgpu_hold_info { uint64_t stream_bytes, held_device_bytes, held_host_bytes, device_batches, host_batches; double keep_ms, spill_ms; };
+int lnr_outgpu_sort_spill(lnr_outgpu *g, uint64_t max_host_bytes, char *err, size_t err_cap) __attribute__((weak));
+void lnr_outgpu_sort_hold_info_get(const lnr_outgpu *g, lnr_outgpu_hold_info *out) __attribute__((weak));
 int lnr_outgpu_sort_begin(lnr_outgpu *g, uint64_t max_bytes, char *err, size_t err_cap) __attribute__((weak));
 int lnr_outgpu_sort_finish(lnr_outgpu *g, uint32_t piece_members, char *err, size_t err_cap) __attribute__((weak));
 int lnr_outgpu_sort_next(lnr_outgpu *g, const char **data, uint64_t *size, const uint64_t **moff, uint32_t *nb, char *err, size_t err_cap) __attribute__((weak));

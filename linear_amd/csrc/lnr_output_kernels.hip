@@ -31,16 +31,22 @@
 //   k_out_scan      member sizes -> offsets
 //   k_bgzf_pack     the slots -> one contiguous run (destination-aligned dword stores), the only bytes that are downloaded
 //
-// Coordinate sort (lnr_writer_sort_*): the BAM records of every batch stay in HBM (device segments), the order is computed on keys alone
-// and the records move once, straight into the buffer the deflate kernel reads.
-//   k_sort_index    per batch, one lane per read: walks the read's records by block_size (byte loads: records start anywhere) and appends
-//                   key = (u32)refID << 32 | (u32)pos, flag, stream offset, device address, size and reference end per record.  The append is
-//                   atomic; the stream offset is part of the order, so the result does not depend on the append order.
+// Coordinate sort (lnr_writer_sort_*): the BAM records of every batch are held until the sort -- without their quality spans (l_seq bytes of
+// 0xff: bam_qual_span), in device segments or, with lnr_writer_sort_spill, in pinned host segments --, the order is computed on keys alone
+// and the records move once more, straight into the buffer the deflate kernel reads.
+//   k_sort_index    per batch, one lane per read: walks the read's full records at g->text by block_size (byte loads: records start anywhere);
+//                   first pass: counts them and sizes the read's held bytes (k_out_scan places the reads); second pass: appends
+//                   key = (u32)refID << 32 | (u32)pos, flag, stream offset, address of the held bytes, full size, reference end and the
+//                   quality span per record.  The append is atomic; the stream offset is part of the order, so the result does not depend on
+//                   the append order.
+//   k_sort_keep     per batch, one wave per read: copies the records into the segment (or the staging buffer of a spilled batch, which one
+//                   device-to-host copy then moves) and leaves the quality spans out; destination-aligned dwords as in k_sort_gather
 //   the sort        rocPRIM's stable radix sort twice: by (reverse bit, stream offset), then by key; k_sort_apply gathers the per-record
 //                   arrays into that order and a scan of the sorted sizes places every record in the sorted stream S
 //   k_sort_gather   per piece: one workgroup per 0xff00 bytes of S (= one BGZF member); bisection finds the first record that reaches into
 //                   the tile, waves copy record after record (destination-aligned dwords put together from two aligned source dwords,
-//                   single bytes at both ends; a piece of 8 KiB or more is copied by the whole workgroup).  No atomics.
+//                   single bytes at both ends; a piece of 8 KiB or more is copied by the whole workgroup): held bytes, the 0xff run of the
+//                   quality span, held bytes again.  Spilled records are read straight out of the pinned memory.  No atomics.
 //   per piece       k_bgzf_deflate / k_out_scan / k_bgzf_pack as for any text
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>   // AMD's native primitives library: the stable radix sort and the scan of the coordinate sort
@@ -501,29 +507,34 @@ __global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, const u
 }
 
 // ---- coordinate sort
-struct SortArrays { u64 *key; u32 *flag; u64 *soff; u64 *addr; u32 *size; i64 *end; };     // per record, in arrival order
-// recs: the batch's records as they lie in their segment; roff[n + 1]: the reads' offsets in them (what k_out_scan left).  COUNT: only
-// *counter += records; else record number base + (*counter)++ is filled in.  A block_size that does not fit its read ends the read's walk
-// in both passes alike (the encoder writes none).
-template <bool COUNT> __global__ __launch_bounds__(256) void k_sort_index(const uint8_t *recs, const u64 *roff, u32 n, u64 stream_base, SortArrays A, u64 base, unsigned long long *counter) {
+struct SortArrays { u64 *key; u32 *flag; u64 *soff; u64 *addr; u32 *size; i64 *end; u32 *qoff, *lseq; };     // per record, in arrival order
+// recs: the batch's full records at g->text; roff[n + 1]: the reads' offsets in them (what k_out_scan left).  COUNT: *counter += records and
+// cpos[k] = the bytes read k's records take in the hold (without their quality spans); else cpos[k] is where those bytes start (cpos after
+// k_out_scan), hold the address of the batch's held bytes, and record number base + (*counter)++ is filled in.  A block_size that does not
+// fit its read ends the read's walk in both passes alike (the encoder writes none).
+template <bool COUNT> __global__ __launch_bounds__(256) void k_sort_index(const uint8_t *recs, const u64 *roff, u32 n, u64 stream_base, SortArrays A, u64 base, unsigned long long *counter,
+                                                                          u64 *cpos, u64 hold) {
     const u32 k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     u64 p = roff[k];
     const u64 e = roff[k + 1];
     u32 cnt = 0;
+    u64 c = COUNT ? 0 : cpos[k];
     while (p + 36 <= e) {
         const u64 sz = 4ULL + le32_at(recs + p);
         if (sz < 36 || p + sz > e) break;
+        const BamQual q = bam_qual_span(recs + p, sz);
         if (COUNT) cnt++;
         else {
             const BamKey key = bam_key(recs + p, sz);
             const u64 i = base + atomicAdd(counter, 1ULL);
             A.key[i] = bam_sort_key(key); A.flag[i] = key.flag; A.soff[i] = stream_base + p;
-            A.addr[i] = (u64)(recs + p); A.size[i] = (u32)sz; A.end[i] = key.end;
+            A.addr[i] = hold + c; A.size[i] = (u32)sz; A.end[i] = key.end; A.qoff[i] = q.qoff; A.lseq[i] = q.l_seq;
         }
+        c += sz - q.l_seq;
         p += sz;
     }
-    if (COUNT && cnt) atomicAdd(counter, (unsigned long long)cnt);
+    if (COUNT) { cpos[k] = c; if (cnt) atomicAdd(counter, (unsigned long long)cnt); }
 }
 // first pass of the sort: (reverse bit, stream offset) as one key, the record's number as the value
 __global__ __launch_bounds__(256) void k_sort_prep(const u32 *flag, const u64 *soff, u64 n, u64 *k1, u32 *v1) {
@@ -535,10 +546,12 @@ __global__ __launch_bounds__(256) void k_sort_take(const u64 *key, const u32 *pe
     if (i < n) out[i] = key[perm[i]];
 }
 // the per-record arrays in sorted order; size64[n] = 0, so that the scan over n + 1 elements leaves the total in off[n]
-__global__ __launch_bounds__(256) void k_sort_apply(SortArrays A, const u32 *perm, u64 n, u64 *s_addr, u64 *s_size, u32 *s_flag, i64 *s_end) {
+__global__ __launch_bounds__(256) void k_sort_apply(SortArrays A, const u32 *perm, u64 n, u64 *s_addr, u64 *s_size, u32 *s_flag, i64 *s_end, u32 *s_qoff, u32 *s_lseq) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { const u32 r = perm[i]; s_addr[i] = A.addr[r]; s_size[i] = A.size[r]; s_flag[i] = A.flag[r]; s_end[i] = A.end[r]; }
-    else if (i == n) s_size[i] = 0;
+    if (i < n) {
+        const u32 r = perm[i];
+        s_addr[i] = A.addr[r]; s_size[i] = A.size[r]; s_flag[i] = A.flag[r]; s_end[i] = A.end[r]; s_qoff[i] = A.qoff[r]; s_lseq[i] = A.lseq[r];
+    } else if (i == n) s_size[i] = 0;
 }
 // len bytes src -> dst by lanes t of nt (nt >= 3): single bytes up to dst's first dword boundary and after its last whole dword, between them
 // destination-aligned dwords put together from two aligned source dwords.  Reads at most 3 bytes before src (never below its dword) and 3
@@ -556,9 +569,43 @@ __device__ __forceinline__ void copy_bytes(uint8_t *dst, const uint8_t *src, u32
     const u32 done = head + 4 * words;
     if (t < len - done) dst[done + t] = src[done + t];
 }
+// len bytes 0xff at dst, dealt to the lanes as copy_bytes deals them
+__device__ __forceinline__ void fill_bytes(uint8_t *dst, u32 len, u32 t, u32 nt) {
+    u32 head = (4 - (u32)((uintptr_t)dst & 3)) & 3;
+    if (head > len) head = len;
+    if (t < head) dst[t] = 0xff;
+    const u32 words = (len - head) / 4;
+    u32 *dw = reinterpret_cast<u32 *>(dst + head);
+    for (u32 w = t; w < words; w += nt) dw[w] = 0xffffffffu;
+    const u32 done = head + 4 * words;
+    if (t < len - done) dst[done + t] = 0xff;
+}
+// The batch's records at recs (g->text) -> hold, without their quality spans: one wave per read (four to a workgroup) walks the read's
+// records and copies what lies before and after each span; cpos[k]: where read k's held bytes start (k_sort_index<true>, scanned).  All
+// of the walk is wave-uniform.  Reads of recs stay inside [0, roff[n] + 3]; writes inside hold[cpos[k], cpos[k + 1]).
+__global__ __launch_bounds__(256) void k_sort_keep(const uint8_t *recs, const u64 *roff, const u64 *cpos, u32 n, uint8_t *hold) {
+    const u32 k = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (k >= n) return;
+    u64 p = roff[k];
+    const u64 e = roff[k + 1];
+    uint8_t *d = hold + cpos[k];
+    while (p + 36 <= e) {
+        const u64 sz = 4ULL + le32_at(recs + p);
+        if (sz < 36 || p + sz > e) break;
+        const BamQual q = bam_qual_span(recs + p, sz);
+        if (q.l_seq) {
+            copy_bytes(d, recs + p, q.qoff, lane, 64u);
+            copy_bytes(d + q.qoff, recs + p + q.qoff + q.l_seq, (u32)(sz - q.qoff - q.l_seq), lane, 64u);
+        } else copy_bytes(d, recs + p, (u32)sz, lane, 64u);
+        d += sz - q.l_seq;
+        p += sz;
+    }
+}
 constexpr u32 GATHER_BIG = 8192;               // a piece of a record this long is copied by the whole workgroup, a shorter one by one wave
-// S[a, b) -> out (4-byte aligned), one workgroup per BLOCK_TEXT bytes; s_off[n + 1]: the records' offsets in S, s_addr[n] where they lie
-__global__ __launch_bounds__(256) void k_sort_gather(const u64 *s_off, const u64 *s_addr, u64 n, u64 a, u64 b, uint8_t *out) {
+// S[a, b) -> out (4-byte aligned), one workgroup per BLOCK_TEXT bytes; s_off[n + 1]: the records' offsets in S, s_addr[n] where their held
+// bytes lie (device memory or pinned host memory alike), s_qoff / s_lseq[n] the quality span the hold leaves out.  Bytes [x0, x1) of a
+// record are held bytes up to qoff, 0xff up to qoff + l_seq, then held bytes again, l_seq further down.
+__global__ __launch_bounds__(256) void k_sort_gather(const u64 *s_off, const u64 *s_addr, const u32 *s_qoff, const u32 *s_lseq, u64 n, u64 a, u64 b, uint8_t *out) {
     const u64 t0 = a + (u64)blockIdx.x * lnr_def::BLOCK_TEXT;
     const u64 t1 = t0 + lnr_def::BLOCK_TEXT < b ? t0 + lnr_def::BLOCK_TEXT : b;
     u64 lo = 0, hi = n;                          // the last record that starts at or before t0 (s_off[0] = 0)
@@ -573,7 +620,17 @@ __global__ __launch_bounds__(256) void k_sort_gather(const u64 *s_off, const u64
             if (c1 <= c0) continue;
             const u32 len = (u32)(c1 - c0);
             if ((len >= GATHER_BIG) != (big != 0)) continue;
-            copy_bytes(dst + (c0 - t0), reinterpret_cast<const uint8_t *>(s_addr[r]) + (c0 - o), len, big ? threadIdx.x : lane, big ? 256u : 64u);
+            const u32 t = big ? threadIdx.x : lane, nt = big ? 256u : 64u;
+            const uint8_t *src = reinterpret_cast<const uint8_t *>(s_addr[r]);
+            uint8_t *d = dst + (c0 - t0);
+            const u64 x0 = c0 - o, x1 = c1 - o, l = s_lseq[r];
+            if (l == 0) { copy_bytes(d, src + x0, len, t, nt); continue; }
+            const u64 q0 = s_qoff[r], q1 = q0 + l;
+            if (x0 < q0) copy_bytes(d, src + x0, (u32)((x1 < q0 ? x1 : q0) - x0), t, nt);
+            const u64 f0 = x0 > q0 ? x0 : q0, f1 = x1 < q1 ? x1 : q1;
+            if (f0 < f1) fill_bytes(d + (f0 - x0), (u32)(f1 - f0), t, nt);
+            const u64 p0 = x0 > q1 ? x0 : q1;
+            if (p0 < x1) copy_bytes(d + (p0 - x0), src + (p0 - l), (u32)(x1 - p0), t, nt);
         }
 }
 
@@ -581,18 +638,23 @@ double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono:
 
 struct Buf { void *p = nullptr; u64 cap = 0; };
 
-struct SortSeg { char *p; u64 cap, used; };       // cap: bytes for records; the allocation has 8 more (copy_bytes reads past a record's end)
+// cap: bytes for records; the allocation has 8 more (copy_bytes reads past a record's end).  A host segment (pinned, alloc != nullptr) has
+// HOST_FRONT bytes in front of p as well, and dev is what the kernels read it by.
+struct SortSeg { char *p; u64 cap, used; char *alloc = nullptr, *dev = nullptr; };
 struct SortState {
     int on = 0;                                 // 0 off, 1 collecting, 2 sorted: pieces go out
     u64 max_bytes = 0, stream = 0, nrec = 0, rec_cap = 0;
-    std::vector<SortSeg> segs;
-    Buf key, flag, soff, addr, size, end;       // per record in arrival order, rec_cap entries
-    Buf k1, k2, v1, v2, tmp, s_addr, s_size, s_off, s_flag, s_end, counter;      // the sort's scratch and the arrays in sorted order (keys: k2)
+    int spill = 0; u64 max_host = 0;            // lnr_outgpu_sort_spill: the host tier and its budget
+    std::vector<SortSeg> segs, hsegs;           // the device tier, the host tier
+    Buf key, flag, soff, addr, size, end, qoff, lseq;       // per record in arrival order, rec_cap entries
+    Buf k1, k2, v1, v2, tmp, s_addr, s_size, s_off, s_flag, s_end, s_qoff, s_lseq, counter;      // the sort's scratch and the arrays in sorted order (keys: k2)
+    Buf cpos, stage;                            // per batch: the reads' offsets in the hold; the device staging of a batch on its way to the host tier
     u32 piece_members = 0; u64 members = 0, cursor = 0;
     std::vector<u64> moff;                      // member offsets of the last piece
     lnr_outgpu_sort_info info{};
+    lnr_outgpu_hold_info hold{};
 };
-constexpr u64 SORT_SEG_MIN = 256ULL << 20;
+constexpr u64 SORT_SEG_MIN = 256ULL << 20, SORT_HOST_SEG = 64ULL << 20, HOST_FRONT = 16;
 
 }  // namespace
 
@@ -632,10 +694,15 @@ int dev_need(Buf &b, u64 bytes, char *err, size_t err_cap) {
     b.cap = want;
     return 0;
 }
+std::vector<Buf *> sort_bufs(SortState &S) {        // every device buffer of the sort but the segments
+    return {&S.key, &S.flag, &S.soff, &S.addr, &S.size, &S.end, &S.qoff, &S.lseq, &S.k1, &S.k2, &S.v1, &S.v2, &S.tmp, &S.s_addr, &S.s_size, &S.s_off, &S.s_flag, &S.s_end,
+            &S.s_qoff, &S.s_lseq, &S.counter, &S.cpos, &S.stage};
+}
 void sort_free(lnr_outgpu *g) {
     SortState &S = g->sort;
     for (SortSeg &sg : S.segs) (void)hipFree(sg.p);
-    for (Buf *b : {&S.key, &S.flag, &S.soff, &S.addr, &S.size, &S.end, &S.k1, &S.k2, &S.v1, &S.v2, &S.tmp, &S.s_addr, &S.s_size, &S.s_off, &S.s_flag, &S.s_end, &S.counter})
+    for (SortSeg &sg : S.hsegs) (void)hipHostFree(sg.alloc);
+    for (Buf *b : sort_bufs(S))
         if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
     S = SortState();
 }
@@ -701,55 +768,95 @@ int bgzf_run(lnr_outgpu *g, const uint8_t *d_text, u64 total, const char **data,
     return 0;
 }
 
-// sort mode: the batch's `total` record bytes at g->text (roff: the reads' offsets, n + 1) into a segment, their keys into the arrays.
-// Nothing of the state changes unless everything succeeded.
-int sort_add(lnr_outgpu *g, u64 total, const u64 *roff, u32 n, char *err, size_t err_cap) {
+// sort mode: the batch's `total` record bytes at g->text (roff: the reads' offsets, n + 1) into a segment without their quality spans, their
+// keys into the arrays.  The tier: the device while the held bytes stay under max_bytes and a segment can be had, else -- with
+// lnr_outgpu_sort_spill on -- pinned host memory under its own budget, else -4.  Nothing of the state changes unless everything succeeded.
+int sort_add_to(lnr_outgpu *g, u64 total, const u64 *roff, u32 n, SortSeg &fresh, char *err, size_t err_cap) {
     SortState &S = g->sort;
-    if (total == 0) return 0;
-    if (S.max_bytes && S.stream + total > S.max_bytes) {
-        snprintf(err, err_cap, "sort: %llu record bytes held on the device, %llu more asked for, max_device_bytes is %llu", (unsigned long long)S.stream, (unsigned long long)total, (unsigned long long)S.max_bytes);
-        return -4;
-    }
-    SortSeg *sg = S.segs.empty() ? nullptr : &S.segs.back();
-    u64 at = sg ? (sg->used + 15) & ~15ULL : 0;
-    if (!sg || at + total > sg->cap) {
-        u64 want = SORT_SEG_MIN;
-        if (S.max_bytes && S.max_bytes - S.stream < want) want = S.max_bytes - S.stream;
-        if (want < total) want = total;
-        void *p = nullptr;
-        if (hipMalloc(&p, want + 8) != hipSuccess) {
-            (void)hipGetLastError();
-            snprintf(err, err_cap, "sort: %llu record bytes held on the device, a segment of %llu bytes for %llu more could not be allocated", (unsigned long long)S.stream, (unsigned long long)want, (unsigned long long)total);
-            return -4;
-        }
-        S.segs.push_back({(char *)p, want, 0});
-        sg = &S.segs.back(); at = 0;
-    }
-    uint8_t *recs = (uint8_t *)sg->p + at;
     int s;
     if (!g->h_sort) OUT_CK(hipHostMalloc((void **)&g->h_sort, 2 * sizeof(u64), hipHostMallocDefault), -4);
-    if ((s = dev_need(S.counter, 16, err, err_cap))) return s;
+    if ((s = dev_need(S.counter, 16, err, err_cap)) || (s = dev_need(S.cpos, 8ULL * (n + 1ULL), err, err_cap))) return s;
     unsigned long long *counter = (unsigned long long *)S.counter.p;
-    OUT_CK(hipMemcpyAsync(recs, g->text.p, total, hipMemcpyDeviceToDevice, g->st), -3);
+    u64 *cpos = (u64 *)S.cpos.p;
+    const uint8_t *recs = (const uint8_t *)g->text.p;
     OUT_CK(hipMemsetAsync(counter, 0, 16, g->st), -3);
     SortArrays A{};
     const u32 grid = (n + 255) / 256;
-    OUT_CK(hipEventRecord(g->bev[0], g->st), -3);
-    hipLaunchKernelGGL(k_sort_index<true>, dim3(grid), dim3(256), 0, g->st, (const uint8_t *)recs, roff, n, S.stream, A, S.nrec, counter);
-    OUT_CK(hipEventRecord(g->bev[1], g->st), -3);
+    OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
+    hipLaunchKernelGGL(k_sort_index<true>, dim3(grid), dim3(256), 0, g->st, recs, roff, n, S.stream, A, S.nrec, counter, cpos, 0ULL);
+    OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
+    hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, g->st, cpos, n);
     OUT_CK(hipMemcpyAsync(g->h_sort, counter, 8, hipMemcpyDeviceToHost, g->st), -3);
+    OUT_CK(hipMemcpyAsync(g->h_sort + 1, cpos + n, 8, hipMemcpyDeviceToHost, g->st), -3);
     OUT_CK(hipStreamSynchronize(g->st), -3);
     OUT_CK(hipGetLastError(), -3);
-    const u64 more = g->h_sort[0];
+    const u64 more = g->h_sort[0], held = g->h_sort[1];
     if (S.nrec + more > 0xffffffffULL) { snprintf(err, err_cap, "sort: more than 2^32 - 1 records"); return -6; }
+    if (held > total) { snprintf(err, err_cap, "sort: %llu bytes to hold of a batch of %llu", (unsigned long long)held, (unsigned long long)total); return -8; }
+    // the tier and the batch's place in it
+    const u64 dev_held = S.hold.held_device_bytes, host_held = S.hold.held_host_bytes;
+    SortSeg *sg = nullptr;
+    u64 at = 0;
+    bool host = false;
+    char why[160] = "";
+    if (!(S.max_bytes && dev_held + held > S.max_bytes)) {
+        sg = S.segs.empty() ? nullptr : &S.segs.back();
+        at = sg ? (sg->used + 15) & ~15ULL : 0;
+        if (!sg || at + held > sg->cap) {
+            u64 want = SORT_SEG_MIN;
+            if (S.max_bytes && S.max_bytes - dev_held < want) want = S.max_bytes - dev_held;
+            if (want < held) want = held;
+            void *p = nullptr;
+            if (hipMalloc(&p, want + 8) == hipSuccess) { fresh = SortSeg{(char *)p, want, 0}; sg = &fresh; at = 0; }
+            else {
+                (void)hipGetLastError();
+                sg = nullptr;
+                snprintf(why, sizeof why, "a segment of %llu bytes could not be allocated", (unsigned long long)want);
+            }
+        }
+    } else snprintf(why, sizeof why, "max_device_bytes is %llu", (unsigned long long)S.max_bytes);
+    if (!sg && !S.spill) {
+        if (S.max_bytes && dev_held + held > S.max_bytes)
+            snprintf(err, err_cap, "sort: %llu record bytes held on the device, %llu more asked for, max_device_bytes is %llu", (unsigned long long)dev_held, (unsigned long long)held, (unsigned long long)S.max_bytes);
+        else snprintf(err, err_cap, "sort: %llu record bytes held on the device, %s for %llu more", (unsigned long long)dev_held, why, (unsigned long long)held);
+        return -4;
+    }
+    if (!sg) {
+        host = true;
+        bool ok = host_held + held <= S.max_host && host_held + held >= host_held;
+        if (ok) {
+            sg = S.hsegs.empty() ? nullptr : &S.hsegs.back();
+            at = sg ? (sg->used + 15) & ~15ULL : 0;
+            if (!sg || at + held > sg->cap) {
+                u64 want = SORT_HOST_SEG;
+                if (S.max_host - host_held < want) want = S.max_host - host_held;
+                if (want < held) want = held;
+                void *p = nullptr, *d = nullptr;
+                if (hipHostMalloc(&p, HOST_FRONT + want + 8, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, p, 0) == hipSuccess) {
+                    fresh = SortSeg{(char *)p + HOST_FRONT, want, 0, (char *)p, (char *)d + HOST_FRONT};
+                    sg = &fresh; at = 0;
+                } else {
+                    (void)hipGetLastError();
+                    if (p) (void)hipHostFree(p);
+                    sg = nullptr; ok = false;
+                }
+            }
+        }
+        if (!ok) {
+            snprintf(err, err_cap, "sort: %llu record bytes held on the device (%s), %llu in host memory, %llu more asked for, max_host_bytes is %llu%s", (unsigned long long)dev_held, why,
+                     (unsigned long long)host_held, (unsigned long long)held, (unsigned long long)S.max_host, host_held + held <= S.max_host ? ": a pinned segment could not be allocated" : "");
+            return -4;
+        }
+        if ((s = dev_need(S.stage, held + 8, err, err_cap))) return s;
+    }
     if (S.nrec + more > S.rec_cap) {              // grow: new arrays, the old entries copied over
         const u64 cap = (S.nrec + more) + (S.nrec + more) / 2 + 1024;
-        struct { Buf *b; u64 w; } arr[6] = {{&S.key, 8}, {&S.flag, 4}, {&S.soff, 8}, {&S.addr, 8}, {&S.size, 4}, {&S.end, 8}};
+        struct { Buf *b; u64 w; } arr[8] = {{&S.key, 8}, {&S.flag, 4}, {&S.soff, 8}, {&S.addr, 8}, {&S.size, 4}, {&S.end, 8}, {&S.qoff, 4}, {&S.lseq, 4}};
         for (auto &x : arr) {
             void *p = nullptr;
             if (hipMalloc(&p, cap * x.w) != hipSuccess) {
                 (void)hipGetLastError();
-                snprintf(err, err_cap, "sort: %llu record bytes held on the device, the arrays for %llu records could not be allocated", (unsigned long long)S.stream, (unsigned long long)cap);
+                snprintf(err, err_cap, "sort: %llu record bytes held on the device, the arrays for %llu records could not be allocated", (unsigned long long)dev_held, (unsigned long long)cap);
                 return -4;
             }
             if (S.nrec && hipMemcpy(p, x.b->p, S.nrec * x.w, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(p); snprintf(err, err_cap, "sort: copying the record arrays failed"); return -3; }
@@ -758,19 +865,48 @@ int sort_add(lnr_outgpu *g, u64 total, const u64 *roff, u32 n, char *err, size_t
         }
         S.rec_cap = cap;
     }
-    A = SortArrays{(u64 *)S.key.p, (u32 *)S.flag.p, (u64 *)S.soff.p, (u64 *)S.addr.p, (u32 *)S.size.p, (i64 *)S.end.p};
+    A = SortArrays{(u64 *)S.key.p, (u32 *)S.flag.p, (u64 *)S.soff.p, (u64 *)S.addr.p, (u32 *)S.size.p, (i64 *)S.end.p, (u32 *)S.qoff.p, (u32 *)S.lseq.p};
+    uint8_t *hold = host ? (uint8_t *)S.stage.p : (uint8_t *)sg->p + at;           // where k_sort_keep writes
+    const u64 addr = (u64)((host ? sg->dev : sg->p) + at);                         // where k_sort_gather will read
     OUT_CK(hipMemsetAsync(counter, 0, 16, g->st), -3);
+    OUT_CK(hipEventRecord(g->bev[0], g->st), -3);
+    hipLaunchKernelGGL(k_sort_keep, dim3((n + 3) / 4), dim3(256), 0, g->st, recs, roff, (const u64 *)cpos, n, hold);
+    OUT_CK(hipEventRecord(g->bev[1], g->st), -3);
     OUT_CK(hipEventRecord(g->bev[2], g->st), -3);
-    hipLaunchKernelGGL(k_sort_index<false>, dim3(grid), dim3(256), 0, g->st, (const uint8_t *)recs, roff, n, S.stream, A, S.nrec, counter);
+    hipLaunchKernelGGL(k_sort_index<false>, dim3(grid), dim3(256), 0, g->st, recs, roff, n, S.stream, A, S.nrec, counter, cpos, addr);
     OUT_CK(hipEventRecord(g->bev[3], g->st), -3);
     OUT_CK(hipStreamSynchronize(g->st), -3);
     OUT_CK(hipGetLastError(), -3);
-    float f0 = 0, f1 = 0;
-    OUT_CK(hipEventElapsedTime(&f0, g->bev[0], g->bev[1]), -3);
+    double spill_ms = 0;
+    if (host && held) {                           // the batch's way to the host tier: one DMA copy out of the staging buffer
+        const double t0 = wall_ms();
+        OUT_CK(hipMemcpyAsync(sg->p + at, hold, held, hipMemcpyDeviceToHost, g->st), -3);
+        OUT_CK(hipStreamSynchronize(g->st), -3);
+        spill_ms = wall_ms() - t0;
+    }
+    float f0 = 0, f1 = 0, f2 = 0;
+    OUT_CK(hipEventElapsedTime(&f0, g->ev[0], g->ev[1]), -3);
     OUT_CK(hipEventElapsedTime(&f1, g->bev[2], g->bev[3]), -3);
+    OUT_CK(hipEventElapsedTime(&f2, g->bev[0], g->bev[1]), -3);
+    // everything succeeded: the state moves on
+    if (sg == &fresh) { std::vector<SortSeg> &v = host ? S.hsegs : S.segs; v.push_back(fresh); sg = &v.back(); fresh = SortSeg{nullptr, 0, 0}; }
     S.info.index_ms += f0 + f1;
-    sg->used = at + total; S.stream += total; S.nrec += more;
+    S.hold.keep_ms += f2; S.hold.spill_ms += spill_ms;
+    sg->used = at + held; S.stream += total; S.nrec += more;
+    if (host) { S.hold.held_host_bytes += held; S.hold.host_batches++; } else { S.hold.held_device_bytes += held; S.hold.device_batches++; }
+    S.hold.stream_bytes = S.stream;
     return 0;
+}
+int sort_add(lnr_outgpu *g, u64 total, const u64 *roff, u32 n, char *err, size_t err_cap) {
+    if (total == 0) return 0;
+    SortSeg fresh{nullptr, 0, 0};                 // a segment made for this batch: the state's only once the batch is in
+    std::vector<SortSeg> &segs = g->sort.segs, &hsegs = g->sort.hsegs;
+    if (segs.size() == segs.capacity()) segs.reserve(2 * segs.size() + 4);         // (so that taking the segment in cannot fail)
+    if (hsegs.size() == hsegs.capacity()) hsegs.reserve(2 * hsegs.size() + 4);
+    const int s = sort_add_to(g, total, roff, n, fresh, err, err_cap);
+    if (fresh.alloc) (void)hipHostFree(fresh.alloc);
+    else if (fresh.p) (void)hipFree(fresh.p);
+    return s;
 }
 
 }  // namespace
@@ -944,6 +1080,14 @@ int lnr_outgpu_sort_begin(lnr_outgpu *g, uint64_t max_bytes, char *err, size_t e
     return 0;
 }
 
+int lnr_outgpu_sort_spill(lnr_outgpu *g, uint64_t max_host_bytes, char *err, size_t err_cap) {
+    if (g->sort.on != 1) { snprintf(err, err_cap, "the sort mode is not collecting"); return -1; }
+    g->sort.spill = max_host_bytes ? 1 : 0; g->sort.max_host = max_host_bytes;
+    return 0;
+}
+
+void lnr_outgpu_sort_hold_info_get(const lnr_outgpu *g, lnr_outgpu_hold_info *out) { *out = g->sort.hold; }
+
 int lnr_outgpu_sort_finish(lnr_outgpu *g, uint32_t piece_members, char *err, size_t err_cap) {
     SortState &S = g->sort;
     if (S.on != 1) { snprintf(err, err_cap, "the sort mode is not collecting"); return -1; }
@@ -959,8 +1103,9 @@ int lnr_outgpu_sort_finish(lnr_outgpu *g, uint32_t piece_members, char *err, siz
         t2 = t1 > t3 ? t1 : t3;
         if ((s = dev_need(S.k1, 8 * n, err, err_cap)) || (s = dev_need(S.k2, 8 * n, err, err_cap)) || (s = dev_need(S.v1, 4 * n, err, err_cap)) || (s = dev_need(S.v2, 4 * n, err, err_cap)) ||
             (s = dev_need(S.tmp, t2 + 16, err, err_cap)) || (s = dev_need(S.s_addr, 8 * n, err, err_cap)) || (s = dev_need(S.s_size, 8 * (n + 1), err, err_cap)) ||
-            (s = dev_need(S.s_off, 8 * (n + 1), err, err_cap)) || (s = dev_need(S.s_flag, 4 * n, err, err_cap)) || (s = dev_need(S.s_end, 8 * n, err, err_cap))) return s;
-        const SortArrays A{(u64 *)S.key.p, (u32 *)S.flag.p, (u64 *)S.soff.p, (u64 *)S.addr.p, (u32 *)S.size.p, (i64 *)S.end.p};
+            (s = dev_need(S.s_off, 8 * (n + 1), err, err_cap)) || (s = dev_need(S.s_flag, 4 * n, err, err_cap)) || (s = dev_need(S.s_end, 8 * n, err, err_cap)) ||
+            (s = dev_need(S.s_qoff, 4 * n, err, err_cap)) || (s = dev_need(S.s_lseq, 4 * n, err, err_cap))) return s;
+        const SortArrays A{(u64 *)S.key.p, (u32 *)S.flag.p, (u64 *)S.soff.p, (u64 *)S.addr.p, (u32 *)S.size.p, (i64 *)S.end.p, (u32 *)S.qoff.p, (u32 *)S.lseq.p};
         u64 *k1 = (u64 *)S.k1.p, *k2 = (u64 *)S.k2.p;
         u32 *v1 = (u32 *)S.v1.p, *v2 = (u32 *)S.v2.p;
         const u32 grid = (u32)((n + 256) / 256);          // (n + 1 lanes: k_sort_apply writes the scan's last input)
@@ -971,7 +1116,7 @@ int lnr_outgpu_sort_finish(lnr_outgpu *g, uint32_t piece_members, char *err, siz
         hipLaunchKernelGGL(k_sort_take, dim3(grid), dim3(256), 0, g->st, (const u64 *)A.key, (const u32 *)v2, n, k1);
         tb = t2;
         OUT_CK(rocprim::radix_sort_pairs(S.tmp.p, tb, k1, k2, v2, v1, (size_t)n, 0u, 64u, g->st), -3);          // stably by key: k2 sorted keys, v1 the order
-        hipLaunchKernelGGL(k_sort_apply, dim3(grid), dim3(256), 0, g->st, A, (const u32 *)v1, n, (u64 *)S.s_addr.p, (u64 *)S.s_size.p, (u32 *)S.s_flag.p, (i64 *)S.s_end.p);
+        hipLaunchKernelGGL(k_sort_apply, dim3(grid), dim3(256), 0, g->st, A, (const u32 *)v1, n, (u64 *)S.s_addr.p, (u64 *)S.s_size.p, (u32 *)S.s_flag.p, (i64 *)S.s_end.p, (u32 *)S.s_qoff.p, (u32 *)S.s_lseq.p);
         tb = t2;
         OUT_CK(rocprim::exclusive_scan(S.tmp.p, tb, (u64 *)S.s_size.p, (u64 *)S.s_off.p, (u64)0, (size_t)(n + 1), rocprim::plus<u64>(), g->st), -3);
         OUT_CK(hipEventRecord(g->bev[1], g->st), -3);
@@ -989,7 +1134,7 @@ int lnr_outgpu_sort_finish(lnr_outgpu *g, uint32_t piece_members, char *err, siz
     S.info.records = n; S.info.record_bytes = S.stream; S.info.members = S.members;
     u64 held = 0;
     for (const SortSeg &sg : S.segs) held += sg.cap + 8;
-    for (const Buf *b : {&S.key, &S.flag, &S.soff, &S.addr, &S.size, &S.end, &S.k1, &S.k2, &S.v1, &S.v2, &S.tmp, &S.s_addr, &S.s_size, &S.s_off, &S.s_flag, &S.s_end, &S.counter}) held += b->cap;
+    for (const Buf *b : sort_bufs(S)) held += b->cap;
     S.info.device_bytes = held;
     S.on = 2;
     return 0;
@@ -1010,7 +1155,7 @@ int lnr_outgpu_sort_next(lnr_outgpu *g, const char **data, uint64_t *size, const
     int s;
     if ((s = dev_need(g->text, b - a + 8, err, err_cap))) return s;
     OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
-    hipLaunchKernelGGL(k_sort_gather, dim3(cnt), dim3(256), 0, g->st, (const u64 *)S.s_off.p, (const u64 *)S.s_addr.p, S.nrec, a, b, (uint8_t *)g->text.p);
+    hipLaunchKernelGGL(k_sort_gather, dim3(cnt), dim3(256), 0, g->st, (const u64 *)S.s_off.p, (const u64 *)S.s_addr.p, (const u32 *)S.s_qoff.p, (const u32 *)S.s_lseq.p, S.nrec, a, b, (uint8_t *)g->text.p);
     OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
     if ((s = bgzf_run(g, (const uint8_t *)g->text.p, b - a, data, size, err, err_cap))) return s;
     if (g->bz.blocks != cnt) { snprintf(err, err_cap, "sort: a piece of %u members came back as %llu", cnt, (unsigned long long)g->bz.blocks); return -8; }
