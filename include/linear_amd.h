@@ -373,7 +373,7 @@ lnr_status lnr_writer_bgzf_stats(const lnr_writer *w, lnr_bgzf_stats *out);
  * lnr_writer_format_bam (host threads; the in-library yardstick of the GPU forms): the records of a batch back to back.  ONE function
  * for both forms: reads_concat == NULL -- no SEQ (l_seq 0) and read_len_or_off is read_len[n]; otherwise SEQ as lnr_writer_format_seq prints
  * it, lnr_writer_set_genome is required (else LNR_ERR_ARG) and read_len_or_off is read_off[n + 1].  lnr_writer_format_bam_gpu takes the
- * same arguments (host memory) and formats on the GPU (k_out_measure_bam / k_out_scan / k_out_emit_bam); lnr_writer_format_bam_dev takes
+ * same arguments (host memory) and formats on the GPU (k_out_measure<Bam> / k_out_scan / k_out_emit<Bam>); lnr_writer_format_bam_dev takes
  * what lnr_filter_batch_dev hands out, the batch's d_off and its device bases d_reads_concat or NULL.  With lnr_writer_set_bgzf off
  * the two return the raw record bytes, with it on BGZF members of them, compressed where they lie.  A .bam file = the members of
  * lnr_writer_bgzf_bytes_gpu(the header), of every batch, and lnr_writer_bgzf_eof.  No record: zero bytes.  Before lnr_writer_gpu_open:

@@ -312,26 +312,16 @@ lnr_status lnr_writer_gpu_times(const lnr_writer *wr, double *ms5) {
     return LNR_OK;
 }
 
-// what: 1 = SAM records, 2 = APF.  Reads are formatted on `threads` host threads and concatenated in read order.
-// reads_concat != nullptr (SAM only): read_len holds n + 1 read offsets instead of n lengths, and SEQ is printed
-static lnr_status format_on_host(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_len, const char *read_ids,
-                                 const uint64_t *id_off, int what, uint32_t threads, const char **text, uint64_t *size) {
-    const Writer &w = wr->w;
-    uint32_t n = cords->n_reads;
+// The reads of a batch on `threads` host threads: thread t formats a contiguous share of them into a string of its own with read(k, out),
+// and the strings are concatenated in read order into the writer's text.
+extern "C++" {
+template <class F> static lnr_status reads_on_threads(lnr_writer *wr, uint32_t n, uint32_t threads, const char **text, uint64_t *size, F read) {
     if (threads < 1) threads = 1;
     if (threads > n) threads = n ? n : 1;
     std::vector<std::string> part(threads);
     auto work = [&](uint32_t t) {
         uint32_t lo = (uint32_t)((u64)n * t / threads), hi = (uint32_t)((u64)n * (t + 1) / threads);
-        std::vector<Rec> recs;
-        std::string &o = part[t];
-        for (uint32_t k = lo; k < hi; k++) {
-            u64 a = cords->cord_off[k], e = cords->cord_off[k + 1];
-            const char *id = read_ids + id_off[k];
-            if (reads_concat) sam_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k + 1] - read_len[k], id, o, recs, reads_concat + read_len[k]);
-            else if (what == 1) sam_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k], id, o, recs);
-            else apf_read(w, cords->cords_str + a, e - a, read_len[k], id, k > 0, o);
-        }
+        for (uint32_t k = lo; k < hi; k++) read(k, part[t]);
     };
     std::vector<std::thread> th;
     for (uint32_t t = 1; t < threads; t++) th.emplace_back(work, t);
@@ -342,6 +332,21 @@ static lnr_status format_on_host(lnr_writer *wr, const lnr_cords *cords, const u
     *text = wr->w.text.data();
     *size = wr->w.text.size();
     return LNR_OK;
+}
+}  // extern "C++"
+// what: 1 = SAM records, 2 = APF.
+// reads_concat != nullptr (SAM only): read_len holds n + 1 read offsets instead of n lengths, and SEQ is printed
+static lnr_status format_on_host(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_len, const char *read_ids,
+                                 const uint64_t *id_off, int what, uint32_t threads, const char **text, uint64_t *size) {
+    const Writer &w = wr->w;
+    return reads_on_threads(wr, cords->n_reads, threads, text, size, [&](uint32_t k, std::string &o) {
+        thread_local std::vector<Rec> recs;                      // sam_read's scratch, one per thread
+        u64 a = cords->cord_off[k], e = cords->cord_off[k + 1];
+        const char *id = read_ids + id_off[k];
+        if (reads_concat) sam_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k + 1] - read_len[k], id, o, recs, reads_concat + read_len[k]);
+        else if (what == 1) sam_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k], id, o, recs);
+        else apf_read(w, cords->cords_str + a, e - a, read_len[k], id, k > 0, o);
+    });
 }
 lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
                              int what, uint32_t threads, const char **text, uint64_t *size) {
@@ -391,7 +396,7 @@ lnr_status lnr_writer_format_seq_dev(lnr_writer *wr, const lnr_cords_dev *cords,
 }
 
 // ---- BAM: the header on the host; the records by the shared logic of lnr_output_hd.h, here through a memory sink on host threads (the
-// yardstick of the GPU forms below), there in k_out_measure_bam / k_out_emit_bam
+// yardstick of the GPU forms below), there in k_out_measure<Bam> / k_out_emit<Bam>
 static void put_le32(std::string &o, uint32_t v) { for (int b = 0; b < 4; b++) o += (char)(v >> (8 * b)); }
 lnr_status lnr_writer_bam_header(lnr_writer *wr, const char *command_line, int pbsv, const char **data, uint64_t *size) {
     if (!wr || !data || !size) return LNR_ERR_ARG;
@@ -423,31 +428,17 @@ lnr_status lnr_writer_format_bam(lnr_writer *wr, const lnr_cords *cords, const u
                                  const uint64_t *id_off, uint32_t threads, const char **data, uint64_t *size) {
     if (!wr || !cords || !read_len || !read_ids || !id_off || !data || !size || (reads_concat && !seq_ready(wr))) return LNR_ERR_ARG;
     const Writer &w = wr->w;
-    const uint32_t n = cords->n_reads, nseq = (uint32_t)w.gid.size();
+    const uint32_t nseq = (uint32_t)w.gid.size();
     std::string blob; std::vector<u64> goff;
     for (const std::string &g : w.gid) { goff.push_back(blob.size()); blob += g; blob += '\0'; }
     const lnr_out::Params P{blob.data(), goff.data(), w.glen.data(), nseq, w.thd_large_X, w.thd_DI, w.thd_X};
-    if (threads < 1) threads = 1;
-    if (threads > n) threads = n ? n : 1;
-    std::vector<std::string> part(threads);
-    auto work = [&](uint32_t t) {
-        uint32_t lo = (uint32_t)((u64)n * t / threads), hi = (uint32_t)((u64)n * (t + 1) / threads);
-        StrSink o{part[t]};
-        for (uint32_t k = lo; k < hi; k++) {
-            const u64 a = cords->cord_off[k], nc = cords->cord_off[k + 1] - a;
-            const u64 L = reads_concat ? read_len[k + 1] - read_len[k] : read_len[k];
-            const lnr_out::SeqSrc q{nullptr, nullptr, w.glen.data(), nseq, reads_concat ? reads_concat + read_len[k] : nullptr, L, w.genome};      // the borrowed sequences, each where it lies
-            lnr_out::bam_read(o, P, reads_concat ? &q : nullptr, cords->cords_str + a, cords->cords_end + a, nc, L, read_ids + id_off[k]);
-        }
-    };
-    std::vector<std::thread> th;
-    for (uint32_t t = 1; t < threads; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &t : th) t.join();
-    wr->w.text.clear();
-    for (auto &p : part) wr->w.text += p;
-    *data = wr->w.text.data(); *size = wr->w.text.size();
-    return LNR_OK;
+    return reads_on_threads(wr, cords->n_reads, threads, data, size, [&](uint32_t k, std::string &out) {
+        StrSink o{out};
+        const u64 a = cords->cord_off[k], nc = cords->cord_off[k + 1] - a;
+        const u64 L = reads_concat ? read_len[k + 1] - read_len[k] : read_len[k];
+        const lnr_out::SeqSrc q{nullptr, nullptr, w.glen.data(), nseq, reads_concat ? reads_concat + read_len[k] : nullptr, L, w.genome};      // the borrowed sequences, each where it lies
+        lnr_out::bam_read(o, P, reads_concat ? &q : nullptr, cords->cords_str + a, cords->cords_end + a, nc, L, read_ids + id_off[k]);
+    });
 }
 lnr_status lnr_writer_format_bam_gpu(lnr_writer *wr, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_len, const char *read_ids,
                                      const uint64_t *id_off, const char **data, uint64_t *size) {

@@ -2,34 +2,38 @@
 // HBM, then one copy into pinned host memory.  gfx950, wave64.  Every byte comes from lnr_output_hd.h, the same text the CPU test pins.
 //
 // Three steps on the writer's own stream:
-//   k_out_measure  bytes of text per read                      (one wave per read)
-//   k_out_scan     exclusive scan -> 64-bit text offsets, total read back through pinned memory
-//   k_out_emit     every read writes its text at its offset     (one wave per read; placement by the scan alone, no atomics)
-// Tiling: workgroup = one wave = one read, lane = item (cord j of the read, lnr_output_hd.h) in tiles of 64 cords.  Per tile the lanes size
-// their items with the counting sink, a wave scan turns sizes into positions, the lanes format again into an LDS window that mirrors the
-// 4-byte-aligned destination, and the wave copies the window out as coalesced dword stores (single bytes only in the first and last dword
-// of a tile, which neighbouring tiles / reads share).  Text longer than the window takes more rounds: a lane formats once per window its item
-// touches and the sink drops what lies outside.  The block header of an APF item and the record of a SAM item look ahead along the read
-// inside one lane; read index, pointers, counts and the read's text offset are wave-uniform (blockIdx), so the compiler keeps them scalar.
+//   k_out_measure<Fmt>  bytes of text per read                  (one wave per read)
+//   k_out_scan          exclusive scan -> 64-bit text offsets, total read back through pinned memory
+//   k_out_emit<Fmt>     every read writes its text at its offset (one wave per read; placement by the scan alone, no atomics)
+// Both kernels are format_read<Fmt, EMIT>, the one skeleton of a read.  Tiling: workgroup = one wave = one read, lane = item (cord j of the
+// read, lnr_output_hd.h) in tiles of 64 cords.  An item is head, body, tail.  Per tile the lanes size their items with the counting sink, a
+// wave scan turns sizes into positions, the lanes format head and tail again into an LDS window that mirrors the 4-byte-aligned
+// destination, and the wave copies byte ranges of the window out: the whole tile where no item has a body (consecutive items touch), else
+// per record its head range and its tail range.  Text longer than the window takes more rounds: a lane formats once per window its head or
+// tail touches and the sink drops what lies outside.  The body of a record -- its SEQ -- is 10-20 kB where head and tail are some hundred
+// bytes, and is written by the whole wave, record after record of the tile: the owning lane walks its record once more and streams the
+// SEGMENTS of the SEQ (lnr_output_hd.h) into an LDS table, SEG_CAP at a time, then every lane produces destination-aligned dwords -- finds
+// its segment by bisection over the table's SEQ positions (SegCursor), loads the source bytes (genome forward; read forward, or backward and
+// complemented for flag 16).  The block header of an APF item and the record of a SAM item look ahead along the read inside one lane; read
+// index, pointers, counts and the read's text offset are wave-uniform (blockIdx), so the compiler keeps them scalar.
 //
-// SAM with SEQ (lnr_writer_format_seq_gpu / _dev: k_out_measure_seq, k_out_emit_seq): a record line is head, SEQ, tail, and the SEQ is 10-20 kB
-// where head and tail are some hundred bytes.  Head and tail go the way above, lane = item, through the LDS window; the window starts out
-// as zeros, which no text holds, so the copy stores what was formatted and leaves the SEQ bytes between them alone.  The SEQ bytes are
-// written by the whole wave, record after record of the tile: the owning lane walks its record once more and streams the SEGMENTS of the
-// SEQ (lnr_output_hd.h) into an LDS table, SEG_CAP at a time, then every lane produces destination-aligned dwords -- finds its segment
-// by bisection over the table's SEQ positions, loads the source bytes (genome forward; read forward, or backward and complemented for
-// flag 16), maps them through ACGTN.  Single-byte stores: the first and last dword of a SEQ, which it shares with head and tail, and a
-// dword that straddles a refill of the table.  The measure kernel sums element counts and touches no base.
+// The formats are small policy structs that answer only what differs (see the comment above them):
+//   Text    SAM without SEQ, and APF (lnr_writer_format_gpu / _dev): an item is its head alone
+//   SamSeq  SAM with SEQ (lnr_writer_format_seq_gpu / _dev): head, the letters mapped through ACGTN, tail; measuring sums element counts and
+//           touches no base
+//   Bam     BAM records without SEQ and with it (lnr_writer_format_bam_gpu / _dev): head (block_size, core, QNAME, CIGAR words), SEQ packed
+//           two bases to a byte (a lane's dword is 8 bases) plus the 0xff run, tag
 //
-// BAM records (lnr_writer_format_bam_gpu / _dev: k_out_measure_bam, k_out_emit_bam): the same three steps with the binary record of
-// lnr_output_hd.h in the text's place, without SEQ and with it; see the comment above format_read_bam.
+// Every store of a byte range that is not a lane's own -- the window copies, the SEQ letters and nibbles, the 0xff runs, the copies of the
+// sort and the BGZF pack -- is lnr_span_hd.h's span_store with another word source: whole dwords where the dword lies inside the range,
+// single bytes in the first and the last dword, which neighbouring ranges share.  The CPU test pins that routine under the sanitizers.
 //
 // BGZF output (lnr_writer_set_bgzf): the text stays in HBM and is compressed there, every 0xff00 bytes of it into one BGZF member by
 // lnr_deflate_hd.h -- the same text the CPU test pins against zlib.
 //   k_bgzf_deflate  one workgroup of 512 lanes per block (a grid of at most one workgroup per CU walks the blocks): the block's text and
 //                   the hash table in LDS, the member image built in the table's place, then copied to the block's 65536-byte slot
 //   k_out_scan      member sizes -> offsets
-//   k_bgzf_pack     the slots -> one contiguous run (destination-aligned dword stores), the only bytes that are downloaded
+//   k_bgzf_pack     the slots -> one contiguous run (span_copy), the only bytes that are downloaded
 //
 // Coordinate sort (lnr_writer_sort_*): the BAM records of every batch are held until the sort -- without their quality spans (l_seq bytes of
 // 0xff: bam_qual_span), in device segments or, with lnr_writer_sort_spill, in pinned host segments --, the order is computed on keys alone
@@ -40,13 +44,13 @@
 //                   quality span per record.  The append is atomic; the stream offset is part of the order, so the result does not depend on
 //                   the append order.
 //   k_sort_keep     per batch, one wave per read: copies the records into the segment (or the staging buffer of a spilled batch, which one
-//                   device-to-host copy then moves) and leaves the quality spans out; destination-aligned dwords as in k_sort_gather
+//                   device-to-host copy then moves) and leaves the quality spans out (span_copy)
 //   the sort        rocPRIM's stable radix sort twice: by (reverse bit, stream offset), then by key; k_sort_apply gathers the per-record
 //                   arrays into that order and a scan of the sorted sizes places every record in the sorted stream S
 //   k_sort_gather   per piece: one workgroup per 0xff00 bytes of S (= one BGZF member); bisection finds the first record that reaches into
-//                   the tile, waves copy record after record (destination-aligned dwords put together from two aligned source dwords,
-//                   single bytes at both ends; a piece of 8 KiB or more is copied by the whole workgroup): held bytes, the 0xff run of the
-//                   quality span, held bytes again.  Spilled records are read straight out of the pinned memory.  No atomics.
+//                   the tile, waves copy record after record (span_copy: destination-aligned dwords put together from two aligned source
+//                   dwords; a piece of 8 KiB or more is copied by the whole workgroup): held bytes, the 0xff run of the quality span
+//                   (span_fill), held bytes again.  Spilled records are read straight out of the pinned memory.  No atomics.
 //   per piece       k_bgzf_deflate / k_out_scan / k_bgzf_pack as for any text
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>   // AMD's native primitives library: the stable radix sort and the scan of the coordinate sort
@@ -60,6 +64,7 @@
 #include "lnr_deflate_hd.h"
 #include "lnr_output_hd.h"
 #include "lnr_output_hook.h"
+#include "lnr_span_hd.h"
 
 namespace {
 
@@ -78,68 +83,15 @@ __device__ __forceinline__ u64 wave_incl_scan_u64(u64 v) {
     return v;
 }
 
-struct ReadArgs {
-    Params P;
-    const u64 *coff, *cs, *ce, *len; int len_is_off;
-    const char *ids; const u64 *idoff;
-    int what;
-};
-
-template <class S> __device__ __forceinline__ void item_text(S &s, const ReadArgs &A, const u64 *cs, const u64 *ce, u64 nc, u64 j, u64 L, const char *id, bool blank,
-                                                             u64 it, u64 n_rec) {
-    if (A.what == 2) apf_item(s, A.P, cs, nc, j, L, id, blank);
-    else sam_item(s, A.P, cs, ce, nc, j, L, id, it, n_rec);
+// the wave copies staged positions [a, b) that fall into the window at wlo (4-byte aligned) from lds to dst; staged position p <-> dst[p]
+__device__ __forceinline__ void window_out(const char *lds, u64 wlo, uint8_t *dst, u64 a, u64 b, u32 lane) {
+    const u64 lo = a > wlo ? a : wlo, hi = b < wlo + OUT_WIN ? b : wlo + OUT_WIN;
+    if (lo >= hi) return;
+    const u32 *w = reinterpret_cast<const u32 *>(lds) + (((lo & ~3ULL) - wlo) >> 2);
+    span_store(dst + lo, (u32)(hi - lo), lane, 64u, [=](u32 q, bool) { return w[q >> 2]; });
 }
 
-// one wave = read k.  EMIT false: returns the bytes of its text.  EMIT true: writes them to text + toff.
-template <bool EMIT> __device__ u64 format_read(const ReadArgs &A, u32 k, char *text, u64 toff, char *lds) {
-    const int lane = threadIdx.x & 63;
-    const u64 a = A.coff[k], nc = A.coff[k + 1] - a;
-    const u64 *cs = A.cs + a, *ce = A.ce + a;
-    const u64 L = A.len_is_off ? A.len[k + 1] - A.len[k] : A.len[k];
-    const char *id = A.ids + A.idoff[k];
-    const bool blank = k > 0;
-    u64 n_rec = 0;
-    if (A.what == 1)
-        for (u64 base = 1; base < nc; base += 64) {
-            u64 j = base + lane;
-            n_rec += (u64)__popcll(__ballot(j < nc && rec_first(cs, ce, j, A.P.thd_large_X)));
-        }
-    const u32 mis = (u32)(toff & 3);           // the LDS window mirrors the destination from a 4-byte boundary on
-    char *dst = text + (toff - mis);           // staged position p of the read's text <-> dst[p]
-    u64 pos = 0, rec_carry = 0;
-    for (u64 base = 1; base < nc; base += 64) {
-        const u64 j = base + lane;
-        const bool item = j < nc && (A.what == 2 || rec_first(cs, ce, j, A.P.thd_large_X));
-        const u64 bal = __ballot(item);
-        const u64 it = rec_carry + (u64)__popcll(bal & ((1ULL << lane) - 1ULL));
-        u64 sz = 0;
-        if (item) { CountSink c; item_text(c, A, cs, ce, nc, j, L, id, blank, it, n_rec); sz = c.n; }
-        const u64 incl = wave_incl_scan_u64(sz);
-        const u64 tile_total = __shfl(incl, 63, 64);
-        if constexpr (EMIT) {
-            const u64 s0 = mis + pos, s1 = s0 + tile_total, mine = s0 + incl - sz;
-            for (u64 wlo = s0 & ~3ULL; wlo < s1; wlo += OUT_WIN) {
-                if (sz && mine < wlo + OUT_WIN && mine + sz > wlo) { LdsSink s{lds, mine - wlo}; item_text(s, A, cs, ce, nc, j, L, id, blank, it, n_rec); }
-                __syncthreads();               // (the workgroup is this one wave; all loop bounds here are wave-uniform)
-                const u64 lo = wlo > s0 ? wlo : s0, hi = wlo + OUT_WIN < s1 ? wlo + OUT_WIN : s1;
-                for (u32 d = lane; d < OUT_WIN / 4; d += 64) {
-                    const u64 p = wlo + 4ULL * d;
-                    if (p >= hi) break;
-                    if (p + 4 <= lo) continue;
-                    if (p >= lo && p + 4 <= hi) *reinterpret_cast<u32 *>(dst + p) = reinterpret_cast<const u32 *>(lds)[d];
-                    else for (u32 b = 0; b < 4; b++) if (p + b >= lo && p + b < hi) dst[p + b] = lds[4 * d + b];
-                }
-                __syncthreads();
-            }
-        }
-        pos += tile_total;
-        rec_carry += (u64)__popcll(bal);
-    }
-    return pos;
-}
-
-// ---- SAM with SEQ
+// ---- the SEQ of a record, written by the whole wave off a table of its segments (lnr_output_hd.h)
 constexpr u32 SEG_CAP = 256;                   // segments of a record in LDS at a time
 struct SeqArgs { const uint8_t *genome; const u64 *gstart; const uint8_t *reads; };       // (A.len holds read offsets here: read k = reads + len[k])
 struct SegTable { u64 pos[SEG_CAP + 1], x[SEG_CAP], y[SEG_CAP]; u32 kind[SEG_CAP]; };       // pos: SEQ position of segment i, pos[i + 1] its end
@@ -150,141 +102,44 @@ struct SegFill {                               // keeps segments skip .. skip + 
         if (i < SEG_CAP) { t->pos[i] = p; t->pos[i + 1] = p + c; t->x[i] = x; t->y[i] = y; t->kind[i] = kind; }
     }
 };
-
-// the wave writes SEQ positions [tab.pos[0], tab.pos[cnt]) of one record; staged position of SEQ position p = q0 + p
-__device__ __forceinline__ void seq_copy(const SegTable *tab, u32 cnt, const RecSrc &r, char *dst, u64 q0) {
-    const int lane = threadIdx.x & 63;
+struct SegCursor {                             // the last segment that starts at or before SEQ position `first` (bisection), then a forward walk
+    const SegTable *tab; u32 s = 0; u64 s_lo, s_hi;
+    __device__ SegCursor(const SegTable *t, u32 cnt, u64 first) : tab(t) {
+        for (u32 hi = cnt; hi - s > 1;) { const u32 mid = (s + hi) >> 1; if (tab->pos[mid] <= first) s = mid; else hi = mid; }
+        s_lo = tab->pos[s]; s_hi = tab->pos[s + 1];
+    }
+    __device__ u64 to(u64 sp) {                // moves on to the segment of sp; returns sp's offset in it
+        while (sp >= s_hi) { s++; s_lo = s_hi; s_hi = tab->pos[s + 1]; }
+        return sp - s_lo;
+    }
+};
+// letters: SEQ positions [tab.pos[0], tab.pos[cnt]) of one record; staged position of SEQ position p = q0 + p.  A lane's dword is 4 bases.
+__device__ __forceinline__ void seq_copy(const SegTable *tab, u32 cnt, const RecSrc &r, uint8_t *dst, u64 q0, u32 lane) {
     const u64 e0 = q0 + tab->pos[0], e1 = q0 + tab->pos[cnt];
-    for (u64 p = (e0 & ~3ULL) + 4ULL * lane; p < e1; p += 256) {
-        const u64 first = (p > e0 ? p : e0) - q0;
-        u32 s = 0, hi = cnt;                   // the last segment that starts at or before `first`
-        while (hi - s > 1) { const u32 mid = (s + hi) >> 1; if (tab->pos[mid] <= first) s = mid; else hi = mid; }
-        u64 s_lo = tab->pos[s], s_hi = tab->pos[s + 1];
+    span_store(dst + e0, (u32)(e1 - e0), lane, 64u, [&](u32 q, bool) {
+        const u64 p = (e0 & ~3ULL) + q;
+        SegCursor c(tab, cnt, (p > e0 ? p : e0) - q0);
         u32 word = 0;
         for (u32 b = 0; b < 4; b++) {
             const u64 pb = p + b;
             if (pb < e0 || pb >= e1) continue;
-            const u64 sp = pb - q0;
-            while (sp >= s_hi) { s++; s_lo = s_hi; s_hi = tab->pos[s + 1]; }
-            const u64 o = sp - s_lo;
-            word |= (u32)(uint8_t)seq_char(r, tab->kind[s], tab->x[s] + o, tab->y[s] + o) << (8 * b);
+            const u64 o = c.to(pb - q0);
+            word |= (u32)(uint8_t)seq_char(r, tab->kind[c.s], tab->x[c.s] + o, tab->y[c.s] + o) << (8 * b);
         }
-        if (p >= e0 && p + 4 <= e1) *reinterpret_cast<u32 *>(dst + p) = word;
-        else for (u32 b = 0; b < 4; b++) if (p + b >= e0 && p + b < e1) dst[p + b] = (char)(word >> (8 * b));
-    }
+        return word;
+    });
 }
-
-// one wave = read k, as format_read
-template <bool EMIT> __device__ u64 format_read_seq(const ReadArgs &A, const SeqArgs &Q, u32 k, char *text, u64 toff, char *lds, SegTable *tab) {
-    const int lane = threadIdx.x & 63;
-    const u64 a = A.coff[k], nc = A.coff[k + 1] - a;
-    const u64 *cs = A.cs + a, *ce = A.ce + a;
-    const u64 L = A.len[k + 1] - A.len[k];
-    const SeqSrc q{Q.genome, Q.gstart, A.P.glen, A.P.nseq, Q.reads + A.len[k], L};
-    const char *id = A.ids + A.idoff[k];
-    u64 n_rec = 0;
-    for (u64 base = 1; base < nc; base += 64) {
-        u64 j = base + lane;
-        n_rec += (u64)__popcll(__ballot(j < nc && rec_first(cs, ce, j, A.P.thd_large_X)));
-    }
-    const u32 mis = (u32)(toff & 3);
-    char *dst = text + (toff - mis);
-    u64 pos = 0, rec_carry = 0;
-    for (u64 base = 1; base < nc; base += 64) {
-        const u64 j = base + lane;
-        const bool item = j < nc && rec_first(cs, ce, j, A.P.thd_large_X);
-        const u64 bal = __ballot(item);
-        const u64 it = rec_carry + (u64)__popcll(bal & ((1ULL << lane) - 1ULL));
-        u64 hsz = 0, bases = 0, tsz = 0;       // head (with the '*' of an empty SEQ), SEQ, tail
-        if (item) {
-            CountSink h; bases = sam_head(h, A.P, cs, ce, nc, j, L, id); hsz = h.n + (bases == 0);
-            CountSink t; sam_tail(t, A.P, cs, ce, nc, L, it, n_rec); tsz = t.n;
-        }
-        const u64 sz = hsz + bases + tsz;
-        const u64 incl = wave_incl_scan_u64(sz);
-        const u64 tile_total = __shfl(incl, 63, 64);
-        if constexpr (EMIT) {
-            const u64 s0 = mis + pos, s1 = s0 + tile_total, mine = s0 + incl - sz, tpos = mine + hsz + bases;
-            for (u64 wlo = s0 & ~3ULL; wlo < s1; wlo += OUT_WIN) {
-                const bool hin = item && mine < wlo + OUT_WIN && mine + hsz > wlo, tin = item && tpos < wlo + OUT_WIN && tpos + tsz > wlo;
-                if (!__ballot(hin || tin)) continue;               // a window inside one SEQ
-                for (u32 d = lane; d < OUT_WIN / 4; d += 64) reinterpret_cast<u32 *>(lds)[d] = 0;
-                __syncthreads();
-                if (hin) { LdsSink s{lds, mine - wlo}; if (sam_head(s, A.P, cs, ce, nc, j, L, id) == 0) s.put('*'); }
-                if (tin) { LdsSink s{lds, tpos - wlo}; sam_tail(s, A.P, cs, ce, nc, L, it, n_rec); }
-                __syncthreads();
-                for (u32 d = lane; d < OUT_WIN / 4; d += 64) {     // zero bytes: outside the tile, or SEQ
-                    const u32 v = reinterpret_cast<const u32 *>(lds)[d];
-                    const u64 p = wlo + 4ULL * d;
-                    if (v == 0) continue;
-                    if (((v - 0x01010101u) & ~v & 0x80808080u) == 0) *reinterpret_cast<u32 *>(dst + p) = v;
-                    else for (u32 b = 0; b < 4; b++) if ((v >> (8 * b)) & 0xff) dst[p + b] = (char)(v >> (8 * b));
-                }
-                __syncthreads();
-            }
-            for (u64 todo = __ballot(item && bases > 0); todo; todo &= todo - 1) {        // the records of the tile, one after the other
-                const int own = __ffsll((unsigned long long)todo) - 1;
-                const u64 lo = base + (u64)own;                    // its first cord: wave-uniform
-                const u64 q0 = __shfl(mine + hsz, own, 64);
-                const RecSrc r = rec_src(q, cs, lo);
-                u32 done = 0, total;
-                do {
-                    u32 seen = 0;
-                    if (lane == own) { SegFill f{tab, done}; SegOps<SegFill> so(f, cx(cs[lo])); record_ops(so, A.P, cs, ce, nc, lo, L); seen = so.k; }
-                    __syncthreads();
-                    total = (u32)__builtin_amdgcn_readfirstlane((int)__shfl(seen, own, 64));
-                    const u32 cnt = total - done < SEG_CAP ? total - done : SEG_CAP;
-                    if (cnt) seq_copy(tab, cnt, r, dst, q0);
-                    done += cnt;
-                    __syncthreads();
-                } while (done < total);
-            }
-        }
-        pos += tile_total;
-        rec_carry += (u64)__popcll(bal);
-    }
-    return pos;
-}
-
-// ---- BAM records (lnr_writer_format_bam_gpu / _dev: k_out_measure_bam, k_out_emit_bam).  A record is head (block_size, core, QNAME, CIGAR
-// words), packed SEQ, the 0xff run, tag (lnr_output_hd.h).  Head and tag go lane = record through the LDS window as the text forms do, but a
-// BAM core is full of zero bytes, so nothing marks a window byte as "not formatted": the wave copies explicit byte RANGES out of the window --
-// the whole tile without SEQ (head and tag of consecutive records touch), per record its head range and its tag range with SEQ.  Packed SEQ
-// is written by the whole wave off the segment table as k_out_emit_seq writes its letters: a lane's dword is 8 bases, found by bisection,
-// and may straddle segments; a table round that ends on an odd base hands the high nibble on (`carry`) and leaves the byte to the next
-// round; the last byte of an odd SEQ gets a low nibble of 0.  The 0xff run is a wave-wide fill.  Same LDS as k_out_emit_seq (window + table).
-// the wave copies staged positions [a, b) that fall into the window at wlo (4-byte aligned) from lds to dst: dwords, single bytes at the edges
-__device__ __forceinline__ void copy_range(const char *lds, u64 wlo, char *dst, u64 a, u64 b) {
-    const int lane = threadIdx.x & 63;
-    const u64 lo = a > wlo ? a : wlo, hi = b < wlo + OUT_WIN ? b : wlo + OUT_WIN;
-    if (lo >= hi) return;
-    for (u64 p = (lo & ~3ULL) + 4ULL * lane; p < hi; p += 256) {
-        const u32 d = (u32)(p - wlo) >> 2;
-        if (p >= lo && p + 4 <= hi) *reinterpret_cast<u32 *>(dst + p) = reinterpret_cast<const u32 *>(lds)[d];
-        else for (u32 b4 = 0; b4 < 4; b4++) if (p + b4 >= lo && p + b4 < hi) dst[p + b4] = lds[4 * d + b4];
-    }
-}
-// the wave fills staged positions [a, b) with 0xff
-__device__ __forceinline__ void fill_ff(char *dst, u64 a, u64 b) {
-    const int lane = threadIdx.x & 63;
-    for (u64 p = (a & ~3ULL) + 4ULL * lane; p < b; p += 256) {
-        if (p >= a && p + 4 <= b) *reinterpret_cast<u32 *>(dst + p) = 0xffffffffu;
-        else for (u32 b4 = 0; b4 < 4; b4++) if (p + b4 >= a && p + b4 < b) dst[p + b4] = (char)0xff;
-    }
-}
-// the wave writes the packed bytes of SEQ bases [tab.pos[0], tab.pos[cnt]) of one record; staged position of packed byte j = q0 + j.
-// A first base at an odd position shares its byte with `carry`, the nibble of the base before it; a last base at an even position is
-// left to the next round unless this round is the record's last (then its byte's low nibble is 0).
-__device__ __forceinline__ void seq_pack_copy(const SegTable *tab, u32 cnt, const RecSrc &r, char *dst, u64 q0, u32 carry, bool last_round) {
-    const int lane = threadIdx.x & 63;
+// nibbles: the packed bytes of SEQ bases [tab.pos[0], tab.pos[cnt]) of one record; staged position of packed byte j = q0 + j.  A lane's
+// dword is 8 bases.  A first base at an odd position shares its byte with `carry`, the nibble of the base before it; a last base at an even
+// position is left to the next round unless this round is the record's last (then its byte's low nibble is 0).
+__device__ __forceinline__ void seq_pack_copy(const SegTable *tab, u32 cnt, const RecSrc &r, uint8_t *dst, u64 q0, u32 carry, bool last_round, u32 lane) {
     const u64 b0 = tab->pos[0], b1 = tab->pos[cnt];
     const u64 e0 = q0 + (b0 >> 1), e1 = q0 + (last_round ? (b1 + 1) >> 1 : b1 >> 1);
-    for (u64 p = (e0 & ~3ULL) + 4ULL * lane; p < e1; p += 256) {
+    span_store(dst + e0, (u32)(e1 - e0), lane, 64u, [&](u32 q, bool) {
+        const u64 p = (e0 & ~3ULL) + q;
         u64 first = 2 * ((p > e0 ? p : e0) - q0);
         if (first < b0) first = b0;
-        u32 s = 0, hi = cnt;                   // the last segment that starts at or before `first`
-        while (hi - s > 1) { const u32 mid = (s + hi) >> 1; if (tab->pos[mid] <= first) s = mid; else hi = mid; }
-        u64 s_lo = tab->pos[s], s_hi = tab->pos[s + 1];
+        SegCursor c(tab, cnt, first);
         u32 word = 0;
         for (u32 b = 0; b < 4; b++) {
             const u64 pb = p + b;
@@ -295,93 +150,146 @@ __device__ __forceinline__ void seq_pack_copy(const SegTable *tab, u32 cnt, cons
                 u32 nb;
                 if (sp < b0) nb = carry;
                 else if (sp >= b1) nb = 0;
-                else {
-                    while (sp >= s_hi) { s++; s_lo = s_hi; s_hi = tab->pos[s + 1]; }
-                    const u64 o = sp - s_lo;
-                    nb = seq_nib(r, tab->kind[s], tab->x[s] + o, tab->y[s] + o);
-                }
+                else { const u64 o = c.to(sp); nb = seq_nib(r, tab->kind[c.s], tab->x[c.s] + o, tab->y[c.s] + o); }
                 byte |= h ? nb : nb << 4;
             }
             word |= byte << (8 * b);
         }
-        if (p >= e0 && p + 4 <= e1) *reinterpret_cast<u32 *>(dst + p) = word;
-        else for (u32 b = 0; b < 4; b++) if (p + b >= e0 && p + b < e1) dst[p + b] = (char)(word >> (8 * b));
-    }
+        return word;
+    });
 }
 
-// one wave = read k, as format_read.  seq: records carry SEQ (Q holds the genome and the reads, A.len read offsets)
-template <bool EMIT> __device__ __forceinline__ u64 format_read_bam(const ReadArgs &A, const SeqArgs &Q, bool seq, u32 k, char *text, u64 toff, char *lds, SegTable *tab) {
-    const int lane = threadIdx.x & 63;
-    const u64 a = A.coff[k], nc = A.coff[k + 1] - a;
-    const u64 *cs = A.cs + a, *ce = A.ce + a;
-    const u64 L = A.len_is_off ? A.len[k + 1] - A.len[k] : A.len[k];
-    const SeqSrc q{Q.genome, Q.gstart, A.P.glen, A.P.nseq, seq ? Q.reads + A.len[k] : nullptr, L};
-    const char *id = A.ids + A.idoff[k];
-    const u64 qlen = str_len(id);
-    u64 n_rec = 0;
-    for (u64 base = 1; base < nc; base += 64) {
-        u64 j = base + lane;
-        n_rec += (u64)__popcll(__ballot(j < nc && rec_first(cs, ce, j, A.P.thd_large_X)));
+// ---- one read, one wave
+struct ReadArgs {
+    Params P;
+    const u64 *coff, *cs, *ce, *len; int len_is_off;
+    const char *ids; const u64 *idoff;
+    int what, seq;                             // seq: records carry SEQ (Q holds the genome and the reads, len read offsets)
+    SeqArgs Q;
+};
+struct Read { const u64 *cs, *ce; u64 nc, L; const char *id; bool blank; u64 n_rec; };      // read k's slice of the batch: wave-uniform
+struct Sizes { u64 head = 0, body = 0, tail = 0; };       // an item's bytes: head and tail are formatted by its lane through the LDS window, the body between them is written by the wave
+
+// The formats.  A format answers what differs between them: whether cord j is an item, the item's three sizes, "format head / tail into
+// this sink", whether consecutive items touch (no body anywhere: the tile is one byte range), and "write the body of a record for this round
+// of its segment table".  Everything else is format_read's.
+// (All of it is inlined into the kernel, by force: the formats hold references to the kernel's by-value arguments, and one call left out of
+// line would make the compiler copy those into scratch memory.)
+struct Text {                                  // SAM without SEQ, and APF: an item is its head alone
+    static constexpr bool BODY = false;
+    using Item = Sizes;
+    const ReadArgs &A; const Read &R;
+    __device__ __forceinline__ bool item(u64 j) const { return A.what == 2 || rec_first(R.cs, R.ce, j, A.P.thd_large_X); }
+    __device__ __forceinline__ bool touch() const { return true; }
+    __device__ __forceinline__ void size(Item &z, u64 j, u64 it) const { CountSink c; head(c, z, j, it); z.head = c.n; }
+    template <class S> __device__ __forceinline__ void head(S &s, const Item &, u64 j, u64 it) const {
+        if (A.what == 2) apf_item(s, A.P, R.cs, R.nc, j, R.L, R.id, R.blank);
+        else sam_item(s, A.P, R.cs, R.ce, R.nc, j, R.L, R.id, it, R.n_rec);
     }
-    const u32 mis = (u32)(toff & 3);
-    char *dst = text + (toff - mis);
+    template <class S> __device__ __forceinline__ void tail(S &, u64) const {}
+};
+struct SamSeq {                                // head (with the '*' of an empty SEQ), letters, tail
+    static constexpr bool BODY = true;
+    using Item = Sizes;
+    const ReadArgs &A; const Read &R;
+    __device__ __forceinline__ bool item(u64 j) const { return rec_first(R.cs, R.ce, j, A.P.thd_large_X); }
+    __device__ __forceinline__ bool touch() const { return false; }
+    __device__ __forceinline__ void size(Item &z, u64 j, u64 it) const {
+        CountSink h; z.body = sam_head(h, A.P, R.cs, R.ce, R.nc, j, R.L, R.id); z.head = h.n + (z.body == 0);
+        CountSink t; tail(t, it); z.tail = t.n;
+    }
+    template <class S> __device__ __forceinline__ void head(S &s, const Item &, u64 j, u64) const { if (sam_head(s, A.P, R.cs, R.ce, R.nc, j, R.L, R.id) == 0) s.put('*'); }
+    template <class S> __device__ __forceinline__ void tail(S &s, u64 it) const { sam_tail(s, A.P, R.cs, R.ce, R.nc, R.L, it, R.n_rec); }
+    __device__ __forceinline__ void body(const SegTable *tab, u32 cnt, const RecSrc &r, uint8_t *dst, u64 q0, bool, u32 &, u32 lane) const { seq_copy(tab, cnt, r, dst, q0, lane); }
+};
+// BAM records, with SEQ and without: head (block_size, core, QNAME, CIGAR words), packed SEQ plus the 0xff run, tag (lnr_output_hd.h).  A
+// table round that ends on an odd base hands the high nibble on (`carry`) and leaves the byte to the next round; the record's last round
+// also fills the 0xff run behind the packed bytes.
+struct Bam {
+    static constexpr bool BODY = true;
+    struct Item : Sizes { BamCount c; u64 bases = 0; };
+    const ReadArgs &A; const Read &R; u64 qlen;
+    __device__ __forceinline__ Bam(const ReadArgs &a, const Read &r) : A(a), R(r), qlen(str_len(r.id)) {}
+    __device__ __forceinline__ bool item(u64 j) const { return rec_first(R.cs, R.ce, j, A.P.thd_large_X); }
+    __device__ __forceinline__ bool touch() const { return !A.seq; }      // without SEQ head and tag of consecutive records touch
+    __device__ __forceinline__ void size(Item &z, u64 j, u64 it) const {
+        record_ops(z.c, A.P, R.cs, R.ce, R.nc, j, R.L);
+        z.head = bam_head_size(qlen, z.c.k);
+        z.bases = A.seq ? z.c.seq : 0; z.body = bam_packed(z.bases) + z.bases;
+        CountSink t; tail(t, it); z.tail = t.n;
+    }
+    template <class S> __device__ __forceinline__ void head(S &s, const Item &z, u64 j, u64) const { bam_head(s, A.P, R.cs, R.ce, R.nc, j, R.L, R.id, z.c, z.bases, z.tail); }
+    template <class S> __device__ __forceinline__ void tail(S &s, u64 it) const { bam_tail(s, A.P, R.cs, R.ce, R.nc, R.L, it, R.n_rec); }
+    __device__ __forceinline__ void body(const SegTable *tab, u32 cnt, const RecSrc &r, uint8_t *dst, u64 q0, bool last_round, u32 &carry, u32 lane) const {
+        seq_pack_copy(tab, cnt, r, dst, q0, carry, last_round, lane);
+        const u64 o = tab->pos[cnt] - 1 - tab->pos[cnt - 1];                // the round's last base: the next round's carry
+        carry = seq_nib(r, tab->kind[cnt - 1], tab->x[cnt - 1] + o, tab->y[cnt - 1] + o);
+        if (last_round) { const u64 nb = tab->pos[cnt]; span_fill(dst + q0 + bam_packed(nb), 0xff, (u32)nb, lane, 64u); }
+    }
+};
+
+// one wave = read k.  EMIT false: returns the bytes of its text.  EMIT true: writes them to text + toff.
+template <class Fmt, bool EMIT> __device__ __forceinline__ u64 format_read(const ReadArgs &A, u32 k, char *text, u64 toff, char *lds, SegTable *tab) {
+    const u32 lane = threadIdx.x & 63;
+    const u64 a = A.coff[k], nc = A.coff[k + 1] - a;
+    Read R{A.cs + a, A.ce + a, nc, A.len_is_off ? A.len[k + 1] - A.len[k] : A.len[k], A.ids + A.idoff[k], k > 0, 0};
+    const Fmt F{A, R};
+    if (A.what != 2)                            // (an APF item does not ask how many there are)
+        for (u64 base = 1; base < nc; base += 64) {
+            const u64 j = base + lane;
+            R.n_rec += (u64)__popcll(__ballot(j < nc && F.item(j)));
+        }
+    const SeqSrc q{A.Q.genome, A.Q.gstart, A.P.glen, A.P.nseq, A.seq ? A.Q.reads + A.len[k] : nullptr, R.L};      // (used where the format has bodies)
+    const u32 mis = (u32)(toff & 3);           // the LDS window mirrors the destination from a 4-byte boundary on
+    uint8_t *dst = reinterpret_cast<uint8_t *>(text) + (toff - mis);      // staged position p of the read's text <-> dst[p]
     u64 pos = 0, rec_carry = 0;
     for (u64 base = 1; base < nc; base += 64) {
         const u64 j = base + lane;
-        const bool item = j < nc && rec_first(cs, ce, j, A.P.thd_large_X);
+        const bool item = j < nc && F.item(j);
         const u64 bal = __ballot(item);
         const u64 it = rec_carry + (u64)__popcll(bal & ((1ULL << lane) - 1ULL));
-        BamCount c;
-        u64 hsz = 0, bases = 0, tsz = 0;       // head, SEQ bases (packed + the 0xff run between head and tag), tag
-        if (item) {
-            record_ops(c, A.P, cs, ce, nc, j, L);
-            hsz = bam_head_size(qlen, c.k);
-            bases = seq ? c.seq : 0;
-            CountSink t; bam_tail(t, A.P, cs, ce, nc, L, it, n_rec); tsz = t.n;
-        }
-        const u64 sz = hsz + bam_packed(bases) + bases + tsz;
+        typename Fmt::Item z;
+        if (item) F.size(z, j, it);
+        const u64 sz = z.head + z.body + z.tail;
         const u64 incl = wave_incl_scan_u64(sz);
         const u64 tile_total = __shfl(incl, 63, 64);
         if constexpr (EMIT) {
-            const u64 s0 = mis + pos, s1 = s0 + tile_total, mine = s0 + incl - sz, tpos = mine + sz - tsz;
-            for (u64 wlo = s0 & ~3ULL; wlo < s1; wlo += OUT_WIN) {
-                const bool hin = item && mine < wlo + OUT_WIN && mine + hsz > wlo, tin = item && tsz && tpos < wlo + OUT_WIN && tpos + tsz > wlo;
+            const u64 s0 = mis + pos, s1 = s0 + tile_total, mine = s0 + incl - sz, tpos = mine + z.head + z.body;
+            for (u64 wlo = s0 & ~3ULL; wlo < s1; wlo += OUT_WIN) {      // text longer than the window takes more rounds
+                const bool hin = z.head && mine < wlo + OUT_WIN && mine + z.head > wlo, tin = z.tail && tpos < wlo + OUT_WIN && tpos + z.tail > wlo;
                 const u64 in = __ballot(hin || tin);
-                if (!in) continue;                                 // a window inside one SEQ
-                if (hin) { LdsSink s{lds, mine - wlo}; bam_head(s, A.P, cs, ce, nc, j, L, id, c, bases, tsz); }
-                if (tin) { LdsSink s{lds, tpos - wlo}; bam_tail(s, A.P, cs, ce, nc, L, it, n_rec); }
-                __syncthreads();
-                if (!seq) copy_range(lds, wlo, dst, s0, s1);       // head and tag of consecutive records touch: the tile is one range
+                if (!in) continue;                                 // a window inside one body
+                if (hin) { LdsSink s{lds, mine - wlo}; F.head(s, z, j, it); }
+                if (tin) { LdsSink s{lds, tpos - wlo}; F.tail(s, it); }
+                __syncthreads();               // (the workgroup is this one wave; all loop bounds here are wave-uniform)
+                if (F.touch()) window_out(lds, wlo, dst, s0, s1, lane);
                 else
-                    for (u64 todo = in; todo; todo &= todo - 1) {
+                    for (u64 todo = in; todo; todo &= todo - 1) {  // a body lies between head and tail: two ranges per record
                         const int own = __ffsll((unsigned long long)todo) - 1;
-                        const u64 h0 = __shfl(mine, own, 64), h1 = h0 + __shfl(hsz, own, 64), t0 = __shfl(tpos, own, 64), t1 = t0 + __shfl(tsz, own, 64);
-                        copy_range(lds, wlo, dst, h0, h1);
-                        copy_range(lds, wlo, dst, t0, t1);
+                        const u64 h0 = __shfl(mine, own, 64), h1 = h0 + __shfl(z.head, own, 64), t0 = __shfl(tpos, own, 64), t1 = t0 + __shfl(z.tail, own, 64);
+                        window_out(lds, wlo, dst, h0, h1, lane);
+                        window_out(lds, wlo, dst, t0, t1, lane);
                     }
                 __syncthreads();
             }
-            for (u64 todo = __ballot(item && bases > 0); todo; todo &= todo - 1) {        // the records of the tile, one after the other
-                const int own = __ffsll((unsigned long long)todo) - 1;
-                const u64 lo = base + (u64)own;                    // its first cord: wave-uniform
-                const u64 q0 = __shfl(mine + hsz, own, 64), nb = __shfl(bases, own, 64);
-                const RecSrc r = rec_src(q, cs, lo);
-                fill_ff(dst, q0 + bam_packed(nb), q0 + bam_packed(nb) + nb);
-                u32 done = 0, total, carry = 0;
-                do {
-                    u32 seen = 0;
-                    if (lane == own) { SegFill f{tab, done}; SegOps<SegFill> so(f, cx(cs[lo])); record_ops(so, A.P, cs, ce, nc, lo, L); seen = so.k; }
-                    __syncthreads();
-                    total = (u32)__builtin_amdgcn_readfirstlane((int)__shfl(seen, own, 64));
-                    const u32 cnt = total - done < SEG_CAP ? total - done : SEG_CAP;
-                    if (cnt) {
-                        seq_pack_copy(tab, cnt, r, dst, q0, carry, done + cnt == total);
-                        const u64 last = tab->pos[cnt] - 1 - tab->pos[cnt - 1];        // the round's last base: the next round's carry
-                        carry = seq_nib(r, tab->kind[cnt - 1], tab->x[cnt - 1] + last, tab->y[cnt - 1] + last);
-                    }
-                    done += cnt;
-                    __syncthreads();
-                } while (done < total);
+            if constexpr (Fmt::BODY) {
+                for (u64 todo = __ballot(z.body > 0); todo; todo &= todo - 1) {        // the records of the tile, one after the other
+                    const int own = __ffsll((unsigned long long)todo) - 1;
+                    const u64 lo = base + (u64)own;                    // its first cord: wave-uniform
+                    const u64 q0 = __shfl(mine + z.head, own, 64);
+                    const RecSrc r = rec_src(q, R.cs, lo);
+                    u32 done = 0, total, carry = 0;
+                    do {                                               // the owning lane walks its record again, SEG_CAP segments into the table per round
+                        u32 seen = 0;
+                        if (lane == (u32)own) { SegFill f{tab, done}; SegOps<SegFill> so(f, cx(R.cs[lo])); record_ops(so, A.P, R.cs, R.ce, nc, lo, R.L); seen = so.k; }
+                        __syncthreads();
+                        total = (u32)__builtin_amdgcn_readfirstlane((int)__shfl(seen, own, 64));
+                        const u32 cnt = total - done < SEG_CAP ? total - done : SEG_CAP;
+                        if (cnt) F.body(tab, cnt, r, dst, q0, done + cnt == total, carry, lane);
+                        done += cnt;
+                        __syncthreads();
+                    } while (done < total);
+                }
             }
         }
         pos += tile_total;
@@ -390,33 +298,19 @@ template <bool EMIT> __device__ __forceinline__ u64 format_read_bam(const ReadAr
     return pos;
 }
 
-__global__ __launch_bounds__(64) void k_out_measure_bam(ReadArgs A, SeqArgs Q, int seq, u64 *sizes) {
-    u64 s = format_read_bam<false>(A, Q, seq != 0, blockIdx.x, nullptr, 0, nullptr, nullptr);
+template <class Fmt> __global__ __launch_bounds__(64) void k_out_measure(ReadArgs A, u64 *sizes) {
+    const u64 s = format_read<Fmt, false>(A, blockIdx.x, nullptr, 0, nullptr, nullptr);
     if (threadIdx.x == 0) sizes[blockIdx.x] = s;
 }
-__global__ __launch_bounds__(64) void k_out_emit_bam(ReadArgs A, SeqArgs Q, int seq, const u64 *toff, char *text) {
+template <class Fmt> __global__ __launch_bounds__(64) void k_out_emit(ReadArgs A, const u64 *toff, char *text) {
     __shared__ __attribute__((aligned(16))) char lds[OUT_WIN];
-    __shared__ SegTable tab;
-    format_read_bam<true>(A, Q, seq != 0, blockIdx.x, text, toff[blockIdx.x], lds, &tab);
+    SegTable *tab = nullptr;
+    if constexpr (Fmt::BODY) { __shared__ SegTable t; tab = &t; }
+    format_read<Fmt, true>(A, blockIdx.x, text, toff[blockIdx.x], lds, tab);
 }
-
-__global__ __launch_bounds__(64) void k_out_measure_seq(ReadArgs A, SeqArgs Q, u64 *sizes) {
-    u64 s = format_read_seq<false>(A, Q, blockIdx.x, nullptr, 0, nullptr, nullptr);
-    if (threadIdx.x == 0) sizes[blockIdx.x] = s;
-}
-__global__ __launch_bounds__(64) void k_out_emit_seq(ReadArgs A, SeqArgs Q, const u64 *toff, char *text) {
-    __shared__ __attribute__((aligned(16))) char lds[OUT_WIN];
-    __shared__ SegTable tab;
-    format_read_seq<true>(A, Q, blockIdx.x, text, toff[blockIdx.x], lds, &tab);
-}
-
-__global__ __launch_bounds__(64) void k_out_measure(ReadArgs A, u64 *sizes) {
-    u64 s = format_read<false>(A, blockIdx.x, nullptr, 0, nullptr);
-    if (threadIdx.x == 0) sizes[blockIdx.x] = s;
-}
-__global__ __launch_bounds__(64) void k_out_emit(ReadArgs A, const u64 *toff, char *text) {
-    __shared__ __attribute__((aligned(16))) char lds[OUT_WIN];
-    format_read<true>(A, blockIdx.x, text, toff[blockIdx.x], lds);
+template <class Fmt> void launch_format(bool emit, u32 n, hipStream_t st, const ReadArgs &A, u64 *sizes, char *text) {
+    if (emit) hipLaunchKernelGGL(k_out_emit<Fmt>, dim3(n), dim3(64), 0, st, A, (const u64 *)sizes, text);
+    else hipLaunchKernelGGL(k_out_measure<Fmt>, dim3(n), dim3(64), 0, st, A, sizes);
 }
 // in place: a[0 .. n) sizes -> exclusive offsets, a[n] = total.  One workgroup: n is the reads of a batch.
 __global__ __launch_bounds__(1024) void k_out_scan(u64 *a, u32 n) {
@@ -488,22 +382,11 @@ __global__ __launch_bounds__(DEF_THREADS) void k_bgzf_deflate(const uint8_t *tex
         __syncthreads();
     }
 }
-// slot k -> out + off[k], off[k + 1] - off[k] bytes: destination-aligned dwords put together from two aligned dwords of the slot
+// slot k -> out + off[k], off[k + 1] - off[k] bytes
 __global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, const u64 *off, uint8_t *out) {
-    const u32 k = blockIdx.x, t = threadIdx.x;
-    const uint8_t *src = slots + (u64)k * lnr_def::MEMBER_CAP;
+    const u32 k = blockIdx.x;
     const u64 o = off[k];
-    const u32 m = (u32)(off[k + 1] - o);
-    uint8_t *dst = out + o;
-    u32 head = (4 - (u32)(o & 3)) & 3;
-    if (head > m) head = m;
-    if (t < head) dst[t] = src[t];
-    const u32 words = (m - head) / 4, r = 8 * (head & 3);
-    const u32 *sw = reinterpret_cast<const u32 *>(src);     // source byte head + 4 w = word w of sw shifted by r bits (head < 4)
-    u32 *dw = reinterpret_cast<u32 *>(dst + head);
-    for (u32 w = t; w < words; w += 256) dw[w] = r ? (sw[w] >> r) | (sw[w + 1] << (32 - r)) : sw[w];
-    const u32 done = head + 4 * words;
-    if (t < m - done) dst[done + t] = src[done + t];
+    span_copy(out + o, slots + (u64)k * lnr_def::MEMBER_CAP, (u32)(off[k + 1] - o), threadIdx.x, 256u);
 }
 
 // ---- coordinate sort
@@ -553,33 +436,6 @@ __global__ __launch_bounds__(256) void k_sort_apply(SortArrays A, const u32 *per
         s_addr[i] = A.addr[r]; s_size[i] = A.size[r]; s_flag[i] = A.flag[r]; s_end[i] = A.end[r]; s_qoff[i] = A.qoff[r]; s_lseq[i] = A.lseq[r];
     } else if (i == n) s_size[i] = 0;
 }
-// len bytes src -> dst by lanes t of nt (nt >= 3): single bytes up to dst's first dword boundary and after its last whole dword, between them
-// destination-aligned dwords put together from two aligned source dwords.  Reads at most 3 bytes before src (never below its dword) and 3
-// bytes past src + len: the segments' slack.
-__device__ __forceinline__ void copy_bytes(uint8_t *dst, const uint8_t *src, u32 len, u32 t, u32 nt) {
-    u32 head = (4 - (u32)((uintptr_t)dst & 3)) & 3;
-    if (head > len) head = len;
-    if (t < head) dst[t] = src[t];
-    const u32 words = (len - head) / 4;
-    const uint8_t *s = src + head;
-    const u32 sh = (u32)((uintptr_t)s & 3), r = 8 * sh;
-    const u32 *sw = reinterpret_cast<const u32 *>(s - sh);
-    u32 *dw = reinterpret_cast<u32 *>(dst + head);
-    for (u32 w = t; w < words; w += nt) dw[w] = r ? (sw[w] >> r) | (sw[w + 1] << (32 - r)) : sw[w];
-    const u32 done = head + 4 * words;
-    if (t < len - done) dst[done + t] = src[done + t];
-}
-// len bytes 0xff at dst, dealt to the lanes as copy_bytes deals them
-__device__ __forceinline__ void fill_bytes(uint8_t *dst, u32 len, u32 t, u32 nt) {
-    u32 head = (4 - (u32)((uintptr_t)dst & 3)) & 3;
-    if (head > len) head = len;
-    if (t < head) dst[t] = 0xff;
-    const u32 words = (len - head) / 4;
-    u32 *dw = reinterpret_cast<u32 *>(dst + head);
-    for (u32 w = t; w < words; w += nt) dw[w] = 0xffffffffu;
-    const u32 done = head + 4 * words;
-    if (t < len - done) dst[done + t] = 0xff;
-}
 // The batch's records at recs (g->text) -> hold, without their quality spans: one wave per read (four to a workgroup) walks the read's
 // records and copies what lies before and after each span; cpos[k]: where read k's held bytes start (k_sort_index<true>, scanned).  All
 // of the walk is wave-uniform.  Reads of recs stay inside [0, roff[n] + 3]; writes inside hold[cpos[k], cpos[k + 1]).
@@ -594,9 +450,9 @@ __global__ __launch_bounds__(256) void k_sort_keep(const uint8_t *recs, const u6
         if (sz < 36 || p + sz > e) break;
         const BamQual q = bam_qual_span(recs + p, sz);
         if (q.l_seq) {
-            copy_bytes(d, recs + p, q.qoff, lane, 64u);
-            copy_bytes(d + q.qoff, recs + p + q.qoff + q.l_seq, (u32)(sz - q.qoff - q.l_seq), lane, 64u);
-        } else copy_bytes(d, recs + p, (u32)sz, lane, 64u);
+            span_copy(d, recs + p, q.qoff, lane, 64u);
+            span_copy(d + q.qoff, recs + p + q.qoff + q.l_seq, (u32)(sz - q.qoff - q.l_seq), lane, 64u);
+        } else span_copy(d, recs + p, (u32)sz, lane, 64u);
         d += sz - q.l_seq;
         p += sz;
     }
@@ -624,13 +480,13 @@ __global__ __launch_bounds__(256) void k_sort_gather(const u64 *s_off, const u64
             const uint8_t *src = reinterpret_cast<const uint8_t *>(s_addr[r]);
             uint8_t *d = dst + (c0 - t0);
             const u64 x0 = c0 - o, x1 = c1 - o, l = s_lseq[r];
-            if (l == 0) { copy_bytes(d, src + x0, len, t, nt); continue; }
+            if (l == 0) { span_copy(d, src + x0, len, t, nt); continue; }
             const u64 q0 = s_qoff[r], q1 = q0 + l;
-            if (x0 < q0) copy_bytes(d, src + x0, (u32)((x1 < q0 ? x1 : q0) - x0), t, nt);
+            if (x0 < q0) span_copy(d, src + x0, (u32)((x1 < q0 ? x1 : q0) - x0), t, nt);
             const u64 f0 = x0 > q0 ? x0 : q0, f1 = x1 < q1 ? x1 : q1;
-            if (f0 < f1) fill_bytes(d + (f0 - x0), (u32)(f1 - f0), t, nt);
+            if (f0 < f1) span_fill(d + (f0 - x0), 0xff, (u32)(f1 - f0), t, nt);
             const u64 p0 = x0 > q1 ? x0 : q1;
-            if (p0 < x1) copy_bytes(d + (p0 - x0), src + (p0 - l), (u32)(x1 - p0), t, nt);
+            if (p0 < x1) span_copy(d + (p0 - x0), src + (p0 - l), (u32)(x1 - p0), t, nt);
         }
 }
 
@@ -638,8 +494,8 @@ double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono:
 
 struct Buf { void *p = nullptr; u64 cap = 0; };
 
-// cap: bytes for records; the allocation has 8 more (copy_bytes reads past a record's end).  A host segment (pinned, alloc != nullptr) has
-// HOST_FRONT bytes in front of p as well, and dev is what the kernels read it by.
+// cap: bytes for records; the allocation has 8 more (span_copy reads up to 3 bytes past a record's end: lnr_span_hd.h).  A host segment
+// (pinned, alloc != nullptr) has HOST_FRONT bytes in front of p as well, and dev is what the kernels read it by.
 struct SortSeg { char *p; u64 cap, used; char *alloc = nullptr, *dev = nullptr; };
 struct SortState {
     int on = 0;                                 // 0 off, 1 collecting, 2 sorted: pieces go out
@@ -988,7 +844,8 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     A.P.thd_large_X = b->thd_large_X; A.P.thd_DI = b->thd_DI; A.P.thd_X = b->thd_X;
     A.what = b->what;
     const bool seq = b->reads != nullptr;      // SAM / BAM with SEQ: b->read_len holds n + 1 offsets in both forms
-    SeqArgs Q{(const uint8_t *)g->genome.p, (const u64 *)g->gstart.p, b->reads};
+    A.seq = seq ? 1 : 0;
+    A.Q = SeqArgs{(const uint8_t *)g->genome.p, (const u64 *)g->gstart.p, b->reads};
     // read ids: once per call, '\0'-separated blob + offsets
     double t0 = wall_ms();
     const u64 id_bytes = b->id_off[n - 1] + strlen(b->read_ids + b->id_off[n - 1]) + 1;
@@ -1011,7 +868,7 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
             const u64 bases = b->read_len[n];
             if ((s = dev_need(g->reads, bases + 1, err, err_cap))) return s;
             if (bases) OUT_CK(hipMemcpyAsync(g->reads.p, b->reads, bases, hipMemcpyHostToDevice, g->st), -3);
-            Q.reads = (const uint8_t *)g->reads.p;
+            A.Q.reads = (const uint8_t *)g->reads.p;
         }
         A.coff = (const u64 *)g->coff.p; A.cs = (const u64 *)g->cs.p; A.ce = (const u64 *)g->ce.p; A.len = (const u64 *)g->len.p; A.len_is_off = seq ? 1 : 0;
     }
@@ -1020,9 +877,8 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     u64 *sizes = (u64 *)g->sizes.p;
     OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
     const bool bam = b->what == 3;
-    if (bam) hipLaunchKernelGGL(k_out_measure_bam, dim3(n), dim3(64), 0, g->st, A, Q, seq ? 1 : 0, sizes);
-    else if (seq) hipLaunchKernelGGL(k_out_measure_seq, dim3(n), dim3(64), 0, g->st, A, Q, sizes);
-    else hipLaunchKernelGGL(k_out_measure, dim3(n), dim3(64), 0, g->st, A, sizes);
+    const auto launch = bam ? launch_format<Bam> : seq ? launch_format<SamSeq> : launch_format<Text>;
+    launch(false, n, g->st, A, sizes, nullptr);
     OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
     hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, g->st, sizes, n);
     OUT_CK(hipEventRecord(g->ev[2], g->st), -3);
@@ -1033,9 +889,7 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     if ((s = dev_need(g->text, total + 8, err, err_cap))) return s;
     if (!g->bgzf && (s = host_need(g, total, err, err_cap))) return s;
     OUT_CK(hipEventRecord(g->ev[3], g->st), -3);
-    if (bam) hipLaunchKernelGGL(k_out_emit_bam, dim3(n), dim3(64), 0, g->st, A, Q, seq ? 1 : 0, (const u64 *)sizes, (char *)g->text.p);
-    else if (seq) hipLaunchKernelGGL(k_out_emit_seq, dim3(n), dim3(64), 0, g->st, A, Q, (const u64 *)sizes, (char *)g->text.p);
-    else hipLaunchKernelGGL(k_out_emit, dim3(n), dim3(64), 0, g->st, A, (const u64 *)sizes, (char *)g->text.p);
+    launch(true, n, g->st, A, sizes, (char *)g->text.p);
     OUT_CK(hipEventRecord(g->ev[4], g->st), -3);
     OUT_CK(hipStreamSynchronize(g->st), -3);
     OUT_CK(hipGetLastError(), -3);

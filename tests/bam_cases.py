@@ -91,9 +91,7 @@ def split_bam(raw: bytes):
     return raw[8:8 + l_text], refs, raw[p:]
 
 
-def many_records(n=66):
-    """one read of n records (every cord ends a block), strands alternating: two tiles of records, every record with an SA tag of n - 1 entries"""
-    return [(5000 + 50_000 * b, 10 + 3 * b, b & 1, 0, True, 96) for b in range(n)]
+many_records = wc.many_records
 
 
 def build_seq():

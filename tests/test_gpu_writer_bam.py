@@ -1,4 +1,4 @@
-"""GPU: BAM records encoded on the device (lnr_writer_format_bam_gpu / _dev, k_out_measure_bam / k_out_emit_bam in
+"""GPU: BAM records encoded on the device (lnr_writer_format_bam_gpu / _dev, k_out_measure<Bam> / k_out_emit<Bam> in
 linear_amd/csrc/lnr_output_kernels.hip).  On every shape of tests/bam_cases.py, without and with SEQ: the kernel's bytes == the host form
 (lnr_writer_format_bam) == bam_cases.bam_of_sam of the text format_gpu gives; the device form behind a Filter result; with the BGZF switch
 on the members walk and inflate to the switch-off bytes; buffer reuse; set_genome / gpu_open in either order; a whole file; the front-end's

@@ -1,4 +1,4 @@
-"""GPU: the SEQ column on the writer's GPU side (lnr_writer_format_seq_gpu / _dev, k_out_measure_seq / k_out_emit_seq in
+"""GPU: the SEQ column on the writer's GPU side (lnr_writer_format_seq_gpu / _dev, k_out_measure<SamSeq> / k_out_emit<SamSeq> in
 linear_amd/csrc/lnr_output_kernels.hip): byte for byte the host writer's text (lnr_writer_format_seq, itself pinned to the real program's
 -ss 1 output in tests/test_output_seq_cpu.py) on the shapes of tests/writer_seq_cases.py; buffer reuse across calls of other sizes and
 kinds; the device form behind a Filter result; the front-end's --sam-seq against the real program's text; the error paths."""

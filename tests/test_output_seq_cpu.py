@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import cases, writer_seq_cases as sc
+from tests import cases, writer_cases as wc, writer_seq_cases as sc
 from tests.test_cli_golden_cpu import MODE_OPTS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -120,6 +120,46 @@ def test_shared_logic_equals_host_writer(shim, writer, preset):
     assert any(b"N" * 100 in f[9] for f in recs if f[1] == b"0") and any(b"N" * 100 in f[9] for f in recs if f[1] == b"16")     # X over equal bases, both strands
     assert bool(re.search(rb"[=XID]80[DI]", b"\n".join(f[5] for f in recs))) == (preset == 1)
     assert sum(1 for f in recs if len(f) > 11 and f[11].startswith(b"SA:Z:")) >= 8
+
+
+def test_tile_and_window_shapes_are_in_the_cases(writer):
+    """Counted from the host writer's output: the 70-record read of writer_cases.synthetic() gives every format of the kernels' read
+    skeleton a second tile of records (records 64 .. 69, with SEQ: with bodies), a head that straddles a window edge, and a record whose
+    tail lies in a later window than its head.  (Reads without cords and with the dummy cord alone: the first two of synthetic().)"""
+    from tests import bam_cases as bmc
+    w = writer(2)
+    coff, cs, ce, reads, off, ids = sc.synthetic()
+    rl = np.diff(off.astype(np.int64)).astype(np.uint64)
+    rid = wc.MANY.encode()
+    assert ids.count(wc.MANY) == 1 and sorted(int(coff[k + 1] - coff[k]) for k in range(len(ids)))[:2] == [0, 1]
+    shapes = {}
+    for name, text in (("sam", w.format(coff, cs, ce, rl, ids, "sam")), ("sam_seq", w.format_seq(coff, cs, ce, reads, off, ids))):
+        t0 = text.find(rid + b"\t")
+        assert t0 > 0 and text[t0 - 1:t0] == b"\n"
+        fields = [(l + b"\n").split(b"\t") for l in text[t0:].split(b"\n") if l.startswith(rid + b"\t")]
+        whole = [len(b"\t".join(f)) for f in fields]
+        if name == "sam":
+            items = [(n, 0, 0) for n in whole]                                      # Text: an item is its head alone
+        else:
+            items = [(len(b"\t".join(f[:9])) + 1, len(f[9]), n - len(b"\t".join(f[:10]))) for f, n in zip(fields, whole)]
+            assert all(b > 0 for _, b, _ in items[64:])                              # bodies in the second tile
+        shapes[name] = (len(items), wc.tile_shapes(items, t0))
+    for name, raw in (("bam", w.format_bam(coff, cs, ce, rl, ids)), ("bam_seq", w.format_bam(coff, cs, ce, None, ids, reads=reads, read_off=off))):
+        p, t0, items = 0, None, []
+        for r in bmc.walk_records(raw):
+            size = 36 + len(r["name"]) + 1 + 4 * len(r["cigar"]) + (r["l_seq"] + 1) // 2 + r["l_seq"] + len(r["tags"])
+            if r["name"] == rid:
+                t0 = p if t0 is None else t0
+                items.append((36 + len(r["name"]) + 1 + 4 * len(r["cigar"]), (r["l_seq"] + 1) // 2 + r["l_seq"], len(r["tags"])))
+            p += size
+        shapes[name] = (len(items), wc.tile_shapes(items, t0))
+    for name, (n, tiles) in shapes.items():
+        assert n == 70 and len(tiles) == 2, name                                    # rec_carry = 64 in the second tile
+        if name == "bam":                                                           # (the format Bam meets the two shapes below with SEQ)
+            continue
+        assert sum(st for st, _ in tiles) >= 1, (name, tiles)                        # a head across a window edge
+        if name != "sam":
+            assert sum(tl for _, tl in tiles) >= 1, (name, tiles)                    # a tail windows behind its head
 
 
 @pytest.mark.parametrize("preset", [1, 2])

@@ -67,6 +67,29 @@ def blocks(strands_per_block, x0=5000, gid=1):
     return out
 
 
+MANY = "many" + "y" * 23                                       # the QNAME of synthetic()'s 70-record read
+
+
+def tile_shapes(items, t0, win=8192):
+    """What the kernels' read skeleton meets in one read.  items: (head, body, tail) bytes of the read's records in order, every cord of
+    the read a record; t0: the read's offset in the batch's text.  Per tile of 64 records: (heads that straddle an edge of the LDS window,
+    records whose tail starts in a later window than their head) -- windows of `win` bytes from the tile's start rounded down to 4."""
+    out, pos = [], t0
+    for first in range(0, len(items), 64):
+        wl, st, tl = pos & ~3, 0, 0
+        for h, b, t in items[first:first + 64]:
+            st += (pos - wl) // win != (pos + h - 1 - wl) // win
+            tl += bool(t) and (pos + h + b - wl) // win > (pos - wl) // win
+            pos += h + b + t
+        out.append((st, tl))
+    return out
+
+
+def many_records(n=66):
+    """one read of n records (every cord ends a block), strands alternating: two tiles of records, every record with an SA tag of n - 1 entries"""
+    return [(5000 + 50_000 * b, 10 + 3 * b, b & 1, 0, True, 96) for b in range(n)]
+
+
 def synthetic():
     B = Batch()
     B.read([], dummy=False)                                    # 0 cords
@@ -103,6 +126,8 @@ def synthetic():
     B.read([(3000, 40, 0, 0, False, 192), (3100, 140, 0, 0, False, 192), (3200, 240, 0, 0, False, 192)])          # overlapping cords on one diagonal: '=' merges
     B.read(run(3000, step=100, w=96))                          # text 1000x that of its neighbours
     B.read(run(1))
+    B.read(many_records(70), rid=MANY)                         # 70 records: a second tile of records that starts at record 64; some 150 kB of SA tags, so heads straddle
+    B.read(run(2))                                             # window edges and tails lie windows behind their heads (counted in tests/test_output_seq_cpu.py)
     return B.arrays()
 
 

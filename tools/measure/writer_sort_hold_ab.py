@@ -2,11 +2,12 @@
 """What the compact hold and the host tier of the GPU writer's sort mode cost, on the bench workload's cords: one lnr_filter_batch_dev of
 --reads synthetic 10 kb reads, then, without SEQ and with it, in rotating order within this process, the whole sorted file's record
 members and its index (lnr_writer_sort_begin + lnr_writer_format_bam_gpu + lnr_writer_sort_finish + every lnr_writer_sort_next piece +
-lnr_writer_sort_bai + lnr_writer_sort_end: leg B of tools/measure/writer_sort_ab.py) three ways:
-    P   the PARENT commit's library (--parent-lib PATH: liblinear_amd.so built from a checkout of the parent), which holds full records
+lnr_writer_sort_bai + lnr_writer_sort_end: leg B of tools/measure/writer_sort_ab.py) these ways:
+    P   the PARENT commit's library (--parent-lib PATH: liblinear_amd.so built from a checkout of the parent)
     B   this tree's library, everything on the device
     S   this tree's library, lnr_writer_sort_begin(1) + lnr_writer_sort_spill: every record goes to pinned host memory and comes back over
         the bus in k_sort_gather
+    T   S with the parent's library, where that has the host tier
 --reps timed rotations (at least 3) after --warmup; medians and the range (min .. max).  Before any timing the pieces of every leg are
 inflated and compared with lnr_writer_sort_host of the host form's records byte for byte, and P's, B's and S's file bytes with each
 other.  Prints one JSON line (also written to --out FILE): times, B over P against the range of P's own runs, the per-stage milliseconds
@@ -67,7 +68,6 @@ def parent_writer():
     for name in api.EXPORTS:
         if hasattr(lib, name):
             getattr(lib, name).argtypes, getattr(lib, name).restype = getattr(mine, name).argtypes, getattr(mine, name).restype
-    assert not hasattr(lib, "lnr_writer_sort_spill"), "--parent-lib is not the parent's library: it has the host tier"
     w = api.Writer.__new__(api.Writer)
     w.lib = lib
     arr = (C.c_char_p * len(gids))(*[g.encode() for g in gids])
@@ -80,6 +80,9 @@ def parent_writer():
 
 writers = {"P": parent_writer(), "B": api.Writer(gids, glen)}
 writers["S"] = writers["B"]
+PARENT_SPILLS = hasattr(writers["P"].lib, "lnr_writer_sort_spill")
+if PARENT_SPILLS:
+    writers["T"] = writers["P"]                   # T: the parent's library with every record spilled, S's counterpart
 for w in (writers["P"], writers["B"]):
     w.set_genome(genome)
     w.gpu_open(0)
@@ -101,8 +104,8 @@ def call(leg, seq, keep=False):
 
     def ck(st):
         assert st == 0, (leg, st, L.lnr_writer_error(w.h))
-    ck(L.lnr_writer_sort_begin(w.h, 1 if leg == "S" else 0))
-    if leg == "S":
+    ck(L.lnr_writer_sort_begin(w.h, 1 if leg in "ST" else 0))
+    if leg in "ST":
         ck(L.lnr_writer_sort_spill(w.h, a.host_bytes))
     ck(L.lnr_writer_format_bam_gpu(w.h, C.byref(hc), p_reads if seq else None, p_off if seq else p_rl, blob, p_ido, *out))
     assert size.value == 0
@@ -119,7 +122,7 @@ def call(leg, seq, keep=False):
     bai = C.string_at(data, size.value) if keep else size.value
     ck(L.lnr_writer_sort_info_get(w.h, C.byref(info)))
     st = {k: getattr(info, k) for k, _ in api.LnrSortInfo._fields_}
-    if leg != "P":
+    if hasattr(L, "lnr_writer_sort_hold_info_get"):      # (a parent from before the compact hold has no such call)
         ck(L.lnr_writer_sort_hold_info_get(w.h, C.byref(hold)))
         st.update({k: getattr(hold, k) for k, _ in api.LnrSortHoldInfo._fields_})
     ck(L.lnr_writer_sort_end(w.h))
@@ -130,7 +133,7 @@ def med(v):
     return {"ms_median": round(statistics.median(v) * 1e3, 2), "ms_min": round(min(v) * 1e3, 2), "ms_max": round(max(v) * 1e3, 2), "ms": [round(x * 1e3, 2) for x in v]}
 
 
-LEGS = "PBS"
+LEGS = "PBST" if PARENT_SPILLS else "PBS"
 res = {"workload": a.workload, "reads": n, "cords": int(cs.size), "reps": a.reps, "warmup": a.warmup, "write_phase_to_a_file_measured": False, "a_run_that_needs_the_host_tier_measured": False}
 for seq in (False, True):
     tag = "seq" if seq else "plain"
@@ -142,14 +145,14 @@ for seq in (False, True):
         files[leg] = (b"".join(pieces), bai)
         assert gzip.decompress(files[leg][0] + wb.bgzf_eof()) == want, f"{tag} {leg}: the pieces are not sort_host of the host form's records"
         print(f"[writer_sort_hold_ab] {tag} {leg}: pieces checked", file=sys.stderr, flush=True)
-    assert files["P"] == files["B"] == files["S"], f"{tag}: the legs' file bytes or indexes differ"
+    assert all(files[leg] == files["P"] for leg in LEGS), f"{tag}: the legs' file bytes or indexes differ"
     del files, want, pieces
     for _ in range(a.warmup):
         for leg in LEGS:
             call(leg, seq)
     t, stages = {k: [] for k in LEGS}, {k: [] for k in LEGS}
     for rep in range(a.reps):
-        for leg in (LEGS[rep % 3:] + LEGS[:rep % 3]):
+        for leg in (LEGS[rep % len(LEGS):] + LEGS[:rep % len(LEGS)]):
             t0 = time.perf_counter()
             total, bai, st = call(leg, seq)
             t[leg].append(time.perf_counter() - t0)
@@ -160,13 +163,14 @@ for seq in (False, True):
         r[leg] = med(t[leg])
         last = stages[leg][-1]
         r[leg]["info"] = {k: (round(statistics.median(s[k] for s in stages[leg]), 3) if k.endswith("_ms") else last[k]) for k in last}
+        r[leg]["info_reps"] = {k: [round(s[k], 4) for s in stages[leg]] for k in last if k.endswith("_ms")}      # every repetition: a spread can be taken
     sB, sS = r["B"]["info"], r["S"]["info"]
     r["record_bytes"], r["held_bytes"] = sB["record_bytes"], sB["held_device_bytes"]
     r["held_over_record_bytes"] = round(sB["held_device_bytes"] / sB["record_bytes"], 4)
     r["B_over_P_time"] = round(r["B"]["ms_median"] / r["P"]["ms_median"], 4)
     r["B_median_above_P_slowest"] = r["B"]["ms_median"] > r["P"]["ms_max"]
     r["S_over_B_time"] = round(r["S"]["ms_median"] / r["B"]["ms_median"], 4)
-    for leg, s in (("P", r["P"]["info"]), ("B", sB), ("S", sS)):     # bytes written by the gather (S) and bytes it reads (held) per second
+    for leg, s in [(leg, r[leg]["info"]) for leg in LEGS]:     # bytes written by the gather (S) and bytes it reads (held) per second
         r[leg]["gather_GBps_written"] = round(s["record_bytes"] / s["gather_ms"] / 1e6, 1)
     r["S"]["gather_GBps_read_from_host"] = round(sS["held_host_bytes"] / sS["gather_ms"] / 1e6, 1)
     r["S"]["spill_GBps"] = round(sS["held_host_bytes"] / sS["spill_ms"] / 1e6, 1)
