@@ -264,6 +264,44 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
                                const uint64_t **off /* n+1, host */, uint32_t *n_out);
 lnr_status lnr_reader_gpu_times(const lnr_reader *r, double *ms5);
 uint32_t lnr_reader_gpu_tile(void);
+/* Plain gzip input (one member or several, as gzip / pigz write them) inflated on the device -- opt-in.  A single member is inflated in parallel
+ * from DEFLATE block starts: the compressed bytes are read in rounds (LNR_READER_GZ_ROUND bytes, default 64 MiB) cut into chunks
+ * (LNR_READER_GZ_CHUNK bytes, default 128 KiB, at least 1 KiB); every chunk is searched for a non-final dynamic-Huffman block start and decoded
+ * from it with the 32 KiB history unknown; the pieces are chained in order -- a piece counts only where the decode of the piece before it ended
+ * exactly on its start -- and the history is filled in afterwards.  The result never rests on a guess; a stream of fixed or stored blocks only
+ * is decoded by one wave per round (slow, correct).  CRC32 and ISIZE of every member's trailer are checked; bytes behind the last member that
+ * start no member are passed over, as gzread passes over them.
+ * lnr_reader_gpu_gzip(r, 1): after lnr_reader_gpu_open and before the first read (else LNR_ERR_ARG).  A regular file that starts with a gzip
+ * member that is not BGZF is then mapped and lnr_reader_next_dev reads it by rounds, the text staying on the device; at a member that is not
+ * BGZF inside a BGZF file the gzip rounds take over where gzread takes over without the switch, and keep the file to its end.  Without the
+ * switch nothing changes.  The host takes the stream over -- for a FASTQ that leaves the four-line form, and at a lnr_reader_next after
+ * lnr_reader_next_dev -- through a fresh gzread stream moved to the text offset with gzseek, which inflates the file once more from its start.
+ * A corrupt or cut stream: LNR_ERR_ARG, lnr_reader_error names the compressed file offset of the piece or trailer and the reason; blocks
+ * delivered before it stay delivered; the reader can only be closed after that.  The text inflated in front of the failure is parsed as
+ * the end of the file: where the stream breaks inside a record, the cut record may be delivered as a record (as lnr_reader_next delivers it
+ * when gzread fails) before the next call reports the error.  lnr_reader_gpu_gzip_stats: counts of the last
+ * lnr_reader_next_dev and of all calls so far.
+ * lnr_gunzip_gpu: the same stages over a host buffer, no parse: gz[0, size) -> text[0, *text_size), size <= 2^31.  Text beyond text_cap, and a
+ * corrupt stream: LNR_ERR_ARG with the reason and the compressed offset in err (text_size = the bytes of the rounds before it); no usable
+ * device, or a library without its device half: LNR_ERR_NO_DEVICE.  stats may be NULL; its `last` is the last round. */
+typedef struct {
+    uint64_t rounds, members;        /* rounds that delivered text; members whose trailer was checked */
+    uint64_t chunks, candidates;     /* chunks of those rounds; block-start candidates the chain came to (on them or past them) */
+    uint64_t true_pieces;            /* pieces the chain landed on, the rounds' first pieces included */
+    uint64_t false_candidates;       /* candidates a true piece's decode passed: true_pieces + false_candidates = candidates + rounds */
+    uint64_t deflate_blocks;         /* DEFLATE blocks decoded */
+    uint64_t compressed_bytes, text_bytes;
+    uint64_t window_symbols;         /* text bytes that were references into the history of their piece */
+    uint64_t gzread_bytes;           /* text bytes that came through gzread instead (the reader only; total: lnr_reader_next's too) */
+    uint64_t grown_rounds;           /* rounds in which no block completed: run again with twice the bytes */
+    double find_ms, measure_ms, stitch_ms, emit_ms, chain_ms, resolve_ms;   /* the six kernels (HIP events) */
+    double parse_ms, upload_ms, download_ms;                                 /* measure + scan + emit of the reader (events); copies (wall) */
+} lnr_gzip_counts;
+typedef struct { lnr_gzip_counts last, total; } lnr_gzip_stats;
+lnr_status lnr_reader_gpu_gzip(lnr_reader *r, int on);
+lnr_status lnr_reader_gpu_gzip_stats(const lnr_reader *r, lnr_gzip_stats *out);
+lnr_status lnr_gunzip_gpu(int32_t device, const uint8_t *gz, uint64_t size, uint8_t *text, uint64_t text_cap, uint64_t *text_size, lnr_gzip_stats *stats,
+                          char *err, size_t err_cap);
 /* BAM input (an extension: the reference reads FASTA / FASTQ).  A read file whose first four inflated bytes are "BAM\1" is read as BAM, aligned
  * or unaligned, whatever its name; lnr_reader_next reads it through gzread, lnr_reader_next_dev in both ways it reads BGZF text (device inflate,
  * or gzread into the pinned staging buffer under LNR_READER_BGZF=0) and delivers the blocks lnr_reader_next delivers.  A record is a read as

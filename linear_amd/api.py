@@ -56,6 +56,19 @@ class LnrInflateStats(C.Structure):
     _fields_ = [("last", LnrInflateCounts), ("total", LnrInflateCounts)]
 
 
+GZIP_COUNTS = ("rounds", "members", "chunks", "candidates", "true_pieces", "false_candidates", "deflate_blocks", "compressed_bytes", "text_bytes",
+               "window_symbols", "gzread_bytes", "grown_rounds")
+GZIP_MS = ("find_ms", "measure_ms", "stitch_ms", "emit_ms", "chain_ms", "resolve_ms", "parse_ms", "upload_ms", "download_ms")
+
+
+class LnrGzipCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in GZIP_COUNTS] + [(k, C.c_double) for k in GZIP_MS]
+
+
+class LnrGzipStats(C.Structure):
+    _fields_ = [("last", LnrGzipCounts), ("total", LnrGzipCounts)]
+
+
 class LnrBamCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("records", "skipped", "reverse", "tiles", "repaired_tiles")] + [(k, C.c_double) for k in ("find_ms", "stitch_ms", "emit_ms")]
 
@@ -80,6 +93,7 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_writer_set_bgzf", "lnr_writer_bgzf_bytes_gpu", "lnr_writer_bgzf_eof", "lnr_writer_bgzf_stats",
            "lnr_writer_bam_header", "lnr_writer_format_bam", "lnr_writer_format_bam_gpu", "lnr_writer_format_bam_dev",
            "lnr_reader_gpu_open", "lnr_reader_next_dev", "lnr_reader_gpu_times", "lnr_reader_gpu_tile", "lnr_reader_gpu_inflate_stats",
+           "lnr_reader_gpu_gzip", "lnr_reader_gpu_gzip_stats", "lnr_gunzip_gpu",
            "lnr_reader_gpu_bam_stats", "lnr_reader_gpu_bam_tile", "lnr_reader_format",
            "lnr_writer_sort_begin", "lnr_writer_sort_finish", "lnr_writer_sort_next", "lnr_writer_sort_bai", "lnr_writer_sort_info_get", "lnr_writer_sort_end",
            "lnr_writer_sort_host", "lnr_writer_bai_host", "lnr_writer_sort_spill", "lnr_writer_sort_hold_info_get"]
@@ -140,6 +154,10 @@ def load_library() -> C.CDLL:
     lib.lnr_reader_next_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_u64p), C.POINTER(C.c_uint32)]
     lib.lnr_reader_gpu_times.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.lnr_reader_gpu_inflate_stats.argtypes = [C.c_void_p, C.POINTER(LnrInflateStats)]
+    lib.lnr_reader_gpu_gzip.argtypes = [C.c_void_p, C.c_int]
+    lib.lnr_reader_gpu_gzip_stats.argtypes = [C.c_void_p, C.POINTER(LnrGzipStats)]
+    lib.lnr_gunzip_gpu.argtypes = [C.c_int32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(LnrGzipStats),
+                                   C.c_char_p, C.c_size_t]
     lib.lnr_reader_gpu_tile.restype = C.c_uint32
     lib.lnr_reader_gpu_tile.argtypes = []
     lib.lnr_reader_gpu_bam_stats.argtypes = [C.c_void_p, C.POINTER(LnrBamStats)]
@@ -378,6 +396,27 @@ class Filter:
         return {k: getattr(st, k) for k, _ in LnrStats._fields_}
 
 
+def _gzip_stats(st) -> dict:
+    return {w: {k: getattr(getattr(st, w), k) for k, _ in LnrGzipCounts._fields_} for w in ("last", "total")}
+
+
+def gunzip_gpu(gz: bytes, text_cap: int, device: int = -1):
+    """Every member of the plain gzip bytes `gz` inflated on the device (lnr_gunzip_gpu): (text, stats).  text_cap = room for the text.
+    LNR_READER_GZ_CHUNK / LNR_READER_GZ_ROUND in the environment set the chunk and round sizes."""
+    lib = load_library()
+    out = np.zeros(max(int(text_cap), 1), np.uint8)
+    n = C.c_uint64()
+    st = LnrGzipStats()
+    err = C.create_string_buffer(512)
+    s = lib.lnr_gunzip_gpu(device, gz, len(gz), out.ctypes.data_as(C.POINTER(C.c_uint8)), int(text_cap), C.byref(n), C.byref(st), err, len(err))
+    if s != 0:
+        e = LnrError(s, lib.lnr_strerror(s).decode(), err.value.decode())
+        e.text = out[: n.value].tobytes()
+        e.stats = _gzip_stats(st)
+        raise e
+    return out[: n.value].tobytes(), _gzip_stats(st)
+
+
 class Reader:
     """FASTA / FASTQ (plain or gzip) or BAM (found by content) -> blocks in the ABI's layout (host code; no GPU needed)."""
 
@@ -433,6 +472,16 @@ class Reader:
         st = LnrInflateStats()
         self._ck(self.lib.lnr_reader_gpu_inflate_stats(self.h, C.byref(st)))
         return {w: {k: getattr(getattr(st, w), k) for k, _ in LnrInflateCounts._fields_} for w in ("last", "total")}
+
+    def gpu_gzip(self, on: bool = True) -> None:
+        """Plain gzip files (not BGZF) are inflated on the device, in parallel from DEFLATE block starts.  After gpu_open, before the first read."""
+        self._ck(self.lib.lnr_reader_gpu_gzip(self.h, 1 if on else 0))
+
+    def gpu_gzip_stats(self) -> dict:
+        """Plain gzip input: {"last": counts of the last next_dev, "total": of all calls} (the fields of lnr_gzip_counts)."""
+        st = LnrGzipStats()
+        self._ck(self.lib.lnr_reader_gpu_gzip_stats(self.h, C.byref(st)))
+        return _gzip_stats(st)
 
     @staticmethod
     def gpu_tile() -> int:

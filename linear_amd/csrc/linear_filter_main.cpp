@@ -69,6 +69,7 @@ lnr_status lnr_writer_format_bam_dev(lnr_writer *, const lnr_cords_dev *, const 
 lnr_status lnr_reader_gpu_open(lnr_reader *, int32_t, uint32_t) __attribute__((weak));
 lnr_status lnr_reader_next_dev(lnr_reader *, uint64_t, uint32_t, const uint8_t **, const uint64_t **, const uint64_t **, uint32_t *) __attribute__((weak));
 int lnr_reader_format(lnr_reader *) __attribute__((weak));
+lnr_status lnr_reader_gpu_gzip(lnr_reader *, int) __attribute__((weak));                // --gpu-gunzip
 // entry points only --sort uses
 lnr_status lnr_writer_sort_begin(lnr_writer *, uint64_t) __attribute__((weak));
 lnr_status lnr_writer_sort_finish(lnr_writer *, uint32_t, lnr_sort_info *) __attribute__((weak));
@@ -86,7 +87,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0, gpu_gunzip = 0;
     uint64_t sort_device_mem = 0, sort_host_mem = 0;      // --sort-device-mem / --sort-host-mem in bytes
     bool has_sort_device_mem = false, has_sort_host_mem = false;
     std::vector<int> devices;
@@ -130,6 +131,8 @@ static void usage() {
             "    --gpu-writer               format .sam / .apf text and encode .bam records on the first GPU in use instead of the writer's host threads {off}\n"
             "    --gpu-reader               parse the read files on the first GPU in use and keep the reads there: reader -> filter -> writer on device buffers {off}\n"
             "                               (one GPU; with --sam-seq it needs --gpu-writer: the read bases are not on the host)\n"
+            "    --gpu-gunzip               --gpu-reader: inflate plain gzip read files (.fastq.gz / .fa.gz, not BGZF) on the GPU, in parallel from DEFLATE\n"
+            "                               block starts, instead of through zlib on the host; needs --gpu-reader {off}\n"
             "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n"
             "    --bgzf                     compress the text on the GPU and write PREFIX.sam.gz / PREFIX.apf.gz (BGZF); needs --gpu-writer {off}\n"
             "    --sort                     sort the .bam / _pbsv.bam by coordinate on the GPU and write PREFIX.bam.bai next to it; needs -ot with 4 or 8 and\n"
@@ -164,6 +167,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         if (name == "gpu-writer") { o.gpu_writer = 1; continue; }                                  // a switch: takes no value
         if (name == "sam-seq") { o.sam_seq = 1; continue; }
         if (name == "gpu-reader") { o.gpu_reader = 1; continue; }
+        if (name == "gpu-gunzip") { o.gpu_gunzip = 1; continue; }
         if (name == "bgzf") { o.bgzf = 1; continue; }
         if (name == "sort") { o.sort = 1; continue; }
         size_t eq = name.find('=');
@@ -346,6 +350,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "\033[1;31mE:\033[0m -ot 4 / 8 (BAM output) is encoded and compressed on the GPU: it needs --gpu-writer (BAM on the writer's host threads is not built)\n");
         return 1;
     }
+    if (o.gpu_gunzip && !o.gpu_reader) { fprintf(stderr, "\033[1;31mE:\033[0m --gpu-gunzip inflates the read files on the GPU that parses them: it needs --gpu-reader\n"); return 1; }
     if (o.bgzf && !o.gpu_writer) { fprintf(stderr, "\033[1;31mE:\033[0m --bgzf compresses the text on the GPU that formats it: it needs --gpu-writer\n"); return 1; }
     if (o.thread < 1) o.thread = 1;
     if (o.gpus < 1) o.gpus = 1;
@@ -468,6 +473,7 @@ int main(int argc, char **argv) {
         std::string why;
         if (!lnr_filter_batch_dev || !lnr_cords_to_host || !lnr_writer_format_dev || !lnr_writer_format_seq_dev || !lnr_writer_format_bam_dev || !lnr_reader_gpu_open || !lnr_reader_next_dev)
             why = "no usable device: this library has no device form of the filter";
+        else if (o.gpu_gunzip && !lnr_reader_gpu_gzip) why = "--gpu-gunzip: this library has no device inflate of plain gzip";
         else if (G != 1) why = "the device chain runs on one GPU (--gpus 1)";
         else if (o.sam_seq && !o.gpu_writer) why = "with --sam-seq the reads stay on the device: add --gpu-writer";
         else {
@@ -515,6 +521,7 @@ int main(int argc, char **argv) {
             for (size_t f = 0; f < o.r_paths.size() && !failed; f++) {
                 if (lnr_reader_open(o.r_paths[f].c_str(), &cur) != LNR_OK) { cur = nullptr; fail("can't open read file " + o.r_paths[f]); break; }
                 if (lnr_reader_gpu_open(cur, o.devices[0], 3) != LNR_OK) { fail(std::string("--gpu-reader: ") + lnr_reader_error(cur)); break; }
+                if (o.gpu_gunzip && lnr_reader_gpu_gzip(cur, 1) != LNR_OK) { fail(std::string("--gpu-gunzip: ") + lnr_reader_error(cur)); break; }
                 for (;;) {
                     DBlock *b = nullptr;
                     if (!freeq.pop(b) || failed) break;

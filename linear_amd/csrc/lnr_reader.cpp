@@ -14,6 +14,7 @@
 #include "lnr_reader_hook.h"
 #include "lnr_inflate_hd.h"
 #include "lnr_bam_hd.h"
+#include "lnr_gunzip_hd.h"
 
 // Plain (not gzip) files take a PARALLEL path (f4's reason to exist: feed a GPU that filters 2 M reads/s): the file is mapped, one pass of
 // memchr finds the record boundaries of the next block (a FASTA record ends before the next '>' at a line start; a FASTQ record is taken as four
@@ -77,6 +78,15 @@ struct lnr_reader {
     uint64_t bam_ord = 0, bam_off = 0;
     std::vector<unsigned char> bam_tmp;
     lnr_bam_counts bam_last{}, bam_total{};
+    // plain gzip on the device (lnr_reader_gpu_gzip): the file is mapped at `map` with use_map false, as for BGZF.  gz_live: the rounds
+    // read the file from gz_pos (a member's header) or, inside a member, from bit gz_bit of the file.  The device text
+    // [gkeep_from, gkeep_from + gcarry) is what the last window left; text_made = text bytes the device has inflated so far (BGZF blocks
+    // included), so text_made - gcarry is the offset in the uncompressed stream at which a gzread stream would go on
+    std::string path;
+    bool started = false, gzp = false, gz_live = false, gz_in_member = false, gz_end = false, gz_failed = false;
+    uint64_t gz_pos = 0, gz_bit = 0, gz_mtext = 0, gkeep_from = 0, gcarry = 0, text_made = 0, gz_grow = 1;
+    uint32_t gz_hist = 0, gz_crc = 0;
+    lnr_rdgpu_gz_counts gzs_last{}, gzs_total{};
 
     bool fill() {
         if (eof) return false;
@@ -144,6 +154,39 @@ static bool bgzf_to_stream(lnr_reader *r) {
     return true;
 }
 
+// ---- plain gzip rounds (lnr_reader_gpu_gzip).  "Continue the serial stream at the first text byte the device path has not used up": a
+// member cannot be entered in its middle by zlib without its history, so a fresh gzread stream is opened and moved to the text offset with
+// gzseek -- which inflates the file once more from its start.  Accepted: the hand-over is rare (a FASTQ that leaves the four-line form, a
+// lnr_reader_next behind lnr_reader_next_dev).
+static bool gz_to_stream(lnr_reader *r) {
+    const uint64_t at = r->text_made - r->gcarry;
+    r->gz_live = false; r->gcarry = r->gkeep_from = 0;
+    gzFile nf = gzopen(r->path.c_str(), "rb");
+    if (!nf) { r->err = "cannot reopen " + r->path; return false; }
+    gzbuffer(nf, 1u << 20);
+    if (at && gzseek(nf, (z_off_t)at, SEEK_SET) < 0) { int e; r->err = std::string("moving the gzip stream to text offset ") + std::to_string(at) + ": " + gzerror(nf, &e); gzclose(nf); return false; }
+    if (r->f) gzclose(r->f);
+    r->f = nf;
+    r->pos = r->end = 0; r->eof = false; r->gz_done = false;
+    return true;
+}
+static lnr_status gz_fail(lnr_reader *r, uint32_t status, uint64_t off) {
+    snprintf(r->gerr, sizeof r->gerr, "gzip data at file offset %llu: %s", (unsigned long long)off, lnr_gz::status_text(status));
+    r->err = r->gerr; r->gz_failed = true;
+    return LNR_ERR_ARG;
+}
+// the member at gz_pos, or the end of the file's members.  LNR_OK, or the header's error
+static lnr_status gz_next_member(lnr_reader *r) {
+    while (!r->gz_in_member && !r->gz_end) {
+        if (r->gz_pos >= r->map_len) { r->gz_end = true; break; }
+        uint64_t data = 0;
+        const uint32_t st = lnr_gz::member_at(r->map, r->map_len, r->gz_pos, r->gz_pos == 0, &data);
+        if (st == lnr_gz::PASS_OVER) { r->gz_end = true; break; }
+        if (st) return gz_fail(r, st, r->gz_pos);
+        r->gz_bit = data * 8; r->gz_in_member = true; r->gz_hist = 0; r->gz_crc = 0; r->gz_mtext = 0;
+    }
+    return LNR_OK;
+}
 // ---- BAM (format 3; every decision from lnr_bam_hd.h).  The records come through the gzread stream one after the other.
 static lnr_status bam_fail(lnr_reader *r, uint64_t ord, uint64_t off, const char *why) {
     char m[200];
@@ -224,6 +267,7 @@ lnr_status lnr_reader_open(const char *path, lnr_reader **out) {
     if (!r->f) { delete r; return LNR_ERR_ARG; }
     gzbuffer(r->f, 1u << 20);
     r->buf.resize(4u << 20);
+    r->path = path;
     if (!getenv("LNR_READER_SERIAL")) {
         int fd = open(path, O_RDONLY);
         struct stat st;
@@ -464,11 +508,20 @@ lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64
     *n_out = 0;
     off[0] = 0;
     r->ids.clear(); r->id_off.assign(1, 0);
+    r->started = true;
+    if (r->gz_live) {
+        if (r->gz_failed) { r->err = r->gerr; return LNR_ERR_ARG; }
+        if (r->text_made == 0) r->gz_live = false;                    // nothing was read on the device: r->f stands at the start of the file
+        else if (!gz_to_stream(r)) return LNR_ERR_ARG;
+    }
     if (r->bgzf) {
         if (r->bpos == 0 && r->chain.empty()) r->bgzf = false;       // nothing was read on the device: r->f stands at the start of the file, as ever
         else if (!bgzf_to_stream(r)) return LNR_ERR_ARG;              // next_dev has read ahead on the device: the stream goes on where it stopped
     }
-    return next_from(r, dst, dst_cap, off, max_reads, n_out, 0, 0, false);
+    const uint64_t gz0 = r->gz_bytes;
+    const lnr_status s = next_from(r, dst, dst_cap, off, max_reads, n_out, 0, 0, false);
+    if (r->gzp) r->gzs_total.gzread_bytes += r->gz_bytes - gz0;      // (the total counts what this entry point read through gzread, too)
+    return s;
 }
 
 // ---- the GPU twin: the same blocks, parsed on the device into device memory (lnr_reader_kernels.hip behind lnr_reader_hook.h)
@@ -508,6 +561,64 @@ lnr_status lnr_reader_gpu_inflate_stats(const lnr_reader *r, lnr_inflate_stats *
     return LNR_OK;
 }
 
+static_assert(sizeof(lnr_gzip_counts) == sizeof(lnr_rdgpu_gz_counts), "lnr_rdgpu_gz_counts has the layout of lnr_gzip_counts");
+static void gz_counts_out(lnr_gzip_counts &o, const lnr_rdgpu_gz_counts &c) { memcpy(&o, &c, sizeof o); }
+
+lnr_status lnr_reader_gpu_gzip(lnr_reader *r, int on) {
+    if (!r) return LNR_ERR_ARG;
+    if (!r->gpu) { r->err = "lnr_reader_gpu_gzip: lnr_reader_gpu_open has not been called on this reader"; return LNR_ERR_ARG; }
+    if (r->started) { r->err = "lnr_reader_gpu_gzip: the reader has been read from"; return LNR_ERR_ARG; }
+    if (!lnr_rdgpu_gzip_round) { r->err = "lnr_reader_gpu_gzip: this library was linked without its device half"; return LNR_ERR_NO_DEVICE; }
+    if (!on) {
+        if (r->gz_live) { r->gz_live = false; if (r->map) munmap((void *)r->map, r->map_len); r->map = nullptr; r->map_len = 0; }
+        r->gzp = false;
+        return LNR_OK;
+    }
+    if (r->gzp) return LNR_OK;
+    if (getenv("LNR_READER_SERIAL") || (getenv("LNR_READER_BGZF") && atoi(getenv("LNR_READER_BGZF")) == 0)) return LNR_OK;   // the file is read as any gzip file
+    r->gzp = true;
+    if (r->bgzf || r->use_map || r->map) return LNR_OK;              // BGZF keeps precedence (the rounds take over at a member that is not BGZF); plain text
+    int fd = open(r->path.c_str(), O_RDONLY);
+    struct stat st;
+    unsigned char magic[2] = {0, 0};
+    if (fd >= 0 && fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size >= 10 && (uint64_t)st.st_size <= (1ULL << 40) && pread(fd, magic, 2, 0) == 2 &&
+        magic[0] == 0x1f && magic[1] == 0x8b) {
+        void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (m != MAP_FAILED) {
+            r->map = (const unsigned char *)m; r->map_len = (size_t)st.st_size; (void)madvise(m, r->map_len, MADV_SEQUENTIAL);
+            r->gz_live = true; r->gz_pos = 0;
+        }
+    }
+    if (fd >= 0) close(fd);
+    return LNR_OK;
+}
+
+lnr_status lnr_reader_gpu_gzip_stats(const lnr_reader *r, lnr_gzip_stats *out) {
+    if (!r || !out || !r->gpu) return LNR_ERR_ARG;
+    gz_counts_out(out->last, r->gzs_last); gz_counts_out(out->total, r->gzs_total);
+    return LNR_OK;
+}
+
+// plain gzip over a host buffer: the stages of the reader's gzip rounds, no parse
+lnr_status lnr_gunzip_gpu(int32_t device, const uint8_t *gz, uint64_t size, uint8_t *text, uint64_t text_cap, uint64_t *text_size, lnr_gzip_stats *stats,
+                          char *err, size_t err_cap) {
+    char local[256] = "";
+    if (!err || !err_cap) { err = local; err_cap = sizeof local; }
+    err[0] = 0;
+    if ((!gz && size) || (!text && text_cap) || !text_size) { snprintf(err, err_cap, "lnr_gunzip_gpu: null argument"); return LNR_ERR_ARG; }
+    *text_size = 0;
+    if (stats) *stats = lnr_gzip_stats{};
+    if (!lnr_rdgpu_gunzip) { snprintf(err, err_cap, "no usable device %d: this library was linked without its device half", (int)device); return LNR_ERR_NO_DEVICE; }
+    lnr_rdgpu_gz_counts last{}, total{};
+    uint64_t bad_off = 0;
+    uint32_t bad = 0;
+    const int s = lnr_rdgpu_gunzip(device, gz, size, text, text_cap, text_size, &last, &total, &bad_off, &bad, err, err_cap);
+    if (stats) { gz_counts_out(stats->last, last); gz_counts_out(stats->total, total); }
+    if (s) return (lnr_status)s;
+    if (bad) { snprintf(err, err_cap, "gzip data at file offset %llu: %s", (unsigned long long)bad_off, lnr_gz::status_text(bad)); return LNR_ERR_ARG; }
+    return LNR_OK;
+}
+
 // Windows of text go to the device until the block is full, the file ends or the four-line FASTQ form breaks (hand-over: the serial parser
 // takes the rest of the file, its records are uploaded).  LNR_READER_GPU_WINDOW = bytes of text per window (default 256 MiB; a window that
 // holds no whole record is doubled): block boundaries do not depend on it.
@@ -525,6 +636,8 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
     r->ids.clear(); r->id_off.assign(1, 0);
     r->ist_last = lnr_inflate_counts{};
     r->bam_last = lnr_bam_counts{};
+    r->gzs_last = lnr_rdgpu_gz_counts{};
+    r->started = true;
     if (r->bam_failed) return LNR_ERR_ARG;
     const uint64_t gz0 = r->gz_bytes;
     struct StatsAtExit {                                          // the counts of this call join the totals however it ends
@@ -539,6 +652,12 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
             lnr_bam_counts &bl = r->bam_last, &bt = r->bam_total;
             bt.records += bl.records; bt.skipped += bl.skipped; bt.reverse += bl.reverse; bt.tiles += bl.tiles; bt.repaired_tiles += bl.repaired_tiles;
             bt.find_ms += bl.find_ms; bt.stitch_ms += bl.stitch_ms; bt.emit_ms += bl.emit_ms;
+            if (r->gzp) {
+                double ms5[5] = {0, 0, 0, 0, 0};
+                lnr_rdgpu_times(r->gpu, ms5);
+                r->gzs_last.gzread_bytes = r->gz_bytes - gz0; r->gzs_last.parse_ms = ms5[1] + ms5[2] + ms5[3]; r->gzs_last.download_ms = ms5[4];
+                lnr_rdgpu_gz_add(&r->gzs_total, &r->gzs_last);
+            }
         }
     } stats_at_exit{r, gz0};
     uint64_t wcap = 256ULL << 20, grow = 1, used = 0;
@@ -577,6 +696,110 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
         const unsigned char *text = nullptr;
         uint64_t len = 0, lead = 0;
         bool eof = false;
+        if (r->gz_live) {                                         // plain gzip: rounds of the member inflated on the device behind what the last window left
+            if (r->gz_failed) { if (n) break; r->err = r->gerr; return LNR_ERR_ARG; }
+            const uint64_t chunk = lnr_gz::env_bytes("LNR_READER_GZ_CHUNK", 128ULL << 10, 1024, 1ULL << 30), round = lnr_gz::env_bytes("LNR_READER_GZ_ROUND", 64ULL << 20, 1024, 1ULL << 31);
+            constexpr uint64_t TEXT_MAX = (1ULL << 30) - 65536;
+            bool stuck = false;
+            if (lnr_status s = gz_next_member(r)) { if (n) break; return s; }
+            while (!r->gz_end && !r->gz_failed && r->gcarry < want && !stuck) {
+                const uint64_t rb = r->gz_bit >> 3;
+                if (rb >= r->map_len) { gz_fail(r, lnr_inf::E_INPUT_END, r->map_len); break; }      // the file ends behind a member's header
+                if (r->gcarry >= TEXT_MAX) { stuck = true; break; }
+                uint64_t rsize = want - r->gcarry + 2 * chunk;            // text is seldom smaller than its compressed bytes: no more of them than text is wanted
+                if (rsize > round) rsize = round;
+                if (rsize > (1ULL << 31) / r->gz_grow) rsize = 1ULL << 31; else rsize *= r->gz_grow;
+                const uint64_t clen = r->map_len - rb < rsize ? r->map_len - rb : rsize;
+                lnr_rdgpu_gzip job{};
+                job.comp = r->map + rb; job.comp_len = clen; job.start_bit = (uint32_t)(r->gz_bit & 7); job.hist = r->gz_hist; job.chunk = chunk;
+                job.keep_from = r->gkeep_from; job.carry = r->gcarry; job.text_cap = TEXT_MAX - r->gcarry; job.threads = r->threads;
+                lnr_rdgpu_gzip_result gr{};
+                if (int s = lnr_rdgpu_gzip_round(r->gpu, &job, &gr, r->gerr, sizeof r->gerr)) { r->gz_failed = true; return gfail(s); }
+                lnr_rdgpu_gz_counts c = gr.counts;
+                if (gr.status) { lnr_rdgpu_gz_add(&r->gzs_last, &c); gz_fail(r, gr.status, rb + gr.bad_off); break; }
+                if (!gr.pieces) {                                 // no block completed
+                    c.grown_rounds = 1;
+                    lnr_rdgpu_gz_add(&r->gzs_last, &c);
+                    if (gr.stop == lnr_gz::AT_BUDGET) { stuck = true; break; }                     // the device text is full: what it holds is parsed first
+                    if (rb + clen >= r->map_len) { gz_fail(r, lnr_inf::E_INPUT_END, rb); break; }
+                    if (rsize >= (1ULL << 31)) { r->err = "a DEFLATE block is longer than the reader's staging limit"; return LNR_ERR_LIMIT; }
+                    r->gz_grow *= 2;
+                    continue;
+                }
+                r->gz_grow = 1;
+                r->gkeep_from = 0; r->gcarry += gr.text; r->text_made += gr.text;
+                r->gz_bit = rb * 8 + gr.end_bit;
+                r->gz_crc = lnr_inf::crc_combine(r->gz_crc, gr.crc, gr.text);
+                r->gz_hist = r->gz_hist + gr.text > lnr_gz::WIN ? lnr_gz::WIN : (uint32_t)(r->gz_hist + gr.text);
+                r->gz_mtext += gr.text;
+                c.compressed_bytes = ((r->gz_bit + 7) >> 3) - rb;
+                if (gr.stop == lnr_gz::AT_FINAL) {                // the trailer; then the next member, or the end of the file
+                    uint64_t next = 0;
+                    const uint32_t st = lnr_gz::check_trailer(r->map, r->map_len, r->gz_bit, r->gz_crc, r->gz_mtext, &next);
+                    if (st) { lnr_rdgpu_gz_add(&r->gzs_last, &c); gz_fail(r, st, (r->gz_bit + 7) >> 3); break; }   // (the text in front of it is delivered, as gzread delivers it)
+                    c.members = 1;
+                    r->gz_in_member = false; r->gz_pos = next;
+                    lnr_rdgpu_gz_add(&r->gzs_last, &c);
+                    if (gz_next_member(r)) break;
+                    continue;
+                }
+                lnr_rdgpu_gz_add(&r->gzs_last, &c);
+                if (gr.stop == lnr_gz::AT_BUDGET) { stuck = true; break; }
+            }
+            const uint64_t tl = r->gcarry;
+            const bool gend = r->gz_end || r->gz_failed;
+            if (!tl) {
+                if (r->gz_failed) { if (n) break; r->err = r->gerr; return LNR_ERR_ARG; }
+                if (r->gz_end) break;
+                r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT;
+            }
+            lnr_rdgpu_bgzf job{};                                 // no block to inflate: the parse of the device text
+            job.keep_from = r->gkeep_from; job.carry = tl;
+            lnr_rdgpu_window w{};
+            w.fmt = r->format; w.eof = gend; w.slot = slot; w.threads = r->threads;
+            w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
+            lnr_rdgpu_result res{};
+            lnr_rdgpu_bgzf_result br{};
+            if (int s = lnr_rdgpu_parse_bgzf(r->gpu, &job, &w, &res, &br, r->gerr, sizeof r->gerr)) { r->gz_failed = true; return gfail(s); }
+            if (r->format == 0 && w.fmt == 3) {                   // "BAM\1" in a plain gzip file: read through gzread, as without the switch
+                r->gkeep_from = 0;
+                if (!gz_to_stream(r)) return LNR_ERR_ARG;
+                continue;
+            }
+            if (r->format == 0 && br.first >= 0) r->format = w.fmt;
+            bool handover = br.first >= 0 && !br.parsed;
+            if (br.parsed) {
+                for (uint64_t k = 0; k < res.n; k++) {
+                    r->ids.insert(r->ids.end(), br.ids + br.id_off[k], br.ids + br.id_off[k] + br.id_len[k]);
+                    r->ids.push_back('\0');
+                    r->id_off.push_back(r->ids.size());
+                }
+                n += (uint32_t)res.n; used += res.bases;
+                r->records += res.n; r->bases += res.bases;
+                r->g_recs += res.n; r->g_text += res.consumed;
+                handover = res.handover != 0;
+            }
+            const uint64_t adv = br.lead + (br.parsed ? res.consumed : 0);
+            r->gkeep_from = br.parsed ? res.consumed : br.lead;
+            r->gcarry = tl - adv;
+            if (handover) {
+                if (r->gz_failed) { r->err = r->gerr; return LNR_ERR_ARG; }
+                if (!gz_to_stream(r)) return LNR_ERR_ARG;
+                r->gpu_serial = true;
+                break;
+            }
+            if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
+            if (res.full) { full = true; break; }
+            if (gend && r->gcarry == 0) { if (r->gz_failed && !n) { r->err = r->gerr; return LNR_ERR_ARG; } break; }
+            if (br.parsed && res.n == 0) {
+                if (stuck || gend) {
+                    if (r->gz_failed) { r->err = r->gerr; return LNR_ERR_ARG; }
+                    r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT;
+                }
+                grow *= 2;
+            }
+            continue;
+        }
         if (r->bgzf) {                                            // a run of whole BGZF blocks, inflated on the device behind what the last window left
             if (r->bfailed) { r->err = r->gerr; return LNR_ERR_ARG; }
             std::vector<lnr_rdgpu_bgzf_blk> tab;
@@ -598,9 +821,19 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
                 r->bpos += size;
             }
             if (!r->bend && !r->bstop && r->bpos >= r->map_len) r->bend = true;
+            // with lnr_reader_gpu_gzip the gzip rounds take over at a member that is not BGZF, where gzread takes over without it
+            auto to_rounds = [&]() {
+                r->bgzf = false; r->chain.clear(); r->bskip = 0;
+                r->gz_live = true; r->gz_pos = r->bpos; r->gz_in_member = false; r->gz_end = false;
+                r->gkeep_from = r->bkeep_from; r->gcarry = r->bcarry; r->bkeep_from = r->bcarry = 0;
+            };
             if (!tl) {
                 if (r->bend) break;
-                if (r->bstop) { if (!bgzf_to_stream(r)) return LNR_ERR_ARG; continue; }
+                if (r->bstop) {
+                    if (r->gzp && r->format != 3) { to_rounds(); continue; }
+                    if (!bgzf_to_stream(r)) return LNR_ERR_ARG;
+                    continue;
+                }
             }
             if (tl + 65536 > (1ULL << 30) && tl < want) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
             lnr_rdgpu_bgzf job{};
@@ -658,6 +891,7 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
             if (int s = lnr_rdgpu_parse_bgzf(r->gpu, &job, &w, &res, &br, r->gerr, sizeof r->gerr)) { r->bfailed = true; return gfail(s); }
             if (br.bad_status) return bad_block(br.bad_blk, br.bad_status);
             r->ist_last.blocks += tab.size(); r->ist_last.compressed_bytes += job.comp_len; r->ist_last.text_bytes += fresh;
+            r->text_made += fresh;
             if (r->format == 0 && w.fmt == 3) {                   // "BAM\1": the text stays on the device whole, the next pass reads it as records
                 r->format = 3; r->bkeep_from = 0; r->bcarry = tl;
                 continue;
@@ -676,7 +910,8 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
                 handover = res.handover != 0;
             }
             advance(br.lead, br.parsed ? res.consumed : 0, br.parsed ? res.consumed : br.lead);
-            if (handover || r->bstop) {                           // the stream goes on at the first byte the device has not used up
+            if (r->bstop && !handover && r->gzp) to_rounds();
+            else if (handover || r->bstop) {                      // the stream goes on at the first byte the device has not used up
                 if (!bgzf_to_stream(r)) return LNR_ERR_ARG;
                 if (handover) { r->gpu_serial = true; break; }
             }

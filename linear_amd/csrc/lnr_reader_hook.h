@@ -59,6 +59,29 @@ struct lnr_rdgpu_bam_result {
 int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, const lnr_rdgpu_bam_in *in, lnr_rdgpu_result *r,
                         lnr_rdgpu_bam_result *br, char *err, size_t err_cap) __attribute__((weak));
 uint32_t lnr_rdgpu_bam_tile(void) __attribute__((weak));
+// ---- plain gzip input (lnr_gunzip_hd.h): counts of one round / of a call, in the layout of lnr_gzip_counts
+struct lnr_rdgpu_gz_counts {
+    uint64_t rounds, members, chunks, candidates, true_pieces, false_candidates, deflate_blocks, compressed_bytes, text_bytes, window_symbols, gzread_bytes, grown_rounds;
+    double find_ms, measure_ms, stitch_ms, emit_ms, chain_ms, resolve_ms, parse_ms, upload_ms, download_ms;
+};
+// one round for the reader: comp = the mapped file from the byte that holds the member's next bit (start_bit 0..7 into it), comp_len bytes
+// of it; hist bytes of history exist in the window the device keeps (0: a member starts); the device text [keep_from, keep_from + carry) is
+// what the last window left.  status != 0: the data is bad at comp + bad_off.  pieces == 0: no block completed (stop 2: the bytes end inside
+// a block; 3: the block's text is more than text_cap) and nothing has changed; else moved = 1: the device text is now [0, carry + text),
+// end_bit = the next bit of the member (from comp), stop 1 = a final block was passed, crc = CRC32 of the round's text.
+struct lnr_rdgpu_gzip { const uint8_t *comp; uint64_t comp_len; uint32_t start_bit, hist; uint64_t chunk, keep_from, carry, text_cap; uint32_t threads, pad; };
+struct lnr_rdgpu_gzip_result { uint32_t status, stop, pieces, crc, moved, pad; uint64_t bad_off, end_bit, text; lnr_rdgpu_gz_counts counts; };
+int lnr_rdgpu_gzip_round(lnr_rdgpu *g, const lnr_rdgpu_gzip *job, lnr_rdgpu_gzip_result *out, char *err, size_t err_cap) __attribute__((weak));
+static inline void lnr_rdgpu_gz_add(lnr_rdgpu_gz_counts *t, const lnr_rdgpu_gz_counts *c) {      // the one place that knows the fields: 12 counts, 9 times
+    uint64_t *tu = &t->rounds; const uint64_t *cu = &c->rounds;
+    for (int i = 0; i < 12; i++) tu[i] += cu[i];
+    double *td = &t->find_ms; const double *cd = &c->find_ms;
+    for (int i = 0; i < 9; i++) td[i] += cd[i];
+}
+// every member of gz[0, size) -> text (host buffers).  0 with *bad_status != 0: the stream is bad at compressed offset *bad_off
+// (lnr_gz::status_text), *text_size = the text of the rounds before it
+int lnr_rdgpu_gunzip(int32_t device, const uint8_t *gz, uint64_t size, uint8_t *text, uint64_t text_cap, uint64_t *text_size, lnr_rdgpu_gz_counts *last,
+                     lnr_rdgpu_gz_counts *total, uint64_t *bad_off, uint32_t *bad_status, char *err, size_t err_cap) __attribute__((weak));
 void lnr_rdgpu_inflate_times(const lnr_rdgpu *g, double *ms2) __attribute__((weak));   // last block: inflate kernel, header gather (HIP events)
 int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, size_t err_cap) __attribute__((weak));
 // makes block `slot` hold dst_cap bases and max_reads + 1 offsets; hands out its device arrays and the host copy of the offsets

@@ -29,6 +29,7 @@
 #endif
 #include "lnr_inflate_hd.h"
 #include "lnr_bam_hd.h"
+#include "lnr_gunzip_hd.h"
 
 namespace {
 
@@ -384,6 +385,8 @@ double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono:
 struct Buf { void *p = nullptr; u64 cap = 0; };
 struct Pin { void *p = nullptr; u64 cap = 0; };
 struct Block { Buf reads, off; Pin h_off; };
+struct GzDev;
+void gz_free(GzDev *G);
 
 }  // namespace
 
@@ -407,6 +410,7 @@ struct lnr_rdgpu {
     hipEvent_t ev_b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_i[4] = {nullptr, nullptr, nullptr, nullptr};
     double ms_inf[2] = {0, 0};
+    GzDev *gz = nullptr;                        // plain gzip rounds (lnr_rdgpu_gzip_round): buffers and the window, on g->st
 };
 
 namespace {
@@ -456,6 +460,7 @@ void free_all(lnr_rdgpu *g) {
     for (hipEvent_t e : g->ev_up) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : g->ev_m) if (e) (void)hipEventDestroy(e);
+    if (g->gz) gz_free(g->gz);
     if (g->st) (void)hipStreamDestroy(g->st);
     if (g->s_copy) (void)hipStreamDestroy(g->s_copy);
 }
@@ -678,18 +683,11 @@ static int inflate_window(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, const lnr_rdg
     return 0;
 }
 
-int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
-                         char *err, size_t err_cap) {
-    *br = lnr_rdgpu_bgzf_result{};
-    br->first = -1;
-    *r = lnr_rdgpu_result{};
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
+// measure / scan / emit over the tlen bytes of text at g->text (its first hl bytes lie at g->h_head), the header bytes of the taken records
+// gathered: what follows the inflate of a BGZF window, and the rounds of a plain gzip file.  The caller has set the device.
+static int parse_device_text(lnr_rdgpu *g, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br, u64 tlen, u64 hl, char *err, size_t err_cap) {
     int s;
-    u64 tlen = job->carry + job->new_text, hl = 0;
     float f = 0;
-    if ((s = inflate_window(g, job, w, &br->bad_blk, &br->bad_status, &hl, err, err_cap)) || br->bad_status) return s;
     u8 *d_text = (u8 *)g->text.p;
     if (w->fmt == 0 && lnr_bam::is_magic((const u8 *)g->h_head.p, hl)) { w->fmt = 3; br->first = 'B'; return 0; }     // BAM: lnr_rdgpu_parse_bam reads this text
     // ---- a window starts at a record start: white space in front of it (the start of the file) is skipped
@@ -747,6 +745,20 @@ int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_wind
             if (br->id_len[k] > r->hdr[2 * k + 1] - r->hdr[2 * k]) { snprintf(err, err_cap, "internal: gathered header of record %llu", (unsigned long long)k); return -8; }
     }
     return 0;
+}
+
+int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
+                         char *err, size_t err_cap) {
+    *br = lnr_rdgpu_bgzf_result{};
+    br->first = -1;
+    *r = lnr_rdgpu_result{};
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    RD_CK(hipSetDevice(g->device), -3);
+    int s;
+    u64 tlen = job->carry + job->new_text, hl = 0;
+    if ((s = inflate_window(g, job, w, &br->bad_blk, &br->bad_status, &hl, err, err_cap)) || br->bad_status) return s;
+    return parse_device_text(g, w, r, br, tlen, hl, err, err_cap);
 }
 
 int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, const lnr_rdgpu_bam_in *in, lnr_rdgpu_result *r,
@@ -935,3 +947,363 @@ void lnr_rdgpu_close(lnr_rdgpu *g) {
 }
 
 }  // extern "C"
+
+// ---- plain gzip: one member inflated in parallel from DEFLATE block starts.  Every decision comes from lnr_gunzip_hd.h.
+// A round = a run of compressed bytes with a known start bit and the 32 KiB of text in front of it, cut into chunks.  Separate launches on
+// one stream, no kernel waits for another workgroup:
+//   k_gz_find      one wave per chunk (not chunk 0: it holds the round's start), lane = bit offset: the first offset that passes
+//                  lnr_gz::is_dynamic_start, by ballot and first lane; a chunk without one ends at its last bit
+//   k_gz_measure   one wave per chunk that has a candidate (and chunk 0): the counting decode up to the first boundary at or past the next candidate
+//   k_gz_stitch    one wave, in order (lnr_gz::stitch_round): which candidates a true piece's decode lands on exactly, counting on where it
+//                  overshoots; the true pieces with their text offsets, the round's end bit and text, cut at the text cap
+//   k_gz_emit      one wave per true piece: the decode again, into one u16 per text byte (lane 0 stores literals, all lanes copy a match or
+//                  a stored run: the store / fence / load pattern of WaveSink)
+//   k_gz_chain     one wave, pieces in order: the last 32 Ki symbols in front of every piece start resolved in place, 64 lanes side by side
+//   k_gz_resolve   one wave per tile of text: every symbol through its piece's window into bytes; the tile's CRC32 from 64 slices
+//   k_gz_keep      the last 32 KiB of (old window, round text): the next round's window
+namespace {
+
+using lnr_gz::u16;
+constexpr u32 GZ_TILE = 16384;                 // text bytes per wave of k_gz_resolve (64 CRC slices of 256 bytes)
+
+__device__ __forceinline__ u64 gz_uniform(u64 v) {
+    return (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)v) | ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(v >> 32)) << 32);
+}
+
+__global__ __launch_bounds__(64) void k_gz_find(const u8 *comp, u64 clen, u64 start_bit, u64 chunk, u32 nchunk, u64 *cand) {
+    const u32 c = blockIdx.x, lane = threadIdx.x;
+    if (c >= nchunk) return;
+    u64 found = lnr_gz::NONE;
+    if (c) {
+        u64 lo, hi;
+        lnr_gz::chunk_bits(start_bit, clen, chunk, c, lo, hi);
+        for (u64 g = lo; g < hi; g += 64) {
+            const u64 b = g + lane;
+            const u64 m = __ballot(b < hi && lnr_gz::is_dynamic_start(comp, clen, b));
+            if (m) { found = g + ctz(m); break; }
+        }
+    }
+    if (lane == 0) cand[c] = found;
+}
+
+__global__ __launch_bounds__(64) void k_gz_measure(const u8 *comp, u64 clen, u64 start_bit, const u64 *cand, u32 nchunk, lnr_gz::Meas *meas) {
+    __shared__ lnr_inf::Tables T;
+    const u32 c = blockIdx.x;
+    if (c >= nchunk || (c && cand[c] == lnr_gz::NONE)) return;
+    const u32 nc = lnr_gz::next_cand(cand, nchunk, c + 1);
+    const u64 from = gz_uniform(c ? cand[c] : start_bit), stop = gz_uniform(nc < nchunk ? cand[nc] : lnr_gz::NONE);
+    lnr_gz::CountSink cs;
+    const lnr_gz::Meas m = lnr_gz::decode_chunk(comp, clen, from, stop, lnr_gz::NONE, cs, T);
+    if (threadIdx.x == 0) meas[c] = m;
+}
+
+__global__ __launch_bounds__(64) void k_gz_stitch(const u8 *comp, u64 clen, u64 start_bit, const u64 *cand, const lnr_gz::Meas *meas, u32 nchunk, u64 text_cap,
+                                                  lnr_gz::Piece *pieces, lnr_gz::Round *out) {
+    __shared__ lnr_inf::Tables T;
+    const lnr_gz::Round R = lnr_gz::stitch_round(comp, clen, start_bit, cand, meas, nchunk, text_cap, T, pieces, threadIdx.x == 0);
+    if (threadIdx.x == 0) *out = R;
+}
+
+struct WaveSymSink {
+    u16 *sym; u32 lane;
+    __device__ void lit(u64 pos, u8 b) { if (lane == 0) sym[pos] = b; }
+    __device__ void match(u64 pos, u32 len, u32 dist) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        for (u32 i = lane; i < len; i += 64) sym[pos + i] = lnr_gz::sym_copy(sym, pos, dist, i);
+    }
+    __device__ void stored(u64 pos, const u8 *src, u32 n) { for (u32 i = lane; i < n; i += 64) sym[pos + i] = src[i]; }
+};
+
+// bad[p] != 0: the second decode of piece p did not end where the first one did (cannot happen: both are the same function of the same bytes)
+__global__ __launch_bounds__(64) void k_gz_emit(const u8 *comp, u64 clen, const lnr_gz::Piece *pieces, u32 npieces, u16 *sym, u64 text, u32 *bad) {
+    __shared__ lnr_inf::Tables T;
+    const u32 p = blockIdx.x;
+    if (p >= npieces) return;
+    lnr_gz::Piece P = pieces[p];
+    P.start_bit = gz_uniform(P.start_bit); P.end_bit = gz_uniform(P.end_bit); P.text_off = gz_uniform(P.text_off); P.text = gz_uniform(P.text);
+    u32 b = 1;
+    if (P.text_off <= text && P.text <= text - P.text_off) {
+        WaveSymSink o{sym + P.text_off, threadIdx.x};
+        const lnr_gz::Meas E = lnr_gz::decode_chunk(comp, clen, P.start_bit, P.end_bit, P.text, o, T);
+        b = (E.end_bit != P.end_bit || E.text != P.text) ? 1u : 0u;
+    }
+    if (threadIdx.x == 0) bad[p] = b;
+}
+
+struct GzChain { u64 win_syms; u32 bad_piece, status; };
+
+__global__ __launch_bounds__(64) void k_gz_chain(const lnr_gz::Piece *pieces, u32 npieces, u16 *sym, u64 text, const u8 *win, u32 hist, const u32 *bad, GzChain *out) {
+    const u32 lane = threadIdx.x;
+    u64 refs = 0;
+    u32 status = lnr_inf::OK, bad_piece = 0;
+    for (u32 p = 0; p < npieces && status == lnr_inf::OK; p++) {
+        lnr_gz::Piece P = pieces[p];
+        P.text_off = gz_uniform(P.text_off); P.text = gz_uniform(P.text);
+        if (bad[p] || P.text_off > text || P.text > text - P.text_off) { status = lnr_inf::E_TABLE; bad_piece = p; break; }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");             // what other lanes resolved in the pieces before
+        u32 fail = 0;
+        for (u64 t = lnr_gz::chain_from(P) + lane; t < P.text_off + P.text; t += 64) {
+            const u32 was = sym[t];
+            const int v = lnr_gz::resolve_sym(sym, P.text_off, t, win, hist);
+            if (v < 0) fail = 1; else { sym[t] = (u16)v; refs += was >= 256; }
+        }
+        if (__ballot(fail)) { status = lnr_inf::E_DISTANCE; bad_piece = p; }
+    }
+    for (int d = 32; d; d >>= 1) refs += (u64)(u32)__shfl_xor((int)(u32)refs, d, 64) | ((u64)(u32)__shfl_xor((int)(u32)(refs >> 32), d, 64) << 32);
+    if (lane == 0) { GzChain o; o.win_syms = refs; o.bad_piece = bad_piece; o.status = status; *out = o; }
+}
+
+struct GzTile { u32 crc, refs, bad, pad; };
+
+__global__ __launch_bounds__(64) void k_gz_resolve(const lnr_gz::Piece *pieces, u32 npieces, const u16 *sym, u64 text, const u8 *win, u32 hist, u8 *out, GzTile *tiles) {
+    const u32 lane = threadIdx.x;
+    const u64 t0 = (u64)blockIdx.x * GZ_TILE, t1 = t0 + GZ_TILE < text ? t0 + GZ_TILE : text;
+    if (t0 >= text || !npieces) return;
+    u32 lo = 0, hi = npieces - 1;                                           // the last piece whose text starts at or in front of t0
+    while (lo < hi) { const u32 mid = (lo + hi + 1) / 2; if (pieces[mid].text_off <= t0) lo = mid; else hi = mid - 1; }
+    u32 p = lo, refs = 0, fail = 0;
+    for (u64 g = t0; g < t1; g += 64) {
+        while (p + 1 < npieces && pieces[p + 1].text_off <= g) p++;
+        const u64 t = g + lane;
+        if (t < t1) {
+            u32 q = p;
+            while (q + 1 < npieces && pieces[q + 1].text_off <= t) q++;
+            const u32 was = sym[t];
+            const int v = lnr_gz::resolve_sym(sym, pieces[q].text_off, t, win, hist);
+            if (v < 0) fail = 1; else out[t] = (u8)v;
+            refs += was >= 256;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");                 // the CRC slices read what other lanes stored
+    const u64 n = t1 - t0, S = (n + 63) / 64, a = lane * S < n ? lane * S : n, e = a + S < n ? a + S : n;
+    u32 x = lnr_inf::crc_shift(lnr_inf::crc_of(out + t0 + a, e - a), n - e);
+    for (int d = 32; d; d >>= 1) { x ^= (u32)__shfl_xor((int)x, d, 64); refs += (u32)__shfl_xor((int)refs, d, 64); }
+    const u64 anyfail = __ballot(fail);
+    if (lane == 0) { GzTile o; o.crc = x; o.refs = refs; o.bad = anyfail ? 1u : 0u; o.pad = 0; tiles[blockIdx.x] = o; }
+}
+
+__global__ __launch_bounds__(256) void k_gz_keep(const u8 *old_win, const u8 *text, u64 n, u8 *new_win) {
+    const u32 j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= lnr_gz::WIN) return;
+    new_win[j] = n >= lnr_gz::WIN ? text[n - lnr_gz::WIN + j] : j + n < lnr_gz::WIN ? old_win[j + n] : text[j + n - lnr_gz::WIN];
+}
+
+// the buffers and the stream of the gzip rounds
+struct GzDev {
+    hipStream_t st = nullptr;
+    bool own_stream = true;                    // (the reader's rounds run on the reader's stream)
+    hipEvent_t ev[8] = {};
+    Buf comp, cand, meas, pieces, round, sym, bad, chain, tiles, text, win[2];
+    Pin h_round, h_chain, h_tiles;
+    u32 cur_win = 0;
+    ~GzDev() {
+        for (Buf *b : {&comp, &cand, &meas, &pieces, &round, &sym, &bad, &chain, &tiles, &text, &win[0], &win[1]}) if (b->p) (void)hipFree(b->p);
+        for (Pin *b : {&h_round, &h_chain, &h_tiles}) if (b->p) (void)hipHostFree(b->p);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (st && own_stream) (void)hipStreamDestroy(st);
+    }
+};
+
+// One round on the device, in two steps; compressed bytes [0, clen) lie at G.comp, the window in G.win[G.cur_win].
+// gz_plan: find, measure, stitch -> *R (ms6[0..2] +=).  gz_fill, where R has pieces and no status: emit, chain, resolve -> R->text bytes at
+// `out` (device), the window moved on, *crc = CRC32 of the round's text (ms6[3..5] +=); a reference before the member's first byte sets R->status.
+int gz_plan(GzDev &G, u64 clen, u64 start_bit, u64 chunk, u64 text_cap, lnr_gz::Round *R, u32 *nchunk_out, double *ms6, char *err, size_t err_cap) {
+    using namespace lnr_gz;
+    const u32 nchunk = chunks_of(start_bit, clen, chunk);
+    *nchunk_out = nchunk;
+    if (!nchunk) { *R = empty_round(start_bit); return 0; }               // not a byte: AT_INPUT, nothing is launched
+    int s;
+    if ((s = dev_need(G.cand, 8ULL * nchunk, err, err_cap)) || (s = dev_need(G.meas, (u64)nchunk * sizeof(Meas), err, err_cap)) ||
+        (s = dev_need(G.pieces, (u64)nchunk * sizeof(Piece), err, err_cap)) || (s = dev_need(G.round, sizeof(Round), err, err_cap)) ||
+        (s = dev_need(G.bad, 4ULL * nchunk, err, err_cap)) || (s = dev_need(G.chain, sizeof(GzChain), err, err_cap))) return s;
+    if (!pin_need(G.h_round, sizeof(Round)) || !pin_need(G.h_chain, sizeof(GzChain))) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    const u8 *comp = (const u8 *)G.comp.p;
+    RD_CK(hipEventRecord(G.ev[0], G.st), -3);
+    hipLaunchKernelGGL(k_gz_find, dim3(nchunk), dim3(64), 0, G.st, comp, clen, start_bit, chunk, nchunk, (u64 *)G.cand.p);
+    RD_CK(hipEventRecord(G.ev[1], G.st), -3);
+    hipLaunchKernelGGL(k_gz_measure, dim3(nchunk), dim3(64), 0, G.st, comp, clen, start_bit, (const u64 *)G.cand.p, nchunk, (Meas *)G.meas.p);
+    RD_CK(hipEventRecord(G.ev[2], G.st), -3);
+    hipLaunchKernelGGL(k_gz_stitch, dim3(1), dim3(64), 0, G.st, comp, clen, start_bit, (const u64 *)G.cand.p, (const Meas *)G.meas.p, nchunk, text_cap,
+                       (Piece *)G.pieces.p, (Round *)G.round.p);
+    RD_CK(hipEventRecord(G.ev[3], G.st), -3);
+    RD_CK(hipMemcpyAsync(G.h_round.p, G.round.p, sizeof(Round), hipMemcpyDeviceToHost, G.st), -3);
+    RD_CK(hipStreamSynchronize(G.st), -3);
+    RD_CK(hipGetLastError(), -3);
+    *R = *(const Round *)G.h_round.p;
+    float f = 0;
+    for (int k = 0; k < 3; k++) { RD_CK(hipEventElapsedTime(&f, G.ev[k], G.ev[k + 1]), -3); ms6[k] += f; }
+    if (R->pieces > nchunk || R->text > text_cap) { snprintf(err, err_cap, "internal: the stitch found %u pieces", R->pieces); return -8; }
+    return 0;
+}
+int gz_fill(GzDev &G, u64 clen, u64 start_bit, u32 hist, lnr_gz::Round *R, u8 *out, u32 *crc, u64 *win_syms, double *ms6, char *err, size_t err_cap) {
+    using namespace lnr_gz;
+    int s;
+    float f = 0;
+    const u8 *comp = (const u8 *)G.comp.p;
+    *crc = 0; *win_syms = 0;
+    const u32 ntile = (u32)((R->text + GZ_TILE - 1) / GZ_TILE);
+    if ((s = dev_need(G.sym, 2 * R->text + 16, err, err_cap)) ||
+        (s = dev_need(G.tiles, (u64)(ntile + 1) * sizeof(GzTile), err, err_cap))) return s;
+    if (!pin_need(G.h_tiles, (u64)(ntile + 1) * sizeof(GzTile))) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    const u8 *win = (const u8 *)G.win[G.cur_win].p;
+    RD_CK(hipEventRecord(G.ev[4], G.st), -3);
+    hipLaunchKernelGGL(k_gz_emit, dim3(R->pieces), dim3(64), 0, G.st, comp, clen, (const Piece *)G.pieces.p, R->pieces, (u16 *)G.sym.p, R->text, (u32 *)G.bad.p);
+    RD_CK(hipEventRecord(G.ev[5], G.st), -3);
+    hipLaunchKernelGGL(k_gz_chain, dim3(1), dim3(64), 0, G.st, (const Piece *)G.pieces.p, R->pieces, (u16 *)G.sym.p, R->text, win, hist, (const u32 *)G.bad.p, (GzChain *)G.chain.p);
+    RD_CK(hipEventRecord(G.ev[6], G.st), -3);
+    if (ntile) hipLaunchKernelGGL(k_gz_resolve, dim3(ntile), dim3(64), 0, G.st, (const Piece *)G.pieces.p, R->pieces, (const u16 *)G.sym.p, R->text, win, hist, out, (GzTile *)G.tiles.p);
+    RD_CK(hipEventRecord(G.ev[7], G.st), -3);
+    hipLaunchKernelGGL(k_gz_keep, dim3(WIN / 256), dim3(256), 0, G.st, win, (const u8 *)out, R->text, (u8 *)G.win[G.cur_win ^ 1].p);
+    RD_CK(hipMemcpyAsync(G.h_chain.p, G.chain.p, sizeof(GzChain), hipMemcpyDeviceToHost, G.st), -3);
+    if (ntile) RD_CK(hipMemcpyAsync(G.h_tiles.p, G.tiles.p, (u64)ntile * sizeof(GzTile), hipMemcpyDeviceToHost, G.st), -3);
+    RD_CK(hipStreamSynchronize(G.st), -3);
+    RD_CK(hipGetLastError(), -3);
+    G.cur_win ^= 1;
+    for (int k = 3; k < 6; k++) { RD_CK(hipEventElapsedTime(&f, G.ev[k + 1], G.ev[k + 2]), -3); ms6[k] += f; }
+    const GzChain C = *(const GzChain *)G.h_chain.p;
+    if (C.status) { R->status = C.status; R->bad_bit = start_bit; return 0; }
+    *win_syms = C.win_syms;
+    const GzTile *T = (const GzTile *)G.h_tiles.p;
+    u32 c = 0;
+    for (u32 k = 0; k < ntile; k++) {                                      // the tiles' CRCs folded in order
+        if (T[k].bad) { R->status = lnr_inf::E_DISTANCE; R->bad_bit = start_bit; return 0; }
+        const u64 n = (u64)k * GZ_TILE + GZ_TILE < R->text ? GZ_TILE : R->text - (u64)k * GZ_TILE;
+        c = lnr_inf::crc_combine(c, T[k].crc, n);
+        *win_syms += T[k].refs;
+    }
+    *crc = c;
+    return 0;
+}
+
+void gz_free(GzDev *G) { delete G; }
+
+}  // namespace
+
+// One round of a plain gzip member for the reader: the round's compressed bytes up, find / measure / stitch; where it has pieces, the carried
+// text to the front of g->text and the round's text resolved behind it.  Afterwards the device text is [0, carry + out->text).
+extern "C" int lnr_rdgpu_gzip_round(lnr_rdgpu *g, const lnr_rdgpu_gzip *job, lnr_rdgpu_gzip_result *out, char *err, size_t err_cap) {
+    using namespace lnr_gz;
+    *out = lnr_rdgpu_gzip_result{};
+    if (!job->comp_len || job->comp_len > (1ULL << 31) || job->start_bit > 7 || job->hist > WIN || job->carry > (1ULL << 30) || job->text_cap > (1ULL << 30) - job->carry ||
+        job->keep_from + job->carry > g->text.cap) { snprintf(err, err_cap, "internal: gzip round of %llu bytes", (unsigned long long)job->comp_len); return -8; }
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    RD_CK(hipSetDevice(g->device), -3);
+    int s;
+    if (!g->gz) {
+        g->gz = new (std::nothrow) GzDev();
+        if (!g->gz) return -4;
+        g->gz->st = g->st; g->gz->own_stream = false;
+        for (hipEvent_t &e : g->gz->ev) RD_CK(hipEventCreate(&e), -3);
+        if ((s = dev_need(g->gz->win[0], WIN, err, err_cap)) || (s = dev_need(g->gz->win[1], WIN, err, err_cap))) return s;
+    }
+    GzDev &G = *g->gz;
+    lnr_rdgpu_gz_counts &C = out->counts;
+    if ((s = dev_need(G.comp, job->comp_len + 16, err, err_cap))) return s;
+    double t0 = wall_ms();
+    if ((s = upload_pageable(g, (u8 *)G.comp.p, job->comp, job->comp_len, job->threads, err, err_cap))) return s;
+    RD_CK(hipStreamSynchronize(g->s_copy), -3);
+    C.upload_ms = wall_ms() - t0;
+    Round R;
+    u32 nchunk = 0, crc = 0;
+    u64 refs = 0;
+    double ms6[6] = {0, 0, 0, 0, 0, 0};
+    if ((s = gz_plan(G, job->comp_len, job->start_bit, job->chunk, job->text_cap, &R, &nchunk, ms6, err, err_cap))) return s;
+    if (!R.status && R.pieces) {
+        // the text buffer: whole tiles; the carried text moves to its front (into a new buffer where this one is too small)
+        const u64 tlen = job->carry + R.text, need = bam_text_cap(tlen) + 16;
+        if (need > g->text.cap) {
+            Buf nb;
+            if ((s = dev_need(nb, need, err, err_cap))) return s;
+            if (job->carry) {
+                hipError_t e = hipMemcpyAsync(nb.p, (u8 *)g->text.p + job->keep_from, job->carry, hipMemcpyDeviceToDevice, g->st);
+                if (e == hipSuccess) e = hipStreamSynchronize(g->st);
+                if (e != hipSuccess) { (void)hipFree(nb.p); snprintf(err, err_cap, "moving the carried text: %s", hipGetErrorString(e)); return -3; }
+            }
+            if (g->text.p) (void)hipFree(g->text.p);
+            g->text = nb;
+        } else if ((s = move_text(g, (u8 *)g->text.p, 0, job->keep_from, job->carry, err, err_cap))) return s;
+        if ((s = gz_fill(G, job->comp_len, job->start_bit, job->hist, &R, (u8 *)g->text.p + job->carry, &crc, &refs, ms6, err, err_cap))) return s;
+        out->moved = 1;
+    }
+    out->status = R.status; out->stop = R.stop; out->pieces = R.pieces; out->crc = crc;
+    out->bad_off = R.bad_bit >> 3; out->end_bit = R.end_bit; out->text = R.text;
+    C.find_ms = ms6[0]; C.measure_ms = ms6[1]; C.stitch_ms = ms6[2]; C.emit_ms = ms6[3]; C.chain_ms = ms6[4]; C.resolve_ms = ms6[5];
+    if (!R.status && R.pieces) {
+        C.rounds = 1; C.chunks = nchunk; C.true_pieces = R.pieces; C.false_candidates = R.falses; C.candidates = R.cands;
+        C.deflate_blocks = R.blocks; C.compressed_bytes = (R.end_bit + 7) >> 3; C.text_bytes = R.text; C.window_symbols = refs;
+    }
+    return 0;
+}
+
+extern "C" int lnr_rdgpu_gunzip(int32_t device, const uint8_t *gz, uint64_t size, uint8_t *text, uint64_t text_cap, uint64_t *text_size, lnr_rdgpu_gz_counts *last,
+                                lnr_rdgpu_gz_counts *total, uint64_t *bad_off, uint32_t *bad_status, char *err, size_t err_cap) {
+    using namespace lnr_gz;
+    *text_size = 0; *bad_off = 0; *bad_status = 0;
+    *last = lnr_rdgpu_gz_counts{}; *total = lnr_rdgpu_gz_counts{};
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) { snprintf(err, err_cap, "no usable HIP device for the GPU inflate"); return -2; }
+    DeviceGuard dg;
+    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
+    if (device < 0) device = dg.prev < 0 ? 0 : dg.prev;
+    if (device >= count) { snprintf(err, err_cap, "no usable HIP device %d for the GPU inflate (%d present)", (int)device, count); return -2; }
+    if (size > (1ULL << 31)) { snprintf(err, err_cap, "%llu compressed bytes: beyond the staging limit of 2^31", (unsigned long long)size); return -6; }
+    RD_CK(hipSetDevice(device), -2);
+    const u64 chunk = lnr_gz::env_bytes("LNR_READER_GZ_CHUNK", 128ULL << 10, 1024, 1ULL << 30), round = lnr_gz::env_bytes("LNR_READER_GZ_ROUND", 64ULL << 20, 1024, 1ULL << 31);
+    GzDev G;
+    int s;
+    RD_CK(hipStreamCreateWithFlags(&G.st, hipStreamNonBlocking), -3);
+    for (hipEvent_t &e : G.ev) RD_CK(hipEventCreate(&e), -3);
+    if ((s = dev_need(G.comp, size + 16, err, err_cap)) || (s = dev_need(G.win[0], WIN, err, err_cap)) || (s = dev_need(G.win[1], WIN, err, err_cap))) return s;
+    double t0 = wall_ms();
+    if (size) RD_CK(hipMemcpyAsync(G.comp.p, gz, size, hipMemcpyHostToDevice, G.st), -3);
+    RD_CK(hipStreamSynchronize(G.st), -3);
+    total->upload_ms += wall_ms() - t0;
+    u64 off = 0, done = 0;
+    auto fail = [&](u32 status, u64 at) { *bad_status = status; *bad_off = at; *text_size = done; return 0; };
+    for (bool first = true; off < size; first = false) {
+        u64 data = 0;
+        u32 st = member_at(gz, size, off, first, &data);
+        if (st == PASS_OVER) break;
+        if (st) return fail(st, off);
+        u64 start_bit = data * 8, rsize = round, mtext = 0;
+        u32 hist = 0, crc = 0;
+        for (;;) {
+            const u64 rb = start_bit >> 3, clen = size - rb < rsize ? size : rb + rsize;
+            const u64 cap = text_cap - done < (1ULL << 30) ? text_cap - done : 1ULL << 30;
+            Round R;
+            u32 nchunk = 0, rcrc = 0;
+            u64 refs = 0;
+            lnr_rdgpu_gz_counts L{};
+            double ms6[6] = {0, 0, 0, 0, 0, 0};
+            if ((s = gz_plan(G, clen, start_bit, chunk, cap, &R, &nchunk, ms6, err, err_cap))) return s;
+            if (!R.status && R.pieces) {
+                if ((s = dev_need(G.text, R.text + 16, err, err_cap)) || (s = gz_fill(G, clen, start_bit, hist, &R, (u8 *)G.text.p, &rcrc, &refs, ms6, err, err_cap))) return s;
+            }
+            bool grown;
+            u64 rs2 = rsize;
+            st = round_verdict(R, clen, size, rs2, grown);
+            if (st == E_TEXT_CAP && R.pieces && cap < text_cap - done) st = 0;          // cut at the 1 GiB a round may hold, not at the caller's buffer
+            L.find_ms = ms6[0]; L.measure_ms = ms6[1]; L.stitch_ms = ms6[2]; L.emit_ms = ms6[3]; L.chain_ms = ms6[4]; L.resolve_ms = ms6[5];
+            if (!st && !grown) {
+                t0 = wall_ms();
+                if (R.text) RD_CK(hipMemcpy(text + done, G.text.p, R.text, hipMemcpyDeviceToHost), -3);
+                L.download_ms = wall_ms() - t0;
+                L.rounds = 1; L.chunks = nchunk; L.true_pieces = R.pieces; L.false_candidates = R.falses; L.candidates = R.cands;
+                L.deflate_blocks = R.blocks; L.compressed_bytes = ((R.end_bit + 7) >> 3) - rb; L.text_bytes = R.text; L.window_symbols = refs;
+            } else if (grown) L.grown_rounds = 1;
+            *last = L;
+            lnr_rdgpu_gz_add(total, &L);
+            if (st) return fail(st, (R.status ? R.bad_bit : R.end_bit) >> 3);
+            if (grown) { rsize = rs2; continue; }
+            crc = lnr_inf::crc_combine(crc, rcrc, R.text);
+            hist = hist + R.text > WIN ? WIN : (u32)(hist + R.text);
+            done += R.text; mtext += R.text; start_bit = R.end_bit; rsize = round;
+            if (R.stop == AT_FINAL) break;
+        }
+        if ((st = check_trailer(gz, size, start_bit, crc, mtext, &off))) return fail(st, (start_bit + 7) >> 3);
+        total->members++;
+    }
+    *text_size = done;
+    return 0;
+}
