@@ -395,23 +395,11 @@ inline Round round_host(const u8 *comp, u64 clen, u64 start_bit, u64 chunk, cons
     S.rounds++;
     return R;
 }
-// the window behind a round: the last WIN bytes of (old window, round text)
-inline void window_after(u8 *win, u32 &hist, const u8 *text, u64 n) {
-    if (n >= WIN) { for (u32 j = 0; j < WIN; j++) win[j] = text[n - WIN + j]; hist = WIN; return; }
+// the window behind a round: the last WIN bytes of (old window, round text); how many of them exist is the walker's (Member::hist)
+inline void window_after(u8 *win, const u8 *text, u64 n) {
+    if (n >= WIN) { for (u32 j = 0; j < WIN; j++) win[j] = text[n - WIN + j]; return; }
     for (u32 j = 0; j + n < WIN; j++) win[j] = win[j + n];
     for (u64 j = 0; j < n; j++) win[WIN - n + j] = text[j];
-    hist = hist + n > WIN ? WIN : (u32)(hist + n);
-}
-// what a driver does with a round that failed or made no progress.  0: go on (grown: with the round doubled); else the status to report
-inline u32 round_verdict(const Round &R, u64 clen, u64 size, u64 &rsize, bool &grown) {
-    grown = false;
-    if (R.status) return R.status;
-    if (R.pieces) return R.stop == AT_BUDGET ? E_TEXT_CAP : 0u;
-    if (R.stop == AT_BUDGET) return E_TEXT_CAP;
-    if (clen >= size) return lnr_inf::E_INPUT_END;       // the file ends inside a block
-    if (rsize >= (1ULL << 31)) return E_LIMIT;
-    rsize *= 2; grown = true;
-    return 0;
 }
 // a member starts at gz + off?  0: yes, *data = offset of its DEFLATE data; PASS_OVER: the bytes behind a member start none and are passed
 // over, as gzread does; else the status
@@ -423,36 +411,77 @@ inline u32 member_at(const u8 *gz, u64 size, u64 off, bool first, u64 *data) {
     return st;
 }
 
+// ---- the member walker: where a driver stands in gz[0, size), and what a round moves.  Every driver (gunzip_host, lnr_rdgpu_gunzip, the
+// reader's gzip source) loops: member_enter, a round of member_round_size bytes from start_bit, round_verdict, member_fold.
+struct Member {
+    bool in_member = false, end = false;                 // start_bit .. mtext are valid; no member starts at pos (or the file ends there)
+    u64 pos = 0, start_bit = 0, mtext = 0, grow = 1;     // the next member's header; the member's next bit, in the file; its text so far; the round's factor
+    u32 hist = 0, crc = 0;                               // bytes of history in the window; CRC32 of the member's text so far
+};
+// the member at pos, where the walker stands between two.  0 (then in_member or end holds), or the header's status (at pos)
+inline u32 member_enter(Member &m, const u8 *gz, u64 size) {
+    if (m.in_member || m.end) return 0;
+    u64 data = 0;
+    const u32 st = m.pos >= size ? PASS_OVER : member_at(gz, size, m.pos, m.pos == 0, &data);
+    if (st) { m.end = st == PASS_OVER; return m.end ? 0 : st; }
+    m.in_member = true; m.start_bit = data * 8; m.mtext = 0; m.hist = 0; m.crc = 0;
+    return 0;
+}
+// base compressed bytes per round, times the factor of the rounds that completed no block
+inline u64 member_round_size(const Member &m, u64 base) { return base > (1ULL << 31) / m.grow ? 1ULL << 31 : base * m.grow; }
+// what a driver does with a round of rsize bytes up to file offset clen that failed or made no progress.  0: go on (grown: the same round
+// again, doubled); else the status to report, *bad_off = the compressed offset it belongs to
+inline u32 round_verdict(Member &m, const Round &R, u64 clen, u64 size, u64 rsize, bool &grown, u64 *bad_off) {
+    grown = false;
+    u32 st;
+    if (R.status) st = R.status;
+    else if (R.stop == AT_BUDGET) st = E_TEXT_CAP;
+    else if (R.pieces) return 0;
+    else if (clen >= size) st = lnr_inf::E_INPUT_END;    // the file ends inside a block
+    else if (rsize >= (1ULL << 31)) st = E_LIMIT;
+    else { m.grow *= 2; grown = true; return 0; }
+    *bad_off = (R.status ? R.bad_bit : R.end_bit) >> 3;
+    return st;
+}
+// a round with pieces joins the member: its text (CRC32 rcrc), the history, the next bit.  Behind a final block the trailer is checked
+// (its status, at *bad_off: the round's text stands, as gzread delivers it) and the walker stands in front of the next member (*final)
+inline u32 member_fold(Member &m, const u8 *gz, u64 size, const Round &R, u32 rcrc, bool *final, u64 *bad_off) {
+    m.grow = 1;
+    m.crc = lnr_inf::crc_combine(m.crc, rcrc, R.text);
+    m.hist = m.hist + R.text > WIN ? WIN : (u32)(m.hist + R.text);
+    m.mtext += R.text; m.start_bit = R.end_bit;
+    *final = false;
+    if (R.stop != AT_FINAL) return 0;
+    u64 next = 0;
+    const u32 st = check_trailer(gz, size, m.start_bit, m.crc, m.mtext, &next);
+    if (st) { *bad_off = (m.start_bit + 7) >> 3; return st; }
+    m.in_member = false; m.pos = next; *final = true;
+    return 0;
+}
+
 // every member of gz[0, size): text at out (room for cap bytes).  0 or the status, *bad_off = the compressed offset it belongs to
 inline u32 gunzip_host(const u8 *gz, u64 size, u8 *out, u64 cap, u64 *text_size, u64 chunk, u64 round, Stats &S, u64 *bad_off) {
     Scratch W;
     std::vector<u8> win(WIN);
-    u64 off = 0, total = 0;
+    u64 total = 0;
     *text_size = 0; *bad_off = 0;
     if (size > (1ULL << 31)) return E_LIMIT;
     if (chunk < 1024) chunk = 1024;
     if (round < 1024) round = 1024;
-    for (bool first = true; off < size; first = false) {
-        u64 data = 0;
-        u32 st = member_at(gz, size, off, first, &data);
-        if (st == PASS_OVER) break;
-        if (st) { *bad_off = off; return st; }
-        u64 start_bit = data * 8, rsize = round, mtext = 0;
-        u32 hist = 0, crc = 0;
-        for (;;) {
-            const u64 rb = start_bit >> 3, clen = size - rb < rsize ? size : rb + rsize;
-            const Round R = round_host(gz, clen, start_bit, chunk, win.data(), hist, out + total, cap - total, W, S);
-            bool grown;
-            if ((st = round_verdict(R, clen, size, rsize, grown))) { *bad_off = (R.status ? R.bad_bit : R.end_bit) >> 3; *text_size = total; return st; }
-            if (grown) { S.grown++; continue; }
-            crc = lnr_inf::crc_combine(crc, lnr_inf::crc_of(out + total, R.text), R.text);
-            window_after(win.data(), hist, out + total, R.text);
-            total += R.text; mtext += R.text; start_bit = R.end_bit; rsize = round;
-            if (R.stop == AT_FINAL) break;
-        }
-        *text_size = total;
-        if ((st = check_trailer(gz, size, start_bit, crc, mtext, &off))) { *bad_off = (start_bit + 7) >> 3; return st; }
-        S.members++;
+    Member m;
+    for (;;) {
+        u32 st = member_enter(m, gz, size);
+        if (st) { *bad_off = m.pos; return st; }
+        if (m.end) break;
+        const u64 rsize = member_round_size(m, round), rb = m.start_bit >> 3, clen = size - rb < rsize ? size : rb + rsize;
+        const Round R = round_host(gz, clen, m.start_bit, chunk, win.data(), m.hist, out + total, cap - total, W, S);
+        bool grown, final;
+        if ((st = round_verdict(m, R, clen, size, rsize, grown, bad_off))) return st;
+        if (grown) { S.grown++; continue; }
+        window_after(win.data(), out + total, R.text);
+        *text_size = total += R.text;
+        if ((st = member_fold(m, gz, size, R, lnr_inf::crc_of(out + total - R.text, R.text), &final, bad_off))) return st;
+        S.members += final;
     }
     S.comp_bytes += size; S.text_bytes += total;
     return 0;

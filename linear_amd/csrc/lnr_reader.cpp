@@ -15,6 +15,7 @@
 #include "lnr_inflate_hd.h"
 #include "lnr_bam_hd.h"
 #include "lnr_gunzip_hd.h"
+#include "lnr_window_hd.h"
 
 // Plain (not gzip) files take a PARALLEL path (f4's reason to exist: feed a GPU that filters 2 M reads/s): the file is mapped, one pass of
 // memchr finds the record boundaries of the next block (a FASTA record ends before the next '>' at a line start; a FASTQ record is taken as four
@@ -40,53 +41,46 @@
 #include <thread>
 #include <vector>
 
+enum Src { SRC_STREAM, SRC_MAP, SRC_BGZF, SRC_GZIP };       // who gives lnr_reader_next_dev its text: gzread, the mapped file, the BGZF chain, the gzip rounds
+struct DevText { uint64_t keep_from = 0, carry = 0; };      // device text [keep_from, keep_from + carry) is what the last window left (SRC_BGZF, SRC_GZIP)
+
 struct lnr_reader {
-    gzFile f = nullptr;
-    std::vector<unsigned char> buf;
-    size_t pos = 0, end = 0;
-    bool eof = false;
+    // ---- the reader: what the file is, the last block's ids, the totals
+    std::string path, err; bool started = false;
     int format = 0;              // 0 unknown, 1 FASTA, 2 FASTQ, 3 BAM (by content: the first four inflated bytes)
-    std::string err;
-    std::vector<char> ids;       // ids of the last block, '\0' separated
-    std::vector<uint8_t> spill;  // a record that did not fit the last block any more (a gzip stream cannot be rewound): first record of the next
-    std::vector<char> spill_id;
-    bool have_spill = false;
-    std::vector<uint64_t> id_off;
-    uint64_t records = 0, bases = 0;
-    unsigned char tab[256];
-    // the mapped file of the parallel path (plain files only)
-    const unsigned char *map = nullptr; size_t map_len = 0, mpos = 0; bool use_map = false; unsigned threads = 8;
-    // the GPU twin (lnr_reader_gpu_open / lnr_reader_next_dev): its device side, the slot of the next block, "the serial parser has taken over",
-    // "the inflate stream has ended", and the host block the serial parser's records pass through on their way up
-    lnr_rdgpu *gpu = nullptr; uint32_t gslots = 0, gslot = 0; bool gpu_serial = false, gz_done = false;
-    std::unique_ptr<uint8_t[]> hblock; uint64_t hblock_cap = 0;
-    uint64_t g_text = 0, g_recs = 0;     // text bytes and records the windows have used up so far: sizes the next window
-    char gerr[256] = "";
-    // BGZF (device inflate): the file is mapped at `map` with use_map false.  The chain is walked one window at a time from bpos on;
-    // `chain` = the blocks whose text lies on the device and is not used up, byte 0 of the device text = byte bskip of chain[0]'s text
-    struct BBlk { uint64_t off; uint32_t size, isize; };
-    bool bgzf = false, bend = false, bstop = false, bfailed = false;   // live; the chain reached the end of the file; the member at bpos is not BGZF
-    int bfd = -1;
-    uint64_t bpos = 0, bskip = 0, bkeep_from = 0, bcarry = 0;         // device text [bkeep_from, bkeep_from + bcarry) is what the last window left
-    std::vector<BBlk> chain;
-    lnr_inflate_counts ist_last{}, ist_total{};
+    Src src = SRC_STREAM;        // (lnr_reader_next knows SRC_MAP alone: it reads every other file through the stream)
+    std::vector<char> ids; std::vector<uint64_t> id_off;             // ids of the last block, '\0' separated
+    uint64_t records = 0, bases = 0; unsigned char tab[256];
+    // ---- the stream: gzread through buf; a record that did not fit the last block any more (a gzip stream cannot be rewound) is the first of the next
+    gzFile f = nullptr; std::vector<unsigned char> buf; size_t pos = 0, end = 0;
+    bool eof = false, gz_done = false;                                // of fill(); of the GPU twin's own gzread into the staging buffer
     uint64_t gz_bytes = 0;                                            // text bytes that came out of gzread
-    // BAM: the header has been passed; a record was refused (the reader can only be closed); the header's n_ref; records passed so far
+    std::vector<uint8_t> spill; std::vector<char> spill_id; bool have_spill = false;
+    // ---- the mapped file: SRC_MAP parses it in place (plain files only); SRC_BGZF and SRC_GZIP upload its compressed bytes
+    const unsigned char *map = nullptr; size_t map_len = 0, mpos = 0; unsigned threads = 8;
+    // ---- the BGZF chain (device inflate), walked one window at a time from bpos on; `chain` = the blocks whose text lies on the device and
+    // is not used up, byte 0 of the device text = byte bskip of chain[0]'s text.  bend: the chain reached the end of the file; bstop: the
+    // member at bpos is not BGZF
+    bool bend = false, bstop = false, bfailed = false; int bfd = -1; uint64_t bpos = 0, bskip = 0;
+    std::vector<lnr_win::Block> chain;
+    lnr_inflate_counts ist_last{}, ist_total{};
+    // ---- the gzip member (lnr_reader_gpu_gzip: gzp), inflated in rounds from the mapped file.  text_made = text bytes the device has
+    // inflated so far (BGZF blocks included), so text_made - dtext.carry is the offset in the uncompressed stream at which a gzread stream
+    // would go on
+    bool gzp = false, gz_failed = false; lnr_gz::Member gzm; uint64_t text_made = 0;
+    lnr_rdgpu_gz_counts gzs_last{}, gzs_total{};
+    // ---- BAM: the header has been passed; a record was refused (the reader can only be closed); the header's n_ref; records passed so far
     // (skipped ones included) and the offset of the next one in the uncompressed stream -- what an error message names
-    bool bam_hdr = false, bam_failed = false;
-    int32_t bam_nref = 0;
-    uint64_t bam_ord = 0, bam_off = 0;
+    bool bam_hdr = false, bam_failed = false; int32_t bam_nref = 0; uint64_t bam_ord = 0, bam_off = 0;
     std::vector<unsigned char> bam_tmp;
     lnr_bam_counts bam_last{}, bam_total{};
-    // plain gzip on the device (lnr_reader_gpu_gzip): the file is mapped at `map` with use_map false, as for BGZF.  gz_live: the rounds
-    // read the file from gz_pos (a member's header) or, inside a member, from bit gz_bit of the file.  The device text
-    // [gkeep_from, gkeep_from + gcarry) is what the last window left; text_made = text bytes the device has inflated so far (BGZF blocks
-    // included), so text_made - gcarry is the offset in the uncompressed stream at which a gzread stream would go on
-    std::string path;
-    bool started = false, gzp = false, gz_live = false, gz_in_member = false, gz_end = false, gz_failed = false;
-    uint64_t gz_pos = 0, gz_bit = 0, gz_mtext = 0, gkeep_from = 0, gcarry = 0, text_made = 0, gz_grow = 1;
-    uint32_t gz_hist = 0, gz_crc = 0;
-    lnr_rdgpu_gz_counts gzs_last{}, gzs_total{};
+    // ---- the GPU twin (lnr_reader_gpu_open / lnr_reader_next_dev): its device side, the slot of the next block, "the serial parser has
+    // taken over", the text on the device, the host block the serial parser's records pass through on their way up
+    lnr_rdgpu *gpu = nullptr; uint32_t gslots = 0, gslot = 0; bool gpu_serial = false;
+    DevText dtext; std::unique_ptr<uint8_t[]> hblock; uint64_t hblock_cap = 0;
+    uint64_t g_text = 0, g_recs = 0;     // text bytes and records the windows have used up so far: sizes the next window
+    std::vector<uint64_t> span_off; std::vector<uint32_t> span_len;   // the names of a window of host text (names_of_spans)
+    char gerr[256] = "";
 
     bool fill() {
         if (eof) return false;
@@ -133,7 +127,7 @@ struct lnr_reader {
 static bool bgzf_to_stream(lnr_reader *r) {
     const uint64_t off = r->chain.empty() ? r->bpos : r->chain[0].off;
     uint64_t skip = r->chain.empty() ? 0 : r->bskip;
-    r->bgzf = false; r->chain.clear(); r->bskip = r->bcarry = r->bkeep_from = 0;
+    r->src = SRC_STREAM; r->chain.clear(); r->bskip = 0; r->dtext = DevText{};
     int fd = dup(r->bfd);
     gzFile nf = nullptr;
     if (fd < 0 || lseek(fd, (off_t)off, SEEK_SET) < 0 || !(nf = gzdopen(fd, "rb"))) {
@@ -159,8 +153,8 @@ static bool bgzf_to_stream(lnr_reader *r) {
 // gzseek -- which inflates the file once more from its start.  Accepted: the hand-over is rare (a FASTQ that leaves the four-line form, a
 // lnr_reader_next behind lnr_reader_next_dev).
 static bool gz_to_stream(lnr_reader *r) {
-    const uint64_t at = r->text_made - r->gcarry;
-    r->gz_live = false; r->gcarry = r->gkeep_from = 0;
+    const uint64_t at = r->text_made - r->dtext.carry;
+    r->src = SRC_STREAM; r->dtext = DevText{};
     gzFile nf = gzopen(r->path.c_str(), "rb");
     if (!nf) { r->err = "cannot reopen " + r->path; return false; }
     gzbuffer(nf, 1u << 20);
@@ -175,17 +169,10 @@ static lnr_status gz_fail(lnr_reader *r, uint32_t status, uint64_t off) {
     r->err = r->gerr; r->gz_failed = true;
     return LNR_ERR_ARG;
 }
-// the member at gz_pos, or the end of the file's members.  LNR_OK, or the header's error
+// the member at gzm.pos, or the end of the file's members.  LNR_OK, or the header's error
 static lnr_status gz_next_member(lnr_reader *r) {
-    while (!r->gz_in_member && !r->gz_end) {
-        if (r->gz_pos >= r->map_len) { r->gz_end = true; break; }
-        uint64_t data = 0;
-        const uint32_t st = lnr_gz::member_at(r->map, r->map_len, r->gz_pos, r->gz_pos == 0, &data);
-        if (st == lnr_gz::PASS_OVER) { r->gz_end = true; break; }
-        if (st) return gz_fail(r, st, r->gz_pos);
-        r->gz_bit = data * 8; r->gz_in_member = true; r->gz_hist = 0; r->gz_crc = 0; r->gz_mtext = 0;
-    }
-    return LNR_OK;
+    const uint32_t st = lnr_gz::member_enter(r->gzm, r->map, r->map_len);
+    return st ? gz_fail(r, st, r->gzm.pos) : LNR_OK;
 }
 // ---- BAM (format 3; every decision from lnr_bam_hd.h).  The records come through the gzread stream one after the other.
 static lnr_status bam_fail(lnr_reader *r, uint64_t ord, uint64_t off, const char *why) {
@@ -256,6 +243,299 @@ static lnr_status bam_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64
     return LNR_OK;
 }
 
+// t += c for the counts structs of the public header: NU counts, then ND times (lnr_rdgpu_gz_add is the third of the kind)
+template <int NU, int ND, class C> static void counts_add_n(C &t, const C &c) {
+    static_assert(sizeof(C) == 8 * (NU + ND), "NU 64-bit counts and ND doubles");
+    uint64_t *tu = (uint64_t *)&t; const uint64_t *cu = (const uint64_t *)&c;
+    for (int i = 0; i < NU; i++) tu[i] += cu[i];
+    double *td = (double *)(tu + NU); const double *cd = (const double *)(cu + NU);
+    for (int i = 0; i < ND; i++) td[i] += cd[i];
+}
+static_assert(offsetof(lnr_inflate_counts, inflate_ms) == 8 * 4 && offsetof(lnr_bam_counts, find_ms) == 8 * 5, "where the times begin");
+static void counts_add(lnr_inflate_counts &t, const lnr_inflate_counts &c) { counts_add_n<4, 2>(t, c); }
+static void counts_add(lnr_bam_counts &t, const lnr_bam_counts &c) { counts_add_n<5, 3>(t, c); }
+
+// ---- the GPU twin's loop (lnr_reader_next_dev): size the window, ask the source for it, parse it, account for it, tell the
+// source what was used, decide (lnr_win::decide).  One call's state, what a source hands to the parse, what the parse leaves behind:
+struct Call { lnr_reader *r; uint32_t slot; uint32_t n = 0; uint64_t used = 0, grow = 1; };   // n records and `used` bases in the block; the window's factor
+struct Window {
+    lnr_rdgpu_window w{};            // the limits; host text: w.text / w.len, byte 0 starts a record
+    lnr_rdgpu_bgzf job{};            // device text: what the last window left and the blocks to inflate behind it
+    std::vector<lnr_rdgpu_bgzf_blk> tab;
+    size_t chain0 = 0;               // SRC_BGZF: tab[k] is chain[chain0 + k]
+    uint64_t len = 0;                // lnr_win::Seen::len
+    bool ended = false, stuck = false;
+};
+struct Parsed {
+    lnr_rdgpu_result res{};
+    lnr_rdgpu_names names{};
+    uint64_t lead = 0, passed = 0;   // device text used up in front of the parsed text; records in front of res.consumed (BAM: skipped ones included)
+    bool parsed = false, handover = false;
+};
+enum Got { GOT_WINDOW, GOT_AGAIN, GOT_END, GOT_ERROR };     // (GOT_ERROR: *st and r->err are set)
+static Got fail(lnr_reader *r, lnr_status *st, lnr_status s, const char *why) { r->err = why; *st = s; return GOT_ERROR; }
+static Got gfail(lnr_reader *r, lnr_status *st, int s) { return fail(r, st, (lnr_status)s, r->gerr); }
+static Got bam_header_fail(lnr_reader *r, lnr_status *st, const char *why) { r->bam_failed = true; return fail(r, st, LNR_ERR_ARG, why); }
+static const char *const TOO_LONG = "a record is longer than the reader's window";
+static bool is_ws(unsigned char c) { return c == '\n' || c == '\r' || c == ' ' || c == '\t'; }
+static void put_back(lnr_reader *r, const uint8_t *p, uint64_t left) {       // what a window of the stream did not use goes back in front of the stream
+    if (r->buf.size() < left) r->buf.resize(left);
+    memcpy(r->buf.data(), p, left);
+    r->pos = 0; r->end = left;
+}
+
+// SRC_GZIP: rounds of the member inflated on the device behind what the last window left, until the device text holds `want` bytes
+static Got gzip_window(Call &c, uint64_t want, Window &W, lnr_status *st) {
+    lnr_reader *r = c.r;
+    lnr_gz::Member &m = r->gzm;
+    auto failed = [&]() { return c.n ? GOT_END : gfail(r, st, LNR_ERR_ARG); };      // bad data: the records in front of it are delivered first
+    if (r->gz_failed || gz_next_member(r)) return failed();
+    const uint64_t chunk = lnr_gz::env_bytes("LNR_READER_GZ_CHUNK", 128ULL << 10, 1024, 1ULL << 30), round = lnr_gz::env_bytes("LNR_READER_GZ_ROUND", 64ULL << 20, 1024, 1ULL << 31);
+    constexpr uint64_t TEXT_MAX = lnr_win::WINDOW_MAX - 65536;
+    uint64_t &carry = r->dtext.carry;
+    while (!m.end && !r->gz_failed && carry < want && !W.stuck) {
+        const uint64_t rb = m.start_bit >> 3;
+        if (rb >= r->map_len) { gz_fail(r, lnr_inf::E_INPUT_END, r->map_len); break; }      // the file ends behind a member's header
+        if (carry >= TEXT_MAX) { W.stuck = true; break; }
+        uint64_t base = want - carry + 2 * chunk;                     // text is seldom smaller than its compressed bytes: no more of them than text is wanted
+        if (base > round) base = round;
+        const uint64_t rsize = lnr_gz::member_round_size(m, base), clen = r->map_len - rb < rsize ? r->map_len - rb : rsize;
+        lnr_rdgpu_gzip job{};
+        job.comp = r->map + rb; job.comp_len = clen; job.start_bit = (uint32_t)(m.start_bit & 7); job.hist = m.hist; job.chunk = chunk;
+        job.keep_from = r->dtext.keep_from; job.carry = carry; job.text_cap = TEXT_MAX - carry; job.threads = r->threads;
+        lnr_rdgpu_gzip_result gr{};
+        if (int s = lnr_rdgpu_gzip_round(r->gpu, &job, &gr, r->gerr, sizeof r->gerr)) { r->gz_failed = true; return gfail(r, st, s); }
+        lnr_gz::Round R = lnr_gz::empty_round(rb * 8 + gr.end_bit);   // the round as the walker takes it: in the file's coordinates
+        R.status = gr.status; R.stop = gr.stop; R.pieces = gr.pieces; R.text = gr.text; R.bad_bit = (rb + gr.bad_off) * 8;
+        lnr_rdgpu_gz_counts cn = gr.counts;
+        bool grown, final; uint64_t bad = 0;
+        uint32_t v = lnr_gz::round_verdict(m, R, rb + clen, r->map_len, rsize, grown, &bad);
+        if (!gr.status && v == lnr_gz::E_TEXT_CAP) { W.stuck = true; v = 0; }               // the device text is full: what it holds is parsed first
+        if (!gr.status && !gr.pieces) cn.grown_rounds = 1;            // no block completed
+        if (v || !gr.pieces) {
+            lnr_rdgpu_gz_add(&r->gzs_last, &cn);
+            if (!gr.status && v == lnr_gz::E_LIMIT) return fail(r, st, LNR_ERR_LIMIT, "a DEFLATE block is longer than the reader's staging limit");
+            if (v) { gz_fail(r, v, bad); break; }
+            continue;                                                 // (the same round doubled; stuck: the loop ends)
+        }
+        r->dtext.keep_from = 0; carry += gr.text; r->text_made += gr.text;
+        v = lnr_gz::member_fold(m, r->map, r->map_len, R, gr.crc, &final, &bad);
+        cn.compressed_bytes = ((m.start_bit + 7) >> 3) - rb;
+        cn.members = final;
+        lnr_rdgpu_gz_add(&r->gzs_last, &cn);
+        if (v) { gz_fail(r, v, bad); break; }                         // (the text in front of a bad trailer is delivered, as gzread delivers it)
+        if (final && gz_next_member(r)) break;
+    }
+    W.ended = m.end || r->gz_failed;
+    if (!carry) {
+        if (r->gz_failed) return failed();
+        return m.end ? GOT_END : fail(r, st, LNR_ERR_LIMIT, TOO_LONG);
+    }
+    W.job.keep_from = r->dtext.keep_from; W.job.carry = W.len = carry;      // no block to inflate: the parse of the device text
+    return GOT_WINDOW;
+}
+
+// A member that is not BGZF: with lnr_reader_gpu_gzip the gzip rounds take over there (text only), where gzread takes over without it -- at
+// the first byte the device has not used up (the rounds: r->dtext stays as it is)
+static bool bgzf_give_way(lnr_reader *r) {
+    if (!r->gzp || r->format == 3) return bgzf_to_stream(r);
+    r->src = SRC_GZIP; r->chain.clear(); r->bskip = 0;
+    r->gzm = lnr_gz::Member{}; r->gzm.pos = r->bpos;
+    return true;
+}
+// SRC_BGZF: a run of whole BGZF blocks, to be inflated on the device behind what the last window left
+static Got bgzf_window(Call &c, uint64_t want, Window &W, lnr_status *st) {
+    lnr_reader *r = c.r;
+    if (r->bfailed) return gfail(r, st, LNR_ERR_ARG);
+    const uint64_t c0 = r->bpos;
+    uint64_t fresh = 0, tl = r->dtext.carry;
+    W.chain0 = r->chain.size();
+    while (!r->bend && !r->bstop && tl < want && tl + 65536 <= lnr_win::WINDOW_MAX && r->bpos - c0 < (1ULL << 30)) {
+        if (r->bpos >= r->map_len) { r->bend = true; break; }
+        uint32_t doff = 0;
+        const unsigned char *m = r->map + r->bpos;
+        const uint32_t size = lnr_inf::bgzf_member(m, r->map_len - r->bpos, doff);
+        auto le32 = [](const unsigned char *q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24); };
+        const uint32_t isize = size ? le32(m + size - 4) : 0;
+        if (!size || isize > 65536) { r->bstop = true; break; }     // not a BGZF member (or the chain leaves the file): gzread goes on here
+        if (isize) {
+            W.tab.push_back(lnr_rdgpu_bgzf_blk{r->bpos + doff - c0, fresh, size - doff - 8, isize, le32(m + size - 8), 0});
+            r->chain.push_back(lnr_win::Block{r->bpos, size, isize});
+            fresh += isize; tl += isize;
+        }
+        r->bpos += size;
+    }
+    if (!r->bend && !r->bstop && r->bpos >= r->map_len) r->bend = true;
+    if (!tl) {
+        if (r->bend) return GOT_END;
+        if (r->bstop) return bgzf_give_way(r) ? GOT_AGAIN : (*st = LNR_ERR_ARG, GOT_ERROR);
+    }
+    if (tl + 65536 > lnr_win::WINDOW_MAX && tl < want) return fail(r, st, LNR_ERR_LIMIT, TOO_LONG);
+    W.job.comp = r->map + c0; W.job.comp_len = r->bpos - c0; W.job.blk = W.tab.data(); W.job.nblk = (uint32_t)W.tab.size();
+    W.job.keep_from = r->dtext.keep_from; W.job.carry = r->dtext.carry; W.job.new_text = fresh;
+    W.len = tl; W.ended = r->bend;
+    return GOT_WINDOW;
+}
+
+// SRC_MAP: the next bytes of the mapped file
+static Got map_window(Call &c, uint64_t want, Window &W, lnr_status *) {
+    lnr_reader *r = c.r;
+    while (r->mpos < r->map_len && is_ws(r->map[r->mpos])) r->mpos++;
+    if (r->mpos >= r->map_len) return GOT_END;
+    W.w.text = r->map + r->mpos; W.w.len = W.len = r->map_len - r->mpos < want ? r->map_len - r->mpos : want;
+    W.ended = r->mpos + W.len == r->map_len;
+    return GOT_WINDOW;
+}
+
+// SRC_STREAM: an inflate stream (or any file the reader does not map), gzread into a pinned buffer.  BAM: the header is passed here, the
+// records go up as they are
+static Got stream_window(Call &c, uint64_t want, Window &W, lnr_status *st) {
+    lnr_reader *r = c.r;
+    const uint64_t have = r->end - r->pos;
+    if (want < have + 16) want = have + 16;
+    uint8_t *S = lnr_rdgpu_stage(r->gpu, want);
+    if (!S) return fail(r, st, LNR_ERR_NOMEM, "pinned host allocation failed");
+    memcpy(S, r->buf.data() + r->pos, have);
+    r->pos = r->end = 0;
+    uint64_t len = have, lead = 0;
+    while (!r->gz_done && len < want) {
+        const uint64_t ask = want - len < (1u << 30) ? want - len : (1u << 30);
+        int got = gzread(r->f, S + len, (unsigned)ask);
+        if (got < 0) { int e; return fail(r, st, LNR_ERR_ARG, gzerror(r->f, &e)); }
+        if (got == 0) r->gz_done = true;
+        len += (uint64_t)got; r->gz_bytes += (uint64_t)got;
+    }
+    const bool eof = W.ended = r->gz_done;
+    if (r->format == 0 && lnr_bam::is_magic(S, len)) r->format = 3;
+    if (r->format == 3 && !r->bam_hdr) {
+        const lnr_bam::Header h = lnr_bam::header_span(S, len);
+        if (h.status < 0) return bam_header_fail(r, st, "not a BAM header");
+        if (h.status == 1) {
+            if (eof) return bam_header_fail(r, st, "the file ends inside the BAM header");
+            if (len >= lnr_win::WINDOW_MAX) return fail(r, st, LNR_ERR_LIMIT, "the BAM header is longer than the reader's window");
+            put_back(r, S, len); c.grow *= 2;
+            return GOT_AGAIN;
+        }
+        r->bam_hdr = true; r->bam_nref = h.n_ref; r->bam_off = h.first; lead = h.first;
+    }
+    if (r->format != 3) while (lead < len && is_ws(S[lead])) lead++;
+    if (len == lead) return eof ? GOT_END : GOT_AGAIN;
+    W.w.text = S + lead; W.w.len = len - lead; W.w.pinned = 1; W.len = r->format == 3 ? len : len - lead;
+    return GOT_WINDOW;
+}
+
+// the names of a window of host text in the form the gather gives them: the header spans over the text itself, trailing '\r' dropped
+static void names_of_spans(lnr_reader *r, const unsigned char *text, const uint64_t *hdr, uint64_t n, lnr_rdgpu_names *out) {
+    r->span_off.resize(n); r->span_len.resize(n);
+    for (uint64_t k = 0; k < n; k++) {
+        uint64_t hb = hdr[2 * k], he = hdr[2 * k + 1];
+        while (he > hb && text[he - 1] == '\r') he--;
+        r->span_off[k] = hb; r->span_len[k] = (uint32_t)(he - hb);
+    }
+    *out = lnr_rdgpu_names{(const char *)text, r->span_off.data(), r->span_len.data()};
+}
+
+// the parse of a window: device text (blocks inflated first) or host text, text records or BAM.  GOT_AGAIN: nothing was parsed, the file
+// turned out to be a BAM and the source has been told
+static Got parse_window(Call &c, Window &W, Parsed &P, lnr_status *st) {
+    lnr_reader *r = c.r;
+    const bool dev = r->src == SRC_BGZF || r->src == SRC_GZIP;
+    lnr_rdgpu_bam_result bb{};
+    if (dev) {
+        bool &failed = r->src == SRC_GZIP ? r->gz_failed : r->bfailed;
+        lnr_rdgpu_bgzf_result br{};
+        const lnr_rdgpu_bam_in in{r->bam_hdr ? 1 : 0, r->bam_nref};
+        W.w.fmt = r->format;
+        // BAM records, not text: the same inflate, then find / stitch / take / emit
+        if (int s = r->format == 3 ? lnr_rdgpu_parse_bam(r->gpu, &W.job, &W.w, &in, &P.res, &bb, r->gerr, sizeof r->gerr)
+                                   : lnr_rdgpu_parse_bgzf(r->gpu, &W.job, &W.w, &P.res, &br, r->gerr, sizeof r->gerr)) { failed = true; return gfail(r, st, s); }
+        const lnr_rdgpu_badblk bad = r->format == 3 ? bb.bad_block : br.bad_block;
+        if (bad.status) {                                             // a call that meets a bad block delivers no block
+            snprintf(r->gerr, sizeof r->gerr, "BGZF block at file offset %llu: %s", (unsigned long long)r->chain[W.chain0 + bad.blk].off, lnr_inf::status_text(bad.status));
+            return r->bfailed = true, gfail(r, st, LNR_ERR_ARG);
+        }
+        r->ist_last.blocks += W.tab.size(); r->ist_last.compressed_bytes += W.job.comp_len; r->ist_last.text_bytes += W.job.new_text;
+        if (r->format == 3) {
+            if (bb.hdr_state == 2) return bam_header_fail(r, st, "not a BAM header");
+            if (bb.hdr_state == 1 && r->bend) return bam_header_fail(r, st, "the file ends inside the BAM header");
+            if (bb.hdr_state == 0 && !r->bam_hdr) { r->bam_hdr = true; r->bam_nref = bb.n_ref; r->bam_off = bb.lead; }
+            P.lead = bb.lead;                                         // (the header was moved out of the device text)
+        } else {
+            r->text_made += W.job.new_text;
+            if (r->format == 0 && W.w.fmt == 3) {                     // "BAM\1"
+                if (r->src == SRC_GZIP) return gz_to_stream(r) ? GOT_AGAIN : (*st = LNR_ERR_ARG, GOT_ERROR);     // in a plain gzip file: read through gzread, as without the switch
+                r->format = 3; r->dtext = DevText{0, W.len};          // the text stays on the device whole, the next pass reads it as records
+                return GOT_AGAIN;
+            }
+            if (r->format == 0 && br.first >= 0) r->format = W.w.fmt;
+            P.parsed = br.parsed; P.lead = br.lead; P.names = br.names; P.passed = P.res.n;
+            P.handover = br.parsed ? P.res.handover != 0 : br.first >= 0;      // not a record start: the serial parser reports it
+        }
+    } else if (r->format == 3) {
+        const lnr_rdgpu_bam_in in{1, r->bam_nref};
+        W.w.fmt = 3;
+        if (int s = lnr_rdgpu_parse_bam(r->gpu, nullptr, &W.w, &in, &P.res, &bb, r->gerr, sizeof r->gerr)) return gfail(r, st, s);
+    } else {
+        const unsigned char *text = W.w.text;
+        if (r->format == 0) r->format = text[0] == '>' ? 1 : (text[0] == '@' ? 2 : -1);
+        P.handover = r->format < 0 || text[0] != (r->format == 1 ? '>' : '@');       // (the serial parser reports it)
+        if (!P.handover) {
+            W.w.fmt = r->format;
+            if (int s = lnr_rdgpu_parse(r->gpu, &W.w, &P.res, r->gerr, sizeof r->gerr)) return gfail(r, st, s);
+            names_of_spans(r, text, P.res.hdr, P.res.n, &P.names);     // (no gather here: it would cost a launch and a download per window)
+            P.parsed = true; P.passed = P.res.n; P.handover = P.res.handover != 0;
+        }
+    }
+    if (r->format == 3) {                                             // the error the host reader would meet here, the position in the stream, the counts
+        if (bb.bad) { *st = bam_fail(r, r->bam_ord + bb.bad_ord, r->bam_off + bb.bad_off, bb.bad == 1 ? BAM_INVALID : BAM_CUT); return GOT_ERROR; }
+        r->bam_ord += bb.passed; r->bam_off += P.res.consumed;
+        const lnr_bam_counts wc{P.res.n, bb.skipped, bb.reverse, bb.tiles, bb.repaired, bb.find_ms, bb.stitch_ms, bb.emit_ms};
+        counts_add(r->bam_last, wc);
+        P.parsed = true; P.passed = bb.passed; P.names = bb.names;
+    }
+    return GOT_WINDOW;
+}
+
+// a window was parsed: its names, its records and bases join the block and the totals
+static void window_parsed(Call &c, const Parsed &P) {
+    lnr_reader *r = c.r;
+    for (uint64_t k = 0; k < P.res.n; k++) {
+        const char *id = P.names.ids + P.names.id_off[k];
+        r->ids.insert(r->ids.end(), id, id + P.names.id_len[k]);
+        r->ids.push_back('\0'); r->id_off.push_back(r->ids.size());
+    }
+    c.n += (uint32_t)P.res.n; c.used += P.res.bases; r->records += P.res.n; r->bases += P.res.bases;
+    r->g_recs += P.passed; r->g_text += P.res.consumed;
+}
+
+// the source learns what the window used up (`lead` bytes in front of the parsed text, `consumed` of it); the rest stays for the next
+// window.  Returns the bytes that stay; false: a source that had to give way could not
+static bool window_used(Call &c, const Window &W, const Parsed &P, uint64_t *left) {
+    lnr_reader *r = c.r;
+    const uint64_t consumed = P.parsed ? P.res.consumed : 0, adv = P.lead + consumed;
+    switch (r->src) {
+    case SRC_GZIP: case SRC_BGZF:
+        r->dtext.keep_from = P.parsed ? consumed : P.lead;            // (a parse moves its text to the front of the device text)
+        r->dtext.carry = *left = W.len - adv;
+        if (r->src == SRC_BGZF) {
+            lnr_win::chain_advance(r->chain, r->bskip, adv);
+            if (r->bstop && !P.handover) return bgzf_give_way(r);     // (a hand-over ends the chain by itself)
+        }
+        break;
+    case SRC_MAP: r->mpos += consumed; *left = W.w.len - consumed; break;
+    case SRC_STREAM: put_back(r, W.w.text + consumed, *left = W.w.len - consumed); break;
+    }
+    return true;
+}
+
+// the serial parser takes the rest of the file: the stream goes on at the first byte the device has not used up
+static bool to_serial(lnr_reader *r) {
+    if (r->src == SRC_GZIP) return gz_to_stream(r);
+    if (r->src == SRC_BGZF) return bgzf_to_stream(r);
+    if (r->src == SRC_MAP) { r->src = SRC_STREAM; gzseek(r->f, (z_off_t)r->mpos, SEEK_SET); r->pos = r->end = 0; r->eof = false; }
+    return true;
+}
+
 extern "C" {
 
 lnr_status lnr_reader_open(const char *path, lnr_reader **out) {
@@ -274,14 +554,14 @@ lnr_status lnr_reader_open(const char *path, lnr_reader **out) {
         unsigned char magic[2] = {0, 0};
         if (fd >= 0 && fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 2 && pread(fd, magic, 2, 0) == 2 && !(magic[0] == 0x1f && magic[1] == 0x8b)) {
             void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m != MAP_FAILED) { r->map = (const unsigned char *)m; r->map_len = (size_t)st.st_size; r->use_map = true; (void)madvise(m, r->map_len, MADV_SEQUENTIAL); }
+            if (m != MAP_FAILED) { r->map = (const unsigned char *)m; r->map_len = (size_t)st.st_size; r->src = SRC_MAP; (void)madvise(m, r->map_len, MADV_SEQUENTIAL); }
         } else if (fd >= 0 && magic[0] == 0x1f && magic[1] == 0x8b && S_ISREG(st.st_mode) && st.st_size >= 18 && !(getenv("LNR_READER_BGZF") && atoi(getenv("LNR_READER_BGZF")) == 0)) {
             // gzip: BGZF when the first member says so (the walk of the other members waits for the windows that need them)
             void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
             uint32_t doff = 0;
             if (m != MAP_FAILED && lnr_inf::bgzf_member((const uint8_t *)m, (uint64_t)st.st_size, doff)) {
                 r->map = (const unsigned char *)m; r->map_len = (size_t)st.st_size; (void)madvise(m, r->map_len, MADV_SEQUENTIAL);
-                r->bgzf = true; r->bfd = fd; fd = -1;                 // (the serial and host paths still read through r->f)
+                r->src = SRC_BGZF; r->bfd = fd; fd = -1;                 // (the serial and host paths still read through r->f)
             } else if (m != MAP_FAILED) munmap(m, (size_t)st.st_size);
         }
         if (fd >= 0) close(fd);
@@ -310,7 +590,7 @@ const char *lnr_reader_error(const lnr_reader *r) { return r ? r->err.c_str() : 
 // 3 when the file is a BAM (looked up in the stream's first bytes where nothing was read yet), else the format decided so far
 int lnr_reader_format(lnr_reader *r) {
     if (!r) return 0;
-    if (r->format == 0 && !r->use_map && r->fill() && lnr_bam::is_magic(r->buf.data() + r->pos, r->end - r->pos)) r->format = 3;
+    if (r->format == 0 && r->src != SRC_MAP && r->fill() && lnr_bam::is_magic(r->buf.data() + r->pos, r->end - r->pos)) r->format = 3;
     return r->format;
 }
 
@@ -327,7 +607,7 @@ static lnr_status next_from(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint6
         n = 1; off[1] = used; r->id_off.push_back(r->ids.size());
         r->have_spill = false; r->spill.clear(); r->spill_id.clear();
     }
-    if (r->use_map && !r->have_spill && !serial_only) {
+    if (r->src == SRC_MAP && !r->have_spill && !serial_only) {
         struct Rec { size_t hdr, hdr_end, seq, seq_end; uint64_t nb; };
         std::vector<Rec> recs;
         const unsigned char *M = r->map;
@@ -433,7 +713,7 @@ static lnr_status next_from(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint6
         }
         r->mpos = pos;
         if (fallback_at != (size_t)-1) {                              // the serial parser takes over from this record on
-            r->use_map = false;
+            r->src = SRC_STREAM;
             gzseek(r->f, (z_off_t)fallback_at, SEEK_SET);
             r->pos = r->end = 0; r->eof = false;
         } else { *n_out = n; return LNR_OK; }
@@ -509,13 +789,13 @@ lnr_status lnr_reader_next(lnr_reader *r, uint8_t *dst, uint64_t dst_cap, uint64
     off[0] = 0;
     r->ids.clear(); r->id_off.assign(1, 0);
     r->started = true;
-    if (r->gz_live) {
+    if (r->src == SRC_GZIP) {
         if (r->gz_failed) { r->err = r->gerr; return LNR_ERR_ARG; }
-        if (r->text_made == 0) r->gz_live = false;                    // nothing was read on the device: r->f stands at the start of the file
+        if (r->text_made == 0) r->src = SRC_STREAM;                   // nothing was read on the device: r->f stands at the start of the file
         else if (!gz_to_stream(r)) return LNR_ERR_ARG;
     }
-    if (r->bgzf) {
-        if (r->bpos == 0 && r->chain.empty()) r->bgzf = false;       // nothing was read on the device: r->f stands at the start of the file, as ever
+    if (r->src == SRC_BGZF) {
+        if (r->bpos == 0 && r->chain.empty()) r->src = SRC_STREAM;   // nothing was read on the device: r->f stands at the start of the file, as ever
         else if (!bgzf_to_stream(r)) return LNR_ERR_ARG;              // next_dev has read ahead on the device: the stream goes on where it stopped
     }
     const uint64_t gz0 = r->gz_bytes;
@@ -570,14 +850,14 @@ lnr_status lnr_reader_gpu_gzip(lnr_reader *r, int on) {
     if (r->started) { r->err = "lnr_reader_gpu_gzip: the reader has been read from"; return LNR_ERR_ARG; }
     if (!lnr_rdgpu_gzip_round) { r->err = "lnr_reader_gpu_gzip: this library was linked without its device half"; return LNR_ERR_NO_DEVICE; }
     if (!on) {
-        if (r->gz_live) { r->gz_live = false; if (r->map) munmap((void *)r->map, r->map_len); r->map = nullptr; r->map_len = 0; }
+        if (r->src == SRC_GZIP) { r->src = SRC_STREAM; if (r->map) munmap((void *)r->map, r->map_len); r->map = nullptr; r->map_len = 0; }
         r->gzp = false;
         return LNR_OK;
     }
     if (r->gzp) return LNR_OK;
     if (getenv("LNR_READER_SERIAL") || (getenv("LNR_READER_BGZF") && atoi(getenv("LNR_READER_BGZF")) == 0)) return LNR_OK;   // the file is read as any gzip file
     r->gzp = true;
-    if (r->bgzf || r->use_map || r->map) return LNR_OK;              // BGZF keeps precedence (the rounds take over at a member that is not BGZF); plain text
+    if (r->src != SRC_STREAM || r->map) return LNR_OK;              // BGZF keeps precedence (the rounds take over at a member that is not BGZF); plain text
     int fd = open(r->path.c_str(), O_RDONLY);
     struct stat st;
     unsigned char magic[2] = {0, 0};
@@ -586,7 +866,7 @@ lnr_status lnr_reader_gpu_gzip(lnr_reader *r, int on) {
         void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
         if (m != MAP_FAILED) {
             r->map = (const unsigned char *)m; r->map_len = (size_t)st.st_size; (void)madvise(m, r->map_len, MADV_SEQUENTIAL);
-            r->gz_live = true; r->gz_pos = 0;
+            r->src = SRC_GZIP;
         }
     }
     if (fd >= 0) close(fd);
@@ -627,11 +907,10 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
     if (!r || !d_reads_concat || !d_off || !off || !n_out) return LNR_ERR_ARG;
     *n_out = 0;
     if (!r->gpu) { r->err = "lnr_reader_gpu_open has not been called on this reader"; return LNR_ERR_ARG; }
-    auto gfail = [&](int s) { r->err = r->gerr; return (lnr_status)s; };
-    const uint32_t slot = r->gslot;
+    Call c{r, r->gslot};
     uint8_t *dr; uint64_t *dof, *ho;
-    if (int s = lnr_rdgpu_block(r->gpu, slot, dst_cap, max_reads, &dr, &dof, &ho, r->gerr, sizeof r->gerr)) return gfail(s);
-    r->gslot = (slot + 1) % r->gslots;
+    if (int s = lnr_rdgpu_block(r->gpu, c.slot, dst_cap, max_reads, &dr, &dof, &ho, r->gerr, sizeof r->gerr)) { r->err = r->gerr; return (lnr_status)s; }
+    r->gslot = (c.slot + 1) % r->gslots;
     lnr_rdgpu_times_reset(r->gpu);
     r->ids.clear(); r->id_off.assign(1, 0);
     r->ist_last = lnr_inflate_counts{};
@@ -639,394 +918,57 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
     r->gzs_last = lnr_rdgpu_gz_counts{};
     r->started = true;
     if (r->bam_failed) return LNR_ERR_ARG;
-    const uint64_t gz0 = r->gz_bytes;
     struct StatsAtExit {                                          // the counts of this call join the totals however it ends
         lnr_reader *r; uint64_t gz0;
         ~StatsAtExit() {
-            lnr_inflate_counts &l = r->ist_last, &t = r->ist_total;
-            double ms2[2] = {0, 0};
+            double ms2[2] = {0, 0}, ms5[5] = {0, 0, 0, 0, 0};
             if (lnr_rdgpu_inflate_times) lnr_rdgpu_inflate_times(r->gpu, ms2);
-            l.gzread_bytes = r->gz_bytes - gz0; l.inflate_ms = ms2[0]; l.gather_ms = ms2[1];
-            t.blocks += l.blocks; t.compressed_bytes += l.compressed_bytes; t.text_bytes += l.text_bytes; t.gzread_bytes += l.gzread_bytes;
-            t.inflate_ms += l.inflate_ms; t.gather_ms += l.gather_ms;
-            lnr_bam_counts &bl = r->bam_last, &bt = r->bam_total;
-            bt.records += bl.records; bt.skipped += bl.skipped; bt.reverse += bl.reverse; bt.tiles += bl.tiles; bt.repaired_tiles += bl.repaired_tiles;
-            bt.find_ms += bl.find_ms; bt.stitch_ms += bl.stitch_ms; bt.emit_ms += bl.emit_ms;
-            if (r->gzp) {
-                double ms5[5] = {0, 0, 0, 0, 0};
-                lnr_rdgpu_times(r->gpu, ms5);
-                r->gzs_last.gzread_bytes = r->gz_bytes - gz0; r->gzs_last.parse_ms = ms5[1] + ms5[2] + ms5[3]; r->gzs_last.download_ms = ms5[4];
-                lnr_rdgpu_gz_add(&r->gzs_total, &r->gzs_last);
-            }
+            r->ist_last.gzread_bytes = r->gz_bytes - gz0; r->ist_last.inflate_ms = ms2[0]; r->ist_last.gather_ms = ms2[1];
+            counts_add(r->ist_total, r->ist_last);
+            counts_add(r->bam_total, r->bam_last);
+            if (!r->gzp) return;
+            lnr_rdgpu_times(r->gpu, ms5);
+            r->gzs_last.gzread_bytes = r->gz_bytes - gz0; r->gzs_last.parse_ms = ms5[1] + ms5[2] + ms5[3]; r->gzs_last.download_ms = ms5[4];
+            lnr_rdgpu_gz_add(&r->gzs_total, &r->gzs_last);
         }
-    } stats_at_exit{r, gz0};
-    uint64_t wcap = 256ULL << 20, grow = 1, used = 0;
+    } stats_at_exit{r, r->gz_bytes};
+    uint64_t wcap = lnr_win::WINDOW_CAP;
     if (const char *e = getenv("LNR_READER_GPU_WINDOW")) { long long v = atoll(e); if (v >= 16) wcap = (uint64_t)v; }
-    if (wcap > (1ULL << 30)) wcap = 1ULL << 30;
-    uint32_t n = 0;
-    bool full = false;
-    auto is_ws = [](unsigned char c) { return c == '\n' || c == '\r' || c == ' ' || c == '\t'; };
-    // BAM: what a window's parse leaves behind it -- the error the host reader would meet here, the position in the stream, the counts, the names
-    auto bam_done = [&](const lnr_rdgpu_result &res, const lnr_rdgpu_bam_result &bb) -> lnr_status {
-        if (bb.bad) return bam_fail(r, r->bam_ord + bb.bad_ord, r->bam_off + bb.bad_off, bb.bad == 1 ? BAM_INVALID : BAM_CUT);
-        r->bam_ord += bb.passed; r->bam_off += res.consumed;
-        lnr_bam_counts &c = r->bam_last;
-        c.records += res.n; c.skipped += bb.skipped; c.reverse += bb.reverse; c.tiles += bb.tiles; c.repaired_tiles += bb.repaired;
-        c.find_ms += bb.find_ms; c.stitch_ms += bb.stitch_ms; c.emit_ms += bb.emit_ms;
-        for (uint64_t k = 0; k < res.n; k++) {
-            r->ids.insert(r->ids.end(), bb.ids + bb.id_off[k], bb.ids + bb.id_off[k] + bb.id_len[k]);
-            r->ids.push_back('\0');
-            r->id_off.push_back(r->ids.size());
-        }
-        return LNR_OK;
-    };
-    auto bam_header_fail = [&](const char *why) { r->err = why; r->bam_failed = true; return LNR_ERR_ARG; };
-    while (!r->gpu_serial && !r->have_spill && n < max_reads) {
-        const uint64_t freeb = dst_cap - used, allowed = max_reads - n;
-        // the window: what the free bases can take as text, but no more than the records still allowed will probably need -- by the bytes
-        // per record seen so far (a first window guesses 1 KiB per record; a window that runs out is followed by the next one)
-        uint64_t want = freeb * (r->format == 1 ? 1 : 2) + freeb / 50 + allowed * 128 + 65536;
-        const uint64_t per_rec = r->g_recs ? r->g_text / r->g_recs + 1 : 1024;
-        const uint64_t by_recs = allowed * (per_rec + per_rec / 8) + 65536;
-        if (want > by_recs) want = by_recs;
-        if (want > wcap) want = wcap;
-        want *= grow;
-        if (want > (1ULL << 30)) want = 1ULL << 30;
-        lnr_rdgpu_window w{};
-        const unsigned char *text = nullptr;
-        uint64_t len = 0, lead = 0;
-        bool eof = false;
-        if (r->gz_live) {                                         // plain gzip: rounds of the member inflated on the device behind what the last window left
-            if (r->gz_failed) { if (n) break; r->err = r->gerr; return LNR_ERR_ARG; }
-            const uint64_t chunk = lnr_gz::env_bytes("LNR_READER_GZ_CHUNK", 128ULL << 10, 1024, 1ULL << 30), round = lnr_gz::env_bytes("LNR_READER_GZ_ROUND", 64ULL << 20, 1024, 1ULL << 31);
-            constexpr uint64_t TEXT_MAX = (1ULL << 30) - 65536;
-            bool stuck = false;
-            if (lnr_status s = gz_next_member(r)) { if (n) break; return s; }
-            while (!r->gz_end && !r->gz_failed && r->gcarry < want && !stuck) {
-                const uint64_t rb = r->gz_bit >> 3;
-                if (rb >= r->map_len) { gz_fail(r, lnr_inf::E_INPUT_END, r->map_len); break; }      // the file ends behind a member's header
-                if (r->gcarry >= TEXT_MAX) { stuck = true; break; }
-                uint64_t rsize = want - r->gcarry + 2 * chunk;            // text is seldom smaller than its compressed bytes: no more of them than text is wanted
-                if (rsize > round) rsize = round;
-                if (rsize > (1ULL << 31) / r->gz_grow) rsize = 1ULL << 31; else rsize *= r->gz_grow;
-                const uint64_t clen = r->map_len - rb < rsize ? r->map_len - rb : rsize;
-                lnr_rdgpu_gzip job{};
-                job.comp = r->map + rb; job.comp_len = clen; job.start_bit = (uint32_t)(r->gz_bit & 7); job.hist = r->gz_hist; job.chunk = chunk;
-                job.keep_from = r->gkeep_from; job.carry = r->gcarry; job.text_cap = TEXT_MAX - r->gcarry; job.threads = r->threads;
-                lnr_rdgpu_gzip_result gr{};
-                if (int s = lnr_rdgpu_gzip_round(r->gpu, &job, &gr, r->gerr, sizeof r->gerr)) { r->gz_failed = true; return gfail(s); }
-                lnr_rdgpu_gz_counts c = gr.counts;
-                if (gr.status) { lnr_rdgpu_gz_add(&r->gzs_last, &c); gz_fail(r, gr.status, rb + gr.bad_off); break; }
-                if (!gr.pieces) {                                 // no block completed
-                    c.grown_rounds = 1;
-                    lnr_rdgpu_gz_add(&r->gzs_last, &c);
-                    if (gr.stop == lnr_gz::AT_BUDGET) { stuck = true; break; }                     // the device text is full: what it holds is parsed first
-                    if (rb + clen >= r->map_len) { gz_fail(r, lnr_inf::E_INPUT_END, rb); break; }
-                    if (rsize >= (1ULL << 31)) { r->err = "a DEFLATE block is longer than the reader's staging limit"; return LNR_ERR_LIMIT; }
-                    r->gz_grow *= 2;
-                    continue;
-                }
-                r->gz_grow = 1;
-                r->gkeep_from = 0; r->gcarry += gr.text; r->text_made += gr.text;
-                r->gz_bit = rb * 8 + gr.end_bit;
-                r->gz_crc = lnr_inf::crc_combine(r->gz_crc, gr.crc, gr.text);
-                r->gz_hist = r->gz_hist + gr.text > lnr_gz::WIN ? lnr_gz::WIN : (uint32_t)(r->gz_hist + gr.text);
-                r->gz_mtext += gr.text;
-                c.compressed_bytes = ((r->gz_bit + 7) >> 3) - rb;
-                if (gr.stop == lnr_gz::AT_FINAL) {                // the trailer; then the next member, or the end of the file
-                    uint64_t next = 0;
-                    const uint32_t st = lnr_gz::check_trailer(r->map, r->map_len, r->gz_bit, r->gz_crc, r->gz_mtext, &next);
-                    if (st) { lnr_rdgpu_gz_add(&r->gzs_last, &c); gz_fail(r, st, (r->gz_bit + 7) >> 3); break; }   // (the text in front of it is delivered, as gzread delivers it)
-                    c.members = 1;
-                    r->gz_in_member = false; r->gz_pos = next;
-                    lnr_rdgpu_gz_add(&r->gzs_last, &c);
-                    if (gz_next_member(r)) break;
-                    continue;
-                }
-                lnr_rdgpu_gz_add(&r->gzs_last, &c);
-                if (gr.stop == lnr_gz::AT_BUDGET) { stuck = true; break; }
-            }
-            const uint64_t tl = r->gcarry;
-            const bool gend = r->gz_end || r->gz_failed;
-            if (!tl) {
-                if (r->gz_failed) { if (n) break; r->err = r->gerr; return LNR_ERR_ARG; }
-                if (r->gz_end) break;
-                r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT;
-            }
-            lnr_rdgpu_bgzf job{};                                 // no block to inflate: the parse of the device text
-            job.keep_from = r->gkeep_from; job.carry = tl;
-            lnr_rdgpu_window w{};
-            w.fmt = r->format; w.eof = gend; w.slot = slot; w.threads = r->threads;
-            w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
-            lnr_rdgpu_result res{};
-            lnr_rdgpu_bgzf_result br{};
-            if (int s = lnr_rdgpu_parse_bgzf(r->gpu, &job, &w, &res, &br, r->gerr, sizeof r->gerr)) { r->gz_failed = true; return gfail(s); }
-            if (r->format == 0 && w.fmt == 3) {                   // "BAM\1" in a plain gzip file: read through gzread, as without the switch
-                r->gkeep_from = 0;
-                if (!gz_to_stream(r)) return LNR_ERR_ARG;
-                continue;
-            }
-            if (r->format == 0 && br.first >= 0) r->format = w.fmt;
-            bool handover = br.first >= 0 && !br.parsed;
-            if (br.parsed) {
-                for (uint64_t k = 0; k < res.n; k++) {
-                    r->ids.insert(r->ids.end(), br.ids + br.id_off[k], br.ids + br.id_off[k] + br.id_len[k]);
-                    r->ids.push_back('\0');
-                    r->id_off.push_back(r->ids.size());
-                }
-                n += (uint32_t)res.n; used += res.bases;
-                r->records += res.n; r->bases += res.bases;
-                r->g_recs += res.n; r->g_text += res.consumed;
-                handover = res.handover != 0;
-            }
-            const uint64_t adv = br.lead + (br.parsed ? res.consumed : 0);
-            r->gkeep_from = br.parsed ? res.consumed : br.lead;
-            r->gcarry = tl - adv;
-            if (handover) {
-                if (r->gz_failed) { r->err = r->gerr; return LNR_ERR_ARG; }
-                if (!gz_to_stream(r)) return LNR_ERR_ARG;
-                r->gpu_serial = true;
-                break;
-            }
-            if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
-            if (res.full) { full = true; break; }
-            if (gend && r->gcarry == 0) { if (r->gz_failed && !n) { r->err = r->gerr; return LNR_ERR_ARG; } break; }
-            if (br.parsed && res.n == 0) {
-                if (stuck || gend) {
-                    if (r->gz_failed) { r->err = r->gerr; return LNR_ERR_ARG; }
-                    r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT;
-                }
-                grow *= 2;
-            }
-            continue;
-        }
-        if (r->bgzf) {                                            // a run of whole BGZF blocks, inflated on the device behind what the last window left
-            if (r->bfailed) { r->err = r->gerr; return LNR_ERR_ARG; }
-            std::vector<lnr_rdgpu_bgzf_blk> tab;
-            const uint64_t c0 = r->bpos, chain0 = r->chain.size();
-            uint64_t fresh = 0, tl = r->bcarry;
-            while (!r->bend && !r->bstop && tl < want && tl + 65536 <= (1ULL << 30) && r->bpos - c0 < (1ULL << 30)) {
-                if (r->bpos >= r->map_len) { r->bend = true; break; }
-                uint32_t doff = 0;
-                const unsigned char *m = r->map + r->bpos;
-                const uint32_t size = lnr_inf::bgzf_member(m, r->map_len - r->bpos, doff);
-                auto le32 = [](const unsigned char *q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24); };
-                const uint32_t isize = size ? le32(m + size - 4) : 0;
-                if (!size || isize > 65536) { r->bstop = true; break; }     // not a BGZF member (or the chain leaves the file): gzread goes on here
-                if (isize) {
-                    tab.push_back(lnr_rdgpu_bgzf_blk{r->bpos + doff - c0, fresh, size - doff - 8, isize, le32(m + size - 8), 0});
-                    r->chain.push_back(lnr_reader::BBlk{r->bpos, size, isize});
-                    fresh += isize; tl += isize;
-                }
-                r->bpos += size;
-            }
-            if (!r->bend && !r->bstop && r->bpos >= r->map_len) r->bend = true;
-            // with lnr_reader_gpu_gzip the gzip rounds take over at a member that is not BGZF, where gzread takes over without it
-            auto to_rounds = [&]() {
-                r->bgzf = false; r->chain.clear(); r->bskip = 0;
-                r->gz_live = true; r->gz_pos = r->bpos; r->gz_in_member = false; r->gz_end = false;
-                r->gkeep_from = r->bkeep_from; r->gcarry = r->bcarry; r->bkeep_from = r->bcarry = 0;
-            };
-            if (!tl) {
-                if (r->bend) break;
-                if (r->bstop) {
-                    if (r->gzp && r->format != 3) { to_rounds(); continue; }
-                    if (!bgzf_to_stream(r)) return LNR_ERR_ARG;
-                    continue;
-                }
-            }
-            if (tl + 65536 > (1ULL << 30) && tl < want) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
-            lnr_rdgpu_bgzf job{};
-            job.comp = r->map + c0; job.comp_len = r->bpos - c0; job.blk = tab.data(); job.nblk = (uint32_t)tab.size();
-            job.keep_from = r->bkeep_from; job.carry = r->bcarry; job.new_text = fresh;
-            lnr_rdgpu_window w{};
-            w.fmt = r->format; w.eof = r->bend; w.slot = slot; w.threads = r->threads;
-            w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
-            lnr_rdgpu_result res{};
-            // a call that meets a bad block delivers no block
-            auto bad_block = [&](uint32_t blk, uint32_t status) {
-                snprintf(r->gerr, sizeof r->gerr, "BGZF block at file offset %llu: %s", (unsigned long long)r->chain[chain0 + blk].off, lnr_inf::status_text(status));
-                r->bfailed = true;
-                return gfail(LNR_ERR_ARG);
-            };
-            // what the window used up (`lead` bytes in front of the parsed text, `consumed` of it) leaves the chain; the rest stays on the
-            // device for the next window, `keep_from` = where it starts in the device text
-            auto advance = [&](uint64_t lead, uint64_t consumed, uint64_t keep_from) {
-                const uint64_t adv = lead + consumed;
-                r->bkeep_from = keep_from;
-                r->bcarry = tl - adv;
-                r->bskip += adv;
-                size_t gone = 0;
-                while (gone < r->chain.size() && r->bskip >= r->chain[gone].isize) r->bskip -= r->chain[gone++].isize;
-                r->chain.erase(r->chain.begin(), r->chain.begin() + (long)gone);
-            };
-            // a window without a whole record is doubled
-            auto grow_window = [&]() -> bool {
-                if (tl + 65536 > (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return false; }
-                grow *= 2;
-                return true;
-            };
-            if (r->format == 3) {                                 // BAM records, not text: the same inflate, then find / stitch / take / emit
-                lnr_rdgpu_bam_result bb{};
-                const lnr_rdgpu_bam_in in{r->bam_hdr ? 1 : 0, r->bam_nref};
-                if (int s = lnr_rdgpu_parse_bam(r->gpu, &job, &w, &in, &res, &bb, r->gerr, sizeof r->gerr)) { r->bfailed = true; return gfail(s); }
-                if (bb.bad_status) return bad_block(bb.bad_blk, bb.bad_status);
-                r->ist_last.blocks += tab.size(); r->ist_last.compressed_bytes += job.comp_len; r->ist_last.text_bytes += fresh;
-                if (bb.hdr_state == 2) return bam_header_fail("not a BAM header");
-                if (bb.hdr_state == 1 && r->bend) return bam_header_fail("the file ends inside the BAM header");
-                if (bb.hdr_state == 0 && !r->bam_hdr) { r->bam_hdr = true; r->bam_nref = bb.n_ref; r->bam_off = bb.lead; }
-                if (lnr_status s = bam_done(res, bb)) return s;
-                n += (uint32_t)res.n; used += res.bases;
-                r->records += res.n; r->bases += res.bases;
-                r->g_recs += bb.passed; r->g_text += res.consumed;
-                advance(bb.lead, res.consumed, res.consumed);     // (the header was moved out of the device text)
-                if (r->bstop) { if (!bgzf_to_stream(r)) return LNR_ERR_ARG; }     // a member that is not BGZF: gzread goes on, inside the header too
-                if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
-                if (res.full) { full = true; break; }
-                if (r->bend && r->bcarry == 0) break;
-                if (res.n == 0 && res.consumed == 0 && r->bgzf && !grow_window()) return LNR_ERR_LIMIT;
-                continue;
-            }
-            lnr_rdgpu_bgzf_result br{};
-            if (int s = lnr_rdgpu_parse_bgzf(r->gpu, &job, &w, &res, &br, r->gerr, sizeof r->gerr)) { r->bfailed = true; return gfail(s); }
-            if (br.bad_status) return bad_block(br.bad_blk, br.bad_status);
-            r->ist_last.blocks += tab.size(); r->ist_last.compressed_bytes += job.comp_len; r->ist_last.text_bytes += fresh;
-            r->text_made += fresh;
-            if (r->format == 0 && w.fmt == 3) {                   // "BAM\1": the text stays on the device whole, the next pass reads it as records
-                r->format = 3; r->bkeep_from = 0; r->bcarry = tl;
-                continue;
-            }
-            if (r->format == 0 && br.first >= 0) r->format = w.fmt;
-            bool handover = br.first >= 0 && !br.parsed;          // not a record start: the serial parser reports it
-            if (br.parsed) {
-                for (uint64_t k = 0; k < res.n; k++) {
-                    r->ids.insert(r->ids.end(), br.ids + br.id_off[k], br.ids + br.id_off[k] + br.id_len[k]);
-                    r->ids.push_back('\0');
-                    r->id_off.push_back(r->ids.size());
-                }
-                n += (uint32_t)res.n; used += res.bases;
-                r->records += res.n; r->bases += res.bases;
-                r->g_recs += res.n; r->g_text += res.consumed;
-                handover = res.handover != 0;
-            }
-            advance(br.lead, br.parsed ? res.consumed : 0, br.parsed ? res.consumed : br.lead);
-            if (r->bstop && !handover && r->gzp) to_rounds();
-            else if (handover || r->bstop) {                      // the stream goes on at the first byte the device has not used up
-                if (!bgzf_to_stream(r)) return LNR_ERR_ARG;
-                if (handover) { r->gpu_serial = true; break; }
-            }
-            if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
-            if (res.full) { full = true; break; }
-            if (r->bend && r->bcarry == 0) break;
-            if (br.parsed && res.n == 0 && r->bgzf && !grow_window()) return LNR_ERR_LIMIT;
-            continue;
-        }
-        if (r->use_map) {
-            while (r->mpos < r->map_len && is_ws(r->map[r->mpos])) r->mpos++;
-            if (r->mpos >= r->map_len) break;
-            text = r->map + r->mpos;
-            len = r->map_len - r->mpos < want ? r->map_len - r->mpos : want;
-            eof = r->mpos + len == r->map_len;
-        } else {                                                  // an inflate stream (or any file the reader does not map): gzread into a pinned buffer
-            const uint64_t have = r->end - r->pos;
-            if (want < have + 16) want = have + 16;
-            uint8_t *S = lnr_rdgpu_stage(r->gpu, want);
-            if (!S) { r->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
-            memcpy(S, r->buf.data() + r->pos, have);
-            r->pos = r->end = 0;
-            len = have;
-            while (!r->gz_done && len < want) {
-                const uint64_t ask = want - len < (1u << 30) ? want - len : (1u << 30);
-                int got = gzread(r->f, S + len, (unsigned)ask);
-                if (got < 0) { int e; r->err = gzerror(r->f, &e); return LNR_ERR_ARG; }
-                if (got == 0) r->gz_done = true;
-                len += (uint64_t)got; r->gz_bytes += (uint64_t)got;
-            }
-            eof = r->gz_done;
-            if (r->format == 0 && lnr_bam::is_magic(S, len)) r->format = 3;
-            if (r->format == 3) {                                 // BAM through gzread: the header is passed here, the records go up as they are
-                auto put_back = [&](const uint8_t *p, uint64_t left) {
-                    if (r->buf.size() < left) r->buf.resize(left);
-                    memcpy(r->buf.data(), p, left);
-                    r->pos = 0; r->end = left;
-                };
-                if (!r->bam_hdr) {
-                    const lnr_bam::Header h = lnr_bam::header_span(S, len);
-                    if (h.status < 0) return bam_header_fail("not a BAM header");
-                    if (h.status == 1) {
-                        if (eof) return bam_header_fail("the file ends inside the BAM header");
-                        if (len >= (1ULL << 30)) { r->err = "the BAM header is longer than the reader's window"; return LNR_ERR_LIMIT; }
-                        put_back(S, len); grow *= 2;
-                        continue;
-                    }
-                    r->bam_hdr = true; r->bam_nref = h.n_ref; r->bam_off = h.first; lead = h.first;
-                }
-                if (len == lead) { if (eof) break; continue; }
-                w.fmt = 3; w.eof = eof; w.text = S + lead; w.len = len - lead; w.pinned = 1; w.slot = slot; w.threads = r->threads;
-                w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
-                const lnr_rdgpu_bam_in in{1, r->bam_nref};
-                lnr_rdgpu_result res{};
-                lnr_rdgpu_bam_result bb{};
-                if (int s = lnr_rdgpu_parse_bam(r->gpu, nullptr, &w, &in, &res, &bb, r->gerr, sizeof r->gerr)) return gfail(s);
-                if (lnr_status s = bam_done(res, bb)) return s;
-                n += (uint32_t)res.n; used += res.bases;
-                r->records += res.n; r->bases += res.bases;
-                r->g_recs += bb.passed; r->g_text += res.consumed;
-                put_back(S + lead + res.consumed, w.len - res.consumed);
-                if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
-                if (res.full) { full = true; break; }
-                if (eof && res.consumed == w.len) break;
-                if (res.n == 0 && res.consumed == 0) {
-                    if (len >= (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
-                    grow *= 2;
-                }
-                continue;
-            }
-            while (lead < len && is_ws(S[lead])) lead++;
-            text = S + lead; len -= lead;
-            w.pinned = 1;
-            if (!len) { if (eof) break; continue; }
-        }
-        if (r->format == 0) r->format = text[0] == '>' ? 1 : (text[0] == '@' ? 2 : -1);
-        uint64_t consumed = 0;
-        bool handover = r->format < 0 || text[0] != (r->format == 1 ? '>' : '@');       // (the serial parser reports it)
-        lnr_rdgpu_result res{};
-        if (!handover) {
-            w.fmt = r->format; w.eof = eof; w.text = text; w.len = len; w.slot = slot; w.threads = r->threads;
-            w.rec_base = n; w.base_base = used; w.allowed = allowed; w.free = freeb;
-            if (int s = lnr_rdgpu_parse(r->gpu, &w, &res, r->gerr, sizeof r->gerr)) return gfail(s);
-            for (uint64_t k = 0; k < res.n; k++) {
-                uint64_t hb = res.hdr[2 * k], he = res.hdr[2 * k + 1];
-                while (he > hb && text[he - 1] == '\r') he--;
-                r->ids.insert(r->ids.end(), (const char *)text + hb, (const char *)text + he);
-                r->ids.push_back('\0');
-                r->id_off.push_back(r->ids.size());
-            }
-            n += (uint32_t)res.n; used += res.bases; consumed = res.consumed;
-            r->records += res.n; r->bases += res.bases;
-            r->g_recs += res.n; r->g_text += res.consumed;
-            handover = res.handover != 0;
-        }
-        if (r->use_map) r->mpos += consumed;
-        else {                                                    // what the window did not use goes back in front of the stream
-            const uint64_t left = len - consumed;
-            if (r->buf.size() < left) r->buf.resize(left);
-            memcpy(r->buf.data(), text + consumed, left);
-            r->pos = 0; r->end = left;
-        }
-        if (handover) {
-            if (r->use_map) { r->use_map = false; gzseek(r->f, (z_off_t)r->mpos, SEEK_SET); r->pos = r->end = 0; r->eof = false; }
-            r->gpu_serial = true;
-            break;
-        }
-        if (res.too_big && n == 0) { r->err = "a record is longer than the block"; return LNR_ERR_LIMIT; }
-        if (res.full) { full = true; break; }
-        if (eof && consumed == len) break;
-        if (res.n == 0) {
-            if (len >= (1ULL << 30)) { r->err = "a record is longer than the reader's window"; return LNR_ERR_LIMIT; }
-            grow *= 2;
+    if (wcap > lnr_win::WINDOW_MAX) wcap = lnr_win::WINDOW_MAX;
+    bool full = false, more = true;
+    while (more && !r->gpu_serial && !r->have_spill && c.n < max_reads) {
+        Window W;
+        W.w.slot = c.slot; W.w.threads = r->threads;
+        W.w.rec_base = c.n; W.w.base_base = c.used; W.w.allowed = max_reads - c.n; W.w.free = dst_cap - c.used;
+        const uint64_t want = lnr_win::window_size(W.w.free, W.w.allowed, r->format == 1, r->g_text, r->g_recs, wcap, c.grow);
+        const Src src = r->src;
+        lnr_status st = LNR_OK;
+        Got got = src == SRC_GZIP ? gzip_window(c, want, W, &st) : src == SRC_BGZF ? bgzf_window(c, want, W, &st) : src == SRC_MAP ? map_window(c, want, W, &st) : stream_window(c, want, W, &st);
+        Parsed P;
+        W.w.eof = W.ended;
+        if (got == GOT_WINDOW) got = parse_window(c, W, P, &st);
+        if (got == GOT_AGAIN) continue;
+        if (got != GOT_WINDOW) { if (got == GOT_ERROR) return st; break; }
+        const bool bam = r->format == 3;
+        window_parsed(c, P);
+        lnr_win::Seen s{};
+        if (!window_used(c, W, P, &s.left)) return LNR_ERR_ARG;
+        s.site = src == SRC_GZIP ? lnr_win::GZIP_TEXT : src == SRC_BGZF ? (bam ? lnr_win::BGZF_BAM : lnr_win::BGZF_TEXT) : bam ? lnr_win::STREAM_BAM : lnr_win::HOST_TEXT;
+        s.handover = P.handover; s.too_big = P.res.too_big; s.full = P.res.full; s.n_block = c.n;
+        s.parsed = P.parsed; s.taken = P.res.n; s.consumed = P.res.consumed; s.len = W.len;
+        s.ended = W.ended; s.live = r->src == src; s.stuck = W.stuck; s.failed = src == SRC_GZIP && r->gz_failed;
+        switch (lnr_win::decide(s)) {
+        case lnr_win::HAND_OVER: if (!to_serial(r)) return LNR_ERR_ARG; r->gpu_serial = true; break;
+        case lnr_win::BLOCK_FULL: full = true; more = false; break;
+        case lnr_win::SOURCE_END: more = false; break;
+        case lnr_win::GROW_WINDOW: c.grow *= 2; break;
+        case lnr_win::NEXT_WINDOW: break;
+        case lnr_win::ERR_BLOCK: r->err = "a record is longer than the block"; return LNR_ERR_LIMIT;
+        case lnr_win::ERR_WINDOW: r->err = TOO_LONG; return LNR_ERR_LIMIT;
+        case lnr_win::ERR_SOURCE: r->err = r->gerr; return LNR_ERR_ARG;
         }
     }
+    uint32_t n = c.n;
     if ((r->gpu_serial || r->have_spill) && !full && n < max_reads) {   // the serial parser's share of the block, through a host block
         if (r->hblock_cap < dst_cap) {
             r->hblock.reset(new (std::nothrow) uint8_t[dst_cap ? dst_cap : 1]);
@@ -1034,9 +976,9 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
             r->hblock_cap = dst_cap;
         }
         uint32_t n2 = n;
-        lnr_status s = next_from(r, r->hblock.get(), dst_cap, ho, max_reads, &n2, n, used, true);
+        lnr_status s = next_from(r, r->hblock.get(), dst_cap, ho, max_reads, &n2, n, c.used, true);
         if (s != LNR_OK) return s;
-        if (int s2 = lnr_rdgpu_append(r->gpu, slot, used, r->hblock.get() + used, ho[n2] - used, n, ho + n, n2 - n, r->gerr, sizeof r->gerr)) return gfail(s2);
+        if (int s2 = lnr_rdgpu_append(r->gpu, c.slot, c.used, r->hblock.get() + c.used, ho[n2] - c.used, n, ho + n, n2 - n, r->gerr, sizeof r->gerr)) { r->err = r->gerr; return (lnr_status)s2; }
         n = n2;
     }
     *d_reads_concat = dr; *d_off = dof; *off = ho; *n_out = n;

@@ -21,6 +21,8 @@ struct lnr_rdgpu_result {
     uint32_t handover, full, too_big;                // the serial parser goes on at `consumed`; the next record does not fit; ... and it is the first
     const uint64_t *hdr;             // n pairs (begin, end) of header spans, window offsets (pinned host memory, valid until the next parse)
 };
+struct lnr_rdgpu_names { const char *ids; const uint64_t *id_off; const uint32_t *id_len; };     // header line / name of taken record k: id_len[k] bytes at ids + id_off[k], no trailing '\r'
+struct lnr_rdgpu_badblk { uint32_t blk, status; };   // status != 0: block blk of the window did not inflate (lnr_inf::Status); nothing else of the result is valid
 // ---- BGZF input: the blocks of a window are inflated on the device, behind the text the last window left over
 struct lnr_rdgpu_bgzf_blk { uint64_t coff, ooff; uint32_t clen, isize, crc, pad; };   // DEFLATE data at comp + coff; text at (new text) + ooff
 struct lnr_rdgpu_bgzf {
@@ -30,11 +32,11 @@ struct lnr_rdgpu_bgzf {
     uint64_t new_text;                               // sum of ISIZE: the window's text is carry + new_text bytes
 };
 struct lnr_rdgpu_bgzf_result {
-    uint32_t bad_blk, bad_status;                    // bad_status != 0: block bad_blk did not inflate (lnr_inf::Status); nothing else is valid
+    lnr_rdgpu_badblk bad_block;
     uint64_t lead;                                   // white space skipped at the front of the text (the parse saw the text behind it)
     int first;                                       // first byte behind it, -1: the text is white space up to `lead`
     uint32_t parsed;                                 // 0: no parse ran (format unknown / not a record start: hand-over, or nothing but blanks)
-    const char *ids; const uint64_t *id_off; const uint32_t *id_len;   // header bytes of the taken records, '\r' stripped (pinned, valid until the next parse)
+    lnr_rdgpu_names names;                           // of the taken records (pinned, valid until the next parse)
 };
 // stage these compressed bytes, inflate these blocks behind `carry` bytes, then measure / scan / emit over the device text.  w->text is
 // not used, w->len is set here; w->fmt == 0: decided by the first byte.
@@ -46,7 +48,7 @@ int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_wind
 // metadata (lnr_bam::take), emit and the gather of the names.
 struct lnr_rdgpu_bam_in { int hdr_done; int32_t n_ref; };
 struct lnr_rdgpu_bam_result {
-    uint32_t bad_blk, bad_status;                    // as in lnr_rdgpu_bgzf_result
+    lnr_rdgpu_badblk bad_block;
     uint32_t hdr_state;                              // 0 passed; 1 the window is too short for the header (nothing was parsed); 2 not a BAM header
     int32_t n_ref; uint64_t lead;                    // set when the header was passed by this call: its n_ref and its bytes
     uint32_t bad;                                    // the record the host reader would read next: 1 fails rec_valid, 2 the file ends inside it
@@ -54,7 +56,7 @@ struct lnr_rdgpu_bam_result {
     uint64_t passed;                                 // records in front of `consumed`, skipped ones included
     uint64_t skipped, reverse, tiles, repaired;      // among the passed; of the window
     double find_ms, stitch_ms, emit_ms;
-    const char *ids; const uint64_t *id_off; const uint32_t *id_len;   // names of the taken records (pinned, valid until the next parse)
+    lnr_rdgpu_names names;                           // of the taken records (pinned, valid until the next parse)
 };
 int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, const lnr_rdgpu_bam_in *in, lnr_rdgpu_result *r,
                         lnr_rdgpu_bam_result *br, char *err, size_t err_cap) __attribute__((weak));

@@ -224,7 +224,9 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(const u8 *comp, u64 comp_le
     if (lane == 0) status[b] = st;
 }
 
-// header bytes of the taken records -> one run of bytes the host reads (one wave per record); trailing '\r' dropped as the host parser does
+// header bytes (BAM: names) of the taken records -> one run of bytes the host reads (one wave per record).  STRIP_CR: trailing '\r' dropped
+// as the host parser does for a header line; a BAM name is taken byte for byte
+template <bool STRIP_CR>
 __global__ __launch_bounds__(64) void k_rd_gather(const u8 *text, u64 len, const u64 *hdr, const u64 *dst_off, u64 n, u8 *dst, u64 dst_cap, u32 *lens) {
     const u64 k = blockIdx.x;
     if (k >= n) return;
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(64) void k_rd_gather(const u8 *text, u64 len, const
     const u64 hb = hdr[2 * k], o = dst_off[k];
     u64 he = hdr[2 * k + 1];
     if (hb > he || he > len || o > dst_cap || he - hb > dst_cap - o) { if (lane == 0) lens[k] = ~0u; return; }
-    while (he > hb && text[he - 1] == '\r') he--;
+    if (STRIP_CR) while (he > hb && text[he - 1] == '\r') he--;
     for (u64 i = lane; i < he - hb; i += 64) dst[o + i] = text[hb + i];
     if (lane == 0) lens[k] = (u32)(he - hb);
 }
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(64) void k_rd_gather(const u8 *text, u64 len, const
 //                  the take (lnr_bam::take) runs there
 //   k_bam_emit     the packed SEQ of every taken record -> ordinals at off[k], 16 bases per lane and store, a reverse-strand record
 //                  mirrored and complemented; qualities, CIGAR and aux bytes are never read
-//   k_bam_names    the names of the taken records, byte for byte (k_rd_gather drops trailing '\r': not here)
+//   k_rd_gather<false>  the names of the taken records, byte for byte (a header line loses its trailing '\r': not a name)
 #ifndef LNR_BAM_TILE
 #define LNR_BAM_TILE 131072                    // a multiple of BAM_STAGE; variant builds for the tile-size comparison set it (tools/measure/reader_bam_ab.py)
 #endif
@@ -371,15 +373,6 @@ __global__ __launch_bounds__(64) void k_bam_emit(const u8 *text, u64 len, const 
     }
 }
 
-__global__ __launch_bounds__(64) void k_bam_names(const u8 *text, u64 len, const u64 *span, const u64 *dst_off, u64 n, u8 *dst, u64 dst_cap, u32 *lens) {
-    const u64 k = blockIdx.x;
-    if (k >= n) return;
-    const u64 hb = span[2 * k], he = span[2 * k + 1], o = dst_off[k];
-    if (hb > he || he > len || o > dst_cap || he - hb > dst_cap - o) { if (threadIdx.x == 0) lens[k] = ~0u; return; }
-    for (u64 i = threadIdx.x; i < he - hb; i += 64) dst[o + i] = text[hb + i];
-    if (threadIdx.x == 0) lens[k] = (u32)(he - hb);
-}
-
 double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Buf { void *p = nullptr; u64 cap = 0; };
@@ -415,12 +408,17 @@ struct lnr_rdgpu {
 
 namespace {
 
-struct DeviceGuard {                            // every entry leaves the caller's current device as it found it
+struct DeviceGuard {                            // every entry works on its device (none given: the caller's) and leaves the caller's current device as it found it
     int prev = -1;
+    hipError_t set = hipSuccess;
+    explicit DeviceGuard(int device = -1) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (device >= 0) set = hipSetDevice(device); }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 #define RD_CK(call, status)                                                                                              \
     do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, err_cap, "%s: %s", #call, hipGetErrorString(e_)); return (status); } } while (0)
+#define RD_ON_DEVICE(g)                                                                                                  \
+    DeviceGuard dg((g)->device);                                                                                         \
+    if (dg.set != hipSuccess) { snprintf(err, err_cap, "hipSetDevice(g->device): %s", hipGetErrorString(dg.set)); return -3; }
 
 int dev_need(Buf &b, u64 bytes, char *err, size_t err_cap) {
     if (bytes <= b.cap) return 0;
@@ -504,6 +502,78 @@ int scan_emit(lnr_rdgpu *g, const lnr_rdgpu_window *w, u32 nt, u64 nchunk, u64 m
     return 0;
 }
 
+// measure / scan / emit over the w->len bytes of a window's text.  Host text (w->text) goes up first, chunk by chunk through the pinned
+// staging buffers (or as it is: w->pinned), every chunk measured behind its copy; w->text == null: the text lies in g->text already
+int parse_text(lnr_rdgpu *g, const lnr_rdgpu_window *w, lnr_rdgpu_result *r, char *err, size_t err_cap) {
+    Block &b = g->blk[w->slot];
+    const bool up = w->text != nullptr;
+    const u32 nt = (u32)((w->len + RD_TILE - 1) / RD_TILE);
+    const u64 max_rec = w->allowed < w->len / 2 + 1 ? w->allowed : w->len / 2 + 1;
+    int s = 0;
+    if ((up && (s = dev_need(g->text, (u64)nt * RD_TILE + 16, err, err_cap))) || (s = dev_need(g->sums, (u64)nt * sizeof(Sum), err, err_cap)) ||
+        (s = dev_need(g->carry, (u64)nt * sizeof(Carry), err, err_cap)) || (s = dev_need(g->hdr, 16 * max_rec + 16, err, err_cap))) return s;
+    if (!pin_need(g->h_hdr, 16 * max_rec + 16)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    if (w->base_base + w->free + 16 > b.reads.cap || 8 * (w->rec_base + w->allowed + 1) > b.off.cap) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
+    u8 *d_text = (u8 *)g->text.p;
+    const double t0 = wall_ms();
+    const u64 nchunk = !up || w->pinned ? 1 : (w->len + RD_CHUNK - 1) / RD_CHUNK;
+    while (g->ev_m.size() < 2 * nchunk) { hipEvent_t e; RD_CK(hipEventCreate(&e), -3); g->ev_m.push_back(e); }
+    if (up && !w->pinned) for (Pin &p : g->up) if (!pin_need(p, RD_CHUNK)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    for (u64 k = 0; k < nchunk; k++) {
+        const u64 o = k * RD_CHUNK, len = nchunk == 1 ? w->len : (w->len - o < RD_CHUNK ? w->len - o : RD_CHUNK);
+        if (up) {
+            const void *src = w->text + o;
+            if (!w->pinned) {
+                RD_CK(hipEventSynchronize(g->ev_up[k & 1]), -3);                  // the last copy out of this staging buffer has finished
+                par_copy(g->up[k & 1].p, w->text + o, len, w->threads);
+                src = g->up[k & 1].p;
+            }
+            RD_CK(hipMemcpyAsync(d_text + o, src, len, hipMemcpyHostToDevice, g->s_copy), -3);
+            RD_CK(hipEventRecord(g->ev_up[k & 1], g->s_copy), -3);
+            RD_CK(hipStreamWaitEvent(g->st, g->ev_up[k & 1], 0), -3);
+        }
+        const u32 tile0 = (u32)(o / RD_TILE), tiles = (u32)((len + RD_TILE - 1) / RD_TILE);
+        RD_CK(hipEventRecord(g->ev_m[2 * k], g->st), -3);
+        hipLaunchKernelGGL(k_rd_measure, dim3(tiles), dim3(64), 0, g->st, (const u8 *)d_text, (u64)w->len, w->fmt, tile0, (Sum *)g->sums.p);
+        RD_CK(hipEventRecord(g->ev_m[2 * k + 1], g->st), -3);
+    }
+    if (up) { RD_CK(hipStreamSynchronize(g->s_copy), -3); g->ms[0] += wall_ms() - t0; }
+    return scan_emit(g, w, nt, nchunk, max_rec, r, err, err_cap);
+}
+
+// the bytes of the n spans at g->hdr (the same on the host at g->h_hdr: begin, end in the device text of tlen bytes) -> one run of bytes on
+// the host, one wave per span: the header lines of a text window (strip_cr: without trailing '\r'), the names of a BAM window (`what`, for
+// the messages).  n > 0: returns with the stream synchronised
+int gather_names(lnr_rdgpu *g, bool strip_cr, u64 n, u64 tlen, const char *what, lnr_rdgpu_names *out, char *err, size_t err_cap) {
+    int s;
+    if (!pin_need(g->h_idoff, 8 * n + 8) || !pin_need(g->h_idlen, 4 * n + 4)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    const u64 *span = (const u64 *)g->h_hdr.p; const u32 *lens = (const u32 *)g->h_idlen.p;
+    u64 *ido = (u64 *)g->h_idoff.p, total = 0;
+    for (u64 k = 0; k < n; k++) {
+        if (span[2 * k] > span[2 * k + 1] || span[2 * k + 1] > tlen) { snprintf(err, err_cap, "internal: header span of record %llu", (unsigned long long)k); return -8; }
+        ido[k] = total; total += span[2 * k + 1] - span[2 * k];
+    }
+    if (!pin_need(g->h_idbytes, total + 1)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    out->ids = (const char *)g->h_idbytes.p; out->id_off = ido; out->id_len = lens;
+    if (!n) return 0;
+    if ((s = dev_need(g->idoff, 8 * n, err, err_cap)) || (s = dev_need(g->idlen, 4 * n, err, err_cap)) || (s = dev_need(g->idbytes, total + 1, err, err_cap))) return s;
+    RD_CK(hipMemcpyAsync(g->idoff.p, ido, 8 * n, hipMemcpyHostToDevice, g->st), -3);
+    RD_CK(hipEventRecord(g->ev_i[2], g->st), -3);
+    hipLaunchKernelGGL(strip_cr ? k_rd_gather<true> : k_rd_gather<false>, dim3((u32)n), dim3(64), 0, g->st, (const u8 *)g->text.p, tlen, (const u64 *)g->hdr.p,
+                       (const u64 *)g->idoff.p, n, (u8 *)g->idbytes.p, total, (u32 *)g->idlen.p);
+    RD_CK(hipEventRecord(g->ev_i[3], g->st), -3);
+    RD_CK(hipMemcpyAsync(g->h_idlen.p, g->idlen.p, 4 * n, hipMemcpyDeviceToHost, g->st), -3);
+    if (total) RD_CK(hipMemcpyAsync(g->h_idbytes.p, g->idbytes.p, total, hipMemcpyDeviceToHost, g->st), -3);
+    RD_CK(hipStreamSynchronize(g->st), -3);
+    RD_CK(hipGetLastError(), -3);
+    float f = 0; RD_CK(hipEventElapsedTime(&f, g->ev_i[2], g->ev_i[3]), -3); g->ms_inf[1] += f;
+    for (u64 k = 0; k < n; k++) {                                          // (a span the kernel refused has the length ~0)
+        const u64 l = span[2 * k + 1] - span[2 * k];
+        if (strip_cr ? lens[k] > l : lens[k] != l) { snprintf(err, err_cap, "internal: gathered %s of record %llu", what, (unsigned long long)k); return -8; }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -515,7 +585,6 @@ int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, s
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) { snprintf(err, err_cap, "no usable HIP device for the GPU reader"); return -2; }
     DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
     if (device < 0) device = dg.prev < 0 ? 0 : dg.prev;
     if (device >= count) { snprintf(err, err_cap, "no usable HIP device %d for the GPU reader (%d present)", (int)device, count); return -2; }
     lnr_rdgpu *g = new (std::nothrow) lnr_rdgpu();
@@ -540,9 +609,7 @@ int lnr_rdgpu_open(int32_t device, uint32_t slots, lnr_rdgpu **out, char *err, s
 
 int lnr_rdgpu_block(lnr_rdgpu *g, uint32_t slot, uint64_t dst_cap, uint32_t max_reads, uint8_t **d_reads, uint64_t **d_off, uint64_t **h_off,
                     char *err, size_t err_cap) {
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
+    RD_ON_DEVICE(g);
     Block &b = g->blk[slot];
     int s;
     // 16 spare bytes behind the bases: lnr_filter_batch_dev reads none, the context's own upload keeps the same floor
@@ -556,50 +623,15 @@ int lnr_rdgpu_block(lnr_rdgpu *g, uint32_t slot, uint64_t dst_cap, uint32_t max_
 }
 
 uint8_t *lnr_rdgpu_stage(lnr_rdgpu *g, uint64_t bytes) {
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    if (hipSetDevice(g->device) != hipSuccess) return nullptr;
+    DeviceGuard dg(g->device);
+    if (dg.set != hipSuccess) return nullptr;
     return pin_need(g->stage, bytes) ? (uint8_t *)g->stage.p : nullptr;
 }
 
 int lnr_rdgpu_parse(lnr_rdgpu *g, const lnr_rdgpu_window *w, lnr_rdgpu_result *r, char *err, size_t err_cap) {
     if (!w->len || w->len > (1ULL << 30) || w->slot >= g->slots) { snprintf(err, err_cap, "internal: window of %llu bytes", (unsigned long long)w->len); return -8; }
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
-    Block &b = g->blk[w->slot];
-    const u32 nt = (u32)((w->len + RD_TILE - 1) / RD_TILE);
-    const u64 max_rec = w->allowed < w->len / 2 + 1 ? w->allowed : w->len / 2 + 1;
-    int s;
-    if ((s = dev_need(g->text, (u64)nt * RD_TILE + 16, err, err_cap)) || (s = dev_need(g->sums, (u64)nt * sizeof(Sum), err, err_cap)) ||
-        (s = dev_need(g->carry, (u64)nt * sizeof(Carry), err, err_cap)) || (s = dev_need(g->hdr, 16 * max_rec + 16, err, err_cap))) return s;
-    if (!pin_need(g->h_hdr, 16 * max_rec + 16)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
-    if (w->base_base + w->free + 16 > b.reads.cap || 8 * (w->rec_base + w->allowed + 1) > b.off.cap) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
-    u8 *d_text = (u8 *)g->text.p;
-    // ---- text up, measured chunk by chunk
-    double t0 = wall_ms();
-    const u64 nchunk = w->pinned ? 1 : (w->len + RD_CHUNK - 1) / RD_CHUNK;
-    while (g->ev_m.size() < 2 * nchunk) { hipEvent_t e; RD_CK(hipEventCreate(&e), -3); g->ev_m.push_back(e); }
-    if (!w->pinned) for (Pin &p : g->up) if (!pin_need(p, RD_CHUNK)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
-    for (u64 k = 0; k < nchunk; k++) {
-        const u64 o = w->pinned ? 0 : k * RD_CHUNK, len = w->pinned ? w->len : (w->len - o < RD_CHUNK ? w->len - o : RD_CHUNK);
-        const void *src = w->text + o;
-        if (!w->pinned) {
-            RD_CK(hipEventSynchronize(g->ev_up[k & 1]), -3);                  // the last copy out of this staging buffer has finished
-            par_copy(g->up[k & 1].p, w->text + o, len, w->threads);
-            src = g->up[k & 1].p;
-        }
-        RD_CK(hipMemcpyAsync(d_text + o, src, len, hipMemcpyHostToDevice, g->s_copy), -3);
-        RD_CK(hipEventRecord(g->ev_up[k & 1], g->s_copy), -3);
-        RD_CK(hipStreamWaitEvent(g->st, g->ev_up[k & 1], 0), -3);
-        const u32 tile0 = (u32)(o / RD_TILE), tiles = (u32)((len + RD_TILE - 1) / RD_TILE);
-        RD_CK(hipEventRecord(g->ev_m[2 * k], g->st), -3);
-        hipLaunchKernelGGL(k_rd_measure, dim3(tiles), dim3(64), 0, g->st, (const u8 *)d_text, (u64)w->len, w->fmt, tile0, (Sum *)g->sums.p);
-        RD_CK(hipEventRecord(g->ev_m[2 * k + 1], g->st), -3);
-    }
-    RD_CK(hipStreamSynchronize(g->s_copy), -3);
-    g->ms[0] += wall_ms() - t0;
-    return scan_emit(g, w, nt, nchunk, max_rec, r, err, err_cap);
+    RD_ON_DEVICE(g);
+    return parse_text(g, w, r, err, err_cap);
 }
 
 // pageable host bytes -> device, through the two pinned staging buffers that host threads fill in turn; g->st waits for the last copy
@@ -627,27 +659,30 @@ static int move_text(lnr_rdgpu *g, u8 *text, u64 to, u64 from, u64 n, char *err,
     return 0;
 }
 
+// g->text holds `need` bytes (whole tiles) and the text the last window left, [keep_from, keep_from + carry), stands at its front: moved
+// there, or into a new buffer where this one is too small
+static int text_front(lnr_rdgpu *g, u64 need, u64 keep_from, u64 carry, char *err, size_t err_cap) {
+    if (need <= g->text.cap) return move_text(g, (u8 *)g->text.p, 0, keep_from, carry, err, err_cap);
+    Buf nb;
+    if (int s = dev_need(nb, need, err, err_cap)) return s;
+    if (carry) {
+        hipError_t e = hipMemcpyAsync(nb.p, (u8 *)g->text.p + keep_from, carry, hipMemcpyDeviceToDevice, g->st);
+        if (e == hipSuccess) e = hipStreamSynchronize(g->st);
+        if (e != hipSuccess) { (void)hipFree(nb.p); snprintf(err, err_cap, "moving the carried text: %s", hipGetErrorString(e)); return -3; }
+    }
+    if (g->text.p) (void)hipFree(g->text.p);
+    g->text = nb;
+    return 0;
+}
+
 // the inflate step of a BGZF window: the carried text to the front, the blocks inflated behind it, the first bytes of the text (up to 64 KiB)
-// and the blocks' status words on the host.  bad_status != 0: block bad_blk did not inflate.  The caller has set the device.
-static int inflate_window(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, const lnr_rdgpu_window *w, uint32_t *bad_blk, uint32_t *bad_status, u64 *hl_out,
-                          char *err, size_t err_cap) {
+// and the blocks' status words on the host.  bad->status != 0: block bad->blk did not inflate.  The caller has set the device.
+static int inflate_window(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, const lnr_rdgpu_window *w, lnr_rdgpu_badblk *bad, u64 *hl_out, char *err, size_t err_cap) {
     const u64 tlen = job->carry + job->new_text;
     if (!tlen || tlen > (1ULL << 30) || w->slot >= g->slots || job->comp_len > (1ULL << 31)) { snprintf(err, err_cap, "internal: window of %llu bytes", (unsigned long long)tlen); return -8; }
     if (job->keep_from + job->carry > g->text.cap) { snprintf(err, err_cap, "internal: carried text outside the buffer"); return -8; }
     int s;
-    // ---- the text buffer: whole tiles; the carried text moves to its front (into a new buffer where this one is too small)
-    const u64 need = w->fmt == 3 ? bam_text_cap(tlen) : ((tlen + RD_TILE - 1) / RD_TILE) * RD_TILE + 16;
-    if (need > g->text.cap) {
-        Buf nb;
-        if ((s = dev_need(nb, need, err, err_cap))) return s;
-        if (job->carry) {
-            hipError_t e = hipMemcpyAsync(nb.p, (u8 *)g->text.p + job->keep_from, job->carry, hipMemcpyDeviceToDevice, g->st);
-            if (e == hipSuccess) e = hipStreamSynchronize(g->st);
-            if (e != hipSuccess) { (void)hipFree(nb.p); snprintf(err, err_cap, "moving the carried text: %s", hipGetErrorString(e)); return -3; }
-        }
-        if (g->text.p) (void)hipFree(g->text.p);
-        g->text = nb;
-    } else if ((s = move_text(g, (u8 *)g->text.p, 0, job->keep_from, job->carry, err, err_cap))) return s;
+    if ((s = text_front(g, w->fmt == 3 ? bam_text_cap(tlen) : ((tlen + RD_TILE - 1) / RD_TILE) * RD_TILE + 16, job->keep_from, job->carry, err, err_cap))) return s;
     u8 *d_text = (u8 *)g->text.p;
     // ---- compressed bytes and the block table up, one wave per block
     double t0 = wall_ms();
@@ -677,7 +712,7 @@ static int inflate_window(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, const lnr_rdg
     if (nblk) {
         RD_CK(hipEventElapsedTime(&f, g->ev_i[0], g->ev_i[1]), -3); g->ms_inf[0] += f;
         const u32 *stt = (const u32 *)g->h_bstat.p;
-        for (u32 k = 0; k < nblk; k++) if (stt[k]) { *bad_blk = k; *bad_status = stt[k]; return 0; }
+        for (u32 k = 0; k < nblk; k++) if (stt[k]) { bad->blk = k; bad->status = stt[k]; return 0; }
     }
     *hl_out = hl;
     return 0;
@@ -687,8 +722,6 @@ static int inflate_window(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, const lnr_rdg
 // gathered: what follows the inflate of a BGZF window, and the rounds of a plain gzip file.  The caller has set the device.
 static int parse_device_text(lnr_rdgpu *g, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br, u64 tlen, u64 hl, char *err, size_t err_cap) {
     int s;
-    float f = 0;
-    u8 *d_text = (u8 *)g->text.p;
     if (w->fmt == 0 && lnr_bam::is_magic((const u8 *)g->h_head.p, hl)) { w->fmt = 3; br->first = 'B'; return 0; }     // BAM: lnr_rdgpu_parse_bam reads this text
     // ---- a window starts at a record start: white space in front of it (the start of the file) is skipped
     const u8 *head = (const u8 *)g->h_head.p;
@@ -700,51 +733,13 @@ static int parse_device_text(lnr_rdgpu *g, lnr_rdgpu_window *w, lnr_rdgpu_result
     if (w->fmt == 0) w->fmt = head[lead] == '>' ? FASTA : head[lead] == '@' ? FASTQ : -1;
     if (w->fmt < 0 || head[lead] != (w->fmt == FASTA ? '>' : '@')) return 0;
     if (lead) {
-        if ((s = move_text(g, d_text, 0, lead, tlen - lead, err, err_cap))) return s;
+        if ((s = move_text(g, (u8 *)g->text.p, 0, lead, tlen - lead, err, err_cap))) return s;
         tlen -= lead;
     }
     w->len = tlen; w->text = nullptr; w->pinned = 1;
-    Block &b = g->blk[w->slot];
-    const u32 nt = (u32)((tlen + RD_TILE - 1) / RD_TILE);
-    const u64 max_rec = w->allowed < tlen / 2 + 1 ? w->allowed : tlen / 2 + 1;
-    if ((s = dev_need(g->sums, (u64)nt * sizeof(Sum), err, err_cap)) || (s = dev_need(g->carry, (u64)nt * sizeof(Carry), err, err_cap)) ||
-        (s = dev_need(g->hdr, 16 * max_rec + 16, err, err_cap))) return s;
-    if (!pin_need(g->h_hdr, 16 * max_rec + 16)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
-    if (w->base_base + w->free + 16 > b.reads.cap || 8 * (w->rec_base + w->allowed + 1) > b.off.cap) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
-    while (g->ev_m.size() < 2) { hipEvent_t e; RD_CK(hipEventCreate(&e), -3); g->ev_m.push_back(e); }
-    RD_CK(hipEventRecord(g->ev_m[0], g->st), -3);
-    hipLaunchKernelGGL(k_rd_measure, dim3(nt), dim3(64), 0, g->st, (const u8 *)d_text, (u64)tlen, w->fmt, 0u, (Sum *)g->sums.p);
-    RD_CK(hipEventRecord(g->ev_m[1], g->st), -3);
-    if ((s = scan_emit(g, w, nt, 1, max_rec, r, err, err_cap))) return s;
+    if ((s = parse_text(g, w, r, err, err_cap))) return s;
     br->parsed = 1;
-    // ---- the header bytes of the taken records: their places from the spans (host), the bytes by one wave per record
-    const u64 n = r->n;
-    if (!pin_need(g->h_idoff, 8 * n + 8) || !pin_need(g->h_idlen, 4 * n + 4)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
-    u64 *ido = (u64 *)g->h_idoff.p, total = 0;
-    for (u64 k = 0; k < n; k++) {
-        const u64 hb = r->hdr[2 * k], he = r->hdr[2 * k + 1];
-        if (hb > he || he > tlen) { snprintf(err, err_cap, "internal: header span of record %llu", (unsigned long long)k); return -8; }
-        ido[k] = total; total += he - hb;
-    }
-    br->id_off = ido; br->id_len = (const uint32_t *)g->h_idlen.p;
-    if (!pin_need(g->h_idbytes, total + 1)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
-    br->ids = (const char *)g->h_idbytes.p;
-    if (n) {
-        if ((s = dev_need(g->idoff, 8 * n, err, err_cap)) || (s = dev_need(g->idlen, 4 * n, err, err_cap)) || (s = dev_need(g->idbytes, total + 1, err, err_cap))) return s;
-        RD_CK(hipMemcpyAsync(g->idoff.p, ido, 8 * n, hipMemcpyHostToDevice, g->st), -3);
-        RD_CK(hipEventRecord(g->ev_i[2], g->st), -3);
-        hipLaunchKernelGGL(k_rd_gather, dim3((u32)n), dim3(64), 0, g->st, (const u8 *)d_text, (u64)tlen, (const u64 *)g->hdr.p, (const u64 *)g->idoff.p, n,
-                           (u8 *)g->idbytes.p, total, (u32 *)g->idlen.p);
-        RD_CK(hipEventRecord(g->ev_i[3], g->st), -3);
-        RD_CK(hipMemcpyAsync(g->h_idlen.p, g->idlen.p, 4 * n, hipMemcpyDeviceToHost, g->st), -3);
-        if (total) RD_CK(hipMemcpyAsync(g->h_idbytes.p, g->idbytes.p, total, hipMemcpyDeviceToHost, g->st), -3);
-        RD_CK(hipStreamSynchronize(g->st), -3);
-        RD_CK(hipGetLastError(), -3);
-        RD_CK(hipEventElapsedTime(&f, g->ev_i[2], g->ev_i[3]), -3); g->ms_inf[1] += f;
-        for (u64 k = 0; k < n; k++)
-            if (br->id_len[k] > r->hdr[2 * k + 1] - r->hdr[2 * k]) { snprintf(err, err_cap, "internal: gathered header of record %llu", (unsigned long long)k); return -8; }
-    }
-    return 0;
+    return gather_names(g, true, r->n, tlen, "header", &br->names, err, err_cap);
 }
 
 int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_window *w, lnr_rdgpu_result *r, lnr_rdgpu_bgzf_result *br,
@@ -752,12 +747,10 @@ int lnr_rdgpu_parse_bgzf(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_wind
     *br = lnr_rdgpu_bgzf_result{};
     br->first = -1;
     *r = lnr_rdgpu_result{};
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
+    RD_ON_DEVICE(g);
     int s;
     u64 tlen = job->carry + job->new_text, hl = 0;
-    if ((s = inflate_window(g, job, w, &br->bad_blk, &br->bad_status, &hl, err, err_cap)) || br->bad_status) return s;
+    if ((s = inflate_window(g, job, w, &br->bad_block, &hl, err, err_cap)) || br->bad_block.status) return s;
     return parse_device_text(g, w, r, br, tlen, hl, err, err_cap);
 }
 
@@ -766,9 +759,7 @@ int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_windo
     using namespace lnr_bam;
     *br = lnr_rdgpu_bam_result{};
     *r = lnr_rdgpu_result{};
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
+    RD_ON_DEVICE(g);
     int s;
     u64 tlen;
     int n_ref = in->n_ref;
@@ -777,7 +768,7 @@ int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_windo
         // ---- inflate behind the carried text, then pass the header where it still stands in front
         tlen = job->carry + job->new_text;
         u64 hl = 0;
-        if ((s = inflate_window(g, job, w, &br->bad_blk, &br->bad_status, &hl, err, err_cap)) || br->bad_status) return s;
+        if ((s = inflate_window(g, job, w, &br->bad_block, &hl, err, err_cap)) || br->bad_block.status) return s;
         if (!in->hdr_done) {
             Header h = header_span((const u8 *)g->h_head.p, hl);
             while (h.status == 1 && h.need <= tlen) {                          // a header longer than the head: the head is downloaded again, larger
@@ -862,11 +853,9 @@ int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_windo
     // ---- emit: jobs and chunks up, ordinals and offsets into the block
     u64 *h_off = (u64 *)b.h_off.p;
     const u64 n = T.n;
-    if (!pin_need(g->h_bjobs, (n + 1) * sizeof(BamJob)) || !pin_need(g->h_idoff, 8 * n + 8) || !pin_need(g->h_idlen, 4 * n + 4) || !pin_need(g->h_hdr, 16 * n + 16)) {
-        snprintf(err, err_cap, "pinned host allocation failed"); return -4;
-    }
+    if (!pin_need(g->h_bjobs, (n + 1) * sizeof(BamJob)) || !pin_need(g->h_hdr, 16 * n + 16)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
     BamJob *J = (BamJob *)g->h_bjobs.p;
-    u64 *span = (u64 *)g->h_hdr.p, *ido = (u64 *)g->h_idoff.p, id_total = 0, at = w->base_base, nchunk = 0;
+    u64 *span = (u64 *)g->h_hdr.p, at = w->base_base, nchunk = 0;
     for (u64 i = 0; i < n; i++) {
         const Meta &m = M[which[i]];
         const u32 flag = m.flag_name & 0xffffu, lname = m.flag_name >> 16;
@@ -876,46 +865,32 @@ int lnr_rdgpu_parse_bam(lnr_rdgpu *g, const lnr_rdgpu_bgzf *job, lnr_rdgpu_windo
         at += m.l_seq;
         nchunk += ((u64)m.l_seq + BAM_CHUNK - 1) / BAM_CHUNK;
         span[2 * i] = (u64)m.off + HEAD; span[2 * i + 1] = (u64)m.off + HEAD + lname - 1;
-        ido[i] = id_total; id_total += lname - 1;
     }
     h_off[w->rec_base + n] = at;
     if (at != w->base_base + T.bases || nchunk > 0xffffffffULL) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
-    if (!pin_need(g->h_bchunks, (nchunk + 1) * sizeof(BamChunk)) || !pin_need(g->h_idbytes, id_total + 1)) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
+    if (!pin_need(g->h_bchunks, (nchunk + 1) * sizeof(BamChunk))) { snprintf(err, err_cap, "pinned host allocation failed"); return -4; }
     BamChunk *C = (BamChunk *)g->h_bchunks.p;
     for (u64 i = 0, c = 0; i < n; i++) for (u32 st = 0; st < J[i].l_seq; st += BAM_CHUNK) { C[c].rec = (u32)i; C[c].start = st; c++; }
-    br->ids = (const char *)g->h_idbytes.p; br->id_off = ido; br->id_len = (const uint32_t *)g->h_idlen.p;
     g->ms[4] += wall_ms() - t0;
     RD_CK(hipMemcpyAsync((u64 *)b.off.p + w->rec_base, h_off + w->rec_base, 8 * (n + 1), hipMemcpyHostToDevice, g->st), -3);
     RD_CK(hipEventRecord(g->ev_b[3], g->st), -3);
     if (n) {
         if ((s = dev_need(g->bjobs, n * sizeof(BamJob), err, err_cap)) || (s = dev_need(g->bchunks, (nchunk + 1) * sizeof(BamChunk), err, err_cap)) ||
-            (s = dev_need(g->hdr, 16 * n, err, err_cap)) || (s = dev_need(g->idoff, 8 * n, err, err_cap)) || (s = dev_need(g->idlen, 4 * n, err, err_cap)) ||
-            (s = dev_need(g->idbytes, id_total + 1, err, err_cap))) return s;
+            (s = dev_need(g->hdr, 16 * n, err, err_cap))) return s;
         RD_CK(hipMemcpyAsync(g->bjobs.p, J, n * sizeof(BamJob), hipMemcpyHostToDevice, g->st), -3);
         if (nchunk) RD_CK(hipMemcpyAsync(g->bchunks.p, C, nchunk * sizeof(BamChunk), hipMemcpyHostToDevice, g->st), -3);
         RD_CK(hipMemcpyAsync(g->hdr.p, span, 16 * n, hipMemcpyHostToDevice, g->st), -3);
-        RD_CK(hipMemcpyAsync(g->idoff.p, ido, 8 * n, hipMemcpyHostToDevice, g->st), -3);
         RD_CK(hipEventRecord(g->ev_b[3], g->st), -3);
         if (nchunk) hipLaunchKernelGGL(k_bam_emit, dim3((u32)nchunk), dim3(64), 0, g->st, d_text, tlen, (const BamJob *)g->bjobs.p, (const BamChunk *)g->bchunks.p, (u32)nchunk,
                                        (u8 *)b.reads.p, (u64)(w->base_base + w->free));
         RD_CK(hipEventRecord(g->ev_b[4], g->st), -3);
-        RD_CK(hipEventRecord(g->ev_i[2], g->st), -3);
-        hipLaunchKernelGGL(k_bam_names, dim3((u32)n), dim3(64), 0, g->st, d_text, tlen, (const u64 *)g->hdr.p, (const u64 *)g->idoff.p, n, (u8 *)g->idbytes.p, id_total, (u32 *)g->idlen.p);
-        RD_CK(hipEventRecord(g->ev_i[3], g->st), -3);
-        RD_CK(hipMemcpyAsync(g->h_idlen.p, g->idlen.p, 4 * n, hipMemcpyDeviceToHost, g->st), -3);
-        if (id_total) RD_CK(hipMemcpyAsync(g->h_idbytes.p, g->idbytes.p, id_total, hipMemcpyDeviceToHost, g->st), -3);
     } else RD_CK(hipEventRecord(g->ev_b[4], g->st), -3);
-    RD_CK(hipStreamSynchronize(g->st), -3);
-    RD_CK(hipGetLastError(), -3);
+    if ((s = gather_names(g, false, n, tlen, "name", &br->names, err, err_cap))) return s;      // (ends with the stream synchronised where there are names)
+    if (!n) { RD_CK(hipStreamSynchronize(g->st), -3); RD_CK(hipGetLastError(), -3); }
     float f = 0;
     RD_CK(hipEventElapsedTime(&f, g->ev_b[0], g->ev_b[1]), -3); br->find_ms = f; g->ms[1] += f;
     RD_CK(hipEventElapsedTime(&f, g->ev_b[1], g->ev_b[2]), -3); br->stitch_ms = f; g->ms[2] += f;
     RD_CK(hipEventElapsedTime(&f, g->ev_b[3], g->ev_b[4]), -3); br->emit_ms = f; g->ms[3] += f;
-    if (n) {
-        RD_CK(hipEventElapsedTime(&f, g->ev_i[2], g->ev_i[3]), -3); g->ms_inf[1] += f;
-        for (u64 i = 0; i < n; i++)
-            if (br->id_len[i] != span[2 * i + 1] - span[2 * i]) { snprintf(err, err_cap, "internal: gathered name of record %llu", (unsigned long long)i); return -8; }
-    }
     return 0;
 }
 
@@ -923,9 +898,7 @@ void lnr_rdgpu_inflate_times(const lnr_rdgpu *g, double *ms2) { ms2[0] = g->ms_i
 
 int lnr_rdgpu_append(lnr_rdgpu *g, uint32_t slot, uint64_t base_base, const uint8_t *bases, uint64_t nb, uint64_t rec_base, const uint64_t *off, uint64_t n,
                      char *err, size_t err_cap) {
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
+    RD_ON_DEVICE(g);
     Block &b = g->blk[slot];
     if (base_base + nb + 16 > b.reads.cap || 8 * (rec_base + n + 1) > b.off.cap) { snprintf(err, err_cap, "internal: block accounting"); return -8; }
     if (nb) RD_CK(hipMemcpy((u8 *)b.reads.p + base_base, bases, nb, hipMemcpyHostToDevice), -3);
@@ -938,9 +911,7 @@ void lnr_rdgpu_times_reset(lnr_rdgpu *g) { for (double &m : g->ms) m = 0; g->ms_
 
 void lnr_rdgpu_close(lnr_rdgpu *g) {
     if (!g) return;
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    (void)hipSetDevice(g->device);
+    DeviceGuard dg(g->device);
     (void)hipDeviceSynchronize();
     free_all(g);
     delete g;
@@ -1186,9 +1157,7 @@ extern "C" int lnr_rdgpu_gzip_round(lnr_rdgpu *g, const lnr_rdgpu_gzip *job, lnr
     *out = lnr_rdgpu_gzip_result{};
     if (!job->comp_len || job->comp_len > (1ULL << 31) || job->start_bit > 7 || job->hist > WIN || job->carry > (1ULL << 30) || job->text_cap > (1ULL << 30) - job->carry ||
         job->keep_from + job->carry > g->text.cap) { snprintf(err, err_cap, "internal: gzip round of %llu bytes", (unsigned long long)job->comp_len); return -8; }
-    DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
-    RD_CK(hipSetDevice(g->device), -3);
+    RD_ON_DEVICE(g);
     int s;
     if (!g->gz) {
         g->gz = new (std::nothrow) GzDev();
@@ -1210,19 +1179,7 @@ extern "C" int lnr_rdgpu_gzip_round(lnr_rdgpu *g, const lnr_rdgpu_gzip *job, lnr
     double ms6[6] = {0, 0, 0, 0, 0, 0};
     if ((s = gz_plan(G, job->comp_len, job->start_bit, job->chunk, job->text_cap, &R, &nchunk, ms6, err, err_cap))) return s;
     if (!R.status && R.pieces) {
-        // the text buffer: whole tiles; the carried text moves to its front (into a new buffer where this one is too small)
-        const u64 tlen = job->carry + R.text, need = bam_text_cap(tlen) + 16;
-        if (need > g->text.cap) {
-            Buf nb;
-            if ((s = dev_need(nb, need, err, err_cap))) return s;
-            if (job->carry) {
-                hipError_t e = hipMemcpyAsync(nb.p, (u8 *)g->text.p + job->keep_from, job->carry, hipMemcpyDeviceToDevice, g->st);
-                if (e == hipSuccess) e = hipStreamSynchronize(g->st);
-                if (e != hipSuccess) { (void)hipFree(nb.p); snprintf(err, err_cap, "moving the carried text: %s", hipGetErrorString(e)); return -3; }
-            }
-            if (g->text.p) (void)hipFree(g->text.p);
-            g->text = nb;
-        } else if ((s = move_text(g, (u8 *)g->text.p, 0, job->keep_from, job->carry, err, err_cap))) return s;
+        if ((s = text_front(g, bam_text_cap(job->carry + R.text) + 16, job->keep_from, job->carry, err, err_cap))) return s;
         if ((s = gz_fill(G, job->comp_len, job->start_bit, job->hist, &R, (u8 *)g->text.p + job->carry, &crc, &refs, ms6, err, err_cap))) return s;
         out->moved = 1;
     }
@@ -1244,7 +1201,6 @@ extern "C" int lnr_rdgpu_gunzip(int32_t device, const uint8_t *gz, uint64_t size
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) { snprintf(err, err_cap, "no usable HIP device for the GPU inflate"); return -2; }
     DeviceGuard dg;
-    if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
     if (device < 0) device = dg.prev < 0 ? 0 : dg.prev;
     if (device >= count) { snprintf(err, err_cap, "no usable HIP device %d for the GPU inflate (%d present)", (int)device, count); return -2; }
     if (size > (1ULL << 31)) { snprintf(err, err_cap, "%llu compressed bytes: beyond the staging limit of 2^31", (unsigned long long)size); return -6; }
@@ -1259,50 +1215,42 @@ extern "C" int lnr_rdgpu_gunzip(int32_t device, const uint8_t *gz, uint64_t size
     if (size) RD_CK(hipMemcpyAsync(G.comp.p, gz, size, hipMemcpyHostToDevice, G.st), -3);
     RD_CK(hipStreamSynchronize(G.st), -3);
     total->upload_ms += wall_ms() - t0;
-    u64 off = 0, done = 0;
+    u64 done = 0, bad = 0;
     auto fail = [&](u32 status, u64 at) { *bad_status = status; *bad_off = at; *text_size = done; return 0; };
-    for (bool first = true; off < size; first = false) {
-        u64 data = 0;
-        u32 st = member_at(gz, size, off, first, &data);
-        if (st == PASS_OVER) break;
-        if (st) return fail(st, off);
-        u64 start_bit = data * 8, rsize = round, mtext = 0;
-        u32 hist = 0, crc = 0;
-        for (;;) {
-            const u64 rb = start_bit >> 3, clen = size - rb < rsize ? size : rb + rsize;
-            const u64 cap = text_cap - done < (1ULL << 30) ? text_cap - done : 1ULL << 30;
-            Round R;
-            u32 nchunk = 0, rcrc = 0;
-            u64 refs = 0;
-            lnr_rdgpu_gz_counts L{};
-            double ms6[6] = {0, 0, 0, 0, 0, 0};
-            if ((s = gz_plan(G, clen, start_bit, chunk, cap, &R, &nchunk, ms6, err, err_cap))) return s;
-            if (!R.status && R.pieces) {
-                if ((s = dev_need(G.text, R.text + 16, err, err_cap)) || (s = gz_fill(G, clen, start_bit, hist, &R, (u8 *)G.text.p, &rcrc, &refs, ms6, err, err_cap))) return s;
-            }
-            bool grown;
-            u64 rs2 = rsize;
-            st = round_verdict(R, clen, size, rs2, grown);
-            if (st == E_TEXT_CAP && R.pieces && cap < text_cap - done) st = 0;          // cut at the 1 GiB a round may hold, not at the caller's buffer
-            L.find_ms = ms6[0]; L.measure_ms = ms6[1]; L.stitch_ms = ms6[2]; L.emit_ms = ms6[3]; L.chain_ms = ms6[4]; L.resolve_ms = ms6[5];
-            if (!st && !grown) {
-                t0 = wall_ms();
-                if (R.text) RD_CK(hipMemcpy(text + done, G.text.p, R.text, hipMemcpyDeviceToHost), -3);
-                L.download_ms = wall_ms() - t0;
-                L.rounds = 1; L.chunks = nchunk; L.true_pieces = R.pieces; L.false_candidates = R.falses; L.candidates = R.cands;
-                L.deflate_blocks = R.blocks; L.compressed_bytes = ((R.end_bit + 7) >> 3) - rb; L.text_bytes = R.text; L.window_symbols = refs;
-            } else if (grown) L.grown_rounds = 1;
-            *last = L;
-            lnr_rdgpu_gz_add(total, &L);
-            if (st) return fail(st, (R.status ? R.bad_bit : R.end_bit) >> 3);
-            if (grown) { rsize = rs2; continue; }
-            crc = lnr_inf::crc_combine(crc, rcrc, R.text);
-            hist = hist + R.text > WIN ? WIN : (u32)(hist + R.text);
-            done += R.text; mtext += R.text; start_bit = R.end_bit; rsize = round;
-            if (R.stop == AT_FINAL) break;
+    Member m;
+    for (;;) {
+        u32 st = member_enter(m, gz, size);
+        if (st) return fail(st, m.pos);
+        if (m.end) break;
+        const u64 rsize = member_round_size(m, round), rb = m.start_bit >> 3, clen = size - rb < rsize ? size : rb + rsize;
+        const u64 cap = text_cap - done < (1ULL << 30) ? text_cap - done : 1ULL << 30;
+        Round R;
+        u32 nchunk = 0, rcrc = 0;
+        u64 refs = 0;
+        lnr_rdgpu_gz_counts L{};
+        double ms6[6] = {0, 0, 0, 0, 0, 0};
+        if ((s = gz_plan(G, clen, m.start_bit, chunk, cap, &R, &nchunk, ms6, err, err_cap))) return s;
+        if (!R.status && R.pieces) {
+            if ((s = dev_need(G.text, R.text + 16, err, err_cap)) || (s = gz_fill(G, clen, m.start_bit, m.hist, &R, (u8 *)G.text.p, &rcrc, &refs, ms6, err, err_cap))) return s;
         }
-        if ((st = check_trailer(gz, size, start_bit, crc, mtext, &off))) return fail(st, (start_bit + 7) >> 3);
-        total->members++;
+        bool grown, final = false;
+        st = round_verdict(m, R, clen, size, rsize, grown, &bad);
+        if (st == E_TEXT_CAP && R.pieces && cap < text_cap - done) st = 0;          // cut at the 1 GiB a round may hold, not at the caller's buffer
+        L.find_ms = ms6[0]; L.measure_ms = ms6[1]; L.stitch_ms = ms6[2]; L.emit_ms = ms6[3]; L.chain_ms = ms6[4]; L.resolve_ms = ms6[5];
+        if (!st && !grown) {
+            t0 = wall_ms();
+            if (R.text) RD_CK(hipMemcpy(text + done, G.text.p, R.text, hipMemcpyDeviceToHost), -3);
+            L.download_ms = wall_ms() - t0;
+            L.rounds = 1; L.chunks = nchunk; L.true_pieces = R.pieces; L.false_candidates = R.falses; L.candidates = R.cands;
+            L.deflate_blocks = R.blocks; L.compressed_bytes = ((R.end_bit + 7) >> 3) - rb; L.text_bytes = R.text; L.window_symbols = refs;
+        } else if (grown) L.grown_rounds = 1;
+        *last = L;
+        lnr_rdgpu_gz_add(total, &L);
+        if (st) return fail(st, bad);
+        if (grown) continue;
+        done += R.text;
+        if ((st = member_fold(m, gz, size, R, rcrc, &final, &bad))) return fail(st, bad);
+        total->members += final;
     }
     *text_size = done;
     return 0;

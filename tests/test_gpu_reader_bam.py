@@ -1,4 +1,4 @@
-"""GPU: BAM input of the reader's GPU twin (k_bam_find / k_bam_stitch / k_bam_meta / k_bam_emit / k_bam_names in
+"""GPU: BAM input of the reader's GPU twin (k_bam_find / k_bam_stitch / k_bam_meta / k_bam_emit / k_rd_gather in
 linear_amd/csrc/lnr_reader_kernels.hip behind lnr_reader_next_dev): on every fixture of tests/ubam_cases.py the blocks of lnr_reader_next --
 the same n per call, offsets, ordinals, ids -- through the device inflate and through gzread (LNR_READER_BGZF=0); the counts of
 lnr_reader_gpu_bam_stats against the Python decoder; windows of one BGZF block and of less than a record; the decoy and the long record

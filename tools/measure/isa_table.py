@@ -5,7 +5,7 @@
     python3 tools/measure/isa_table.py api.s [name substring ...]
 
 Per function: instructions, flat / global / ds / scratch loads+stores, lane moves, the forms of s_waitcnt (both counters drained, vmcnt(0)
-alone, a vector load left in flight, lgkmcnt alone), VGPRs and scratch bytes from the function's own resource directives."""
+alone, a vector load left in flight, lgkmcnt alone), VGPRs, SGPRs, LDS bytes, scratch bytes and occupancy from the function's own resource directives."""
 import re
 import sys
 
@@ -19,15 +19,15 @@ def main():
         m = re.match(r"^(_Z\w+|\w+):\s*(;.*)?$", line)
         if m and not line.startswith(".") and not m.group(1).startswith("BB") and not m.group(1).startswith(".L"):
             cur = m.group(1)
-            c = dict(name=cur, ins=0, flat_ld=0, flat_st=0, glob_ld=0, glob_st=0, ds=0, scr_ld=0, scr_st=0, lane=0, w_both=0, w_vm0=0, w_vmN=0, w_lgkm=0, waits=0, vgpr="-", scratch="-")
+            c = dict(name=cur, ins=0, flat_ld=0, flat_st=0, glob_ld=0, glob_st=0, ds=0, scr_ld=0, scr_st=0, lane=0, w_both=0, w_vm0=0, w_vmN=0, w_lgkm=0, waits=0, vgpr="-", sgpr="-", lds="-", scratch="-", occ="-")
             rows.append(c)
             continue
         if c is None:
             continue
         s = line.strip()
-        m = re.match(r"^; (NumVgprs|ScratchSize): (\d+)", s)
+        m = re.match(r"^; (NumVgprs|TotalNumSgprs|LDSByteSize|ScratchSize|Occupancy): (\d+)", s)
         if m:
-            c["vgpr" if m.group(1) == "NumVgprs" else "scratch"] = m.group(2)
+            c[{"NumVgprs": "vgpr", "TotalNumSgprs": "sgpr", "LDSByteSize": "lds", "ScratchSize": "scratch", "Occupancy": "occ"}[m.group(1)]] = m.group(2)
             continue
         if not s or s[0] in ";." or s.endswith(":"):
             continue
@@ -49,7 +49,7 @@ def main():
             elif vm and lg and int(lg.group(1)) == 0: c["w_both"] += 1
             elif vm: c["w_vm0"] += 1
             elif lg: c["w_lgkm"] += 1
-    cols = ("ins", "flat_ld", "flat_st", "glob_ld", "glob_st", "ds", "scr_ld", "scr_st", "lane", "waits", "w_both", "w_vm0", "w_vmN", "w_lgkm", "vgpr", "scratch")
+    cols = ("ins", "flat_ld", "flat_st", "glob_ld", "glob_st", "ds", "scr_ld", "scr_st", "lane", "waits", "w_both", "w_vm0", "w_vmN", "w_lgkm", "vgpr", "sgpr", "lds", "scratch", "occ")
     print("| function | " + " | ".join(cols) + " |")
     print("|---|" + "---|" * len(cols))
     for r in rows:
