@@ -268,6 +268,13 @@ lnr_status lnr_create(const lnr_opts *opts, lnr_ctx **out) {
     ctx->device = dev;
     ctx->tun = tuning_from_env(dev);
     ctx->lane1_nomem_test = ctx->tun.lane1_nomem;
+    if (const char *e = getenv("LNR_DEBUG_OCC")) if (atoi(e)) {
+        // what the runtime lets a CU hold of the single-wave job kernel at its launch configuration (registers, static + dynamic LDS)
+        size_t lds = (ctx->tun.job_lds_bytes + 15) & ~(size_t)15;
+        int nb = -1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, lnr::k_job, 64, lds) != hipSuccess) { (void)hipGetLastError(); nb = -1; }
+        fprintf(stderr, "[lnr] k_job: %d workgroups per CU at %zu B of dynamic LDS\n", nb, lds);
+    }
     ctx->lane[0] = lane_create(ctx, 0);
     bool ok = ctx->lane[0] && ctx->s_copy.create() && ctx->s_down.create() && ctx->ev_down.create() == hipSuccess && ctx->ev_done.create() == hipSuccess;
     if (!ok) { (void)hipGetLastError(); lnr_destroy(ctx); return LNR_ERR_HIP; }

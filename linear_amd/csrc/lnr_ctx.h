@@ -21,7 +21,7 @@ struct Index {
 };
 
 struct Tuning {
-    size_t job_lds_bytes = 6 * 1024;    // LDS half of k_job's two-level arena (LNR_JOB_LDS_KB overrides, for tuning): 2.6 KB static + 6 KB x 16 workgroups fit a CU's 160 KB (measured: 5 KB +2 %, 7 KB +1 %)
+    size_t job_lds_bytes = 4 * 1024;    // LDS half of k_job's two-level arena (LNR_JOB_LDS_KB overrides, for tuning).  At five waves per SIMD a CU holds 20 workgroups while 2.6 KB static + the arena stay within 8 KB each (the runtime's answer: LNR_DEBUG_OCC=1); measured at five waves (profiles/r18): 6 KB = 18 workgroups, 5 KB and 4 KB = 20, and 4 KB is the fastest of them
     u32 heavy_lds_kb = 48;              // LDS arena of k_job_heavy (LNR_HEAVY_LDS_KB)
     u32 mid_cap = 6144, mid_lds_kb = 24;   // reads with at least this many anchors run on 4 waves (k_job_mid: the DP is dealt over the waves); LNR_MID_CAP, LNR_MID_LDS_KB
     u32 heavy_cap = 0xffffffffu;        // reads with at least this many anchors (after the Y filter) take the 16-wave path (LNR_HEAVY_CAP overrides)

@@ -16,6 +16,14 @@
 #include <limits.h>
 #include "ref_sort.h"
 
+// LNR_HD_FI: small members of the values a kernel carves its arrays with (Arena, Vec): as a call they would take the object's address,
+// which keeps the whole object in private memory; inlined by force it can live in registers
+#if defined(__HIPCC__)
+#define LNR_HD_FI __host__ __device__ __forceinline__
+#else
+#define LNR_HD_FI inline
+#endif
+
 namespace lnr {
 
 typedef uint64_t u64;
@@ -108,31 +116,42 @@ LNR_HD inline u64 lnr_uni64(u64 v) { return ((u64)lnr_uni32((u32)(v >> 32)) << 3
 template <class T, class P = T *>
 struct Vec {
     P p; u32 n, cap; int *ovf;
-    LNR_HD void init(P p_, u32 cap_, int *ovf_) { p = p_; n = 0; cap = cap_; ovf = ovf_; }
+    LNR_HD_FI void init(P p_, u32 cap_, int *ovf_) { p = p_; n = 0; cap = cap_; ovf = ovf_; }
     LNR_HD void push(const T &v) { if (n < cap) p[n++] = v; else *ovf = 1; }
     // SIMT-uniform form for code that all lanes of a wave execute together: every lane tracks n, lane 0 stores
-    LNR_HD void push_u(const T &v) {
+    LNR_HD_FI void push_u(const T &v) {
         if (n < cap) { if (lnr_is_leader()) p[n] = v; n++; }
         else if (lnr_is_leader()) *ovf = 1;
     }
     LNR_HD T &operator[](u32 i) { return p[i]; }
     LNR_HD T &back() { return p[n - 1]; }
 };
-// Bump allocator over caller-provided storage.  With `next` set it is two-level: requests that do not
-// fit the fast region (LDS in the kernel) fall through to the next one (global scratch).
+// Bump allocator over caller-provided storage: a value with one or two regions.  With a far region set it is two-level: requests that
+// do not fit the fast region (LDS in the kernel) fall through to the far one (global scratch).  Both regions live in the one object --
+// no pointer to a second allocator -- so that a kernel can keep all of it in registers.
 struct Arena {
-    char *base; u64 off, cap; int ovf; Arena *next;
-    LNR_HD void init(void *b, u64 c) { base = (char *)b; off = 0; cap = c; ovf = 0; next = nullptr; }
-    template <class T> LNR_HD T *get(u64 n) {   // iterative on purpose: no recursion in device code
-        u64 bytes = (n * sizeof(T) + 15) & ~15ULL;
-        Arena *a = this;
-        while (a->off + bytes > a->cap) {
-            if (!a->next) { a->ovf = 1; ovf = 1; return (T *)base; }
-            a = a->next;
-        }
-        T *r = (T *)(a->base + a->off);
-        a->off += bytes;
+    char *base; u64 off, cap; int ovf;   // fast region (the only one after init)
+    char *fbase; u64 foff, fcap;         // far region (fbase == nullptr: none)
+    LNR_HD_FI void init(void *b, u64 c) { base = (char *)b; off = 0; cap = c; ovf = 0; fbase = nullptr; foff = 0; fcap = 0; }
+    // two-level, far region first: the fast region stays empty until set_fast hands it over (the kernel's binning borrows the LDS before)
+    LNR_HD_FI void init_far(void *b, u64 c) { init(b, 0); fbase = (char *)b; fcap = c; }
+    LNR_HD_FI void set_fast(void *b, u64 c) { base = (char *)b; off = 0; cap = c; }
+    // from the last region (all of a one-level arena)
+    // (in a kernel every lane of the wave asks for the same size: taken as wave-uniform, the marks and the arrays' bases stay scalar)
+    template <class T> LNR_HD_FI T *get_far(u64 n) {
+        u64 bytes = lnr_uni64((n * sizeof(T) + 15) & ~15ULL);
+        if (!fbase) return get<T>(n);
+        if (foff + bytes > fcap) { ovf = 1; return (T *)fbase; }
+        T *r = (T *)(fbase + foff);
+        foff += bytes;
         return r;
+    }
+    template <class T> LNR_HD_FI T *get(u64 n) {
+        u64 bytes = lnr_uni64((n * sizeof(T) + 15) & ~15ULL);
+        if (off + bytes <= cap) { T *r = (T *)(base + off); off += bytes; return r; }
+        if (fbase && foff + bytes <= fcap) { T *r = (T *)(fbase + foff); foff += bytes; return r; }
+        ovf = 1;
+        return (T *)base;
     }
 };
 // One level only (the tails: a read's global scratch).  No chain to walk, so in a kernel the base stays a value the compiler can follow
@@ -1204,8 +1223,9 @@ LNR_HD inline FeatViewT<FP> f2_view(GenomeFeatT<FP, OP> g, u64 id) {
 // kernel), then the order-dependent compaction with block-end propagation.
 template <class FV, class GF>
 LNR_HD inline void filter_hits_flags(const u64 *hits, u32 nhits, const FV f1[2], GF g, i32 *keep, u32 first, u32 step) {
+    const FV f1a = f1[0], f1b = f1[1];   // picked by a select: an array indexed by the strand would have to live in memory
     for (u32 it = 1 + first; it < nhits; it += step) {
-        u32 dist = wdist_checked(f1[cord_strand(hits[it])], f2_view(g, cord_id(hits[it])), cord_y(hits[it]) >> 4, cord_x(hits[it]) >> 4);
+        u32 dist = wdist_checked(cord_strand(hits[it]) ? f1b : f1a, f2_view(g, cord_id(hits[it])), cord_y(hits[it]) >> 4, cord_x(hits[it]) >> 4);
         keep[it] = dist < 50 ? 1 : 0;
     }
 }
@@ -1226,9 +1246,10 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FV f1_[2], GF g,
     // (wave form: the uniform state in scalar registers, see extend_window; the count goes back to the caller's vector on every way out)
     CV cords = cords_;
     struct NBack { CV &dst; CV &src; LNR_HD ~NBack() { dst.n = src.n; } } nback_{cords_, cords};
-    FV f1[2] = {f1_[0], f1_[1]};
+    FV f1a = f1_[0], f1b = f1_[1];   // (picked by a select, see filter_hits_flags)
     cords.p = (decltype(cords.p))lnr_uni64((u64)cords.p); cords.n = lnr_uni32(cords.n); cords.cap = lnr_uni32(cords.cap); cords.ovf = (int *)lnr_uni64((u64)cords.ovf);
-    for (int k = 0; k < 2; k++) { f1[k].p = (decltype(f1[k].p))lnr_uni64((u64)f1[k].p); f1[k].n = lnr_uni32(f1[k].n); }
+    f1a.p = (decltype(f1a.p))lnr_uni64((u64)f1a.p); f1a.n = lnr_uni32(f1a.n);
+    f1b.p = (decltype(f1b.p))lnr_uni64((u64)f1b.p); f1b.n = lnr_uni32(f1b.n);
     g.base = (decltype(g.base))lnr_uni64((u64)g.base); g.off = (decltype(g.off))lnr_uni64((u64)g.off); g.nseq = lnr_uni32(g.nseq);
     read_str = lnr_uni64(read_str); read_end = lnr_uni64(read_end); L = lnr_uni64(L);
     hitEnd = (i64)lnr_uni32(nhits);
@@ -1300,11 +1321,11 @@ LNR_HD inline void path_dst_2(const u64 *hits, u32 nhits, const FV f1_[2], GF g,
         if (f_append && cord_id(hi) != view_id) { view_id = cord_id(hi); view_f2 = f2_view(g, view_id); }
 #if defined(LNR_PROF) && defined(__HIP_DEVICE_COMPILE__)
         { unsigned long long t_ = clock64(); pdc_[9] += t_ - pdt_; pdt_ = t_; pdc_[0] += f_append ? 1 : 0; pdc_[10]++; }
-        if (f_append && !extend_window(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end, pdc_)) return;
+        if (f_append && !extend_window(cord_strand(hi) ? f1b : f1a, view_f2, cords, tail, cordy_str, cordy_end, pdc_)) return;
         pdt_ = clock64();
         if (0)
 #endif
-        if (f_append && !extend_window(f1[cord_strand(hi)], view_f2, cords, tail, cordy_str, cordy_end)) return;
+        if (f_append && !extend_window(cord_strand(hi) ? f1b : f1a, view_f2, cords, tail, cordy_str, cordy_end)) return;
         if (f_block_end) { tail |= F_END; if (lnr_is_leader()) cords.p[cords.n - 1] = tail; }
         itt_next = f_block_end ? itt_first : itt_next;
         f_sp_r = false; f_block_end = false;
@@ -1470,10 +1491,8 @@ LNR_HD inline bool job_carve(Arena &ar, u32 cap, JobScratch &S, int *ovf) {
     S.rec.score = ar.get<i32>(c2); S.rec.score2 = ar.get<i32>(c2); S.rec.len = ar.get<i32>(c2);
     S.rec.p2 = ar.get<i32>(c2); S.rec.root = ar.get<i32>(c2); S.rec.leaf = ar.get<i32>(c2);
     // hits / hscore: always behind the fast region (the kernels reuse the whole fast region once the anchor traceback has filled them)
-    Arena &far_ = ar.next ? *ar.next : ar;
-    S.hits.init(far_.get<u64>(c2), c2, ovf);
-    S.hscore.init(far_.get<i32>(c2), c2, ovf);
-    if (far_.ovf) ar.ovf = 1;
+    S.hits.init(ar.get_far<u64>(c2), c2, ovf);
+    S.hscore.init(ar.get_far<i32>(c2), c2, ovf);
     S.cnt = ar.get<i32>(c2); S.chain = ar.get<i32>(c2); S.chain_sc = ar.get<i32>(c2);
     S.sep.init(ar.get<UP>(c2), c2, ovf);
     S.sep_score = ar.get<i32>(c2);

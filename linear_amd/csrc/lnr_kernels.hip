@@ -37,7 +37,10 @@ __global__ void __launch_bounds__(64) k_words_out(CopySegs S) {
     for (u64 i = (u64)(b - w0) * 64 + threadIdx.x; i < n; i += (u64)nwg * 64) dst[i] = src[i];
 }
 
-#if defined(K_JOB_WAVES) && K_JOB_WAVES > 4
+#ifndef K_JOB_WAVES
+#define K_JOB_WAVES 5   // waves per SIMD the single-wave job kernel is compiled for (see k_job)
+#endif
+#if K_JOB_WAVES > 4
 #define JOB_INLINE __forceinline__
 #else
 #define JOB_INLINE
@@ -2493,6 +2496,18 @@ struct SortShare { u64 *a; u32 *L, *R; u64 *tasks, *stg; u32 stg_cap, n; };
 #ifndef SORT_BLOCK_MIN
 #define SORT_BLOCK_MIN 2048
 #endif
+// What the waves of a multi-wave workgroup share for the three phases they run together.  The single-wave kernel has none of it: every
+// static LDS byte there is taken from its arena or from the workgroups a CU holds.
+template <int NW> struct JobShare {
+    DpShare dp;              // what the helper waves need for the DP
+    RadixShare rs;           // ... and for the radix sort
+    u32 rhist[NW][256];      // per-wave digit counts / cursors of the workgroup radix sort
+    u32 rtot[256], rflag;
+    SortShare so;            // ... and for the x-descending sort
+    SortStack sstk[NW];
+    SortDeferQ sq;
+};
+template <> struct JobShare<1> {};
 // (inlined into its four kernels: JobArgs stays in the kernel arguments -- scalar loads, pointers known to be global memory -- instead of
 // reaching the job code as a stack copy behind a call)
 template <int NW>
@@ -2503,17 +2518,11 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
     __shared__ u32 s_nH, s_nhits;
     __shared__ LeaderScratch s_ls;   // introsort stack + tree table: one per workgroup, in LDS
     // the 256 digit counters of the wave radix sort live in the four 64-entry tree tables (used by the traceback only): every
-    // static LDS byte of the single-wave kernel is one byte less for its arena at 16 workgroups per CU
+    // static LDS byte of the single-wave kernel is one byte less for its arena at 20 workgroups per CU
     static_assert(sizeof(s_ls.l_root) + sizeof(s_ls.l_score) + sizeof(s_ls.l_len) + sizeof(s_ls.l_leaf) == 256 * sizeof(u32), "tree tables = 256 words");
     LNR_LDS u32 *hist = as_lds((u32 *)s_ls.l_root);
     __shared__ DpTile<NW> s_tile;    // tiled chaining DP: leaf flags (+ the per-wave candidates of a multi-wave workgroup)
-    __shared__ DpShare s_dp;         // NW > 1: what the helper waves need for the DP
-    __shared__ RadixShare s_rs;      // NW > 1: ... and for the radix sort
-    __shared__ u32 s_rhist[NW > 1 ? NW : 1][256];   // per-wave digit counts / cursors of the workgroup radix sort
-    __shared__ u32 s_rtot[NW > 1 ? 256 : 1], s_rflag;
-    __shared__ SortShare s_so;       // NW > 1: ... and for the x-descending sort
-    __shared__ SortStack s_sstk[NW > 1 ? NW : 1];
-    __shared__ SortDeferQ s_sq;
+    __shared__ JobShare<NW> s_sh;    // NW > 1 only (empty for the single-wave kernel)
     int lane = lane_id();
     int wave = (int)(threadIdx.x >> 6);
     const bool lead = NW == 1 || wave == 0;
@@ -2544,8 +2553,9 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
         u32 m = 0;
         JobScratch S;
         int mode = (int)A.J.mode[j];
-        Arena slow, ar;
+        Arena ar;
         bool ok = true;
+        u64 carve_mark_off = 0, carve_mark_foff = 0;   // the arena's marks in front of job_carve: carving again from them gives the same arrays
 #ifdef LNR_PROF
         for (int q = 0; q < 16; q++) lnr_job_ph[q] = 0;
 #endif
@@ -2558,13 +2568,13 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
             cap = n + 2;   // scratch is sized by the anchors that passed the Y filter (known before the launch), not by the bucket entries
             LNR_TICK(prof, 0, tk_);
             // two-level arena: dynamic LDS first (re-used once binning is done), the job's global scratch behind it
-            slow.init(A.scratch + A.scr_off[j], job_scratch_bytes(cap));
-            LNR_GLOBAL u64 *alt = as_global(slow.get<u64>(cap));   // radix ping-pong buffer; before that, the survivors of the binning pre-filter
+            ar.init_far(A.scratch + A.scr_off[j], job_scratch_bytes(cap));
+            LNR_GLOBAL u64 *alt = as_global(ar.get_far<u64>(cap));   // radix ping-pong buffer; before that, the survivors of the binning pre-filter
             if (NW == 1 && A.stop_after == 1) break;   // (diagnostic: start-up only)
             n = binning_wave(ag, n, alt, dyn_lds, A.lds_bytes, A.nbins);   // uses the dynamic LDS as its histogram
             LNR_TICK(prof, 1, tk_);
             if (NW == 1 && A.stop_after == 2) break;
-            ar.init((void *)(u32 *)dyn_lds, A.arena_lds); ar.next = &slow;
+            ar.set_fast((void *)(u32 *)dyn_lds, A.arena_lds);
             a = ag;
             if (n > 1) {
                 s_alt = alt;
@@ -2574,14 +2584,14 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
                 if (NW == 1) radix_sort_wave(ag, alt, n, hist);
             }
         }
-        if (NW > 1) {
+        if constexpr (NW > 1) {
             // the radix sort of a multi-wave workgroup is dealt over its waves (long arrays only: five barriers per pass)
-            if (threadIdx.x == 0) { s_rs.a = ag; s_rs.alt = s_alt; s_rs.n = (n > 1 && n >= RADIX_BLOCK_MIN) ? n : 0; }
+            if (threadIdx.x == 0) { s_sh.rs.a = ag; s_sh.rs.alt = s_alt; s_sh.rs.n = (n > 1 && n >= RADIX_BLOCK_MIN) ? n : 0; }
             __syncthreads();
-            RadixShare rs = s_rs;
+            RadixShare rs = s_sh.rs;
             if (rs.n) {                                // ends with a workgroup barrier (call / inline: see chain_blocks_prepare_wave)
-                if (NW >= 4) { [[clang::noinline]] radix_sort_block<NW>(rs.a, rs.alt, rs.n, as_lds(s_rhist), as_lds(s_rtot), as_lds(&s_rflag)); }
-                else radix_sort_block<NW>(rs.a, rs.alt, rs.n, as_lds(s_rhist), as_lds(s_rtot), as_lds(&s_rflag));
+                if (NW >= 4) { [[clang::noinline]] radix_sort_block<NW>(rs.a, rs.alt, rs.n, as_lds(s_sh.rhist), as_lds(s_sh.rtot), as_lds(&s_sh.rflag)); }
+                else radix_sort_block<NW>(rs.a, rs.alt, rs.n, as_lds(s_sh.rhist), as_lds(s_sh.rtot), as_lds(&s_sh.rflag));
             }
             else if (lead && n > 1) radix_sort_wave(ag, s_alt, n, hist);
         }
@@ -2599,7 +2609,7 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
             if (m > 1) {
                 // scratch of the sort: position lists in the (dead) radix buffer, task list behind it
                 so_L = (u32 *)(u64 *)s_alt; so_R = so_L + (m + 2);
-                so_tasks = slow.get<u64>((u64)m + 2);
+                so_tasks = ar.get_far<u64>((u64)m + 2);
                 // free LDS behind the arena's current mark can stage the final small sorts when `a` itself is in global memory
                 {
                     bool a_in_lds = (char *)a >= (char *)(u32 *)dyn_lds && (char *)a < (char *)(u32 *)dyn_lds + A.arena_lds;
@@ -2609,18 +2619,19 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
                 if (NW == 1) introsort_xdesc_wave(a, m, so_L, so_R, so_tasks, &s_ls, so_stg, so_stg_cap);
             }
         }
-        if (NW > 1) {
+        if constexpr (NW > 1) {
             // the x-descending sort of a multi-wave workgroup: wave 0 partitions from the top, all waves finish the sub-ranges
-            if (threadIdx.x == 0) { s_so.a = a; s_so.L = so_L; s_so.R = so_R; s_so.tasks = so_tasks; s_so.stg = so_stg; s_so.stg_cap = so_stg_cap; s_so.n = (m > 1 && m >= SORT_BLOCK_MIN) ? m : 0; }
+            if (threadIdx.x == 0) { s_sh.so.a = a; s_sh.so.L = so_L; s_sh.so.R = so_R; s_sh.so.tasks = so_tasks; s_sh.so.stg = so_stg; s_sh.so.stg_cap = so_stg_cap; s_sh.so.n = (m > 1 && m >= SORT_BLOCK_MIN) ? m : 0; }
             __syncthreads();
-            SortShare so = s_so;
-            if (so.n) introsort_xdesc_block<NW>(so.a, so.n, so.L, so.R, so.tasks, s_sstk, &s_sq, so.stg, so.stg_cap);   // ends with a workgroup barrier
+            SortShare so = s_sh.so;
+            if (so.n) introsort_xdesc_block<NW>(so.a, so.n, so.L, so.R, so.tasks, s_sh.sstk, &s_sh.sq, so.stg, so.stg_cap);   // ends with a workgroup barrier
             else if (lead && m > 1) introsort_xdesc_wave(a, m, so_L, so_R, so_tasks, &s_ls, so_stg, so_stg_cap);
         }
         if (lead) {
             LNR_TICK(prof, 15, tk_);
             if (NW == 1 && A.stop_after == 4) break;
-            ok = job_carve(ar, m, S, &s_ovf) && !slow.ovf;
+            carve_mark_off = ar.off; carve_mark_foff = ar.foff;
+            ok = job_carve(ar, m, S, &s_ovf);
             if (ok) {
                 job_fill_xy(a, m, S, (u32)lane, 64);
                 WSYNC();
@@ -2638,18 +2649,18 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
         }
 #endif
         // ---------------- chaining DP
-        if (NW == 1) {
+        if constexpr (NW == 1) {
             if (!ok) break;
             if (m >= 2) {
                 best_chains_wave(S.xs, S.ys, m, S.rec, job_parm(mode).score_type, S.cnt, s_tile.tleaf);
             }
         } else {
             if (threadIdx.x == 0) {
-                s_dp.xs = S.xs; s_dp.ys = S.ys; s_dp.rec = S.rec; s_dp.jlo = S.cnt; s_dp.m = ok ? m : 0;
-                s_dp.score_type = job_parm(mode).score_type; s_dp.abort = ok ? 0 : 1;
+                s_sh.dp.xs = S.xs; s_sh.dp.ys = S.ys; s_sh.dp.rec = S.rec; s_sh.dp.jlo = S.cnt; s_sh.dp.m = ok ? m : 0;
+                s_sh.dp.score_type = job_parm(mode).score_type; s_sh.dp.abort = ok ? 0 : 1;
             }
             __syncthreads();
-            DpShare d = s_dp;
+            DpShare d = s_sh.dp;
             if (d.abort) break;                        // uniform: every wave leaves together
             if (d.m >= 2) best_chains_block<NW>(d.xs, d.ys, d.m, d.rec, d.score_type, d.jlo, s_tile);   // ends with a workgroup barrier
         }
@@ -2681,7 +2692,7 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
             // the keep flags (20 B per hit) and 100 B per block for as many blocks as the rest holds.  A read with more blocks than that (seen
             // only when the counts are known) falls back to the arrays carved before -- same code, other pointers.
             u64 *hits2 = a;   // output of the block filter: the anchors are dead by now and hits never outnumber them (job_blocks_finish)
-            const JobScratch S0 = S;
+            const u32 nhs0 = S.hscore.n;
             u32 nb = 0;
             bool in_lds = false;
             if (A.arena_lds) {
@@ -2716,7 +2727,12 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
                         }
                         if (fits) { in_lds = true; hits2 = lH; }
                     }
-                    if (!in_lds) { WSYNC(); S = S0; }
+                    if (!in_lds) {   // back to the arrays carved before the DP: the same requests from the same marks (only the two counts are state)
+                        WSYNC();
+                        ar.off = carve_mark_off; ar.foff = carve_mark_foff;
+                        job_carve(ar, m, S, &s_ovf);
+                        S.hits.n = nh; S.hscore.n = nhs0;
+                    }
                 }
             }
             if (!in_lds) {
@@ -2799,12 +2815,9 @@ __device__ __forceinline__ void job_group_run(const JobArgs &A, u32 grp, LNR_LDS
 #endif
 }
 
-// K_JOB_WAVES: waves per SIMD the single-wave kernel is compiled for (4: 128 VGPRs; 6: 80 VGPRs with spills -- the compiler's budget
-// for 5 is 104 registers, which the hardware's granule of 8 turns into 4 waves again).  The phase functions above are inlined by force
-// in the register-capped build: a call keeps the callee's own, uncapped register count (traceback 104, introsort 104).
-#ifndef K_JOB_WAVES
-#define K_JOB_WAVES 4
-#endif
+// K_JOB_WAVES: waves per SIMD the single-wave kernel is compiled for (4: 128 VGPRs; 5: 96 VGPRs, the default -- 20 single-wave workgroups
+// per CU with the 4 KB arena it is launched with; 6: 80 VGPRs with spills in the hot loops).  The phase functions above are inlined by
+// force in the register-capped builds: a call keeps the callee's own, uncapped register count (traceback 104, introsort 104).
 __global__ void __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(K_JOB_WAVES, K_JOB_WAVES))) k_job(JobArgs A) {
     extern __shared__ u32 dyn_lds[];
     if (A.grp_lo + blockIdx.x >= A.grp_hi) return;
