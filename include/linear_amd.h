@@ -332,6 +332,35 @@ lnr_status lnr_reader_gpu_bam_stats(const lnr_reader *r, lnr_bam_stats *out);
 int lnr_reader_format(lnr_reader *r);
 uint32_t lnr_reader_gpu_bam_tile(void);
 
+/* The reference genome, from files to sequences resident on `device` (replaces, for a front-end, loading it through lnr_reader_next with
+ * max_reads = 1 and uploading it from the host).  lnr_genome_load_gpu runs, per file, lnr_reader_open + lnr_reader_gpu_open(r, device, 1) and
+ * lnr_reader_next_dev(r, block_bases, ...) until it delivers nothing: FASTA / FASTQ text is parsed on the device, BGZF is inflated there, plain
+ * gzip goes through gzread unless LNR_GENOME_GPU_GZIP asks for the device inflate (lnr_reader_gpu_gzip(r, 1)).  Every delivered block is copied
+ * device to device, on the reader's stream, into an allocation the genome owns (one per block); no base crosses the bus.  The object holds
+ * the sequences the lnr_reader_next(max_reads = 1) loop over the same files delivers, in the same order (files in order, records in file
+ * order): the same lengths, the same Dna5 ordinals, the same header lines (whole; a front-end cuts them at the first blank itself).
+ * block_bases: bases per block, 0 = 2^30 (no record the reader delivers is longer: its text limit is 2^30 bytes); the sequences do not
+ * depend on it.  lnr_genome_info: any out pointer may be NULL; len[nseq], id_off[nseq + 1] and the array d_seq[nseq] are host arrays owned
+ * by the object, ids = the header lines '\0'-separated, d_seq[i] = device address of sequence i (never NULL, also where len[i] == 0; what
+ * lnr_index_build and lnr_writer_set_genome_dev take) -- *d_seq is NULL after lnr_genome_drop_dev.  lnr_genome_to_host: one download into
+ * host memory of the object, kept until lnr_genome_free; repeated calls return the same pointers; after lnr_genome_drop_dev only where it
+ * was called before (else LNR_ERR_ARG).  lnr_genome_drop_dev frees the device copy (lengths, ids and a host copy stay).  Every entry leaves
+ * the caller's current device as it found it.
+ * Errors of lnr_genome_load_gpu (*out is NULL, nothing stays allocated, lnr_genome_error(NULL) = the message of this thread's last failed
+ * load): a file that is a BAM: LNR_ERR_ARG naming the file; a file that cannot be opened: the reader's status; a record longer than
+ * block_bases or whose text exceeds the reader's limit: LNR_ERR_LIMIT naming the file and the record's ordinal in it (from 0); a corrupt
+ * compressed block: the reader's LNR_ERR_ARG text with its file offset; no usable device, or a library linked without its device half:
+ * LNR_ERR_NO_DEVICE.  Files without any sequence: LNR_OK and nseq == 0. */
+typedef struct lnr_genome lnr_genome;
+#define LNR_GENOME_GPU_GZIP 1u   /* plain (non-BGZF) gzip members inflated on the device, as lnr_reader_gpu_gzip(r, 1) */
+lnr_status lnr_genome_load_gpu(const char *const *paths, uint32_t npaths, int32_t device, uint32_t flags, uint64_t block_bases /* 0 = default */, lnr_genome **out);
+lnr_status lnr_genome_info(const lnr_genome *g, uint32_t *nseq, const uint64_t **len /* nseq, host */, const char **ids /* NUL-terminated, whole header lines */,
+                           const uint64_t **id_off /* nseq+1 */, const uint8_t *const **d_seq /* nseq device pointers, host array; NULL after drop_dev */);
+lnr_status lnr_genome_to_host(lnr_genome *g, const uint8_t *const **seq);
+lnr_status lnr_genome_drop_dev(lnr_genome *g);
+const char *lnr_genome_error(const lnr_genome *g);
+void lnr_genome_free(lnr_genome *g);
+
 /* Output side (host threads, and a GPU twin below; replaces, for this path, the calculator's tail cords2BamLink + fillBamRecords, src/mapper.cpp:463-470,
  * src/f_io.cpp:758-1011, src/align_util.cpp:301-343,452-744, and the printer's writeSam / print_cords_apf, src/f_io.cpp:100-207,
  * 313-412): the cords of a batch as SAM records (what = 1) or APF text (what = 2), byte for byte what the reference prints for
@@ -375,6 +404,14 @@ const char *lnr_writer_error(const lnr_writer *w);
  * writer stays independent of any context.  reads_concat / read_off[n + 1]: the layout lnr_filter_batch takes (device memory for _dev).
  * Text lifetime, current device and lnr_writer_gpu_times as for the calls above. */
 lnr_status lnr_writer_set_genome(lnr_writer *w, const uint8_t *const *seq);
+/* The GPU side's copy taken from device memory instead: d_seq = nseq device pointers on the writer's device (a host array, e.g. lnr_genome_info's),
+ * copied device to device on the writer's stream before the call returns; nothing is borrowed.  After lnr_writer_gpu_open (before it: LNR_ERR_ARG).
+ * The GPU SEQ / BAM forms then work as after lnr_writer_set_genome; the host forms keep returning "no bases for SEQ" unless host pointers are
+ * set as well.  A later lnr_writer_set_genome replaces the copy (the next GPU SEQ call uploads the host sequences); NULL = off.
+ * Nothing about d_seq is checked beyond NULL entries: sequence i is read for the genome_len[i] bytes given to lnr_writer_create, whatever
+ * the genome behind the pointers was loaded with (shorter sequences: bytes behind them are read), and pointers into another device's memory
+ * are not refused: the copy then fails with LNR_ERR_HIP, or goes over the peer link where peer access is on. */
+lnr_status lnr_writer_set_genome_dev(lnr_writer *w, const uint8_t *const *d_seq);
 lnr_status lnr_writer_format_seq(lnr_writer *w, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_off,
                                  const char *read_ids, const uint64_t *id_off, uint32_t threads, const char **text, uint64_t *size);
 lnr_status lnr_writer_format_seq_gpu(lnr_writer *w, const lnr_cords *cords, const uint8_t *reads_concat, const uint64_t *read_off,

@@ -96,7 +96,8 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_reader_gpu_gzip", "lnr_reader_gpu_gzip_stats", "lnr_gunzip_gpu",
            "lnr_reader_gpu_bam_stats", "lnr_reader_gpu_bam_tile", "lnr_reader_format",
            "lnr_writer_sort_begin", "lnr_writer_sort_finish", "lnr_writer_sort_next", "lnr_writer_sort_bai", "lnr_writer_sort_info_get", "lnr_writer_sort_end",
-           "lnr_writer_sort_host", "lnr_writer_bai_host", "lnr_writer_sort_spill", "lnr_writer_sort_hold_info_get"]
+           "lnr_writer_sort_host", "lnr_writer_bai_host", "lnr_writer_sort_spill", "lnr_writer_sort_hold_info_get",
+           "lnr_genome_load_gpu", "lnr_genome_info", "lnr_genome_to_host", "lnr_genome_drop_dev", "lnr_genome_error", "lnr_genome_free", "lnr_writer_set_genome_dev"]
 
 
 class LnrBgzfStats(C.Structure):
@@ -198,6 +199,15 @@ def load_library() -> C.CDLL:
     lib.lnr_writer_sort_end.argtypes = [C.c_void_p]
     lib.lnr_writer_sort_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]
     lib.lnr_writer_bai_host.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, _u64p, C.c_uint64, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_genome_load_gpu.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.lnr_genome_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(_u64p), C.POINTER(C.c_void_p), C.POINTER(_u64p), C.POINTER(C.POINTER(C.c_void_p))]
+    lib.lnr_genome_to_host.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_void_p))]
+    lib.lnr_genome_drop_dev.argtypes = [C.c_void_p]
+    lib.lnr_genome_error.restype = C.c_char_p
+    lib.lnr_genome_error.argtypes = [C.c_void_p]
+    lib.lnr_genome_free.restype = None
+    lib.lnr_genome_free.argtypes = [C.c_void_p]
+    lib.lnr_writer_set_genome_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     return lib
 
 
@@ -516,6 +526,90 @@ class Reader:
             pass
 
 
+LNR_GENOME_GPU_GZIP = 1
+
+
+class _GenomeView(np.ndarray):
+    """A view of a Genome's host copy that keeps the Genome (and so the memory) alive: arrays derived from it hold it as their base."""
+    _owner = None
+
+
+class Genome:
+    """The reference genome loaded on the GPU (lnr_genome_load_gpu): files -> device-resident sequences, parsed (and, for BGZF, inflated)
+    on the device.  lens / ids (whole header lines) live on the host; device_ptrs() is what Filter.build_index_ptrs and
+    Writer.set_genome_dev take."""
+
+    def __init__(self, lib, h):
+        self.lib, self.h = lib, h
+        n, lens, ids, ido = C.c_uint32(), _u64p(), C.c_void_p(), _u64p()
+        self._ck(lib.lnr_genome_info(h, C.byref(n), C.byref(lens), C.byref(ids), C.byref(ido), None))
+        self.nseq = n.value
+        self.lens = [int(lens[i]) for i in range(self.nseq)]
+        raw = C.string_at(ids, int(ido[self.nseq])) if self.nseq else b""
+        self.ids = [raw[int(ido[k]):int(ido[k + 1]) - 1].decode(errors="replace") for k in range(self.nseq)]
+
+    @classmethod
+    def load_gpu(cls, paths, device: int = 0, gpu_gzip: bool = False, block_bases: int = 0) -> "Genome":
+        """paths: one file name or a list, read in order.  gpu_gzip: plain gzip files are inflated on the device too (BGZF always is).
+        block_bases: bases per delivered block (0 = 2^30); the sequences do not depend on it."""
+        lib = load_library()
+        if isinstance(paths, (str, bytes, os.PathLike)):
+            paths = [paths]
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        h = C.c_void_p()
+        st = lib.lnr_genome_load_gpu(arr, len(paths), device, LNR_GENOME_GPU_GZIP if gpu_gzip else 0, block_bases, C.byref(h))
+        if st != 0:
+            raise LnrError(st, lib.lnr_strerror(st).decode(), lib.lnr_genome_error(None).decode(errors="replace"))
+        return cls(lib, h)
+
+    def _ck(self, st: int):
+        if st != 0:
+            raise LnrError(st, self.lib.lnr_strerror(st).decode(), self.lib.lnr_genome_error(self.h).decode(errors="replace"))
+
+    def device_ptrs(self):
+        """Device addresses of the sequences (ints, never 0), or None after drop_dev()."""
+        d = C.POINTER(C.c_void_p)()
+        self._ck(self.lib.lnr_genome_info(self.h, None, None, None, None, C.byref(d)))
+        return [int(d[i] or 0) for i in range(self.nseq)] if d else None
+
+    def to_host(self) -> list:
+        """One download (kept by the object): a list of uint8 arrays of Dna5 ordinals, views of the object's host copy.  The arrays hold a
+        reference to the Genome, so the memory lives while one of them (or an array sliced from it) does; close() frees it at once: do
+        not touch the arrays after an explicit close()."""
+        if not self.h:
+            raise LnrError(-1, "invalid argument", "the Genome is closed")
+        p = C.POINTER(C.c_void_p)()
+        self._ck(self.lib.lnr_genome_to_host(self.h, C.byref(p)))
+        out = []
+        for i in range(self.nseq):
+            n = self.lens[i]
+            a = (np.ctypeslib.as_array(C.cast(p[i], _u8p), shape=(n,)) if n else np.zeros(0, np.uint8)).view(_GenomeView)
+            a._owner = self
+            out.append(a)
+        return out
+
+    def build_index(self, flt: "Filter", layout_threads: int = 1) -> "LnrIndexInfo":
+        """lnr_index_build on `flt` (a Filter on the same device) from the device pointers."""
+        ptrs = self.device_ptrs()
+        if ptrs is None:
+            raise LnrError(-1, "invalid argument", "Genome.build_index: the device copy has been dropped (drop_dev)")
+        return flt.build_index_ptrs(ptrs, self.lens, layout_threads)
+
+    def drop_dev(self) -> None:
+        self._ck(self.lib.lnr_genome_drop_dev(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lnr_genome_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Writer:
     """Cords of a batch -> SAM records / APF text: format() on host threads (no GPU needed), format_gpu() / format_dev() on the GPU."""
 
@@ -599,6 +693,14 @@ class Writer:
         arr = (_u8p * max(len(keep), 1))(*[_p(s, _u8p) for s in keep])
         self._genome = (keep, arr)
         self._check(self.lib.lnr_writer_set_genome(self.h, arr))
+
+    def set_genome_dev(self, device_ptrs) -> None:
+        """The GPU side's genome copied from device memory (Genome.device_ptrs()); after gpu_open.  None = off."""
+        if device_ptrs is None:
+            self._check(self.lib.lnr_writer_set_genome_dev(self.h, None))
+            return
+        arr = (C.c_void_p * max(len(device_ptrs), 1))(*[int(p) for p in device_ptrs])
+        self._check(self.lib.lnr_writer_set_genome_dev(self.h, arr))
 
     @staticmethod
     def _seq_args(cord_off, cords_str, cords_end, reads, read_off):

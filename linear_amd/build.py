@@ -31,16 +31,18 @@ def needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+HOST_TUS = ("lnr_reader.cpp", "lnr_output.cpp", "lnr_genome.cpp")      # host code by g++: reader, writer, genome loader (each reaches its device half through a hook header)
 DEVICE_TUS = ["lnr_api.hip", "lnr_gap_kernels.hip", "lnr_output_kernels.hip", "lnr_reader_kernels.hip"]      # compiled side by side (the gap re-mapper's kernels are half of the compile time)
 # sources a translation unit does NOT see: an edit there leaves its object alone (everything else in csrc/ + the public header is a dependency)
 OUT_GPU = {"lnr_output_kernels.hip", "lnr_output_hd.h", "lnr_output_hook.h", "lnr_span_hd.h", "lnr_deflate_hd.h", "lnr_inflate_hd.h"}       # the writer's GPU side: seen by its own unit (and the hook by lnr_output.cpp); the BGZF deflate uses the inflate header's CRC32
 RD_GPU = {"lnr_reader_kernels.hip", "lnr_reader_hd.h", "lnr_reader_hook.h", "lnr_inflate_hd.h", "lnr_bam_hd.h", "lnr_gunzip_hd.h", "lnr_window_hd.h"}       # the reader's GPU side: seen by its own unit (the hook by lnr_reader.cpp, which alone sees lnr_window_hd.h)
 API_HOST = {"lnr_host_util.h", "lnr_ctx.h", "lnr_handover.h", "lnr_index.h", "lnr_batch.h", "lnr_gap_stage.h"}      # host side of lnr_api.hip, included by it alone
-NOT_A_DEP = {"lnr_api.hip": {"lnr_gap_kernels.hip", "lnr_gap_hd.h", "lnr_reader.cpp", "lnr_output.cpp", "linear_filter_main.cpp"} | OUT_GPU | RD_GPU,
-             "lnr_gap_kernels.hip": {"lnr_api.hip", "lnr_kernels.hip", "lnr_reader.cpp", "lnr_output.cpp", "linear_filter_main.cpp"} | OUT_GPU | RD_GPU | API_HOST,
+NOT_A_DEP = {"lnr_api.hip": {"lnr_gap_kernels.hip", "lnr_gap_hd.h", "lnr_reader.cpp", "lnr_output.cpp", "lnr_genome.cpp", "linear_filter_main.cpp"} | OUT_GPU | RD_GPU,
+             "lnr_gap_kernels.hip": {"lnr_api.hip", "lnr_kernels.hip", "lnr_reader.cpp", "lnr_output.cpp", "lnr_genome.cpp", "linear_filter_main.cpp"} | OUT_GPU | RD_GPU | API_HOST,
              "lnr_output_kernels.hip": set(SOURCES) - OUT_GPU - {"ref_sort.h"},
              "lnr_reader_kernels.hip": set(SOURCES) - RD_GPU,
-             "lnr_reader.cpp": set(SOURCES) - {"lnr_reader.cpp", "lnr_reader_hook.h", "lnr_inflate_hd.h", "lnr_bam_hd.h", "lnr_gunzip_hd.h", "lnr_window_hd.h"}, "lnr_output.cpp": set(SOURCES) - {"lnr_output.cpp", "lnr_output_hook.h"}}
+             "lnr_reader.cpp": set(SOURCES) - {"lnr_reader.cpp", "lnr_reader_hook.h", "lnr_inflate_hd.h", "lnr_bam_hd.h", "lnr_gunzip_hd.h", "lnr_window_hd.h"}, "lnr_output.cpp": set(SOURCES) - {"lnr_output.cpp", "lnr_output_hook.h"},
+             "lnr_genome.cpp": set(SOURCES) - {"lnr_genome.cpp", "lnr_reader_hook.h"}}
 
 
 def stale(obj: str, src: str) -> bool:
@@ -59,7 +61,7 @@ def build(force: bool = False, defines: tuple = (), out: str | None = None, only
     if out and only:
         build()
         tag = "." + os.path.basename(out).replace(".so", "")
-        stock = [os.path.join(HERE, s.replace(".cpp", ".o")) for s in ("lnr_reader.cpp", "lnr_output.cpp")] + [os.path.join(HERE, s.replace(".hip", ".o")) for s in DEVICE_TUS if s not in only]
+        stock = [os.path.join(HERE, s.replace(".cpp", ".o")) for s in HOST_TUS] + [os.path.join(HERE, s.replace(".hip", ".o")) for s in DEVICE_TUS if s not in only]
         mine = [(os.path.join(HERE, s.replace(".hip", tag + ".o")), s) for s in only]
         note, want = out + ".defines", " ".join(defines) + "\n"      # what the variant was built with, beside it: other defines, another build
         same = os.path.exists(note) and open(note).read() == want
@@ -79,7 +81,7 @@ def build(force: bool = False, defines: tuple = (), out: str | None = None, only
         tag = "" if not out else "." + os.path.basename(out).replace(".so", "")
         jobs = []
         # host-only translation units (FASTA / FASTQ reader, SAM / APF writer) by the host compiler, device code + C ABI by hipcc, one library
-        for src in ("lnr_reader.cpp", "lnr_output.cpp"):
+        for src in HOST_TUS:
             obj = os.path.join(HERE, src.replace(".cpp", ".o"))
             jobs.append((obj, None if not (force or stale(obj, src)) else ["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-c", os.path.join(CSRC, src), "-o", obj]))
         for src in DEVICE_TUS:

@@ -35,6 +35,10 @@
 //                  (lnr_writer_sort_spill right after every begin).
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
+//   genome on GPU  --gpu-genome (extension): the genome files are loaded by lnr_genome_load_gpu on the first GPU (text parsed there, BGZF inflated
+//                  there, plain gzip too with --gpu-gunzip), the index is built from the device pointers, a GPU writer with --sam-seq takes its
+//                  copy device to device (lnr_writer_set_genome_dev), then the loader's copy is dropped.  What needs host bases (a host writer
+//                  with --sam-seq, --index-mode build on the other GPUs) takes one download (lnr_genome_to_host).  The same bytes as without it.
 //   BAM input      (extension) a read file may be a BAM, aligned or unaligned: found by its content (the first four inflated bytes are "BAM\1"), never
 //                  by its name, with the default host reader and under --gpu-reader (record starts found on the GPU: DESIGN 6h).  Its reads are
 //                  what `samtools fastq` prints: secondary / supplementary records (flag 0x100 / 0x800) are skipped, reverse-strand records
@@ -77,6 +81,14 @@ lnr_status lnr_writer_sort_next(lnr_writer *, const char **, uint64_t *) __attri
 lnr_status lnr_writer_sort_bai(lnr_writer *, uint64_t, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_writer_sort_end(lnr_writer *) __attribute__((weak));
 lnr_status lnr_writer_sort_spill(lnr_writer *, uint64_t) __attribute__((weak));        // (--sort-host-mem alone)
+// entry points only --gpu-genome uses
+lnr_status lnr_genome_load_gpu(const char *const *, uint32_t, int32_t, uint32_t, uint64_t, lnr_genome **) __attribute__((weak));
+lnr_status lnr_genome_info(const lnr_genome *, uint32_t *, const uint64_t **, const char **, const uint64_t **, const uint8_t *const **) __attribute__((weak));
+lnr_status lnr_genome_to_host(lnr_genome *, const uint8_t *const **) __attribute__((weak));
+lnr_status lnr_genome_drop_dev(lnr_genome *) __attribute__((weak));
+const char *lnr_genome_error(const lnr_genome *) __attribute__((weak));
+void lnr_genome_free(lnr_genome *) __attribute__((weak));
+lnr_status lnr_writer_set_genome_dev(lnr_writer *, const uint8_t *const *) __attribute__((weak));
 }
 
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -87,7 +99,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0, gpu_gunzip = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0, gpu_gunzip = 0, gpu_genome = 0;
     uint64_t sort_device_mem = 0, sort_host_mem = 0;      // --sort-device-mem / --sort-host-mem in bytes
     bool has_sort_device_mem = false, has_sort_host_mem = false;
     std::vector<int> devices;
@@ -132,7 +144,10 @@ static void usage() {
             "    --gpu-reader               parse the read files on the first GPU in use and keep the reads there: reader -> filter -> writer on device buffers {off}\n"
             "                               (one GPU; with --sam-seq it needs --gpu-writer: the read bases are not on the host)\n"
             "    --gpu-gunzip               --gpu-reader: inflate plain gzip read files (.fastq.gz / .fa.gz, not BGZF) on the GPU, in parallel from DEFLATE\n"
-            "                               block starts, instead of through zlib on the host; needs --gpu-reader {off}\n"
+            "                               block starts, instead of through zlib on the host; needs --gpu-reader or --gpu-genome (then the genome\n"
+            "                               files are inflated that way, too) {off}\n"
+            "    --gpu-genome               load the genome files on the first GPU in use (text parsed, BGZF inflated there) and build the index from\n"
+            "                               the device copy instead of parsing on one host thread and uploading {off}\n"
             "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n"
             "    --bgzf                     compress the text on the GPU and write PREFIX.sam.gz / PREFIX.apf.gz (BGZF); needs --gpu-writer {off}\n"
             "    --sort                     sort the .bam / _pbsv.bam by coordinate on the GPU and write PREFIX.bam.bai next to it; needs -ot with 4 or 8 and\n"
@@ -168,6 +183,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         if (name == "sam-seq") { o.sam_seq = 1; continue; }
         if (name == "gpu-reader") { o.gpu_reader = 1; continue; }
         if (name == "gpu-gunzip") { o.gpu_gunzip = 1; continue; }
+        if (name == "gpu-genome") { o.gpu_genome = 1; continue; }
         if (name == "bgzf") { o.bgzf = 1; continue; }
         if (name == "sort") { o.sort = 1; continue; }
         size_t eq = name.find('=');
@@ -350,7 +366,11 @@ int main(int argc, char **argv) {
         fprintf(stderr, "\033[1;31mE:\033[0m -ot 4 / 8 (BAM output) is encoded and compressed on the GPU: it needs --gpu-writer (BAM on the writer's host threads is not built)\n");
         return 1;
     }
-    if (o.gpu_gunzip && !o.gpu_reader) { fprintf(stderr, "\033[1;31mE:\033[0m --gpu-gunzip inflates the read files on the GPU that parses them: it needs --gpu-reader\n"); return 1; }
+    if (o.gpu_gunzip && !o.gpu_reader && !o.gpu_genome) { fprintf(stderr, "\033[1;31mE:\033[0m --gpu-gunzip inflates files on the GPU that parses them: it needs --gpu-reader or --gpu-genome\n"); return 1; }
+    if (o.gpu_genome && (!lnr_genome_load_gpu || !lnr_genome_info || !lnr_genome_to_host || !lnr_genome_drop_dev || !lnr_genome_error || !lnr_genome_free || !lnr_writer_set_genome_dev)) {
+        fprintf(stderr, "\033[1;31mE:\033[0m --gpu-genome: this library has no genome loader on the GPU\n");
+        return 1;
+    }
     if (o.bgzf && !o.gpu_writer) { fprintf(stderr, "\033[1;31mE:\033[0m --bgzf compresses the text on the GPU that formats it: it needs --gpu-writer\n"); return 1; }
     if (o.thread < 1) o.thread = 1;
     if (o.gpus < 1) o.gpus = 1;
@@ -359,9 +379,29 @@ int main(int argc, char **argv) {
     o.gpus = (unsigned)o.devices.size();
 
     // ---- genomes (loadRecords over every genome file, ids cut at the first blank: base.cpp:188-195)
+    // --gpu-genome: the files go to the first GPU and are parsed there (lnr_genome_load_gpu); the index is built from the device copy
     std::vector<std::vector<uint8_t> > genome;
     std::vector<std::string> gid;
-    {
+    std::vector<const uint8_t *> gp; std::vector<uint64_t> gl;      // what lnr_index_build takes: host pointers, or the device pointers of gg
+    lnr_genome *gg = nullptr;
+    const double t_genome0 = now();
+    if (o.gpu_genome) {
+        std::vector<const char *> paths;
+        for (const std::string &gpath : o.g_paths) paths.push_back(gpath.c_str());
+        const lnr_status s = lnr_genome_load_gpu(paths.data(), (uint32_t)paths.size(), o.devices[0], o.gpu_gunzip ? LNR_GENOME_GPU_GZIP : 0u, 0, &gg);
+        if (s != LNR_OK) {
+            fprintf(stderr, "\033[1;31mE:\033[0m --gpu-genome: %s%s\n", lnr_genome_error(nullptr),
+                    s == LNR_ERR_LIMIT ? " -- the genome can be loaded without --gpu-genome" : "");
+            return 1;
+        }
+        uint32_t nseq = 0; const uint64_t *len = nullptr, *io = nullptr; const char *ids = nullptr; const uint8_t *const *d_seq = nullptr;
+        lnr_genome_info(gg, &nseq, &len, &ids, &io, &d_seq);
+        for (uint32_t i = 0; i < nseq; i++) {
+            std::string id(ids + io[i]);
+            gid.push_back(id.substr(0, id.find(' ')));
+            gp.push_back(d_seq[i]); gl.push_back(len[i]);
+        }
+    } else {
         std::vector<uint8_t> buf((size_t)1 << 30);
         std::vector<uint64_t> off(2);
         for (const std::string &gpath : o.g_paths) {
@@ -380,9 +420,11 @@ int main(int argc, char **argv) {
             }
             lnr_reader_close(gr);
         }
+        for (const std::vector<uint8_t> &g : genome) { gp.push_back(g.data()); gl.push_back(g.size()); }
     }
-    if (genome.size() >= 1024) { fprintf(stderr, "\033[1;31mE[m01G]:\033[0m Too many reference genoemes <=1024\n"); return 1; }   // linear.cpp:107-113
-    if (genome.empty()) { fprintf(stderr, "E: no reference sequence in the genome files\n"); return 1; }
+    const double t_genome = now() - t_genome0;
+    if (gp.size() >= 1024) { fprintf(stderr, "\033[1;31mE[m01G]:\033[0m Too many reference genoemes <=1024\n"); return 1; }   // linear.cpp:107-113
+    if (gp.empty()) { fprintf(stderr, "E: no reference sequence in the genome files\n"); return 1; }
 
     // ---- contexts (one per GPU) + index
     const unsigned G = o.gpus;
@@ -394,8 +436,15 @@ int main(int argc, char **argv) {
         lnr_status s = lnr_create(&lo, &ctx[g]);
         if (s != LNR_OK) { fprintf(stderr, "E: GPU %d: %s\n", o.devices[g], lnr_strerror(s)); return 1; }
     }
-    std::vector<const uint8_t *> gp; std::vector<uint64_t> gl; std::vector<const char *> gn;
-    for (size_t i = 0; i < genome.size(); i++) { gp.push_back(genome[i].data()); gl.push_back(genome[i].size()); gn.push_back(gid[i].c_str()); }
+    std::vector<const char *> gn;
+    for (const std::string &id : gid) gn.push_back(id.c_str());
+    // --gpu-genome: the host copy of the genome (one download, owned by gg), for what cannot take the device pointers
+    const uint8_t *const *g_host = nullptr;
+    auto genome_on_host = [&]() -> const uint8_t *const * {
+        if (!gg) return gp.data();
+        if (!g_host && lnr_genome_to_host(gg, &g_host) != LNR_OK) { fprintf(stderr, "\033[1;31mE:\033[0m --gpu-genome: %s\n", lnr_genome_error(gg)); exit(1); }
+        return g_host;
+    };
     {
         double t0 = now();
         lnr_status s = lnr_index_build(ctx[0], gp.data(), gl.data(), (uint32_t)gp.size(), o.thread);
@@ -404,8 +453,9 @@ int main(int argc, char **argv) {
         if (G > 1) {
             t0 = now();
             if (o.index_build_each) {
+                const uint8_t *const *hp = genome_on_host();          // (another GPU cannot read the first one's copy without peer access)
                 std::vector<std::thread> th; std::vector<lnr_status> st(G, LNR_OK);
-                for (unsigned g = 1; g < G; g++) th.emplace_back([&, g] { st[g] = lnr_index_build(ctx[g], gp.data(), gl.data(), (uint32_t)gp.size(), o.thread); });
+                for (unsigned g = 1; g < G; g++) th.emplace_back([&, g] { st[g] = lnr_index_build(ctx[g], hp, gl.data(), (uint32_t)gp.size(), o.thread); });
                 for (auto &t : th) t.join();
                 for (unsigned g = 1; g < G; g++) if (st[g] != LNR_OK) { fprintf(stderr, "E: index on GPU %d: %s (%s)\n", o.devices[g], lnr_strerror(st[g]), lnr_last_error(ctx[g])); return 1; }
                 fprintf(stderr, "  Index on %u more GPUs: every GPU built its own in %.3f s (the first took %.3f s)\n", G - 1, now() - t0, t_build);
@@ -416,18 +466,30 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "  Index on %u more GPUs: RCCL broadcast + derived tables in %.3f s (building it took %.3f s; --index-mode build lets every GPU build its own)\n", G - 1, sec, t_build);
             }
         }
+        fprintf(stderr, "  Genome loaded in %.3f s (%s), index built in %.3f s\n", t_genome, o.gpu_genome ? "--gpu-genome: parsed on the GPU" : "host reader, one record at a time", t_build);
         fprintf(stderr, "  End creating index Elapsed time[s] %.2f\n", now() - t_start);
     }
     lnr_writer *wr = nullptr;
     if (lnr_writer_create(gn.data(), gl.data(), (uint32_t)gn.size(), &wr) != LNR_OK) { fprintf(stderr, "E: writer\n"); return 1; }
     lnr_writer_set_preset(wr, o.sensitivity);
     lnr_writer_set_read_group(wr, o.read_group.c_str(), o.sample_name.c_str());
-    if (o.sam_seq) lnr_writer_set_genome(wr, gp.data());                                         // (the genome vectors outlive the writer)
+    if (o.sam_seq && !(gg && o.gpu_writer)) lnr_writer_set_genome(wr, genome_on_host());         // (the genome vectors / gg's host copy outlive the writer)
     if (o.gpu_writer && lnr_writer_gpu_open(wr, o.devices[0]) != LNR_OK) {                       // before any output file is opened
         fprintf(stderr, "\033[1;31mE:\033[0m --gpu-writer: %s\n", lnr_writer_error(wr));
         lnr_writer_destroy(wr);
         for (auto *c : ctx) lnr_destroy(c);
         return 1;
+    }
+    if (gg) {
+        // the GPU writer takes its copy device to device; then the index and the writer hold their own: the loader's copy goes
+        if (o.sam_seq && o.gpu_writer && lnr_writer_set_genome_dev(wr, gp.data()) != LNR_OK) {
+            fprintf(stderr, "\033[1;31mE:\033[0m --gpu-genome: %s\n", lnr_writer_error(wr));
+            lnr_writer_destroy(wr);
+            for (auto *c : ctx) lnr_destroy(c);
+            return 1;
+        }
+        lnr_genome_drop_dev(gg);
+        gp.clear();                                            // (device addresses that are gone)
     }
     // --bgzf: the SAM header goes through the writer's device as well, the BAM headers always; false with a message when that fails
     const bool want_bam = (o.f_output_type & 12) != 0;
@@ -640,6 +702,7 @@ int main(int argc, char **argv) {
         if (cur) lnr_reader_close(cur);
         lnr_writer_destroy(wr);
         for (auto *c : ctx) lnr_destroy(c);
+        if (gg) lnr_genome_free(gg);
         if (failed) { fprintf(stderr, "\033[1;31mE:\033[0m %s\n", err.c_str()); return 1; }
         const double t_reads = now() - t_reads0;
         fprintf(stderr, "  Processed: %llu reads on 1 GPU (device chain); read files in -> output files out: %.3f s = %.0f reads/s\n", (unsigned long long)total_reads.load(), t_reads,
@@ -797,6 +860,7 @@ int main(int argc, char **argv) {
     for (auto &b : blocks) lnr_host_free(b.bases);
     lnr_writer_destroy(wr);
     for (auto *c : ctx) lnr_destroy(c);
+    if (gg) lnr_genome_free(gg);
     if (sh.failed) { fprintf(stderr, "\033[1;31mE:\033[0m %s\n", sh.err.c_str()); return 1; }
     double dt = now() - t_start;
     const double t_reads = now() - t_reads0;

@@ -251,6 +251,7 @@ void apf_read(const Writer &w, const u64 *c, u64 n, u64 L, const char *rid, bool
 
 struct lnr_writer {
     Writer w; lnr_outgpu *gpu = nullptr; bool genome_on_gpu = false; char err[256] = "";
+    bool genome_dev = false;                   // lnr_writer_set_genome_dev: the GPU side's copy came from device memory (the host forms have no bases)
     int sort_state = 0;                        // lnr_writer_sort_*: 0 off, 1 collecting, 2 sorted: pieces go out, 3 every piece handed out
     std::vector<u64> sort_moff;                // offsets of the members handed out so far in the run of record members (+ the end of the last)
     std::string sorted, bai;                   // what lnr_writer_sort_host / _sort_bai / _bai_host return
@@ -358,11 +359,25 @@ lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint6
 lnr_status lnr_writer_set_genome(lnr_writer *wr, const uint8_t *const *seq) {
     if (!wr) return LNR_ERR_ARG;
     wr->w.genome = seq;
-    wr->genome_on_gpu = false;                         // the GPU side takes its copy in the next SEQ call
+    wr->genome_on_gpu = wr->genome_dev = false;        // the GPU side takes its copy in the next SEQ call
     return LNR_OK;
 }
-static bool seq_ready(lnr_writer *wr) {
-    if (wr->w.genome) return true;
+// the GPU side's copy straight from device memory (a genome lnr_genome_load_gpu holds): device to device, at once; d_seq is not kept
+lnr_status lnr_writer_set_genome_dev(lnr_writer *wr, const uint8_t *const *d_seq) {
+    if (!wr) return LNR_ERR_ARG;
+    if (!wr->gpu) { snprintf(wr->err, sizeof wr->err, "lnr_writer_set_genome_dev: lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
+    if (!d_seq) { wr->genome_dev = false; wr->genome_on_gpu = false; return LNR_OK; }      // off (host pointers, where set, are taken again)
+    if (!lnr_outgpu_set_genome_dev) { snprintf(wr->err, sizeof wr->err, "lnr_writer_set_genome_dev: this library was linked without its device half"); return LNR_ERR_NO_DEVICE; }
+    for (size_t i = 0; i < wr->w.glen.size(); i++)
+        if (!d_seq[i]) { snprintf(wr->err, sizeof wr->err, "lnr_writer_set_genome_dev: null sequence pointer"); return LNR_ERR_ARG; }
+    wr->err[0] = 0;
+    lnr_status s = (lnr_status)lnr_outgpu_set_genome_dev(wr->gpu, d_seq, wr->w.glen.data(), (uint32_t)wr->w.glen.size(), wr->err, sizeof wr->err);
+    if (s != LNR_OK) return s;
+    wr->genome_dev = wr->genome_on_gpu = true;
+    return LNR_OK;
+}
+static bool seq_ready(lnr_writer *wr, bool gpu_form = false) {
+    if (wr->w.genome || (gpu_form && wr->genome_dev)) return true;
     snprintf(wr->err, sizeof wr->err, "lnr_writer_set_genome has not been called on this writer: no bases for SEQ");
     return false;
 }
@@ -372,7 +387,7 @@ lnr_status lnr_writer_format_seq(lnr_writer *wr, const lnr_cords *cords, const u
     return format_on_host(wr, cords, reads_concat, read_off, read_ids, id_off, 1, threads, text, size);
 }
 static lnr_status format_seq_on_gpu(lnr_writer *wr, lnr_outgpu_batch &b, const char **text, uint64_t *size) {
-    if (!seq_ready(wr)) return LNR_ERR_ARG;
+    if (!seq_ready(wr, true)) return LNR_ERR_ARG;
     if (!wr->gpu) { snprintf(wr->err, sizeof wr->err, "lnr_writer_gpu_open has not been called on this writer"); return LNR_ERR_ARG; }
     if (!wr->genome_on_gpu) {
         wr->err[0] = 0;

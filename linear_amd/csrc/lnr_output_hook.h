@@ -23,6 +23,8 @@ int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, con
 int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **text, uint64_t *size, char *err, size_t err_cap) __attribute__((weak));
 // the GPU side's own copy of the genome for SEQ: nseq host sequences, one Dna5 ordinal per byte; replaces an earlier copy
 int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) __attribute__((weak));
+// the same copy from nseq sequences in the memory of the writer's device (device-to-device copies on the writer's stream, no host hop)
+int lnr_outgpu_set_genome_dev(lnr_outgpu *g, const uint8_t *const *d_seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) __attribute__((weak));
 void lnr_outgpu_times(const lnr_outgpu *g, double *ms5) __attribute__((weak));   // last call: upload, measure, scan, emit, download
 void lnr_outgpu_close(lnr_outgpu *g) __attribute__((weak));
 // BGZF output (lnr_writer_set_bgzf): on != 0, lnr_outgpu_format compresses its text on the device (k_bgzf_deflate, one BGZF member per

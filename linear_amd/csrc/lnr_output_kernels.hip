@@ -806,7 +806,7 @@ int lnr_outgpu_open(int32_t device, const char *gblob, uint64_t gblob_bytes, con
     return 0;
 }
 
-int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) {
+static int set_genome_from(lnr_outgpu *g, const uint8_t *const *seq, const uint64_t *glen, uint32_t nseq, hipMemcpyKind kind, char *err, size_t err_cap) {
     if (nseq != g->nseq) { snprintf(err, err_cap, "the genome has %u sequences, the writer was opened with %u", nseq, g->nseq); return -1; }
     DeviceGuard dg;
     if (hipGetDevice(&dg.prev) != hipSuccess) dg.prev = -1;
@@ -819,7 +819,7 @@ int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64
     auto step = [&]() -> int {
         if ((s = dev_need(g->genome, start[nseq] + 1, err, err_cap)) || (s = dev_need(g->gstart, 8ULL * nseq + 8, err, err_cap))) return s;
         for (u32 i = 0; i < nseq; i++)
-            if (glen[i]) OUT_CK(hipMemcpyAsync((char *)g->genome.p + start[i], seq[i], glen[i], hipMemcpyHostToDevice, g->st), -3);
+            if (glen[i]) OUT_CK(hipMemcpyAsync((char *)g->genome.p + start[i], seq[i], glen[i], kind, g->st), -3);
         OUT_CK(hipMemcpyAsync(g->gstart.p, start, 8ULL * nseq + 8, hipMemcpyHostToDevice, g->st), -3);
         OUT_CK(hipStreamSynchronize(g->st), -3);
         return 0;
@@ -827,6 +827,12 @@ int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64
     s = step();
     delete[] start;
     return s;
+}
+int lnr_outgpu_set_genome(lnr_outgpu *g, const uint8_t *const *seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) {
+    return set_genome_from(g, seq, glen, nseq, hipMemcpyHostToDevice, err, err_cap);
+}
+int lnr_outgpu_set_genome_dev(lnr_outgpu *g, const uint8_t *const *d_seq, const uint64_t *glen, uint32_t nseq, char *err, size_t err_cap) {
+    return set_genome_from(g, d_seq, glen, nseq, hipMemcpyDeviceToDevice, err, err_cap);
 }
 
 int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **text, uint64_t *size, char *err, size_t err_cap) {

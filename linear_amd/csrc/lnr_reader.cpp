@@ -78,6 +78,7 @@ struct lnr_reader {
     // taken over", the text on the device, the host block the serial parser's records pass through on their way up
     lnr_rdgpu *gpu = nullptr; uint32_t gslots = 0, gslot = 0; bool gpu_serial = false;
     DevText dtext; std::unique_ptr<uint8_t[]> hblock; uint64_t hblock_cap = 0;
+    const uint8_t *last_block = nullptr; uint64_t last_bases = 0;     // the block lnr_reader_next_dev delivered last (lnr_reader_keep_block)
     uint64_t g_text = 0, g_recs = 0;     // text bytes and records the windows have used up so far: sizes the next window
     std::vector<uint64_t> span_off; std::vector<uint32_t> span_len;   // the names of a window of host text (names_of_spans)
     char gerr[256] = "";
@@ -370,7 +371,8 @@ static Got bgzf_window(Call &c, uint64_t want, Window &W, lnr_status *st) {
         if (r->bend) return GOT_END;
         if (r->bstop) return bgzf_give_way(r) ? GOT_AGAIN : (*st = LNR_ERR_ARG, GOT_ERROR);
     }
-    if (tl + 65536 > lnr_win::WINDOW_MAX && tl < want) return fail(r, st, LNR_ERR_LIMIT, TOO_LONG);
+    // (a chain that stops short of `want` because the window is at its largest is parsed like any other: it may well hold whole records --
+    // a genome's windows do, once one chromosome has doubled them -- and lnr_win::decide reports TOO_LONG where it holds none)
     W.job.comp = r->map + c0; W.job.comp_len = r->bpos - c0; W.job.blk = W.tab.data(); W.job.nblk = (uint32_t)W.tab.size();
     W.job.keep_from = r->dtext.keep_from; W.job.carry = r->dtext.carry; W.job.new_text = fresh;
     W.len = tl; W.ended = r->bend;
@@ -820,6 +822,17 @@ lnr_status lnr_reader_gpu_open(lnr_reader *r, int32_t device, uint32_t slots) {
     return LNR_OK;
 }
 
+// for lnr_genome.cpp (declared in lnr_reader_hook.h): a copy of the block delivered last, in device memory of its own; the records passed so far
+int lnr_reader_keep_block(lnr_reader *r, uint64_t bytes, uint8_t **d_out, int32_t *device) {
+    if (!r || !d_out || !device) return LNR_ERR_ARG;
+    if (!r->gpu || !r->last_block || bytes > r->last_bases) { r->err = "lnr_reader_keep_block: no delivered block of that size"; return LNR_ERR_ARG; }
+    if (!lnr_rdgpu_keep || !lnr_rdgpu_device) { r->err = "this library was linked without its device half"; return LNR_ERR_NO_DEVICE; }
+    if (int s = lnr_rdgpu_keep(r->gpu, r->last_block, bytes, d_out, r->gerr, sizeof r->gerr)) { r->err = r->gerr; return s; }
+    *device = lnr_rdgpu_device(r->gpu);
+    return LNR_OK;
+}
+uint64_t lnr_reader_records(const lnr_reader *r) { return r ? r->records : 0; }
+
 uint32_t lnr_reader_gpu_tile(void) { return lnr_rdgpu_tile ? lnr_rdgpu_tile() : 0; }
 uint32_t lnr_reader_gpu_bam_tile(void) { return lnr_rdgpu_bam_tile ? lnr_rdgpu_bam_tile() : 0; }
 
@@ -908,6 +921,7 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
     *n_out = 0;
     if (!r->gpu) { r->err = "lnr_reader_gpu_open has not been called on this reader"; return LNR_ERR_ARG; }
     Call c{r, r->gslot};
+    r->last_block = nullptr; r->last_bases = 0;
     uint8_t *dr; uint64_t *dof, *ho;
     if (int s = lnr_rdgpu_block(r->gpu, c.slot, dst_cap, max_reads, &dr, &dof, &ho, r->gerr, sizeof r->gerr)) { r->err = r->gerr; return (lnr_status)s; }
     r->gslot = (c.slot + 1) % r->gslots;
@@ -982,6 +996,7 @@ lnr_status lnr_reader_next_dev(lnr_reader *r, uint64_t dst_cap, uint32_t max_rea
         n = n2;
     }
     *d_reads_concat = dr; *d_off = dof; *off = ho; *n_out = n;
+    r->last_block = dr; r->last_bases = ho[n];
     return LNR_OK;
 }
 

@@ -98,4 +98,21 @@ void lnr_rdgpu_times(const lnr_rdgpu *g, double *ms5) __attribute__((weak));   /
 void lnr_rdgpu_times_reset(lnr_rdgpu *g) __attribute__((weak));
 uint32_t lnr_rdgpu_tile(void) __attribute__((weak));
 void lnr_rdgpu_close(lnr_rdgpu *g) __attribute__((weak));
+// ---- a genome held on the device (lnr_genome.cpp): the first `bytes` bases of a delivered block copied, device to device on the reader's
+// stream, into an allocation of their own (*d_out, never null, 16 spare bytes behind the bases); complete on return.  The allocation
+// belongs to no reader: _free and _download name the device (lnr_rdgpu_device: the ordinal the reader's GPU side resolved to).
+int lnr_rdgpu_keep(lnr_rdgpu *g, const uint8_t *d_src, uint64_t bytes, uint8_t **d_out, char *err, size_t err_cap) __attribute__((weak));
+int lnr_rdgpu_keep_download(int32_t device, const uint8_t *d_src, uint8_t *dst, uint64_t bytes, char *err, size_t err_cap) __attribute__((weak));
+void lnr_rdgpu_keep_free(int32_t device, uint8_t *d) __attribute__((weak));
+int32_t lnr_rdgpu_device(const lnr_rdgpu *g) __attribute__((weak));
+}
+
+// ---- the other direction: what lnr_reader.cpp itself offers to lnr_genome.cpp (host code, not part of the public header; the reader's GPU
+// side stays the reader's).  lnr_reader_keep_block: the first `bytes` bases of the block the last lnr_reader_next_dev delivered, through
+// lnr_rdgpu_keep; *device = the ordinal the allocation lies on.  A lnr_status; the reason in lnr_reader_error.  lnr_reader_records: records
+// the reader has passed so far, those of a call that ended in an error included -- the ordinal in the file of the record such a call stopped at.
+struct lnr_reader;
+extern "C" {
+int lnr_reader_keep_block(lnr_reader *r, uint64_t bytes, uint8_t **d_out, int32_t *device);
+uint64_t lnr_reader_records(const lnr_reader *r);
 }

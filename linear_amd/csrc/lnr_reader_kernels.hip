@@ -909,6 +909,34 @@ int lnr_rdgpu_append(lnr_rdgpu *g, uint32_t slot, uint64_t base_base, const uint
 void lnr_rdgpu_times(const lnr_rdgpu *g, double *ms5) { for (int i = 0; i < 5; i++) ms5[i] = g->ms[i]; }
 void lnr_rdgpu_times_reset(lnr_rdgpu *g) { for (double &m : g->ms) m = 0; g->ms_inf[0] = g->ms_inf[1] = 0; }
 
+// ---- a genome held on the device: a delivered block moves into an allocation of its own, on the reader's stream, no host hop
+int32_t lnr_rdgpu_device(const lnr_rdgpu *g) { return g->device; }
+
+int lnr_rdgpu_keep(lnr_rdgpu *g, const uint8_t *d_src, uint64_t bytes, uint8_t **d_out, char *err, size_t err_cap) {
+    RD_ON_DEVICE(g);
+    void *p = nullptr;
+    RD_CK(hipMalloc(&p, bytes + 16), -4);
+    hipError_t e = bytes ? hipMemcpyAsync(p, d_src, bytes, hipMemcpyDeviceToDevice, g->st) : hipSuccess;
+    if (e == hipSuccess) e = hipMemsetAsync((u8 *)p + bytes, 0, 16, g->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->st);
+    if (e != hipSuccess) { (void)hipFree(p); snprintf(err, err_cap, "copy of a genome block on the device: %s", hipGetErrorString(e)); return -3; }
+    *d_out = (uint8_t *)p;
+    return 0;
+}
+
+int lnr_rdgpu_keep_download(int32_t device, const uint8_t *d_src, uint8_t *dst, uint64_t bytes, char *err, size_t err_cap) {
+    DeviceGuard dg(device);
+    if (dg.set != hipSuccess) { snprintf(err, err_cap, "hipSetDevice(%d): %s", (int)device, hipGetErrorString(dg.set)); return -3; }
+    if (bytes) RD_CK(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost), -3);
+    return 0;
+}
+
+void lnr_rdgpu_keep_free(int32_t device, uint8_t *d) {
+    if (!d) return;
+    DeviceGuard dg(device);
+    if (dg.set == hipSuccess) (void)hipFree(d);
+}
+
 void lnr_rdgpu_close(lnr_rdgpu *g) {
     if (!g) return;
     DeviceGuard dg(g->device);
