@@ -112,6 +112,8 @@ typedef struct lnr_stats {
     uint32_t gap_second_pass;  /* reads of the gap re-mapper that a 16-wave team of the first stage did: ranked heavy, or handed over by a single wave (arena, cord slot, a sort or chain DP too long for one wave) */
     double gap_ms;             /* device time of the gap re-mapper (-g > 0) */
     uint32_t gap_last_launch;  /* reads the first stage left flagged and the last launch did (a team per read with the largest arena) */
+    uint32_t groups_heavy, groups_mid, groups_wave1;   /* job groups (the jobs of one read in one round) that ran on 16 waves, on 4 or 2 waves and on a
+                                                          single wave, both rounds together: which job kernel the batch's reads took */
 } lnr_stats;
 
 void lnr_opts_default(lnr_opts *o);

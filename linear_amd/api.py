@@ -45,7 +45,8 @@ class LnrAnchors(C.Structure):
 class LnrStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("reads", "bases", "jobs", "samples", "lookups", "bucket_entries", "anchors", "remap_reads", "cords", "seed_bytes")] + \
                [(k, C.c_double) for k in ("prep_ms", "seed_count_ms", "seed_gather_ms", "job_ms", "tail_ms", "total_ms")] + \
-               [(k, C.c_uint32) for k in ("seed_count_launches", "seed_gather_launches", "job_launches", "gap_second_pass")] + [("gap_ms", C.c_double), ("gap_last_launch", C.c_uint32)]
+               [(k, C.c_uint32) for k in ("seed_count_launches", "seed_gather_launches", "job_launches", "gap_second_pass")] + [("gap_ms", C.c_double), ("gap_last_launch", C.c_uint32)] + \
+               [(k, C.c_uint32) for k in ("groups_heavy", "groups_mid", "groups_wave1")]
 
 
 class LnrInflateCounts(C.Structure):

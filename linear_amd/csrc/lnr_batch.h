@@ -316,6 +316,7 @@ lnr_status launch_jobs(Lane *L, JobSet &S, const HostJobs &hj, HandoverScope *ga
         if (fork_m) LCK(hipStreamWaitEvent(sm, L->ev_join_spare, 0));
         laps.lap("launches");
         L->stats.job_launches++;
+        L->stats.groups_heavy += gh - g0; L->stats.groups_mid += gm - gh; L->stats.groups_wave1 += g1 - gm;
         g0 = g1;
         if (g0 < ngrp) LCK(hipStreamSynchronize(sm));   // next slice reuses the scratch
     }

@@ -304,7 +304,10 @@ template <class S> LNR_HD inline void sam_item_seq(S &out, const Params &P, cons
 // l_seq, next_refID -1, next_pos -1, tlen 0, QNAME '\0', one word count << 4 | op per CIGAR element (MIDNSHP=X = 0..8), SEQ at two bases
 // per byte (high nibble first, =ACMGRSVTWYHKDBN = 0..15), l_seq bytes 0xff, and where the line has one the tag SA:Z.  Without SEQ l_seq is 0.
 // Fields narrower than their value take its low bits, as SeqAn's casts do: a QNAME of 255 or more characters (l_read_name is one byte) and
-// more than 65535 CIGAR elements (n_cigar_op is two) give records no reader can walk; both are outside the tested ground.
+// more than 65535 CIGAR elements (n_cigar_op is two) give records no reader can walk; both are outside the tested ground.  How far real
+// input stays from the second bound: the longest record of the `long` case (tests/cases.py, reads of up to 2^20 - 1 bases with 10 % errors)
+// has 12 491 elements, from the error-free half of its 800 kb chimera (asserted in tests/test_gpu_long_reads.py); an error-free read of
+// 2^20 - 1 bases, the most a read can bring, has 35 836 (tests/test_cli_golden_cpu.py).
 // bam_head: block_size, core, QNAME, CIGAR words.  bam_tail: the tag.  Between them: packed SEQ and the 0xff run.
 struct BamCount {                                 // one walk before the first byte: CIGAR elements, reference bases, SEQ bases
     u32 k = 0; u64 reflen = 0, seq = 0;

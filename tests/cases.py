@@ -121,6 +121,63 @@ def case_hbig():
     return [ref], reads, off
 
 
+LONG_MAX = (1 << 20) - 1     # the longest read the cord format holds (y field of 20 bits; LNR_ERR_LIMIT starts at 2^20)
+
+
+def long_refs():
+    """The two references of the long-read inputs (5 Mb together): repeat-rich, and random with N runs."""
+    return [synth.repeat_ref(3_000_000, 7001), synth.add_n_runs(synth.random_ref(2_000_000, 7002), 7003, n_runs=3, max_run=800)]
+
+
+def long_set_a(refs):
+    """Reads of 40 kb to 2^20 - 1 bases (ONT ultra-long): 40 kb, 100 kb, 300 kb, 700 kb and 2^20 - 1 with 8 - 12 % errors, 2^20 - 1 error-free,
+    a chimera (400 kb of refs[0] with 8 % errors + the reverse complement of 400 kb of refs[1]) and 500 kb of random bases."""
+    out = []
+    for k, (L, err) in enumerate(((40_000, .1), (100_000, .1), (300_000, .12), (700_000, .08), (LONG_MAX, .1), (LONG_MAX, 0.0))):
+        r, _, _ = synth.sample_reads(refs, 1, L, err, 7100 + k, "random")
+        out.append(np.ascontiguousarray(r))
+    a, _, _ = synth.sample_reads([refs[0]], 1, 400_000, 0.08, 7110, "none")
+    x = int(np.random.default_rng(7111).integers(1000, refs[1].size - 401_000))
+    out.append(np.concatenate([a, synth.revcomp(refs[1][x:x + 400_000])]))
+    out.append(np.random.default_rng(7112).integers(0, 4, 500_000, dtype=np.uint8))
+    return out
+
+
+def long_set_b(refs):
+    """What the gap re-mapper and the N-skip meet on long reads: poly-A of 2^20 - 1, (AC)n of 600 kb, 200 kb + 100 kb of random bases + 200 kb
+    of refs[1], the same with 50 kb of the reference left out instead, 600 kb of refs[0] whose first 70 000 bases are N (and 500 more at
+    300 000), reads of 65 535 / 65 536 / 65 537 bases with 10 % errors, and 200 kb of refs[1] followed by poly-A up to 2^20 - 1: a read with
+    cords and an uncovered stretch whose 848 000 identical 9-mers take one of k_gap_weight's 16-bit counters past 65 535."""
+    rng = np.random.default_rng(7200)
+    r1, r0 = refs[1], refs[0]
+    out = [np.zeros(LONG_MAX, np.uint8), np.tile(np.array([0, 1], np.uint8), 300_000)]
+    x = 300_000
+    out.append(np.concatenate([r1[x:x + 200_000], rng.integers(0, 4, 100_000, dtype=np.uint8), r1[x + 200_000:x + 400_000]]))
+    out.append(np.concatenate([r1[x:x + 200_000], r1[x + 250_000:x + 450_000]]))
+    n = r0[1_200_000:1_800_000].copy()
+    n[:70_000] = 4
+    n[300_000:300_500] = 4
+    out.append(n)
+    for k, L in enumerate((65_535, 65_536, 65_537)):
+        r, _, _ = synth.sample_reads(refs, 1, L, 0.1, 7210 + k, "random")
+        out.append(np.ascontiguousarray(r))
+    out.append(np.concatenate([r1[900_000:1_100_000], np.zeros(LONG_MAX - 200_000, np.uint8)]))
+    return out
+
+
+LONG_A_IN_CASE = [0, 1, 2, 4, 6, 7]   # set A without the 700 kb and the error-free 2^20 - 1 read (most of the APF text; tests/test_gpu_long_reads.py has them)
+
+
+def case_long():
+    """Reads of 40 kb to 2^20 - 1 bases, the length limit of the cord format, on 5 Mb of reference: one of 2^20 - 1, one of 100 kb (between 2^16
+    and 2^17), one of 300 kb (beyond 2^18), a chimera of two 400 kb halves on different sequences and strands, and 500 kb of junk that goes
+    through the re-map round window by window."""
+    refs = long_refs()
+    a = long_set_a(refs)
+    reads, off = synth.pack_reads([a[i] for i in LONG_A_IN_CASE])
+    return refs, reads, off
+
+
 # HIndex (-i 2) goldens: name -> (builder, [T layouts]); files <name>_i2_T<T>.npz
 CASES_I2 = {
     "c1": (case_c1, [1]),
@@ -129,11 +186,12 @@ CASES_I2 = {
 }
 
 # gap-path goldens (-g 50 and -g 50 -dup 1, made by the reference): name -> (builder, T); files <name>_g50_T<T>.npz
-CASES_G50 = {"ont": (case_ont, 1), "edge": (case_edge, 1), "ccs_sv": (case_ccs_sv, 1), "rep": (case_rep, 1), "chim": (case_chim, 1)}
+CASES_G50 = {"ont": (case_ont, 1), "edge": (case_edge, 1), "ccs_sv": (case_ccs_sv, 1), "rep": (case_rep, 1), "chim": (case_chim, 1),
+             "long": (case_long, 1)}
 
 # goldens made by the REAL `linear filter` program (oracle/_ref/linear, tools/make_cli_golden.py): name -> builder; files cli_<name>.npz hold
 # the program's .sam and .apf bytes at -t 1 for -g 0, -g 50 and -g 50 -dup 1
-CASES_CLI = {"edge": case_edge, "ccs_sv": case_ccs_sv, "rep": case_rep, "chim": case_chim}
+CASES_CLI = {"edge": case_edge, "ccs_sv": case_ccs_sv, "rep": case_rep, "chim": case_chim, "long": case_long}
 CLI_MODES = {"g0": ["-g", "0"], "g50": ["-g", "50"], "g50dup1": ["-g", "50", "-dup", "1"], "gdef": []}
 
 CASES = {
@@ -143,10 +201,12 @@ CASES = {
     "rep": (case_rep, [1, 8]),
     "edge": (case_edge, [1, 3]),
     "scale": (case_scale, [4]),
+    "long": (case_long, [1, 4]),
 }
 
 # reads whose per-stage outputs are stored (default: the first N_STAGE_READS mappable reads)
-STAGE_IDX = {"scale": [0, 45, 85, 100, 119, 125, 131, 160, 163, 166, 167]}
+STAGE_IDX = {"scale": [0, 45, 85, 100, 119, 125, 131, 160, 163, 166, 167],
+             "long": [0, 1]}      # the two shortest mappable reads (40 kb, 100 kb): a stage dump of a 1 Mb read is megabytes of near-random words
 
 N_STAGE_READS = 6   # reads per case whose per-stage outputs are stored
 

@@ -77,6 +77,33 @@ def test_oracle_plus_writer_reproduce_the_real_program(oracle_lib, case_inputs, 
     o.close(); w.close()
 
 
+def test_cigar_elements_of_the_longest_records(oracle_lib):
+    """A BAM record holds 65 535 CIGAR elements (n_cigar_op is 16 bits wide; linear_amd/csrc/lnr_output_hd.h).  The most a read can bring:
+    the error-free read of 2^20 - 1 bases of the long-read inputs has 35 836, the others (8 - 12 % errors, up to 2^20 - 1 bases) at most
+    12 491 -- the distance from the bound as recorded numbers."""
+    import re
+    from linear_amd import build as lb, synth
+    lb.build()
+    from linear_amd.api import Writer
+    refs = cases.long_refs()
+    A = cases.long_set_a(refs)
+    reads, off = synth.pack_reads(A)
+    o = oracle_lib.Checker("oracle", refs, 1)
+    coff, cs, ce, _ = o.map_batch(reads, off, threads=4)
+    o.close()
+    rid, gid = cases.text_ids(len(A), len(refs))
+    w = Writer(gid, [r.size for r in refs])
+    sam = w.format(coff, cs, ce, np.diff(off.astype(np.int64)).astype(np.uint64), rid, "sam")
+    w.close()
+    per = {}
+    for l in sam.split(b"\n"):
+        if l:
+            f = l.split(b"\t")
+            per.setdefault(f[0], []).append(len(re.findall(rb"\d+[MIDNSHP=X]", f[5])))
+    assert A[5].size == cases.LONG_MAX and per[rid[5].encode()] == [35836]
+    assert max(max(v) for k, v in per.items() if k != rid[5].encode()) == 12491
+
+
 @pytest.mark.skipif(not os.path.exists("/root/reference/src/gap_util.cpp"), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name,dup", [("chim", 0), ("edge", 1)])
 def test_every_gap_call_of_the_oracle_replays_through_the_reference(oracle_lib, case_inputs, name, dup):

@@ -538,7 +538,7 @@ def test_gpu_two_pageable_submits_back_to_back(flt, case_inputs):
 
 
 # ---- the gap re-mapper (-g > 0): mapGaps + reformCords on the GPU (k_gap)
-@pytest.mark.parametrize("name", ["ont", "edge", "ccs_sv", "rep", "chim"])
+@pytest.mark.parametrize("name", list(cases.CASES_G50))
 def test_gpu_gap_path_matches_golden(case_inputs, name):
     """lnr_opts.gap_len = 50 [dup = 1] through the C ABI against the cords the real reference produced with -g 50 [-dup 1] on the case as one
     read stream in file order (`-t 1`): the first read that goes through mapExtend / mapExtends changes what every later read sees

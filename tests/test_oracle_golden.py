@@ -70,6 +70,28 @@ def test_oracle_matches_live_reference(oracle_lib):
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
+@pytest.mark.skipif(not os.path.exists("/root/reference/src/pmpfinder.cpp"), reason="reference tree not present (GPU box)")
+@pytest.mark.parametrize("T", [1, 4])
+def test_oracle_long_read_stages_match_live_reference(oracle_lib, case_inputs, T):
+    """The `long` case stores stage dumps of its two shortest reads only (a dump of a 1 Mb read is megabytes); here every read of it, up
+    to 2^20 - 1 bases, is compared stage by stage (raw, filtered, x-sorted anchors, chained hits) and cord by cord with the reference
+    itself.  Nothing is stored."""
+    refs, reads, off = case_inputs("long")
+    o = oracle_lib.Checker("oracle", refs, T)
+    r = oracle_lib.Checker("ref", refs, T)
+    sizes = []
+    for i in range(off.size - 1):
+        rd = reads[int(off[i]):int(off[i + 1])]
+        for s, nm in enumerate(("raw", "filt", "xsort", "hits")):
+            a, b = o.stage(rd, s), r.stage(rd, s)
+            assert np.array_equal(a, b), f"stage {nm} of read {i} ({rd.size} bases)"
+            sizes.append(a.size)
+        a, b = o.map_read(rd), r.map_read(rd)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), f"cords of read {i} ({rd.size} bases)"
+    assert max(sizes) > 50_000, "the longest reads bring tens of thousands of raw anchors"
+    o.close(); r.close()
+
+
 # ---- HIndex (-i 2, SURVEY 8 a21 / f3): ysa is the byte-exact surface (the open-addressed table's layout is not observable)
 PARAMS_I2 = [(n, T) for n, (_, Ts) in cases.CASES_I2.items() for T in Ts]
 
@@ -113,7 +135,7 @@ def test_oracle_hindex_matches_live_reference(oracle_lib):
 
 
 # ---- gap path (-g 50 [-dup 1]): the oracle's restatement (oracle/lnr_gap.inc) against the reference's goldens
-@pytest.mark.parametrize("name", ["ont", "edge", "ccs_sv", "rep", "chim"])
+@pytest.mark.parametrize("name", list(cases.CASES_G50))
 def test_oracle_gap_path_matches_reference_golden(oracle_lib, case_inputs, name):
     """the case as ONE read stream in file order (`linear filter -t 1`): the reference keeps one GapParms per thread for the run and the first
     mapExtend / mapExtends leaves thd_cts_major_limit = 3 behind for every later read (read by read here; the batch entry point -- serial until
