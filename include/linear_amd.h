@@ -464,6 +464,35 @@ lnr_status lnr_writer_format_bam_gpu(lnr_writer *w, const lnr_cords *cords, cons
 lnr_status lnr_writer_format_bam_dev(lnr_writer *w, const lnr_cords_dev *cords, const uint8_t *d_reads_concat_or_null, const uint64_t *d_read_off,
                                      const char *read_ids, const uint64_t *id_off, const char **data, uint64_t *size);
 
+/* PAF output (an extension: the reference writes none).  What the filter computes is an approximate mapping, and PAF is the format general
+ * long-read tools read for one: twelve tab-separated columns and tags, one line per mapping, no header.  One line per SAM record of a read,
+ * in the order lnr_writer_format(what = 1) prints them -- the same segmentation under the writer's preset.  For the record whose first cord
+ * is lo and whose last cord is hi, with the elements of its CIGAR* (S I D = X):
+ *    1  query name      the QNAME of the SAM line
+ *    2  query length    L = read_len[k]
+ *    3, 4  query start, end   0-based, on the ORIGINAL read strand.  lead = y(cords_str[lo]); trail = max(0, (int)(L - y(cords_end[hi]))) -- the
+ *                       two numbers the S elements of the CIGAR* hold.  Forward: lead, L - trail.  Flag 16: trail, L - lead.
+ *    5  strand          '+' or '-' (the strand bit of cords_str[lo])
+ *    6  target name     the RNAME of the SAM line: '*' for a sequence id at or beyond nseq
+ *    7  target length   genome_len[id]; 0 for '*'
+ *    8, 9  target start, end  x(cords_str[lo]) (= POS - 1), and that plus the sum of the = X D counts (no max(1, .) as in the sort key)
+ *    10 matches         the sum of the '=' counts
+ *    11 block length    the sum of the = X I D counts
+ *    12 mapping quality 255
+ *    cg:Z:              the record's merged elements without the S elements, count then op; the tag and its tab are left out when none remains
+ * Numbers are decimal without padding, the line ends with '\n'.  A read without cords gives no line (no PAF for unmapped reads); nothing
+ * is sorted.  lnr_writer_format_paf: on `threads` host threads, the in-library yardstick.  lnr_writer_format_paf_gpu (host cords in) and
+ * lnr_writer_format_paf_dev (what lnr_filter_batch_dev hands out and the batch's d_off) format on the GPU (k_out_measure<Paf> / k_out_scan /
+ * k_out_emit<Paf>) and return the same bytes -- with lnr_writer_set_bgzf on, BGZF members of them (an empty text: zero bytes).  Before
+ * lnr_writer_gpu_open the two return LNR_ERR_ARG.  Text lifetime, errors, current device and lnr_writer_gpu_times as for lnr_writer_format_gpu
+ * / _dev. */
+lnr_status lnr_writer_format_paf(lnr_writer *w, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
+                                 uint32_t threads, const char **text, uint64_t *size);
+lnr_status lnr_writer_format_paf_gpu(lnr_writer *w, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids,
+                                     const uint64_t *id_off, const char **text, uint64_t *size);
+lnr_status lnr_writer_format_paf_dev(lnr_writer *w, const lnr_cords_dev *cords, const uint64_t *d_read_off /* n + 1, the batch's d_off */,
+                                     const char *read_ids, const uint64_t *id_off, const char **text, uint64_t *size);
+
 /* Coordinate-sorted BAM with a BAI index (an extension: the reference tells its users to run `samtools sort` / `samtools index`).
  * A sort mode of the GPU writer.  Between lnr_writer_sort_begin and lnr_writer_sort_finish, lnr_writer_format_bam_gpu / _dev keep the
  * batch's raw records (copied by k_sort_keep into segments the GPU side owns: at least 256 MiB each -- less where max_device_bytes leaves

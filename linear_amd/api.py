@@ -98,7 +98,8 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_reader_gpu_bam_stats", "lnr_reader_gpu_bam_tile", "lnr_reader_format",
            "lnr_writer_sort_begin", "lnr_writer_sort_finish", "lnr_writer_sort_next", "lnr_writer_sort_bai", "lnr_writer_sort_info_get", "lnr_writer_sort_end",
            "lnr_writer_sort_host", "lnr_writer_bai_host", "lnr_writer_sort_spill", "lnr_writer_sort_hold_info_get",
-           "lnr_genome_load_gpu", "lnr_genome_info", "lnr_genome_to_host", "lnr_genome_drop_dev", "lnr_genome_error", "lnr_genome_free", "lnr_writer_set_genome_dev"]
+           "lnr_genome_load_gpu", "lnr_genome_info", "lnr_genome_to_host", "lnr_genome_drop_dev", "lnr_genome_error", "lnr_genome_free", "lnr_writer_set_genome_dev",
+           "lnr_writer_format_paf", "lnr_writer_format_paf_gpu", "lnr_writer_format_paf_dev"]
 
 
 class LnrBgzfStats(C.Structure):
@@ -209,6 +210,9 @@ def load_library() -> C.CDLL:
     lib.lnr_genome_free.restype = None
     lib.lnr_genome_free.argtypes = [C.c_void_p]
     lib.lnr_writer_set_genome_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.lnr_writer_format_paf.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u64p, C.c_char_p, _u64p, C.c_uint32, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_paf_gpu.argtypes = [C.c_void_p, C.POINTER(LnrCords), _u64p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
+    lib.lnr_writer_format_paf_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev), C.c_void_p, C.c_char_p, _u64p, C.POINTER(C.c_void_p), _u64p]
     return lib
 
 
@@ -612,7 +616,8 @@ class Genome:
 
 
 class Writer:
-    """Cords of a batch -> SAM records / APF text: format() on host threads (no GPU needed), format_gpu() / format_dev() on the GPU."""
+    """Cords of a batch -> SAM records / APF text: format() on host threads (no GPU needed), format_gpu() / format_dev() on the GPU; PAF lines
+    likewise: format_paf() / format_paf_gpu() / format_paf_dev()."""
 
     def __init__(self, genome_ids: list[str], genome_len: list[int]):
         self.lib = load_library()
@@ -680,6 +685,30 @@ class Writer:
         blob, ido = self._ids(read_ids)
         text, size = C.c_void_p(), C.c_uint64()
         self._check(self.lib.lnr_writer_format_dev(self.h, C.byref(cords_dev), d_off_ptr, blob, _p(ido, _u64p), {"sam": 1, "apf": 2}[what], C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value) if copy else (text.value, size.value)
+
+    # ---- PAF: one line per SAM record (twelve columns and cg:Z:, include/linear_amd.h)
+    def format_paf(self, cord_off: np.ndarray, cords_str: np.ndarray, cords_end: np.ndarray, read_len: np.ndarray, read_ids: list[str], threads: int = 4) -> bytes:
+        """The PAF lines of the batch on host threads (no GPU needed)."""
+        c, _r, rl, _keep = self._seq_args(cord_off, cords_str, cords_end, np.zeros(1, np.uint8), read_len)
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_paf(self.h, C.byref(c), _p(rl, _u64p), blob, _p(ido, _u64p), threads, C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value)
+
+    def format_paf_gpu(self, cord_off: np.ndarray, cords_str: np.ndarray, cords_end: np.ndarray, read_len: np.ndarray, read_ids: list[str], copy: bool = True):
+        """The bytes of format_paf(), formatted on the GPU; with set_bgzf(True) BGZF members of them."""
+        c, _r, rl, _keep = self._seq_args(cord_off, cords_str, cords_end, np.zeros(1, np.uint8), read_len)
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_paf_gpu(self.h, C.byref(c), _p(rl, _u64p), blob, _p(ido, _u64p), C.byref(text), C.byref(size)))
+        return C.string_at(text, size.value) if copy else (text.value, size.value)
+
+    def format_paf_dev(self, cords_dev: "LnrCordsDev", d_off_ptr: int, read_ids: list[str], copy: bool = True):
+        """Device form: the result of Filter.filter_batch_dev and the batch's device read offsets (n + 1)."""
+        blob, ido = self._ids(read_ids)
+        text, size = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.lnr_writer_format_paf_dev(self.h, C.byref(cords_dev), d_off_ptr, blob, _p(ido, _u64p), C.byref(text), C.byref(size)))
         return C.string_at(text, size.value) if copy else (text.value, size.value)
 
     def set_genome(self, seqs) -> None:

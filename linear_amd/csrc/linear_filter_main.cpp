@@ -35,6 +35,10 @@
 //                  (lnr_writer_sort_spill right after every begin).
 //   SEQ column     --sam-seq (extension): the .sam carries the read sequences the reference prints with -ss 1 (lnr_writer_format_seq / _seq_gpu); the
 //                  option -ss itself stays refused.
+//   PAF output     --paf (extension): PREFIX.paf next to whatever -ot asks for, one line per record of the .sam (twelve columns and cg:Z:, the line's
+//                  definition: include/linear_amd.h), named, split over read files and ordered as the .sam is.  Host writer by default
+//                  (lnr_writer_format_paf), lnr_writer_format_paf_gpu with --gpu-writer, lnr_writer_format_paf_dev in the device chain; with --bgzf
+//                  PREFIX.paf.gz (BGZF members and the EOF marker).  --sort does not touch it.
 //   genome on GPU  --gpu-genome (extension): the genome files are loaded by lnr_genome_load_gpu on the first GPU (text parsed there, BGZF inflated
 //                  there, plain gzip too with --gpu-gunzip), the index is built from the device pointers, a GPU writer with --sam-seq takes its
 //                  copy device to device (lnr_writer_set_genome_dev), then the loader's copy is dropped.  What needs host bases (a host writer
@@ -81,6 +85,10 @@ lnr_status lnr_writer_sort_next(lnr_writer *, const char **, uint64_t *) __attri
 lnr_status lnr_writer_sort_bai(lnr_writer *, uint64_t, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_writer_sort_end(lnr_writer *) __attribute__((weak));
 lnr_status lnr_writer_sort_spill(lnr_writer *, uint64_t) __attribute__((weak));        // (--sort-host-mem alone)
+// entry points only --paf uses
+lnr_status lnr_writer_format_paf(lnr_writer *, const lnr_cords *, const uint64_t *, const char *, const uint64_t *, uint32_t, const char **, uint64_t *) __attribute__((weak));
+lnr_status lnr_writer_format_paf_gpu(lnr_writer *, const lnr_cords *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
+lnr_status lnr_writer_format_paf_dev(lnr_writer *, const lnr_cords_dev *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
 // entry points only --gpu-genome uses
 lnr_status lnr_genome_load_gpu(const char *const *, uint32_t, int32_t, uint32_t, uint64_t, lnr_genome **) __attribute__((weak));
 lnr_status lnr_genome_info(const lnr_genome *, uint32_t *, const uint64_t **, const char **, const uint64_t **, const uint8_t *const **) __attribute__((weak));
@@ -99,7 +107,7 @@ struct Options {
     unsigned gap_len = 1, apx_chain_flag = 1, reform_ccs = 0, bal_flag = 1, f_output_type = 2, f_dup = 0, sensitivity = 1, thread = 16;
     int index_t = 1, feature_t = 2, sequence_sam = 0;
     // extensions of this front-end
-    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0, gpu_gunzip = 0, gpu_genome = 0;
+    unsigned gpus = 1, block_reads = 65536, index_build_each = 0, gpu_writer = 0, sam_seq = 0, gpu_reader = 0, bgzf = 0, sort = 0, gpu_gunzip = 0, gpu_genome = 0, paf = 0;
     uint64_t sort_device_mem = 0, sort_host_mem = 0;      // --sort-device-mem / --sort-host-mem in bytes
     bool has_sort_device_mem = false, has_sort_host_mem = false;
     std::vector<int> devices;
@@ -149,6 +157,8 @@ static void usage() {
             "    --gpu-genome               load the genome files on the first GPU in use (text parsed, BGZF inflated there) and build the index from\n"
             "                               the device copy instead of parsing on one host thread and uploading {off}\n"
             "    --sam-seq                  print the SEQ column of the .sam as the reference does with -ss 1 {off}\n"
+            "    --paf                      write PREFIX.paf next to the -ot outputs: one PAF line (12 columns and cg:Z:) per record of the .sam, in its\n"
+            "                               order; with --bgzf PREFIX.paf.gz; not sorted by --sort {off}\n"
             "    --bgzf                     compress the text on the GPU and write PREFIX.sam.gz / PREFIX.apf.gz (BGZF); needs --gpu-writer {off}\n"
             "    --sort                     sort the .bam / _pbsv.bam by coordinate on the GPU and write PREFIX.bam.bai next to it; needs -ot with 4 or 8 and\n"
             "                               --gpu-writer; every record of a file stays in GPU memory until the file ends (about 0.8 KB per read, with\n"
@@ -186,6 +196,7 @@ static int parse_command_line(int argc, char **argv, Options &o) {
         if (name == "gpu-genome") { o.gpu_genome = 1; continue; }
         if (name == "bgzf") { o.bgzf = 1; continue; }
         if (name == "sort") { o.sort = 1; continue; }
+        if (name == "paf") { o.paf = 1; continue; }
         size_t eq = name.find('=');
         if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
         if (name == "sort-device-mem" || name == "sort-host-mem") {
@@ -262,7 +273,7 @@ struct Shared {
 struct Headers { std::string sam, bam, pbsv; };      // what opens a .sam, a .bam and a _pbsv.bam (compressed where the file is)
 // the output files of the printer (Mapper::p_printResults mapper.cpp:478-509): a new pair when the prefix changes, or once with -o
 struct Outputs {
-    FILE *fsam = nullptr, *fapf = nullptr, *fbam = nullptr, *fpbsv = nullptr;
+    FILE *fsam = nullptr, *fapf = nullptr, *fbam = nullptr, *fpbsv = nullptr, *fpaf = nullptr;
     std::string cur_prefix; bool any_open = false; int cur_file = -1;
     bool bgzf = false;                       // --bgzf: .gz names, the SAM header comes compressed, the EOF marker ends every file
     lnr_writer *sort_wr = nullptr;           // --sort: the writer that holds the records of the files in work; close() sorts and writes them
@@ -282,7 +293,8 @@ struct Outputs {
         fapf = (o.f_output_type & 1) ? fopen((prefix + (bgzf ? ".apf.gz" : ".apf")).c_str(), "wb") : nullptr;
         fbam = (o.f_output_type & 4) ? fopen((prefix + ".bam").c_str(), "wb") : nullptr;
         fpbsv = (o.f_output_type & 8) ? fopen((prefix + "_pbsv.bam").c_str(), "wb") : nullptr;
-        if (((o.f_output_type & 2) && !fsam) || ((o.f_output_type & 1) && !fapf) || ((o.f_output_type & 4) && !fbam) || ((o.f_output_type & 8) && !fpbsv)) {
+        fpaf = o.paf ? fopen((prefix + (bgzf ? ".paf.gz" : ".paf")).c_str(), "wb") : nullptr;
+        if ((o.paf && !fpaf) || ((o.f_output_type & 2) && !fsam) || ((o.f_output_type & 1) && !fapf) || ((o.f_output_type & 4) && !fbam) || ((o.f_output_type & 8) && !fpbsv)) {
             err = "can't write output files with prefix " + prefix;
             return false;
         }
@@ -326,13 +338,14 @@ struct Outputs {
     }
     void close_files() {
         const char *eof = nullptr; uint64_t n = 0;
-        if (bgzf && (fsam || fapf)) lnr_writer_bgzf_eof(&eof, &n);
+        if (bgzf && (fsam || fapf || fpaf)) lnr_writer_bgzf_eof(&eof, &n);
         if (fsam) { if (n) fwrite(eof, 1, n, fsam); fclose(fsam); }
         if (fapf) { if (n) fwrite(eof, 1, n, fapf); fclose(fapf); }
+        if (fpaf) { if (n) fwrite(eof, 1, n, fpaf); fclose(fpaf); }
         if (fbam || fpbsv) lnr_writer_bgzf_eof(&eof, &n);                                // a .bam is BGZF whatever --bgzf says
         if (fbam) { fwrite(eof, 1, n, fbam); fclose(fbam); }
         if (fpbsv) { fwrite(eof, 1, n, fpbsv); fclose(fpbsv); }
-        fsam = fapf = fbam = fpbsv = nullptr;
+        fsam = fapf = fbam = fpbsv = fpaf = nullptr;
     }
 };
 
@@ -369,6 +382,10 @@ int main(int argc, char **argv) {
     if (o.gpu_gunzip && !o.gpu_reader && !o.gpu_genome) { fprintf(stderr, "\033[1;31mE:\033[0m --gpu-gunzip inflates files on the GPU that parses them: it needs --gpu-reader or --gpu-genome\n"); return 1; }
     if (o.gpu_genome && (!lnr_genome_load_gpu || !lnr_genome_info || !lnr_genome_to_host || !lnr_genome_drop_dev || !lnr_genome_error || !lnr_genome_free || !lnr_writer_set_genome_dev)) {
         fprintf(stderr, "\033[1;31mE:\033[0m --gpu-genome: this library has no genome loader on the GPU\n");
+        return 1;
+    }
+    if (o.paf && (!lnr_writer_format_paf || !lnr_writer_format_paf_gpu || !lnr_writer_format_paf_dev)) {
+        fprintf(stderr, "\033[1;31mE:\033[0m --paf: this library has no PAF form of the writer\n");
         return 1;
     }
     if (o.bgzf && !o.gpu_writer) { fprintf(stderr, "\033[1;31mE:\033[0m --bgzf compresses the text on the GPU that formats it: it needs --gpu-writer\n"); return 1; }
@@ -554,7 +571,7 @@ int main(int argc, char **argv) {
             const uint8_t *d_reads = nullptr; const uint64_t *d_off = nullptr;
             std::vector<uint64_t> off, len, id_off, coff, cs, ce;
             std::vector<char> ids;
-            std::string sam, apf, bam;
+            std::string sam, apf, bam, paf;
             uint32_t n = 0; int file = 0;
         };
         Queue<DBlock *> freeq, readyq, doneq;
@@ -633,7 +650,7 @@ int main(int argc, char **argv) {
                 }
                 if (o.gpu_writer) {                                  // the text of the block, from the device buffers
                     const char *text; uint64_t size;
-                    b->sam.clear(); b->apf.clear(); b->bam.clear();
+                    b->sam.clear(); b->apf.clear(); b->bam.clear(); b->paf.clear();
                     if (o.f_output_type & 2) {
                         s = o.sam_seq ? lnr_writer_format_seq_dev(wr, &dev, b->d_reads, b->d_off, b->ids.data(), b->id_off.data(), &text, &size)
                                       : lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 1, &text, &size);
@@ -644,6 +661,11 @@ int main(int argc, char **argv) {
                         s = lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 2, &text, &size);
                         if (s != LNR_OK) { fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; }
                         b->apf.assign(text, size);
+                    }
+                    if (o.paf) {
+                        s = lnr_writer_format_paf_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), &text, &size);
+                        if (s != LNR_OK) { fail(std::string("writer (.paf): ") + lnr_writer_error(wr)); break; }
+                        b->paf.assign(text, size);
                     }
                     if (want_bam) {
                         s = bam_call([&] { return lnr_writer_format_bam_dev(wr, &dev, o.sam_seq ? b->d_reads : nullptr, b->d_off, b->ids.data(), b->id_off.data(), &text, &size); });
@@ -678,6 +700,7 @@ int main(int argc, char **argv) {
                 if (o.gpu_writer) {
                     if (fsam) ok = fwrite(b->sam.data(), 1, b->sam.size(), fsam) == b->sam.size();
                     if (ok && fapf) ok = fwrite(b->apf.data(), 1, b->apf.size(), fapf) == b->apf.size();
+                    if (ok && out.fpaf) ok = fwrite(b->paf.data(), 1, b->paf.size(), out.fpaf) == b->paf.size();
                     if (ok && out.fbam) ok = fwrite(b->bam.data(), 1, b->bam.size(), out.fbam) == b->bam.size();
                     if (ok && out.fpbsv) ok = fwrite(b->bam.data(), 1, b->bam.size(), out.fpbsv) == b->bam.size();
                     if (!ok) { fail("write error"); break; }
@@ -685,6 +708,7 @@ int main(int argc, char **argv) {
                     lnr_cords c{b->n, (uint64_t)b->cs.size(), b->coff.data(), b->cs.data(), b->ce.data()};
                     if (fsam) { if (lnr_writer_format(wr, &c, b->len.data(), b->ids.data(), b->id_off.data(), 1, o.thread, &text, &size) != LNR_OK) { fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fsam) != size) { fail("write error (.sam)"); break; } }
                     if (fapf) { if (lnr_writer_format(wr, &c, b->len.data(), b->ids.data(), b->id_off.data(), 2, o.thread, &text, &size) != LNR_OK) { fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fapf) != size) { fail("write error (.apf)"); break; } }
+                    if (out.fpaf) { if (lnr_writer_format_paf(wr, &c, b->len.data(), b->ids.data(), b->id_off.data(), o.thread, &text, &size) != LNR_OK) { fail(std::string("writer (.paf): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, out.fpaf) != size) { fail("write error (.paf)"); break; } }
                 }
                 us_writer += (uint64_t)((now() - tw0) * 1e6);
                 total_reads += b->n;
@@ -833,6 +857,12 @@ int main(int argc, char **argv) {
             };
             if (fsam) { if (format(1) != LNR_OK) { sh.fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fsam) != size) { sh.fail("write error (.sam)"); break; } }
             if (fapf) { if (format(2) != LNR_OK) { sh.fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; } if (fwrite(text, 1, size, fapf) != size) { sh.fail("write error (.apf)"); break; } }
+            if (out.fpaf) {
+                const lnr_status s = o.gpu_writer ? lnr_writer_format_paf_gpu(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), &text, &size)
+                                                  : lnr_writer_format_paf(wr, &b->cords, b->len.data(), b->ids.data(), b->id_off.data(), o.thread, &text, &size);
+                if (s != LNR_OK) { sh.fail(std::string("writer (.paf): ") + lnr_writer_error(wr)); break; }
+                if (fwrite(text, 1, size, out.fpaf) != size) { sh.fail("write error (.paf)"); break; }
+            }
             if (out.fbam || out.fpbsv) {                                 // one encoding serves both files: they differ in their headers alone
                 lnr_status s = bam_call([&] { return o.sam_seq ? lnr_writer_format_bam_gpu(wr, &b->cords, b->bases, b->off.data(), b->ids.data(), b->id_off.data(), &text, &size)
                                                                : lnr_writer_format_bam_gpu(wr, &b->cords, nullptr, b->len.data(), b->ids.data(), b->id_off.data(), &text, &size); });

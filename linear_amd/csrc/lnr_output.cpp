@@ -42,7 +42,7 @@ inline bool cend(u64 v) { return (v >> 60) & 1ULL; }                // is_cord_b
 inline u64 shift_cord(u64 v, i64 x, i64 y) { return (u64)((i64)v + (x << 20) + y); }   // cords.cpp:135-141 (packed domain)
 
 struct Cig { char op; uint32_t n; };
-struct Rec { int rid; i64 pos; unsigned flag; std::vector<Cig> cigar; };
+struct Rec { int rid; i64 pos; unsigned flag; std::vector<Cig> cigar; u64 lead = 0, trail = 0; };      // lead / trail: the two clips as numbers (what the S elements hold)
 
 inline void push_shrink(std::vector<Cig> &c, char op, uint32_t n) {   // appendCigarShrink f_io.cpp:659-669
     if (!c.empty() && c.back().op == op) c.back().n += n;
@@ -100,6 +100,7 @@ void cords_to_records(const u64 *cs, const u64 *ce, u64 n, u64 L, std::vector<Re
             if (i != 1) { rec_ptr.push_back(recs.size() - 1); end_ptr.push_back(i - 1); }
             f_new = 0;
             Rec r; r.rid = (int)cid(cs[i]); r.pos = (i64)cx(cs[i]); r.flag = flag | (cstrand(cs[i]) ? 16u : 0u);
+            r.lead = cy(cs[i]);
             if (cy(cs[i]) != 0) r.cigar.push_back({'S', (uint32_t)cy(cs[i])});     // insertNewBamRecord align_util.cpp:325-333
             recs.push_back(std::move(r));
             cigar_str = cs[i];
@@ -114,7 +115,7 @@ void cords_to_records(const u64 *cs, const u64 *ce, u64 n, u64 L, std::vector<Re
     }
     for (size_t k = 0; k < end_ptr.size(); k++) {
         i64 clipped = (i64)(int)(L - cy(ce[end_ptr[k]]));
-        if (clipped > 0) recs[rec_ptr[k]].cigar.push_back({'S', (uint32_t)clipped});
+        if (clipped > 0) { recs[rec_ptr[k]].cigar.push_back({'S', (uint32_t)clipped}); recs[rec_ptr[k]].trail = (u64)clipped; }
     }
 }
 
@@ -206,6 +207,37 @@ void sam_read(const Writer &w, const u64 *cs, const u64 *ce, u64 n, u64 L, const
                     saz_done[j] = 1;
                 }
         }
+        out += '\n';
+    }
+}
+
+// PAF: one line per record of sam_read, the twelve columns and cg:Z: (the line's definition: include/linear_amd.h).  No counterpart in the
+// reference; the yardstick of lnr_output_hd.h's paf_item, written on its own over the records' element lists.
+void paf_read(const Writer &w, const u64 *cs, const u64 *ce, u64 n, u64 L, const char *qname, std::string &out, std::vector<Rec> &recs) {
+    cords_to_records(cs, ce, n, L, recs, w.thd_large_X, w.thd_DI, w.thd_X);
+    for (const Rec &r : recs) {
+        const bool rev = (r.flag & 16) != 0, known = (size_t)r.rid < w.gid.size();
+        u64 match = 0, block = 0, ref = 0;
+        std::string cg;
+        for (const Cig &c : r.cigar) {
+            if (c.op == 'S') continue;
+            block += c.n;
+            if (c.op == '=') match += c.n;
+            if (c.op != 'I') ref += c.n;
+            put_u(cg, c.n); cg += c.op;
+        }
+        out += qname; out += '\t';
+        put_u(out, L); out += '\t';
+        put_u(out, rev ? r.trail : r.lead); out += '\t';
+        put_u(out, L - (rev ? r.lead : r.trail)); out += '\t';
+        out += rev ? '-' : '+'; out += '\t';
+        out += known ? w.gid[(size_t)r.rid].c_str() : "*"; out += '\t';
+        put_u(out, known ? w.glen[(size_t)r.rid] : 0); out += '\t';
+        put_u(out, (u64)r.pos); out += '\t';
+        put_u(out, (u64)r.pos + ref); out += '\t';
+        put_u(out, match); out += '\t';
+        put_u(out, block); out += "\t255";
+        if (!cg.empty()) { out += "\tcg:Z:"; out += cg; }
         out += '\n';
     }
 }
@@ -353,6 +385,30 @@ lnr_status lnr_writer_format(lnr_writer *wr, const lnr_cords *cords, const uint6
                              int what, uint32_t threads, const char **text, uint64_t *size) {
     if (!wr || !cords || !read_len || !read_ids || !id_off || !text || !size || (what != 1 && what != 2)) return LNR_ERR_ARG;
     return format_on_host(wr, cords, nullptr, read_len, read_ids, id_off, what, threads, text, size);
+}
+
+// ---- PAF: host threads (the yardstick), GPU with host cords, GPU with device cords (k_out_measure<Paf> / k_out_emit<Paf>)
+lnr_status lnr_writer_format_paf(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
+                                 uint32_t threads, const char **text, uint64_t *size) {
+    if (!wr || !cords || !read_len || !read_ids || !id_off || !text || !size) return LNR_ERR_ARG;
+    const Writer &w = wr->w;
+    return reads_on_threads(wr, cords->n_reads, threads, text, size, [&](uint32_t k, std::string &o) {
+        thread_local std::vector<Rec> recs;
+        const u64 a = cords->cord_off[k], e = cords->cord_off[k + 1];
+        paf_read(w, cords->cords_str + a, cords->cords_end + a, e - a, read_len[k], read_ids + id_off[k], o, recs);
+    });
+}
+lnr_status lnr_writer_format_paf_gpu(lnr_writer *wr, const lnr_cords *cords, const uint64_t *read_len, const char *read_ids, const uint64_t *id_off,
+                                     const char **text, uint64_t *size) {
+    if (!wr || !cords || !read_len || !read_ids || !id_off || !text || !size) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{0, cords->n_reads, cords->n_cords, cords->cord_off, cords->cords_str, cords->cords_end, read_len, read_ids, id_off, 4, 0, 0, 0, nullptr};
+    return format_on_gpu(wr, b, text, size);
+}
+lnr_status lnr_writer_format_paf_dev(lnr_writer *wr, const lnr_cords_dev *cords, const uint64_t *d_read_off, const char *read_ids, const uint64_t *id_off,
+                                     const char **text, uint64_t *size) {
+    if (!wr || !cords || !read_ids || !id_off || !text || !size || (cords->n_reads && !d_read_off)) return LNR_ERR_ARG;
+    lnr_outgpu_batch b{1, cords->n_reads, cords->n_cords, cords->d_cord_off, cords->d_cords_str, cords->d_cords_end, d_read_off, read_ids, id_off, 4, 0, 0, 0, nullptr};
+    return format_on_gpu(wr, b, text, size);
 }
 
 // ---- SAM with the SEQ column (what the reference prints with -ss 1): host, GPU with host cords, GPU with device cords

@@ -8,6 +8,7 @@
 //   APF  item j = the '@' header when cord j - 1 ends a block, then the '|' line of cord j          (print_cords_apf f_io.cpp:100-207)
 //   SAM  item j = the whole record line when cord j starts a record (j == 1 or ifCreateNew_ between j - 1 and j), else nothing
 //                                                                                                 (cords2BamLink f_io.cpp:899-1011)
+//   PAF  item j = the PAF line of the record that cord j starts, else nothing                      (no counterpart in the reference)
 // An item is written through a SINK with put(char): CountSink measures, a byte sink emits, one body serves both, so size and content
 // cannot disagree.  No std::string / std::vector: a record's CIGAR is streamed through a one-element merge window (appendCigarShrink
 // only ever looks at the last element), the SA:Z summary of a record is a second walk over its cords.
@@ -383,7 +384,51 @@ template <class S> LNR_HD inline void bam_item(S &out, const Params &P, const Se
     bam_tail(out, P, cs, ce, n, L, it, n_rec);
 }
 
+// ---- PAF (lnr_writer_format_paf*: include/linear_amd.h has the line's definition).  One line per SAM record, from the same walk: the
+// twelve columns need the sums of the record's elements, so a counting walk comes first and a printing walk writes the cg tag.  The two
+// clips are taken where record_ops takes them -- from the first cord's y and the last cord's end -- because an element stream of one
+// single S does not say which of the two it is.
+struct PafCount {                                 // matches, block length, reference bases, elements of cg; first and last S
+    u64 match = 0, block = 0, ref = 0, s_first = 0, s_last = 0; u32 k = 0;
+    LNR_HD void op(char o, u32 c, u32) {
+        if (o == 'S') return;
+        k++; block += c;
+        if (o == '=') match += c;
+        if (o != 'I') ref += c;
+    }
+};
+template <class S> struct PafCgOps {              // the elements of cg:Z: -- the CIGAR* without its S elements
+    S &out;
+    LNR_HD explicit PafCgOps(S &o) : out(o) {}
+    LNR_HD void op(char o, u32 c, u32) { if (o != 'S') { put_u(out, c); out.put(o); } }
+};
+template <class S> LNR_HD inline void paf_item(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 lo, u64 L, const char *qname) {
+    PafCount c;
+    const u64 hi = record_ops(c, P, cs, ce, n, lo, L);
+    const i64 clipped = (i64)(int)(L - cy(ce[hi]));
+    c.s_first = cy(cs[lo]); c.s_last = clipped > 0 ? (u64)clipped : 0;
+    const bool rev = cstrand(cs[lo]) != 0;
+    const u64 g = (u64)(int)cid(cs[lo]), x = cx(cs[lo]);
+    put_str(out, qname); out.put('\t');
+    put_u(out, L); out.put('\t');
+    put_u(out, rev ? c.s_last : c.s_first); out.put('\t');
+    put_u(out, L - (rev ? c.s_first : c.s_last)); out.put('\t');
+    out.put(rev ? '-' : '+'); out.put('\t');
+    put_str(out, gname(P, g)); out.put('\t');
+    put_u(out, g < P.nseq ? P.glen[g] : 0); out.put('\t');
+    put_u(out, x); out.put('\t');
+    put_u(out, x + c.ref); out.put('\t');
+    put_u(out, c.match); out.put('\t');
+    put_u(out, c.block); put_str(out, "\t255");
+    if (c.k) { put_str(out, "\tcg:Z:"); PafCgOps<S> t(out); record_ops(t, P, cs, ce, n, lo, L); }
+    out.put('\n');
+}
+
 // ---- one read, item after item (what the host shim runs; the kernels deal the items of a read to the lanes of a wave instead)
+template <class S> LNR_HD inline void paf_read(S &out, const Params &P, const u64 *cs, const u64 *ce, u64 n, u64 L, const char *qname) {
+    for (u64 j = 1; j < n; j++)
+        if (rec_first(cs, ce, j, P.thd_large_X)) paf_item(out, P, cs, ce, n, j, L, qname);
+}
 template <class S> LNR_HD inline void apf_read(S &out, const Params &P, const u64 *c, u64 n, u64 L, const char *rid, bool blank_before) {
     for (u64 j = 1; j < n; j++) apf_item(out, P, c, n, j, L, rid, blank_before);
 }

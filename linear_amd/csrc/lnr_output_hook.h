@@ -13,7 +13,8 @@ struct lnr_outgpu_batch {
     const uint64_t *cord_off, *cords_str, *cords_end;
     const uint64_t *read_len;        // dev_form 0: n lengths (host); dev_form 1: n + 1 read offsets (device), length k = off[k + 1] - off[k]
     const char *read_ids; const uint64_t *id_off;      // host, id_off[k] = start of id k; the blob ends with the '\0' of the last id
-    int what;                        // 1 SAM, 2 APF, 3 BAM records
+    int what;                        // 1 SAM, 2 APF, 3 BAM records, 4 PAF lines (lnr_writer_format_paf_gpu / _dev: k_out_measure<Paf> / k_out_emit<Paf>;
+                                     // reads stays NULL, read_len as for SAM without SEQ)
     uint64_t thd_large_X; int64_t thd_DI, thd_X;
     const uint8_t *reads;            // SAM with SEQ: the reads' bases back to back (host or device as dev_form says), and read_len then holds n + 1
                                      // read offsets in both forms; NULL: SEQ prints as '*' (BAM: l_seq 0)

@@ -21,6 +21,7 @@
 //   Text    SAM without SEQ, and APF (lnr_writer_format_gpu / _dev): an item is its head alone
 //   SamSeq  SAM with SEQ (lnr_writer_format_seq_gpu / _dev): head, the letters mapped through ACGTN, tail; measuring sums element counts and
 //           touches no base
+//   Paf     PAF lines (lnr_writer_format_paf_gpu / _dev): one per SAM record, head alone; a lane walks its record twice (sums, then the cg tag)
 //   Bam     BAM records without SEQ and with it (lnr_writer_format_bam_gpu / _dev): head (block_size, core, QNAME, CIGAR words), SEQ packed
 //           two bases to a byte (a lane's dword is 8 bases) plus the 0xff run, tag
 //
@@ -201,6 +202,16 @@ struct SamSeq {                                // head (with the '*' of an empty
     template <class S> __device__ __forceinline__ void head(S &s, const Item &, u64 j, u64) const { if (sam_head(s, A.P, R.cs, R.ce, R.nc, j, R.L, R.id) == 0) s.put('*'); }
     template <class S> __device__ __forceinline__ void tail(S &s, u64 it) const { sam_tail(s, A.P, R.cs, R.ce, R.nc, R.L, it, R.n_rec); }
     __device__ __forceinline__ void body(const SegTable *tab, u32 cnt, const RecSrc &r, uint8_t *dst, u64 q0, bool, u32 &, u32 lane) const { seq_copy(tab, cnt, r, dst, q0, lane); }
+};
+struct Paf {                                   // PAF: one line per SAM record, an item is its head alone (paf_item)
+    static constexpr bool BODY = false;
+    using Item = Sizes;
+    const ReadArgs &A; const Read &R;
+    __device__ __forceinline__ bool item(u64 j) const { return rec_first(R.cs, R.ce, j, A.P.thd_large_X); }
+    __device__ __forceinline__ bool touch() const { return true; }
+    __device__ __forceinline__ void size(Item &z, u64 j, u64 it) const { CountSink c; head(c, z, j, it); z.head = c.n; }
+    template <class S> __device__ __forceinline__ void head(S &s, const Item &, u64 j, u64) const { paf_item(s, A.P, R.cs, R.ce, R.nc, j, R.L, R.id); }
+    template <class S> __device__ __forceinline__ void tail(S &, u64) const {}
 };
 // BAM records, with SEQ and without: head (block_size, core, QNAME, CIGAR words), packed SEQ plus the 0xff run, tag (lnr_output_hd.h).  A
 // table round that ends on an odd base hands the high nibble on (`carry`) and leaves the byte to the next round; the record's last round
@@ -883,7 +894,7 @@ int lnr_outgpu_format(lnr_outgpu *g, const lnr_outgpu_batch *b, const char **tex
     u64 *sizes = (u64 *)g->sizes.p;
     OUT_CK(hipEventRecord(g->ev[0], g->st), -3);
     const bool bam = b->what == 3;
-    const auto launch = bam ? launch_format<Bam> : seq ? launch_format<SamSeq> : launch_format<Text>;
+    const auto launch = bam ? launch_format<Bam> : b->what == 4 ? launch_format<Paf> : seq ? launch_format<SamSeq> : launch_format<Text>;
     launch(false, n, g->st, A, sizes, nullptr);
     OUT_CK(hipEventRecord(g->ev[1], g->st), -3);
     hipLaunchKernelGGL(k_out_scan, dim3(1), dim3(1024), 0, g->st, sizes, n);
