@@ -46,8 +46,7 @@ typedef enum lnr_status {
     LNR_ERR_NOMEM = -4,       /* device or host allocation failed */
     LNR_ERR_NO_INDEX = -5,    /* filter/seed call before lnr_index_build / lnr_index_adopt */
     LNR_ERR_LIMIT = -6,       /* input exceeds a format limit (read >= 2^20, sequence >= 2^30 - 2^20; cords.cpp:13-15) */
-    LNR_ERR_UNSUPPORTED = -7, /* option outside this build (index_type not 1 or 2, feature_type != 2, dup > 1; -i 2 on a reference with fewer
-                                 than three repeated minimizers) */
+    LNR_ERR_UNSUPPORTED = -7, /* option outside this build (index_type not 1 or 2, feature_type != 2, dup > 1) */
     LNR_ERR_INTERNAL = -8     /* device-side capacity overflow that retries could not resolve */
 } lnr_status;
 

@@ -370,7 +370,16 @@ LNR_HD inline u64 chunk_num_samples(i64 t_str, i64 t_end) {
     if (t_end - t_str <= 8) return 0;
     return (u64)((t_end - t_str - 8 + 8) / 9);
 }
-LNR_HD inline u64 genome_feature_count(u64 len) { return len < 48 ? 0 : ((len - 48) >> 4) + 1; }   // pmpfinder.cpp:596
+// f2 entries of a sequence under T layout threads (pmpfinder.cpp:596-602): one per 16 bases -- but a sequence of fewer windows than threads
+// goes through the serial routine (:556-588), whose loop ends at i < len - 49 and so leaves the last entry out when (len - 48) % 16 < 2.
+// The count is visible: next_window / extend stop where x + 12 passes it.
+LNR_HD inline u64 genome_feature_count(u64 len, u32 T) {
+    if (len < 48) return 0;
+    u64 n = ((len - 48) >> 4) + 1;
+    if (n < T) n = 1 + (len >= 50 ? (len - 50) >> 4 : 0);
+    return n;
+}
+LNR_HD inline u64 genome_feature_count(u64 len) { return genome_feature_count(len, 1); }   // the one-thread layout: every window has its entry
 
 // ---------------------------------------------------------------- features ----
 struct F96 { i32 v0, v1, v2, pad; };   // int96 + pad: one 16-byte load per entry

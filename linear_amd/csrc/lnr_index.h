@@ -44,12 +44,19 @@ lnr_status hx_derive(lnr_ctx *ctx) {
     Index &ix = ctx->ix; hipStream_t sm = ctx->stream();
     u64 n = ix.info.hs_len;
     if (n < 2) { ctx->err = "empty HIndex"; return LNR_ERR_ARG; }
-    ix.hx_empty_dir = n - 2;
+    {   // emptyDir: the first zero word (heads and bodies are not zero) -- the last two words, or, where the reference gave up its last block
+        // (build_hindex), the two words in front of what it left of that block: at most six words from the end
+        u64 tn = std::min<u64>(n, 6), tw[6];
+        HIPCK(hipMemcpyAsync(tw, ix.hs.as<u64>() + (n - tn), tn * 8, hipMemcpyDeviceToHost, sm));
+        HIPCK(hipStreamSynchronize(sm));
+        ix.hx_empty_dir = n - 2;
+        for (u64 q = 0; q < tn; q++) if (!tw[q]) { ix.hx_empty_dir = n - tn + q; break; }
+    }
     ENSURE(ix.dir, ix.info.dir_len * 4);
     HIPCK(hipMemsetAsync(ix.dir.p, 0xff, ix.info.dir_len * 4, sm));
     DevBuf flag, tmp;
     ENSURE(flag, (n + 1) * 4 + 16);
-    hipLaunchKernelGGL(k_hx_derive, dim3((u32)((n + 255) / 256)), dim3(256), 0, sm, ix.hs.as<u64>(), n, ix.dir.as<i32>(), flag.as<i32>()); KCHECK();
+    hipLaunchKernelGGL(k_hx_derive, dim3((u32)((n + 255) / 256)), dim3(256), 0, sm, ix.hs.as<u64>(), n, ix.hx_empty_dir, ix.dir.as<i32>(), flag.as<i32>()); KCHECK();
     HIPCK(hipMemsetAsync(flag.as<i32>() + n, 0, 4, sm));
     hipLaunchKernelGGL(k_hx_nodes_mark, dim3(1u << HX_XBITS), dim3(256), 0, sm, ix.hs.as<u64>(), ix.dir.as<i32>(), flag.as<i32>()); KCHECK();
     DevBuf excl;
@@ -176,18 +183,35 @@ lnr_status build_hindex(lnr_ctx *ctx, const u64 *len, u32 nseq, u32 T) {
     i32 ndist = 0;
     HIPCK(hipMemcpyAsync(&ndist, flag.as<i32>() + n, 4, hipMemcpyDeviceToHost, sm));
     HIPCK(hipStreamSynchronize(sm));
-    // _createYSA :1336-1352: with fewer than three merged blocks the reference drops its last block and leaves words of it behind in
-    // file order -- a reference of a few hundred bases; not reproduced
-    if (n - (u64)ndist <= 2) { ctx->err = "reference too small for -i 2 (fewer than three repeated minimizers: the reference's countMove <= 2 branch)"; return LNR_ERR_UNSUPPORTED; }
     u64 ysa_len = n + (u64)ndist + 2;
     ix.info.hs_len = ysa_len;
     ENSURE(ix.hs, ysa_len * 8 + 64);
     hipLaunchKernelGGL(k_hx_assemble, dim3((u32)((n + 255) / 256)), dim3(256), 0, sm, Xs.as<u32>(), bodies.as<u64>(), n, flag.as<i32>(), cntX.as<u32>(), ix.hs.as<u64>(), ysa_len); KCHECK();
+    if (n - (u64)ndist <= 2) {
+        // _createYSA :1336-1352, "abort the last block": with fewer than three merges (every sample is a block of its own before the blocks of
+        // one X are merged: merges = n - ndist) the reference ends ysa in front of its last block -- two zero heads there, emptyDir on them --
+        // and leaves behind what its compaction had put after them: the block's other bodies, unsorted (file order) and with their Y, and
+        // in the last two words what the moves by `merges` places did not overwrite.  A reference of a few dozen samples; a few words, patched here.
+        u32 merges = (u32)(n - (u64)ndist), take = (u32)std::min<u64>(n, 3);
+        u32 hx[3]; u64 hb[3];
+        HIPCK(hipMemcpyAsync(hx, Xs.as<u32>() + (n - take), take * 4, hipMemcpyDeviceToHost, sm));
+        HIPCK(hipMemcpyAsync(hb, bodies.as<u64>() + (n - take), take * 8, hipMemcpyDeviceToHost, sm));
+        HIPCK(hipStreamSynchronize(sm));
+        u32 xl = hx[take - 1], m = 0;
+        std::vector<u64> fb;                                                  // the last block's bodies in file order: (sequence, position) ascending
+        for (u32 q = take; q-- > 0 && hx[q] == xl;) { fb.push_back(hb[q]); m++; }
+        std::sort(fb.begin(), fb.end(), [](u64 a, u64 b) { return (a & HS_MASK40) < (b & HS_MASK40); });
+        std::vector<u64> w(m + 3, 0);                                         // from the block's head on: 0, 0, bodies 2 .. m, then the two last words
+        for (u32 r = 1; r < m; r++) w[1 + r] = fb[r];
+        if (merges == 1) w[m + 1] = fb[m - 1];
+        if (merges == 2) { w[m + 1] = hs_head(2, xl); w[m + 2] = fb[m - 1]; }
+        HIPCK(hipMemcpyAsync(ix.hs.as<u64>() + (ysa_len - 2 - (m + 1)), w.data(), w.size() * 8, hipMemcpyHostToDevice, sm));
+    }
     HIPCK(hipStreamSynchronize(sm));
     return hx_derive(ctx);
 }
 
-void set_index_layout(lnr_ctx *ctx, const u64 *len, u32 nseq) {
+void set_index_layout(lnr_ctx *ctx, const u64 *len, u32 nseq, u32 T) {
     Index &ix = ctx->ix;
     ix.seq_len.assign(len, len + nseq);
     ix.seq_off.assign(nseq, 0);
@@ -196,7 +220,7 @@ void set_index_layout(lnr_ctx *ctx, const u64 *len, u32 nseq) {
     for (u32 i = 0; i < nseq; i++) {
         ix.seq_off[i] = o;
         o += align_up(len[i] + SEQ_PAD, 64);
-        ix.f2_off[i + 1] = ix.f2_off[i] + genome_feature_count(len[i]);
+        ix.f2_off[i + 1] = ix.f2_off[i] + genome_feature_count(len[i], T);
         maxlen = std::max(maxlen, len[i]);
     }
     ix.info.nseq = nseq;
@@ -231,7 +255,7 @@ lnr_status lnr_index_build(lnr_ctx *ctx, const uint8_t *const *seq, const uint64
     DevGuard dg_(ctx->device);
     Index &ix = ctx->ix; hipStream_t sm = ctx->stream();
     ix.has_index = false;
-    set_index_layout(ctx, len, nseq);
+    set_index_layout(ctx, len, nseq, T);
     ix.info.layout_threads = T;
     lnr_status s;
     if ((s = upload_index_layout(ctx)) != LNR_OK) return s;
@@ -363,7 +387,7 @@ lnr_status lnr_index_alloc(lnr_ctx *ctx, const lnr_index_info *info, const uint6
     DevGuard dg_(ctx->device);
     Index &ix = ctx->ix; hipStream_t sm = ctx->stream();
     ix.has_index = false;
-    set_index_layout(ctx, seq_len, info->nseq);
+    set_index_layout(ctx, seq_len, info->nseq, info->layout_threads ? info->layout_threads : 1);
     if (ix.info.genome_bytes != info->genome_bytes || ix.info.f2_len != info->f2_len || ix.info.dir_len != info->dir_len) {
         ctx->err = "index info does not match the sequence lengths";
         return LNR_ERR_ARG;

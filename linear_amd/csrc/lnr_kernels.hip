@@ -982,12 +982,13 @@ __global__ void __launch_bounds__(256) k_hx_assemble(const u32 *Xs, const u64 *b
     if (st) ysa[i + r - 1] = hs_head((u64)c + 1, x);
 }
 // ---- lookup tables derived from ysa (at build and at adopt)
-__global__ void __launch_bounds__(256) k_hx_derive(const u64 *ysa, u64 ysa_len, i32 *hdir, i32 *node_flag) {
+__global__ void __launch_bounds__(256) k_hx_derive(const u64 *ysa, u64 ysa_len, u64 empty_dir, i32 *hdir, i32 *node_flag) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ysa_len) return;
     u64 w = ysa[i];
     node_flag[i] = 0;
-    if (!(w & HS_TYPEFLAG)) { if (hs_head_ptr(w)) hdir[(u32)(w & ((1u << HX_XBITS) - 1))] = (i32)i; }
+    // (words behind emptyDir are what the reference left of a block it gave up: never looked up)
+    if (i < empty_dir && !(w & HS_TYPEFLAG)) { if (hs_head_ptr(w)) hdir[(u32)(w & ((1u << HX_XBITS) - 1))] = (i32)i; }
 }
 // nodes of the blocks of >= 1024 entries: a body whose Y field differs from the word in front of it (head included), _createYSA :1446-1452
 __global__ void __launch_bounds__(256) k_hx_nodes_mark(const u64 *ysa, const i32 *hdir, i32 *node_flag) {

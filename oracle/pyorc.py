@@ -147,6 +147,19 @@ class Checker:
         self._f("seed_lookup")(self.h, _p(read, _u8p), read.size, read_str, read_end, alpha, _p(out, _u64p), out.size, _p(st, _u64p))
         return out[:n], st
 
+    def lookup_hist(self, read: np.ndarray, hist: np.ndarray | None = None) -> np.ndarray:
+        """oracle only, -i 1: adds the bucket length of every lookup the seed stage makes for `read` (forward strand, step 15) to
+        hist[0..400] (uint64; a new one when None) -- which bucket lengths a read set really walks."""
+        assert self.kind == "oracle" and self.index_type == 1
+        if hist is None:
+            hist = np.zeros(401, np.uint64)
+        assert hist.dtype == np.uint64 and hist.size == 401 and hist.flags.c_contiguous
+        read = np.ascontiguousarray(read, dtype=np.uint8)
+        self.lib.orc_lookup_hist.restype = None
+        self.lib.orc_lookup_hist.argtypes = [C.c_void_p, _u8p, C.c_uint64, _u64p]
+        self.lib.orc_lookup_hist(self.h, _p(read, _u8p), read.size, _p(hist, _u64p))
+        return hist
+
     def map_read(self, read: np.ndarray):
         read = np.ascontiguousarray(read, dtype=np.uint8)
         n = self._f("map_read")(self.h, _p(read, _u8p), read.size)

@@ -197,7 +197,7 @@ void *hs_create(const u8 *const *seqs, const u64 *lens, u32 nseq, u32 T) {
         c->seqs.emplace_back(lens[i] + PAD, 0);
         memcpy(c->seqs.back().data(), seqs[i], lens[i]);
         c->lens.push_back(lens[i]);
-        c->f2_off.push_back(c->f2_off.back() + genome_feature_count(lens[i]));
+        c->f2_off.push_back(c->f2_off.back() + genome_feature_count(lens[i], c->T));
     }
     c->f2.resize(c->f2_off.back());
     for (u32 i = 0; i < nseq; i++) features_closed(c->seqs[i].data(), c->f2_off[i + 1] - c->f2_off[i], c->f2.data() + c->f2_off[i]);
