@@ -180,6 +180,33 @@ void lnr_host_free(void *p);
  * streams.  The device inputs must be complete before the call (the caller synchronises the stream that produced them) and
  * the results are complete when the call returns.  Every entry point leaves the caller's current HIP device as it found it. */
 lnr_status lnr_filter_batch_dev(lnr_ctx *ctx, const uint8_t *d_reads_concat, const uint64_t *d_off, uint32_t n, lnr_cords_dev *out);
+/* The device-buffer form in two halves: the same pipeline as lnr_filter_submit / lnr_filter_wait -- the same lanes, tickets and rules -- for
+ * input that lies in HBM already and results that stay there.
+ * lnr_filter_submit_dev takes what lnr_filter_batch_dev takes and returns at once.  Nothing is copied: the batch's input slot records the two
+ * device pointers.  The device inputs must be complete before the call (as for lnr_filter_batch_dev) and stay untouched until the wait that
+ * RETURNS their batch has returned.  h_off_or_null: the same n + 1 offsets on the host (lnr_reader_next_dev returns them); they are copied
+ * during the call and save the library its synchronous read-back of d_off at the start of the batch.  With NULL that read-back happens.
+ * lnr_filter_wait_dev hands out the oldest batch in flight as device arrays, without a download.
+ * The halves combine freely: the submit says where the input is, the wait where the result goes.  A batch submitted by either submit may be
+ * taken by either wait; lnr_filter_wait on a device-submitted batch downloads its cords as for any other.
+ * Everything said above lnr_filter_submit holds for every combination: three batches in flight (a fourth submit: LNR_ERR_ARG), submission
+ * order, a batch's error (LNR_ERR_LIMIT for a read of 2^20 bases included) reported by the wait that takes it with the batches around it
+ * intact, two lanes with gap_len == 0 and the fall-back to one, one batch at a time with LNR_LANES=1 or gap_len > 0, what is refused while
+ * batches are in flight, lnr_destroy, lnr_last_stats.  A wait with nothing in flight returns LNR_ERR_ARG.
+ * Lifetime of a device result: its three arrays stay valid until the SECOND next wait on the context -- lnr_filter_wait or
+ * lnr_filter_wait_dev, whichever -- is CALLED (not: has returned), which mirrors the rule for the host arrays: a writer may format batch k
+ * on the device while the caller already sits in wait(k + 1).  The reason: lnr_filter_wait_dev does not leave the arrays in the lane's
+ * result set, where the lane's next batch but one would be computed over them; it takes the set's buffers out of the lane and gives the lane
+ * the buffers of the result that expires in exchange (pointer swaps under the context's lock, no copy, no allocation once they are grown).
+ * So the lane's set is free when the call returns, exactly as after the download in lnr_filter_wait, and a lane never waits for the caller:
+ * a scheme that kept the set itself occupied until the second next wait would stop the one-lane fall-back, where a batch of lane 1 needs a
+ * set of lane 0 before that wait comes.  Every wait begins by retiring the result handed out by the wait before the last.  In one-lane
+ * mode lnr_filter_wait_dev computes its batch inside the call and nothing ahead (there is no download to compute under), so it never
+ * computes into arrays that are handed out.  After lnr_filter_wait_dev, lnr_cords_to_host has no batch to copy (LNR_ERR_ARG when the
+ * buffers in place are too small) until the next lnr_filter_batch_dev. */
+lnr_status lnr_filter_submit_dev(lnr_ctx *ctx, const uint8_t *d_reads_concat, const uint64_t *d_off /* n+1, device */,
+                                 const uint64_t *h_off_or_null /* the same n+1 values on the host */, uint32_t n);
+lnr_status lnr_filter_wait_dev(lnr_ctx *ctx, lnr_cords_dev *out);
 /* apx_gaps of the last filter call -- apxMap's second output (include/pmpfinder.h:213-225), the input of the reference's gap
  * re-mapper mapGaps (src/mapper.cpp:448-453; not part of this library): per read, the uncovered stretches of the read as pairs of
  * cord words (first, second), as gather_gaps_y_ leaves them before the re-map loop (src/pmpfinder.cpp:2744).  CSR over the reads of

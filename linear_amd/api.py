@@ -99,7 +99,8 @@ EXPORTS = ["lnr_opts_default", "lnr_create", "lnr_destroy", "lnr_strerror", "lnr
            "lnr_writer_sort_begin", "lnr_writer_sort_finish", "lnr_writer_sort_next", "lnr_writer_sort_bai", "lnr_writer_sort_info_get", "lnr_writer_sort_end",
            "lnr_writer_sort_host", "lnr_writer_bai_host", "lnr_writer_sort_spill", "lnr_writer_sort_hold_info_get",
            "lnr_genome_load_gpu", "lnr_genome_info", "lnr_genome_to_host", "lnr_genome_drop_dev", "lnr_genome_error", "lnr_genome_free", "lnr_writer_set_genome_dev",
-           "lnr_writer_format_paf", "lnr_writer_format_paf_gpu", "lnr_writer_format_paf_dev"]
+           "lnr_writer_format_paf", "lnr_writer_format_paf_gpu", "lnr_writer_format_paf_dev",
+           "lnr_filter_submit_dev", "lnr_filter_wait_dev"]
 
 
 class LnrBgzfStats(C.Structure):
@@ -144,6 +145,8 @@ def load_library() -> C.CDLL:
     lib.lnr_set_gap.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     lib.lnr_filter_submit.argtypes = [C.c_void_p, C.c_void_p, _u64p, C.c_uint32]
     lib.lnr_filter_wait.argtypes = [C.c_void_p, C.POINTER(LnrCords)]
+    lib.lnr_filter_submit_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _u64p, C.c_uint32]
+    lib.lnr_filter_wait_dev.argtypes = [C.c_void_p, C.POINTER(LnrCordsDev)]
     lib.lnr_host_alloc.restype = C.c_void_p
     lib.lnr_host_alloc.argtypes = [C.c_size_t]
     lib.lnr_host_free.argtypes = [C.c_void_p]
@@ -367,6 +370,26 @@ class Filter:
     def filter_batch_dev(self, d_reads_ptr: int, d_off_ptr: int, n: int) -> "LnrCordsDev":
         out = LnrCordsDev()
         self._ck(self.lib.lnr_filter_batch_dev(self.h, C.c_void_p(d_reads_ptr), C.c_void_p(d_off_ptr), n, C.byref(out)))
+        return out
+
+    def filter_submit_dev(self, d_reads_ptr: int, d_off_ptr: int, n: int, h_off=None):
+        """Device form of filter_submit (at most three in flight, of either kind): nothing is copied, the device buffers must be complete now
+        and stay untouched until the wait that returns the batch.  h_off: the same n + 1 offsets as a host uint64 array (copied during the
+        call), which saves the library its read-back of d_off."""
+        if h_off is not None:
+            h_off = np.ascontiguousarray(h_off, dtype=np.uint64)
+            assert h_off.size == n + 1
+        self._inflight = getattr(self, "_inflight", [])
+        self._ck(self.lib.lnr_filter_submit_dev(self.h, C.c_void_p(d_reads_ptr), C.c_void_p(d_off_ptr), _p(h_off, _u64p) if h_off is not None else None, n))
+        self._inflight.append(None)
+
+    def filter_wait_dev(self) -> "LnrCordsDev":
+        """The oldest batch in flight (submitted by filter_submit or filter_submit_dev) as device arrays, without a download.  They stay
+        valid until the second next filter_wait / filter_wait_dev of this context is called."""
+        out = LnrCordsDev()
+        self._ck(self.lib.lnr_filter_wait_dev(self.h, C.byref(out)))
+        if getattr(self, "_inflight", None):
+            self._inflight.pop(0)
         return out
 
     def last_gaps(self):

@@ -14,10 +14,12 @@
 //   gap stream     with -g > 0 the reference's result depends on the order reads meet a thread's GapParms (lnr_gap_stream in the header): the blocks
 //                  are taken strictly in file order until a block reports the stream "extended"; from then on every GPU runs freely with that state.
 //                  The result is the reference's `-t 1` result whatever --gpus is.
-//   device chain   --gpu-reader (extension): the reader thread parses the read files on the first GPU (lnr_reader_next_dev, three device blocks), the
-//                  calculator runs lnr_filter_batch_dev on them and the text comes from lnr_cords_to_host + the host writer or, with --gpu-writer,
-//                  from lnr_writer_format_dev / _seq_dev on the same device buffers: no read base crosses PCIe.  One GPU, one batch at a time (the
-//                  device form of the filter has one lane); the same bytes as the default path.
+//   device chain   --gpu-reader (extension): the reader thread parses the read files on the first GPU (lnr_reader_next_dev, five device blocks), the
+//                  calculator hands them to lnr_filter_submit_dev, up to three ahead, and the text comes from lnr_filter_wait + the host writer or,
+//                  with --gpu-writer, from lnr_filter_wait_dev and lnr_writer_format_dev / _seq_dev on the same device buffers: no read base crosses
+//                  PCIe, and the context's two lanes compute the next blocks while the text of one is made.  One GPU; the same bytes as the
+//                  default path.  LNR_CLI_DEV_HALVES=0 in the environment: one lnr_filter_batch_dev at a time on three blocks, as a library
+//                  without the halves gets it.
 //   BGZF output    --bgzf (extension, needs --gpu-writer): the text is compressed on the GPU it was formatted on (lnr_writer_set_bgzf) and the
 //                  outputs are PREFIX.sam.gz / PREFIX.apf.gz: the SAM header through lnr_writer_bgzf_bytes_gpu, every block's members as
 //                  returned, the EOF marker at close.  bgzip -d, zcat and samtools read them.
@@ -71,6 +73,8 @@
 extern "C" {
 lnr_status lnr_filter_batch_dev(lnr_ctx *, const uint8_t *, const uint64_t *, uint32_t, lnr_cords_dev *) __attribute__((weak));
 lnr_status lnr_cords_to_host(lnr_ctx *, lnr_cords *) __attribute__((weak));
+lnr_status lnr_filter_submit_dev(lnr_ctx *, const uint8_t *, const uint64_t *, const uint64_t *, uint32_t) __attribute__((weak));   // (a library without the
+lnr_status lnr_filter_wait_dev(lnr_ctx *, lnr_cords_dev *) __attribute__((weak));                                                  //  halves: one batch at a time)
 lnr_status lnr_writer_format_dev(lnr_writer *, const lnr_cords_dev *, const uint64_t *, const char *, const uint64_t *, int, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_writer_format_seq_dev(lnr_writer *, const lnr_cords_dev *, const uint8_t *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
 lnr_status lnr_writer_format_bam_dev(lnr_writer *, const lnr_cords_dev *, const uint8_t *, const uint64_t *, const char *, const uint64_t *, const char **, uint64_t *) __attribute__((weak));
@@ -98,6 +102,9 @@ const char *lnr_genome_error(const lnr_genome *) __attribute__((weak));
 void lnr_genome_free(lnr_genome *) __attribute__((weak));
 lnr_status lnr_writer_set_genome_dev(lnr_writer *, const uint8_t *const *) __attribute__((weak));
 }
+
+// the device chain's calculator submits ahead through the halves of the device form unless LNR_CLI_DEV_HALVES says otherwise (README: the A/B)
+static const bool DEV_HALVES_DEFAULT = true;
 
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -566,7 +573,7 @@ int main(int argc, char **argv) {
             for (auto *c : ctx) lnr_destroy(c);
             return 1;
         }
-        // reader thread -> calculator -> writer thread, three device blocks of the reader in flight; one batch at a time in the context
+        // reader thread -> calculator -> writer thread over the reader's device blocks
         struct DBlock {
             const uint8_t *d_reads = nullptr; const uint64_t *d_off = nullptr;
             std::vector<uint64_t> off, len, id_off, coff, cs, ce;
@@ -584,7 +591,15 @@ int main(int argc, char **argv) {
             for (auto *c : ctx) lnr_destroy(c);
             return 1;
         }
-        std::vector<DBlock> dblocks(3);
+        // The halves of the device form (lnr_filter_submit_dev / _wait_dev) let the calculator submit ahead; LNR_CLI_DEV_HALVES=0|1 in the
+        // environment chooses between that and one lnr_filter_batch_dev at a time (an A/B switch, not an option).
+        // Blocks: one being read, up to three in the context, one whose text is being made or written -- five; three for the old loop (one
+        // being read, one in the context, one being written).  The reader's device blocks are as many: a block goes back to the reader only
+        // after its batch's wait has returned and its text has been written.
+        bool halves = lnr_filter_submit_dev && lnr_filter_wait_dev && DEV_HALVES_DEFAULT;
+        if (const char *e = getenv("LNR_CLI_DEV_HALVES")) halves = lnr_filter_submit_dev && lnr_filter_wait_dev && atoi(e) != 0;
+        const unsigned NDB = halves ? 5 : 3;
+        std::vector<DBlock> dblocks(NDB);
         for (auto &b : dblocks) freeq.push(&b);
         // --sort with one output per read file: the writer thread ends a file's sort round (lnr_writer_sort_finish .. _begin on `wr`) while this
         // thread would add the next file's records to it.  A fence block (n == 0) goes through the queue in front of the first block of a new
@@ -599,7 +614,7 @@ int main(int argc, char **argv) {
         std::thread reader([&] {
             for (size_t f = 0; f < o.r_paths.size() && !failed; f++) {
                 if (lnr_reader_open(o.r_paths[f].c_str(), &cur) != LNR_OK) { cur = nullptr; fail("can't open read file " + o.r_paths[f]); break; }
-                if (lnr_reader_gpu_open(cur, o.devices[0], 3) != LNR_OK) { fail(std::string("--gpu-reader: ") + lnr_reader_error(cur)); break; }
+                if (lnr_reader_gpu_open(cur, o.devices[0], NDB) != LNR_OK) { fail(std::string("--gpu-reader: ") + lnr_reader_error(cur)); break; }
                 if (o.gpu_gunzip && lnr_reader_gpu_gzip(cur, 1) != LNR_OK) { fail(std::string("--gpu-gunzip: ") + lnr_reader_error(cur)); break; }
                 for (;;) {
                     DBlock *b = nullptr;
@@ -621,64 +636,126 @@ int main(int argc, char **argv) {
                     readyq.push(b);
                 }
                 // the file is read: once its blocks are back the reader goes, with its device blocks and staging buffers
-                DBlock *back[3]; size_t nb = 0;
-                while (nb < 3 && !failed && freeq.pop(back[nb])) nb++;
-                if (nb < 3) break;
+                std::vector<DBlock *> back(NDB); size_t nb = 0;
+                while (nb < NDB && !failed && freeq.pop(back[nb])) nb++;
+                if (nb < NDB) break;
                 lnr_reader_close(cur); cur = nullptr;
                 for (DBlock *b : back) freeq.push(b);
             }
             readyq.close();
         });
+        // (calculator thread) --sort with one output per read file: before the first block of a new output goes to the writer `wr`, the fence.
+        // False: the run has failed.
+        auto pass_fence = [&](DBlock *b) {
+            if (!(o.sort && o.oPath.empty())) return true;
+            const std::string prefix = output_prefix_of(o.r_paths[(size_t)b->file]);
+            if (calc_has_prefix && prefix != calc_prefix) {
+                fence.n = 0; fence.file = b->file;
+                fences_sent++;
+                doneq.push(&fence);
+                std::unique_lock<std::mutex> l(fm);
+                while (fences_passed != fences_sent && !failed) fcv.wait_for(l, std::chrono::milliseconds(50));      // (a failure elsewhere does not signal here)
+                if (failed) return false;
+            }
+            calc_prefix = prefix; calc_has_prefix = true;
+            return true;
+        };
+        auto needs_fence = [&](const DBlock *b) { return o.sort && o.oPath.empty() && calc_has_prefix && output_prefix_of(o.r_paths[(size_t)b->file]) != calc_prefix; };
+        // (calculator thread, --gpu-writer) the text of block b from its device buffers and its cords `dev`
+        auto text_of = [&](DBlock *b, const lnr_cords_dev &dev) {
+            const char *text; uint64_t size;
+            lnr_status s;
+            b->sam.clear(); b->apf.clear(); b->bam.clear(); b->paf.clear();
+            if (o.f_output_type & 2) {
+                s = o.sam_seq ? lnr_writer_format_seq_dev(wr, &dev, b->d_reads, b->d_off, b->ids.data(), b->id_off.data(), &text, &size)
+                              : lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 1, &text, &size);
+                if (s != LNR_OK) { fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); return false; }
+                b->sam.assign(text, size);
+            }
+            if (o.f_output_type & 1) {
+                s = lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 2, &text, &size);
+                if (s != LNR_OK) { fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); return false; }
+                b->apf.assign(text, size);
+            }
+            if (o.paf) {
+                s = lnr_writer_format_paf_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), &text, &size);
+                if (s != LNR_OK) { fail(std::string("writer (.paf): ") + lnr_writer_error(wr)); return false; }
+                b->paf.assign(text, size);
+            }
+            if (want_bam) {
+                s = bam_call([&] { return lnr_writer_format_bam_dev(wr, &dev, o.sam_seq ? b->d_reads : nullptr, b->d_off, b->ids.data(), b->id_off.data(), &text, &size); });
+                if (s != LNR_OK) { fail(std::string("writer (.bam): ") + lnr_writer_error(wr) + sort_hint(o, s)); return false; }
+                b->bam.assign(text, size);
+            }
+            return true;
+        };
+        auto keep_cords = [](DBlock *b, const lnr_cords &c) {
+            b->coff.assign(c.cord_off, c.cord_off + c.n_reads + 1);
+            b->cs.assign(c.cords_str, c.cords_str + c.n_cords);
+            b->ce.assign(c.cords_end, c.cords_end + c.n_cords);
+        };
         std::thread calc([&] {
             DBlock *b = nullptr;
+            if (halves) {
+                // submit(0); submit(1); loop { submit(k + 2); wait(k); text of k }: the lanes compute blocks k + 1 and k + 2 while this thread makes
+                // the text of block k.  A block that would need a fence is held back until everything before it has gone to the writer thread.
+                std::deque<DBlock *> fl;             // submitted, not handed out yet
+                DBlock *held = nullptr;
+                bool eof = false;
+                while (!failed) {
+                    while (!eof && !held && fl.size() < 3) {
+                        DBlock *nb = nullptr;
+                        if (fl.empty()) { if (!readyq.pop(nb)) { eof = true; break; } }
+                        else if (!readyq.try_pop(nb)) break;
+                        if (needs_fence(nb)) { held = nb; break; }
+                        if (!pass_fence(nb)) break;        // (no fence here: it notes the output the block belongs to)
+                        lnr_status s = lnr_filter_submit_dev(ctx[0], nb->d_reads, nb->d_off, nb->off.data(), nb->n);
+                        if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
+                        fl.push_back(nb);
+                    }
+                    if (failed) break;
+                    if (fl.empty()) {
+                        if (!held) { if (eof) break; continue; }
+                        if (!pass_fence(held)) break;      // the pipeline is drained: the fence goes out, then the held block starts the new output
+                        lnr_status s = lnr_filter_submit_dev(ctx[0], held->d_reads, held->d_off, held->off.data(), held->n);
+                        if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
+                        fl.push_back(held); held = nullptr;
+                        continue;
+                    }
+                    b = fl.front(); fl.pop_front();
+                    double tg0 = now();
+                    if (o.gpu_writer) {
+                        lnr_cords_dev dev{};
+                        lnr_status s = lnr_filter_wait_dev(ctx[0], &dev);
+                        if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
+                        if (!text_of(b, dev)) break;
+                    } else {
+                        lnr_cords c{};
+                        lnr_status s = lnr_filter_wait(ctx[0], &c);
+                        if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
+                        keep_cords(b, c);
+                    }
+                    us_gpu += (uint64_t)((now() - tg0) * 1e6);
+                    doneq.push(b);
+                }
+                // (after a failure: the lanes still read the device blocks of what is in flight, and the reader frees them next)
+                for (size_t k = fl.size(); k--;) { lnr_cords_dev d{}; (void)lnr_filter_wait_dev(ctx[0], &d); }
+                doneq.close();
+                return;
+            }
             while (readyq.pop(b) && !failed) {
                 double tg0 = now();
                 lnr_cords_dev dev{};
                 lnr_status s = lnr_filter_batch_dev(ctx[0], b->d_reads, b->d_off, b->n, &dev);
                 if (s != LNR_OK) { fail(std::string("filter: ") + lnr_strerror(s) + " (" + lnr_last_error(ctx[0]) + ")"); break; }
-                if (o.sort && o.oPath.empty()) {
-                    const std::string prefix = output_prefix_of(o.r_paths[(size_t)b->file]);
-                    if (calc_has_prefix && prefix != calc_prefix) {
-                        fence.n = 0; fence.file = b->file;
-                        fences_sent++;
-                        doneq.push(&fence);
-                        std::unique_lock<std::mutex> l(fm);
-                        while (fences_passed != fences_sent && !failed) fcv.wait_for(l, std::chrono::milliseconds(50));      // (a failure elsewhere does not signal here)
-                        if (failed) break;
-                    }
-                    calc_prefix = prefix; calc_has_prefix = true;
-                }
+                if (!pass_fence(b)) break;
                 if (o.gpu_writer) {                                  // the text of the block, from the device buffers
-                    const char *text; uint64_t size;
-                    b->sam.clear(); b->apf.clear(); b->bam.clear(); b->paf.clear();
-                    if (o.f_output_type & 2) {
-                        s = o.sam_seq ? lnr_writer_format_seq_dev(wr, &dev, b->d_reads, b->d_off, b->ids.data(), b->id_off.data(), &text, &size)
-                                      : lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 1, &text, &size);
-                        if (s != LNR_OK) { fail(std::string("writer (.sam): ") + lnr_writer_error(wr)); break; }
-                        b->sam.assign(text, size);
-                    }
-                    if (o.f_output_type & 1) {
-                        s = lnr_writer_format_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), 2, &text, &size);
-                        if (s != LNR_OK) { fail(std::string("writer (.apf): ") + lnr_writer_error(wr)); break; }
-                        b->apf.assign(text, size);
-                    }
-                    if (o.paf) {
-                        s = lnr_writer_format_paf_dev(wr, &dev, b->d_off, b->ids.data(), b->id_off.data(), &text, &size);
-                        if (s != LNR_OK) { fail(std::string("writer (.paf): ") + lnr_writer_error(wr)); break; }
-                        b->paf.assign(text, size);
-                    }
-                    if (want_bam) {
-                        s = bam_call([&] { return lnr_writer_format_bam_dev(wr, &dev, o.sam_seq ? b->d_reads : nullptr, b->d_off, b->ids.data(), b->id_off.data(), &text, &size); });
-                        if (s != LNR_OK) { fail(std::string("writer (.bam): ") + lnr_writer_error(wr) + sort_hint(o, s)); break; }
-                        b->bam.assign(text, size);
-                    }
+                    if (!text_of(b, dev)) break;
                 } else {
                     lnr_cords c{};
                     s = lnr_cords_to_host(ctx[0], &c);
                     if (s != LNR_OK) { fail(std::string("cords: ") + lnr_last_error(ctx[0])); break; }
-                    b->coff.assign(c.cord_off, c.cord_off + c.n_reads + 1);
-                    b->cs.assign(c.cords_str, c.cords_str + c.n_cords);
-                    b->ce.assign(c.cords_end, c.cords_end + c.n_cords);
+                    keep_cords(b, c);
                 }
                 us_gpu += (uint64_t)((now() - tg0) * 1e6);
                 doneq.push(b);

@@ -77,7 +77,20 @@ lnr_status submit_reads(lnr_ctx *ctx, Lane *L, int slot, const u8 *reads, const 
     }
     HIPCK(hipMemcpyAsync(dof.p, o, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, sc));
     HIPCK(hipEventRecord(L->ev_in[slot], sc));
-    L->in_n[slot] = n;
+    L->in_n[slot] = n; L->borrowed[slot] = false;
+    return LNR_OK;
+}
+// The same for a batch that lies on the device already (lnr_filter_submit_dev): the slot records the caller's pointers, nothing is
+// uploaded and ev_in[slot] is not used.  h_off (optional): the offsets on the host, copied now; they save prepare_batch its read-back.
+lnr_status submit_borrowed(lnr_ctx *ctx, Lane *L, int slot, const u8 *d_reads, const u64 *d_off, const u64 *h_off, u32 n) {
+    if (h_off) {
+        for (u32 i = 0; i < n; i++)
+            if (h_off[i + 1] < h_off[i]) { ctx->err = "read offsets not monotone"; return LNR_ERR_ARG; }
+        if (!L->h_off[slot].ensure(((size_t)n + 1) * 8)) { ctx->err = "pinned host allocation failed"; return LNR_ERR_NOMEM; }
+        memcpy(L->h_off[slot].p, h_off, ((size_t)n + 1) * 8);
+    }
+    L->bor_reads[slot] = d_reads; L->bor_off[slot] = d_off; L->bor_hoff[slot] = h_off != nullptr;
+    L->in_n[slot] = n; L->borrowed[slot] = true;
     return LNR_OK;
 }
 
@@ -106,8 +119,12 @@ void lane_release_batch(Lane *L) {
 lnr_status compute_slot(Lane *C, Lane *In, int slot, Pre &P) {
     P = Pre();
     P.valid = true; P.tot = 0; P.n = In->in_n[slot];
-    hipError_t e = hipStreamWaitEvent(C->stream, In->ev_in[slot], 0);
-    P.st = e == hipSuccess ? filter_dev(C, In->in_reads[slot].as<u8>(), In->in_off[slot].as<u64>(), In->in_n[slot], nullptr, In->h_off[slot].as<u64>()) : LNR_ERR_HIP;
+    const bool bor = In->borrowed[slot];      // (device input of the caller's: complete before it was submitted, no upload to wait for)
+    hipError_t e = bor ? hipSuccess : hipStreamWaitEvent(C->stream, In->ev_in[slot], 0);
+    const u8 *d_reads = bor ? In->bor_reads[slot] : In->in_reads[slot].as<u8>();
+    const u64 *d_off = bor ? In->bor_off[slot] : In->in_off[slot].as<u64>();
+    const u64 *h_off = !bor || In->bor_hoff[slot] ? In->h_off[slot].as<u64>() : nullptr;
+    P.st = e == hipSuccess ? filter_dev(C, d_reads, d_off, In->in_n[slot], nullptr, h_off) : LNR_ERR_HIP;
     P.err = C->err.get();
     P.stats = C->stats;
     if (P.st == LNR_OK) {
@@ -131,15 +148,18 @@ void lane_worker(lnr_ctx *top, int li) {
     Lane &Ln = *top->lane[li], &L0 = *top->lane[0];
     (void)hipSetDevice(top->device);
     std::unique_lock<std::mutex> lk(top->mu);
-    auto take_set = [](Lane &R, Ticket *T) {   // (under the lock; R.unhanded < 2, so one of the two is free)
+    // (under the lock; R.unhanded < 2, so one of the two is free.)  Into a free one of the lane's two result sets: the batch computed
+    // before this one may still be waiting for its download.  The buffers change places under the lock, because lnr_filter_wait_dev takes
+    // the buffers of a set that is handed out away from the lane (park_set).  Returns whether the other set has never been sized.
+    auto take_set = [](Lane &R, Ticket *T) {
         T->res_set = R.set_used[0] ? 1 : 0;
         R.set_used[T->res_set] = true;
-    };
-    auto run = [&](Lane &R, Ticket *T) {     // T on lane R's state, with the lock released; R.busy is set
-        // into a free one of the lane's two result sets: the batch computed before this one may still be waiting for its download
         if (T->res_set != R.set_cur) { R.r_off.swap(R.rB_off); R.r_str.swap(R.rB_str); R.r_end.swap(R.rB_end); R.set_cur = T->res_set; }
+        return !R.rB_str.p && !R.set_used[T->res_set ^ 1];   // (an empty batch leaves r_str as it was: its set may hold offsets to hand out)
+    };
+    auto run = [&](Lane &R, Ticket *T, bool size_other) {     // T on lane R's state, with the lock released; R.busy is set
         compute_slot(&R, &Ln, T->slot, T->pre);
-        if (T->pre.st == LNR_OK && !R.rB_str.p) {
+        if (T->pre.st == LNR_OK && size_other) {
             // the lane's first batch: size the other result set now, not in the lane's second batch (with two lanes that one is already
             // past a caller's two warm-up batches, and an allocation stalls the whole device)
             AllocCount count_(&R.allocs);
@@ -156,10 +176,10 @@ void lane_worker(lnr_ctx *top, int li) {
         bool on_own = li == 0 || !top->lane1_off;
         if (on_own) {
             Ln.busy = true;
-            take_set(Ln, T);
+            const bool size_other = take_set(Ln, T);
             lk.unlock();
             if (li == 1 && top->lane1_nomem_test) { top->lane1_nomem_test = false; T->pre = Pre(); T->pre.valid = true; T->pre.st = LNR_ERR_NOMEM; T->pre.err = "LNR_LANE1_NOMEM: allocation failure injected"; }
-            else run(Ln, T);
+            else run(Ln, T, size_other);
             lk.lock();
             Ln.busy = false;
             if (li == 1 && T->pre.st == LNR_ERR_NOMEM) {
@@ -180,9 +200,9 @@ void lane_worker(lnr_ctx *top, int li) {
             top->cv.wait(lk, [&] { return top->quit || (!L0.busy && L0.unhanded < 2); });
             if (top->quit) return;
             L0.busy = true;
-            take_set(L0, T);
+            const bool size_other = take_set(L0, T);
             lk.unlock();
-            run(L0, T);
+            run(L0, T, size_other);
             lk.lock();
             L0.busy = false;
         }
@@ -218,6 +238,75 @@ lnr_status lane0_result(lnr_ctx *ctx, lnr_status st) {
     if (st != LNR_OK) ctx->err = ctx->lane[0]->err.get();
     ctx->stats_pub = ctx->lane[0]->stats;
     return st;
+}
+
+// The start of every wait, of either kind: the device result handed out by the wait before the last one expires (lnr_ctx::park).
+void park_age(lnr_ctx *ctx) {
+    lnr_ctx::Parked &a = ctx->park[0], &b = ctx->park[1];
+    a.off.swap(b.off); a.str.swap(b.str); a.end.swap(b.end);
+}
+// lnr_filter_wait_dev's hand-out of a computed batch P whose result lies in (off, str, end) of a lane: those buffers go to park[0], the
+// expired ones take their place in the lane (sized for this batch before, so that the lane does not allocate in its next one).
+// `mu`: the lock that guards the lane's buffers against its worker (null: the lane computes on the caller's thread).
+lnr_status park_set(lnr_ctx *ctx, const Pre &P, std::mutex *mu, Lane &Ln, int set, lnr_cords_dev *out) {
+    lnr_ctx::Parked &K = ctx->park[0];
+    const size_t nb = ((size_t)P.n + 1) * 8, cb = std::max<u64>(P.tot * 8, 16);
+    if (!K.off.ensure(nb) || !K.off.host_stage(nb) || !K.str.ensure(cb) || !K.end.ensure(cb)) { ctx->err = "device allocation failed"; return LNR_ERR_NOMEM; }
+    {
+        std::unique_lock<std::mutex> lk;
+        if (mu) lk = std::unique_lock<std::mutex>(*mu);
+        const bool cur = !mu || set == Ln.set_cur;
+        (cur ? Ln.r_off : Ln.rB_off).swap(K.off); (cur ? Ln.r_str : Ln.rB_str).swap(K.str); (cur ? Ln.r_end : Ln.rB_end).swap(K.end);
+    }
+    out->n_reads = P.n; out->n_cords = P.tot;
+    out->d_cord_off = K.off.as<u64>(); out->d_cords_str = K.str.as<u64>(); out->d_cords_end = K.end.as<u64>();
+    return LNR_OK;
+}
+
+// The common half of lnr_filter_submit / lnr_filter_submit_dev: picks the lane and the input slot, has `fill` put the batch there (an
+// upload, or the caller's device pointers) and queues it.
+template <class Fill> lnr_status submit_batch(lnr_ctx *ctx, Fill fill) {
+    DevGuard dg_(ctx->device);
+    if (!ctx->ix.has_index) { ctx->err = "no index"; return LNR_ERR_NO_INDEX; }
+    if (ctx->in_count + (ctx->pre.valid ? 1 : 0) + ctx->tickets.size() >= 3) { ctx->err = "three batches already in flight: call lnr_filter_wait or lnr_filter_wait_dev first"; return LNR_ERR_ARG; }
+    if (two_lanes(ctx)) {
+        // the lanes take the batches in turn; an idle context starts with lane 0, so one batch at a time (lnr_filter_batch) never touches lane 1
+        int li = (ctx->tickets.empty() || ctx->lane1_off) ? 0 : (ctx->tickets.back()->lane ^ 1);
+        if (li == 1 && !ctx->lane[1]) {
+            std::unique_ptr<Lane> L1 = lane_create(ctx, 1);
+            if (L1) { std::lock_guard<std::mutex> g(ctx->mu); ctx->lane[1] = std::move(L1); }   // (lane 0's worker looks at lane 1's queue)
+            else { ctx->lane1_off = true; li = 0; }
+        }
+        int slot = 0;
+        for (;;) {
+            Lane &Ln = *ctx->lane[li];
+            { std::lock_guard<std::mutex> g(ctx->mu); slot = 0; while (slot < 2 && Ln.slot_busy[slot]) slot++; }
+            lnr_status s = fill(&Ln, slot);
+            if (s == LNR_ERR_NOMEM && li == 1) { ctx->lane1_off = true; li = 0; continue; }   // no room for a second lane's input: one lane from now on
+            if (s != LNR_OK) return s;
+            break;
+        }
+        Lane &Ln = *ctx->lane[li];
+        if (!Ln.th.joinable()) {
+            try { Ln.th = std::thread(lane_worker, ctx, li); }
+            catch (...) { ctx->err = "worker thread could not be started"; return LNR_ERR_INTERNAL; }
+        }
+        std::unique_ptr<Ticket> T(new Ticket());
+        T->lane = li; T->slot = slot;
+        {
+            std::lock_guard<std::mutex> g(ctx->mu);
+            Ln.slot_busy[slot] = true; Ln.pending++;
+            Ln.work.push_back(T.get());
+        }
+        ctx->tickets.push_back(std::move(T));
+        ctx->cv.notify_all();
+        return LNR_OK;
+    }
+    int slot = (ctx->in_head + ctx->in_count) % 3;
+    lnr_status s = fill(ctx->lane[0].get(), slot);
+    if (s != LNR_OK) return s;
+    ctx->in_count++;
+    return LNR_OK;
 }
 
 }  // namespace
@@ -342,6 +431,8 @@ lnr_status lnr_cords_to_host(lnr_ctx *ctx, lnr_cords *out) {
     Lane *L = ctx->lane[0].get();
     u64 tot = L->last_ncords;
     if (L->h_cord_off.size() != (size_t)L->last_n + 1) L->h_cord_off.assign((size_t)L->last_n + 1, 0);
+    // (lnr_filter_wait_dev took the last batch's buffers out of the lane: what stands in their place may be smaller)
+    if (tot * 8 > L->r_str.cap || tot * 8 > L->r_end.cap) { ctx->err = "lnr_cords_to_host: the last batch was handed out by lnr_filter_wait_dev"; return LNR_ERR_ARG; }
     lnr_status s = hand_out(ctx, L->last_n, tot, std::vector<u64>(L->h_cord_off), L->r_str.p, L->r_end.p, L->stream, nullptr, out);
     if (s != LNR_OK) return s;
     if (tot) HIPCK(hipStreamSynchronize(L->stream));
@@ -356,51 +447,17 @@ void lnr_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
 lnr_status lnr_filter_submit(lnr_ctx *ctx, const uint8_t *reads, const uint64_t *off, uint32_t n) {
     if (!ctx) return LNR_ERR_ARG;
-    DevGuard dg_(ctx->device);
-    if (!ctx->ix.has_index) { ctx->err = "no index"; return LNR_ERR_NO_INDEX; }
-    if (ctx->in_count + (ctx->pre.valid ? 1 : 0) + ctx->tickets.size() >= 3) { ctx->err = "three batches already in flight: call lnr_filter_wait first"; return LNR_ERR_ARG; }
-    if (two_lanes(ctx)) {
-        // the lanes take the batches in turn; an idle context starts with lane 0, so one batch at a time (lnr_filter_batch) never touches lane 1
-        int li = (ctx->tickets.empty() || ctx->lane1_off) ? 0 : (ctx->tickets.back()->lane ^ 1);
-        if (li == 1 && !ctx->lane[1]) {
-            std::unique_ptr<Lane> L1 = lane_create(ctx, 1);
-            if (L1) { std::lock_guard<std::mutex> g(ctx->mu); ctx->lane[1] = std::move(L1); }   // (lane 0's worker looks at lane 1's queue)
-            else { ctx->lane1_off = true; li = 0; }
-        }
-        int slot = 0;
-        for (;;) {
-            Lane &Ln = *ctx->lane[li];
-            { std::lock_guard<std::mutex> g(ctx->mu); slot = 0; while (slot < 2 && Ln.slot_busy[slot]) slot++; }
-            lnr_status s = submit_reads(ctx, &Ln, slot, reads, off, n);
-            if (s == LNR_ERR_NOMEM && li == 1) { ctx->lane1_off = true; li = 0; continue; }   // no room for a second lane's input: one lane from now on
-            if (s != LNR_OK) return s;
-            break;
-        }
-        Lane &Ln = *ctx->lane[li];
-        if (!Ln.th.joinable()) {
-            try { Ln.th = std::thread(lane_worker, ctx, li); }
-            catch (...) { ctx->err = "worker thread could not be started"; return LNR_ERR_INTERNAL; }
-        }
-        std::unique_ptr<Ticket> T(new Ticket());
-        T->lane = li; T->slot = slot;
-        {
-            std::lock_guard<std::mutex> g(ctx->mu);
-            Ln.slot_busy[slot] = true; Ln.pending++;
-            Ln.work.push_back(T.get());
-        }
-        ctx->tickets.push_back(std::move(T));
-        ctx->cv.notify_all();
-        return LNR_OK;
-    }
-    int slot = (ctx->in_head + ctx->in_count) % 3;
-    lnr_status s = submit_reads(ctx, ctx->lane[0].get(), slot, reads, off, n);
-    if (s != LNR_OK) return s;
-    ctx->in_count++;
-    return LNR_OK;
+    return submit_batch(ctx, [&](Lane *L, int slot) { return submit_reads(ctx, L, slot, reads, off, n); });
+}
+lnr_status lnr_filter_submit_dev(lnr_ctx *ctx, const uint8_t *d_reads, const uint64_t *d_off, const uint64_t *h_off, uint32_t n) {
+    if (!ctx) return LNR_ERR_ARG;
+    if (!d_off || (n && !d_reads)) { ctx->err = "null read buffer"; return LNR_ERR_ARG; }
+    return submit_batch(ctx, [&](Lane *L, int slot) { return submit_borrowed(ctx, L, slot, d_reads, d_off, h_off, n); });
 }
 lnr_status lnr_filter_wait(lnr_ctx *ctx, lnr_cords *out) {
     if (!ctx || !out) return LNR_ERR_ARG;
     DevGuard dg_(ctx->device);
+    park_age(ctx);
     if (!ctx->tickets.empty()) {
         // two lanes: the oldest batch in flight is being computed (or was) by its lane's worker; wait for it, download, hand out
         Ticket *T = ctx->tickets.front().get();
@@ -437,6 +494,41 @@ lnr_status lnr_filter_wait(lnr_ctx *ctx, lnr_cords *out) {
         compute_submitted(ctx);
     }
     HIPCK(hipEventSynchronize(ctx->ev_down));
+    ctx->stats_pub = P.stats;
+    return LNR_OK;
+}
+lnr_status lnr_filter_wait_dev(lnr_ctx *ctx, lnr_cords_dev *out) {
+    if (!ctx || !out) return LNR_ERR_ARG;
+    DevGuard dg_(ctx->device);
+    park_age(ctx);
+    out->n_reads = 0; out->n_cords = 0; out->d_cord_off = nullptr; out->d_cords_str = nullptr; out->d_cords_end = nullptr;
+    if (!ctx->tickets.empty()) {
+        // two lanes: as lnr_filter_wait, but for the download -- the set's buffers are taken out of the lane instead (park_set), so the set is
+        // free when this call returns, as it is there
+        Ticket *T = ctx->tickets.front().get();
+        { std::unique_lock<std::mutex> lk(ctx->mu); ctx->cv.wait(lk, [&] { return T->done; }); }
+        Pre P = std::move(T->pre);
+        Lane &Ln = *ctx->lane[T->res_lane];
+        const int T_set = T->res_set;
+        ctx->tickets.pop_front();
+        struct Free { lnr_ctx *c; Lane &l; int set; ~Free() { { std::lock_guard<std::mutex> g(c->mu); l.unhanded--; l.set_used[set] = false; } c->cv.notify_all(); } } free_{ctx, Ln, T_set};
+        if (P.st != LNR_OK) { ctx->err = P.err; return P.st; }
+        lnr_status s = park_set(ctx, P, &ctx->mu, Ln, T_set, out);
+        if (s != LNR_OK) return s;
+        ctx->stats_pub = P.stats;
+        return LNR_OK;
+    }
+    // one lane: the oldest submitted batch is computed now, unless a lnr_filter_wait before this call computed it ahead.  Nothing is
+    // computed ahead here: there is no download to hide it under, and batch k + 1 is computed inside wait(k + 1) at the same cost.
+    if (!ctx->pre.valid) {
+        if (ctx->in_count == 0) { ctx->err = "no batch in flight"; return LNR_ERR_ARG; }
+        compute_submitted(ctx);
+    }
+    Pre P = std::move(ctx->pre);
+    ctx->pre = Pre();
+    if (P.st != LNR_OK) { ctx->err = P.err; return P.st; }
+    lnr_status s = park_set(ctx, P, nullptr, *ctx->lane[0], 0, out);   // (filter_dev returned with the lane's streams idle: the result in r_* is complete)
+    if (s != LNR_OK) return s;
     ctx->stats_pub = P.stats;
     return LNR_OK;
 }

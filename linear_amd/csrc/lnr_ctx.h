@@ -118,6 +118,11 @@ struct Lane {
     PinBuf h_off[3];
     Event ev_in[3];
     u32 in_n[3] = {0, 0, 0};
+    // a slot filled by lnr_filter_submit_dev borrows the caller's device buffers instead: nothing is uploaded, in_reads / in_off / ev_in of
+    // the slot stay unused, and h_off holds the caller's host copy of the offsets when there is one (bor_hoff)
+    bool borrowed[3] = {false, false, false}, bor_hoff[3] = {false, false, false};
+    const u8 *bor_reads[3] = {nullptr, nullptr, nullptr};
+    const u64 *bor_off[3] = {nullptr, nullptr, nullptr};
     // ---- per-read arrays
     DevBuf rlen, rks, nf, f1_off, f1, pk, nm, pk_off;
     DevBuf cords, out_str, out_end, cords_off, cords_cap, ncords, nout, read_err;
@@ -181,6 +186,11 @@ struct lnr_ctx {
     // until the SECOND next result (a writer thread formats batch k while k + 1 runs)
     PinBuf h_cords_str2[2], h_cords_end2[2];
     std::vector<u64> h_cord_off2[2]; int res_slot = 0;
+    // device results handed out by lnr_filter_wait_dev stay valid until the SECOND next wait is called, as the host arrays do.  The wait
+    // takes the three buffers of the batch's result set out of the lane and puts the oldest parked ones in their place (pointer swaps: no
+    // copy, no allocation once all are grown), so the lane's set is free at once -- as after a download -- and no worker ever waits for a
+    // set the caller still reads.  Every wait starts by swapping the two entries: park[0] is then the expired one, park[1] the last handed out.
+    struct Parked { DevBuf off, str, end; } park[2];
     std::vector<u64> h_anchor_off, h_anchors, h_gap_off, h_gap_pairs;
     lnr_stats stats_pub{};               // statistics of the batch handed out last (what lnr_last_stats reports)
     // ---- one lane at a time (-g > 0, LNR_LANES=1): batches wait in lane 0's input slots [in_head, in_head + in_count) and are computed on
